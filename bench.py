@@ -17,6 +17,10 @@ HBM: one launch of the chain kernel, the device line fit that picks the analyzer
 
 Contract: ``python bench.py --gpus N --steps K --warmup W`` (N > 1 under ``python -m
 torch.distributed.run``, which only serves as the process launcher); rank 0 prints ONE JSON line.
+Such a plain run only sets up, warms up, times the K steps and prints the line (metric, value, unit,
+ms_per_step, ...).  --full adds everything else the line used to carry: the CPU baselines, the region
+with batches in flight, the kernel time and roofline, the gather self-check, audit, parity, end-to-end
+and the other configurations.  --dump-outputs DIR writes what the last timed step computed as .npy files.
 """
 
 import os
@@ -127,6 +131,36 @@ def stage(batch, dev, which=None):
     ctx.set_elements([ds] * len(which), [batch['Gmat'][batch['elems'][e]] for e in which],
                      np.tile(batch['D'], (len(which), 1)), [batch['kinds'][e] for e in which])
     return ctx
+
+
+DUMP_H_SAMPLE = 4096            # alpha-solves whose whole H goes into the dump (all H of the batch: 102 MB)
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(ctx, dirname, seed=2025):
+    """What the last timed step computed, as a caller of that path receives it: the per-alpha results of every alpha-solve
+    (chi2, S, Q, iterations, convergence flag, evaluations, v), H of a fixed seeded sample of the alpha-solves (H_sample, rows
+    H_sample_index of the [scan x alpha] problems), and the line-fit alpha of every scan with its H row.  Written as
+    ``dirname/<name>.npy`` in float64; returns the names.  Read straight behind the timed region: nothing is launched again."""
+    res = ctx.fetch(want_v=True, want_H=True)
+    pick_idx, pick_H = ctx.select_fetch(want_H=True)
+    n_chain, n_alpha = res['chi2'].shape
+    n_prob = n_chain * n_alpha
+    sample = np.sort(np.random.default_rng(seed).choice(n_prob, size=min(DUMP_H_SAMPLE, n_prob), replace=False))
+    arrays = dict(chi2=res['chi2'], S=res['S'], Q=res['Q'], n_iter=res['n_iter'], converged=res['converged'],
+                  n_evals=res['n_evals'], v=res['v'], H_sample=res['H'].reshape(n_prob, -1)[sample], H_sample_index=sample,
+                  linefit_index=pick_idx, linefit_H=pick_H)
+    arrays = {k: np.ascontiguousarray(a, dtype=np.float64) for k, a in arrays.items()}
+    if sum(a.nbytes for a in arrays.values()) > DUMP_LIMIT_BYTES:
+        # (batches larger than the default: v of the same sample only)
+        arrays['v_sample'] = np.ascontiguousarray(arrays.pop('v').reshape(n_prob, -1)[sample])
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit('bench.py: --dump-outputs would write %.1f MB, more than %d MB' % (total / 1e6, DUMP_LIMIT_BYTES >> 20))
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + '.npy'), a)
+    return sorted(arrays)
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -741,13 +775,19 @@ def main():
     ap.add_argument('--chains-per-wg', type=int, default=0)
     ap.add_argument('--alpha-split', type=int, default=0)
     ap.add_argument('--wg-per-cu', type=int, default=0)
-    ap.add_argument('--in-flight', type=int, default=4, choices=tuple(range(1, 9)),
-                    help='one rank: behind the timed region (ONE context, one batch at a time: value / ms_per_step) a second region with n '
-                         'batches in flight -- n device contexts (n streams) take the steps in turn, every batch cut into 1 / n as many '
-                         'cold-started pieces (mxe_opts.in_flight) -- reported as value_in_flight / ms_per_step_in_flight; 1: skip it')
+    ap.add_argument('--in-flight', type=int, default=None, choices=tuple(range(1, 9)),
+                    help='with --full, one rank: behind the timed region (ONE context, one batch at a time: value / ms_per_step) a second '
+                         'region with n batches in flight -- n device contexts (n streams) take the steps in turn, every batch cut into 1 / n '
+                         'as many cold-started pieces (mxe_opts.in_flight) -- reported as value_in_flight / ms_per_step_in_flight; 1: skip '
+                         'it (default 4)')
     ap.add_argument('--in-flight-comm', type=int, default=0, choices=tuple(range(0, 9)),
-                    help='--gpus N: behind the region with one context per rank, a region with n contexts per rank in flight, a communicator '
-                         'each (under a watchdog).  OFF by default: it has never run between two GPUs (ADVICE r04); 0 or 1: skip it')
+                    help='with --full, --gpus N: behind the region with one context per rank, a region with n contexts per rank in flight, a '
+                         'communicator each (under a watchdog).  OFF by default: it has never run between two GPUs (ADVICE r04); 0 or 1: skip it')
+    ap.add_argument('--full', action='store_true',
+                    help='besides the timed steps, everything else: CPU baselines, the region with batches in flight, kernel time and '
+                         'roofline, the gather self-check, audit, parity, end-to-end, the other BASELINE configurations')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last of them computed (rank 0) as DIR/<name>.npy (float64)')
     ap.add_argument('--cut-for-in-flight', type=int, default=0,
                     help='counter collection only (tools/round_profile.sh): the ONE context of the timed region is uploaded with '
                          'mxe_opts.in_flight = n -- the launch the batches in flight consist of, alone on the GPU; not a bench line')
@@ -760,6 +800,14 @@ def main():
     ap.add_argument('--force-comm', action='store_true',
                     help='initialise the communicator and run the gather even with one rank (plumbing test)')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    if not args.full and (args.in_flight or 1) > 1:
+        ap.error('--in-flight %d: the region with batches in flight is part of --full' % args.in_flight)
+    if not args.full and args.in_flight_comm > 1:
+        ap.error('--in-flight-comm %d: the region with steps in flight is part of --full' % args.in_flight_comm)
+    if args.in_flight is None:
+        args.in_flight = 4 if args.full else 1
 
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
@@ -776,7 +824,7 @@ def main():
     default_workload = (args.n_orb, args.n_tau, args.n_omega, args.n_alpha) == (16, 200, 500, 100) and args.cut_for_in_flight <= 1
 
     pool_baseline = None
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         # host cores first, before anything initialises the GPU in this process (forked workers)
         pool_baseline = cpu_pool_baseline(build_batch(args.n_orb, args.n_tau, args.n_omega, args.n_alpha, 0))
 
@@ -876,14 +924,19 @@ def main():
         elapsed = float(ctx.allreduce([elapsed], 'max')[0])
     PHASE[0] = 'behind the timed region (kernel time, self-check, extras)'
     host_split = dict(enqueue_ms=1e3 * (t_enq - t0), wait_ms=1e3 * (t_drained - t_enq))
-    # ... and behind it (as in rounds 1-3) the dominant kernel's own duration: HIP events around launches on the library's
-    # stream, back to back, one launch at a time.  (Where it is taken matters by 1-3 % on these boxes: right behind the
-    # warm-up the clocks have not come up (0.84 ms), behind a region with launches in flight they are lower (0.825).)
-    ctx.sync()
-    ctx.timing_mark()
-    for _ in range(50):
-        ctx.launch()
-    k_ms = ctx.ms_since_mark() / 50
+    timed_info = ctx.last_launch_info()
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(ctx, args.dump_outputs)
+    if args.full:
+        # ... and behind it (as in rounds 1-3) the dominant kernel's own duration: HIP events around launches on the library's
+        # stream, back to back, one launch at a time.  (Where it is taken matters by 1-3 % on the MI355X: right behind the
+        # warm-up the clocks have not come up (0.84 ms), behind a region with launches in flight they are lower (0.825).)
+        ctx.sync()
+        ctx.timing_mark()
+        for _ in range(50):
+            ctx.launch()
+        k_ms = ctx.ms_since_mark() / 50
 
     in_flight_region = None
     in_flight_check = None
@@ -946,7 +999,7 @@ def main():
         lanes = [ctx]
 
     gather_checked = None
-    if use_comm and rank == 0:
+    if args.full and use_comm and rank == 0:
         # what arrived: rank 0's own block must be its own results, and (strong scaling) everybody's chi2 must
         # be what rank 0 gets when it solves the whole batch itself
         one_step()
@@ -970,7 +1023,7 @@ def main():
                 ok = ok and bool(np.allclose(got, ref[elems_r], rtol=1e-6, atol=0))
                 off += counts[r]
         gather_checked = bool(ok)
-    elif use_comm:
+    elif args.full and use_comm:
         one_step()
         ctx.gather(0, counts, full=full)
         ctx.sync()
@@ -1005,6 +1058,32 @@ def main():
             dog.cancel()
         return
 
+    value = P_job * args.steps / elapsed
+    if not args.full:
+        # a plain run: the headline and what describes it, nothing that needs a launch or a run of its own
+        line = dict(metric='alpha-solves/s', value=value, unit='alpha-solves/s',
+                    n_gpus=world, steps=args.steps, warmup=args.warmup,
+                    ms_per_step=1e3 * elapsed / args.steps, higher_is_better=True,
+                    scaling=('strong' if strong else 'weak'), vs_baseline=None, dtype='f64', data='synthetic', full=False,
+                    config=dict(
+                        workload=('cfg4: ElementwiseMaxEnt %dx%d G(tau) = %d alpha scans x %d alpha = %d alpha-solves, '
+                                  'n_tau=%d n_omega=%d n_s=%d; ' % (args.n_orb, args.n_orb, n_elem, args.n_alpha,
+                                                                   n_elem * args.n_alpha, args.n_tau, args.n_omega, ctx.n_s)) +
+                                 ('the one batch sharded over %d GPU(s), element e on rank e mod N' % world if strong
+                                  else 'one such batch per GPU (%d GPUs, weak scaling)' % world),
+                        in_flight=1, in_flight_note='one batch at a time',
+                        step='chain kernel + device line fit' + (' + one RCCL gather to rank 0: %.2f MB per step'
+                                                                % (float(np.sum(counts)) * 8 / 1e6) if use_comm else ''),
+                        problems_per_step=P_job, problems_on_rank0=P_rank, kernel=timed_info['kernel'],
+                        waves_per_chain=timed_info['waves_per_chain'], workgroups=timed_info['n_workgroups'],
+                        lds_bytes=timed_info['lds_bytes'], svd_seconds_host=batch['t_svd'], host_split=host_split),
+                    watchdog_fired=False, dumped_outputs=dumped)
+        if use_comm:
+            ctx.comm_destroy()
+        ctx.close()
+        print(json.dumps(line))
+        return
+
     # the rounds of the workgroups of the timed launch (mxe_launch_depth): the build of the full batch does not count them in the
     # timed region (a memset node per launch); one launch with the switch on, outside it -- the tail of the launch as a number
     os.environ['MXE_COUNT_ROUNDS'] = '1'
@@ -1021,7 +1100,6 @@ def main():
     n_left_to_finish = ctx.finish()
     out = ctx.fetch()
     n_conv = int(out['converged'].sum())
-    value = P_job * args.steps / elapsed
 
     # ---- roofline of the dominant kernel (mxe::chain_kernel_mc) ----
     n_s = ctx.n_s
@@ -1144,6 +1222,8 @@ def main():
                                      'every busy slot of a workgroup): the launch is as long as its slowest workgroups, the mean is what a '
                                      'perfectly balanced launch would take (profiles/r05_experiments.txt)')
     line['watchdog_fired'] = False
+    line['full'] = True
+    line['dumped_outputs'] = dumped
     line['in_flight_ok'] = None
     if in_flight_region is not None:
         line['in_flight'] = in_flight_region

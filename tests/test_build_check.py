@@ -1,6 +1,7 @@
 """Build-time guarantees of the shipped kernels: no instantiation spills registers beyond the one documented
 allowance (``make -C maxent_amd/csrc check``: hipcc's own resource report)."""
 import os
+import re
 import shutil
 import subprocess
 
@@ -11,12 +12,15 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.mark.skipif(shutil.which('hipcc') is None and not os.path.exists('/opt/rocm/bin/hipcc'), reason='no hipcc')
 def test_no_shipped_kernel_spills():
-    r = subprocess.run(['make', '-C', os.path.join(ROOT, 'maxent_amd', 'csrc'), 'check'], capture_output=True, text=True)
+    r = subprocess.run(['make', '--no-print-directory', '-C', os.path.join(ROOT, 'maxent_amd', 'csrc'), 'check'],
+                       capture_output=True, text=True)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
-    lines = [l for l in r.stdout.splitlines() if 'scratch' in l]
+    # (only the report lines of the check: other output -- a path, say -- may contain the word too)
+    found = [(l, re.search(r' scratch +(\d+) B occupancy ', l)) for l in r.stdout.splitlines()]
+    report = [(l, int(m.group(1))) for l, m in found if m]
+    lines = [l for l, _ in report]
     assert len(lines) >= 20
-    for l in lines:
-        scratch = int(l.split('scratch')[1].split('B')[0])
+    for l, scratch in report:
         assert scratch == 0 or ('chain_kernel_mcILi32ELi2' in l and scratch <= 200) or \
             ('chain_kernel_mcILi32ELi1' in l and 'ELi8EE' in l and scratch <= 64) or \
             ('chain_kernel_mcILi64ELi1' in l and scratch <= 192) or \

@@ -523,7 +523,7 @@ def test_bench_main_with_the_communicator_path_in_loop_back():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, MASTER_PORT='29437')
-    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--force-comm', '--no-cpu-baseline', '--no-extras',
+    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--full', '--force-comm', '--no-cpu-baseline', '--no-extras',
                         '--steps', '6', '--warmup', '2', '--n-orb', '4', '--n-tau', '100', '--n-omega', '200', '--n-alpha', '20'],
                        capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]

@@ -9,7 +9,7 @@ res = {l: [] for l in libs}
 for rep in range(int(os.environ.get('AB_REPS', '3'))):
     for l in libs:
         env = dict(os.environ, MAXENT_AMD_LIB=os.path.join(ROOT, 'maxent_amd', 'lib', l))
-        out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--no-cpu-baseline', '--no-extras', '--steps', '300'] + extra,
+        out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--full', '--no-cpu-baseline', '--no-extras', '--steps', '300'] + extra,
                              env=env, capture_output=True, text=True)
         d = json.loads(out.stdout.strip().splitlines()[-1])
         res[l].append((d['roofline']['kernel_ms'], d['ms_per_step']))
