@@ -36,6 +36,8 @@
  *     cost_function.py:73-85, maxent_cost_function.py:68-165
  *   TauKernel / PreblurKernel fill + KernelSVD.svd         | mxe_kernel_svd (optional: the host
  *     kernels.py:53-122,244-271,384-393                    |   numpy path stays the default)
+ *   IOmegaKernel fill (stacked real [Re K ; Im K])         | mxe_kernel_svd_iw (the same, for
+ *     + KernelSVD.svd   kernels.py:283-346                 |   Matsubara data)
  *   the arrays of MaxEntResult (numpy allocations)         | mxe_host_alloc / mxe_host_free (optional:
  *     maxent_result.py:835-967                             |   page-locked destinations, one DMA per fetch)
  *
@@ -451,6 +453,18 @@ int  mxe_kernel_svd(int device, int n_tau, int n_omega, const double* tau,
                     int n_b, const double* preblur_b, double threshold, int ns_max,
                     double* out_K, double* out_U, double* out_S, double* out_V,
                     int32_t* out_ns, int32_t* out_info, float* out_ms);
+
+/* IOmegaKernel (reference kernels.py:283-346, K(i w_n, w) = 1 / (i w_n - w)) as the stacked real
+ * matrix of 2 n_iw rows: rows 0..n_iw-1 = Re K = -w / (w_n^2 + w^2), rows n_iw..2 n_iw-1 = Im K
+ * = -w_n / (w_n^2 + w^2).  iomega: the n_iw real Matsubara frequencies w_n.  Everything else --
+ * preblur widths, threshold, ns_max, outputs (with n_tau -> 2 n_iw), error codes -- as
+ * mxe_kernel_svd.  MXE_ERR_LIMIT also when 2 n_iw rows exceed the decomposition's LDS
+ * (n_iw > ~3700). */
+int  mxe_kernel_svd_iw(int device, int n_iw, int n_omega, const double* iomega,
+                       const double* omega, const double* delta,
+                       int n_b, const double* preblur_b, double threshold, int ns_max,
+                       double* out_K, double* out_U, double* out_S, double* out_V,
+                       int32_t* out_ns, int32_t* out_info, float* out_ms);
 
 #ifdef __cplusplus
 }

@@ -3242,28 +3242,31 @@ MXE_CATCH_ALL
 #include "mxe_svd.hip.h"
 
 
-extern "C" int mxe_kernel_svd(int device, int n_tau, int n_omega, const double* tau, const double* omega,
-                              const double* delta, double beta, int n_b, const double* preblur_b,
-                              double threshold, int ns_max, double* out_K, double* out_U, double* out_S,
-                              double* out_V, int32_t* out_ns, int32_t* out_info, float* out_ms)
-try {
-    if (n_tau < 1 || n_omega < 1 || n_b < 1 || !tau || !omega || !delta || !preblur_b || !out_U || !out_S ||
-        !out_V || !out_ns || ns_max < 1 || ns_max > mxe::SVD_RCAP || !(threshold >= 0.0)) return MXE_ERR_ARG;
+namespace {
+// mxe_kernel_svd / mxe_kernel_svd_iw after their argument checks: ``fill(stream, dgrid, domega, dKt)`` writes the
+// unblurred K^T (n_omega columns of m_rows values) from the row grid (n_grid values: tau, or iomega); the preblur
+// stages, the decomposition and the copy-out are the same for every kernel
+template <class Fill>
+int kernel_svd_common(int device, int n_grid, int m_rows, int n_omega, const double* grid, const double* omega,
+                      const double* delta, int n_b, const double* preblur_b, double threshold, int ns_max,
+                      double* out_K, double* out_U, double* out_S, double* out_V, int32_t* out_ns,
+                      int32_t* out_info, float* out_ms, Fill fill)
+{
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return MXE_ERR_NODEVICE;
     if (device < 0 || device >= ndev) return MXE_ERR_ARG;
-    const size_t lds = ((size_t)n_tau + 16 + 8 + mxe::SVD_RCAP + mxe::SVD_RCAP / 2) * sizeof(double);
+    const size_t lds = ((size_t)m_rows + 16 + 8 + mxe::SVD_RCAP + mxe::SVD_RCAP / 2) * sizeof(double);
     if (lds > 60 * 1024) return MXE_ERR_LIMIT;
     SVDCHK(hipSetDevice(device));
     SvdScratch sc;
     SVDCHK(hipStreamCreateWithFlags(&sc.stream, hipStreamNonBlocking));
     SVDCHK(hipEventCreate(&sc.e0));
     SVDCHK(hipEventCreate(&sc.e1));
-    const size_t m = n_tau, n = n_omega, R = mxe::SVD_RCAP;
-    double *dtau, *dom, *ddel, *dKt0, *dr1, *ddc, *dB;
+    const size_t m = m_rows, n = n_omega, R = mxe::SVD_RCAP;
+    double *dgrid, *dom, *ddel, *dKt0, *dr1, *ddc, *dB;
     mxe::SvdParams sp;
-    sp.m = n_tau; sp.n = n_omega; sp.ns_max = ns_max; sp.threshold = threshold;
-    SVDCHK(sc.alloc(&dtau, m)); SVDCHK(sc.alloc(&dom, n)); SVDCHK(sc.alloc(&ddel, n));
+    sp.m = m_rows; sp.n = n_omega; sp.ns_max = ns_max; sp.threshold = threshold;
+    SVDCHK(sc.alloc(&dgrid, n_grid)); SVDCHK(sc.alloc(&dom, n)); SVDCHK(sc.alloc(&ddel, n));
     SVDCHK(sc.alloc(&dKt0, n * m)); SVDCHK(sc.alloc(&dr1, n)); SVDCHK(sc.alloc(&ddc, n)); SVDCHK(sc.alloc(&dB, n * n));
     SVDCHK(sc.alloc(&sp.A, (size_t)n_b * n * m)); SVDCHK(sc.alloc(&sp.Vh, (size_t)n_b * R * m));
     SVDCHK(sc.alloc(&sp.Rm, (size_t)n_b * R * n)); SVDCHK(sc.alloc(&sp.Jt, (size_t)n_b * R * R));
@@ -3271,12 +3274,11 @@ try {
     SVDCHK(sc.alloc(&sp.perm, (size_t)n_b * n));
     SVDCHK(sc.alloc(&sp.out_U, (size_t)n_b * m * ns_max)); SVDCHK(sc.alloc(&sp.out_S, (size_t)n_b * ns_max));
     SVDCHK(sc.alloc(&sp.out_V, (size_t)n_b * n * ns_max)); SVDCHK(sc.alloc(&sp.out_info, (size_t)n_b * 4));
-    SVDCHK(hipMemcpyAsync(dtau, tau, m * 8, hipMemcpyHostToDevice, sc.stream));
+    SVDCHK(hipMemcpyAsync(dgrid, grid, (size_t)n_grid * 8, hipMemcpyHostToDevice, sc.stream));
     SVDCHK(hipMemcpyAsync(dom, omega, n * 8, hipMemcpyHostToDevice, sc.stream));
     SVDCHK(hipMemcpyAsync(ddel, delta, n * 8, hipMemcpyHostToDevice, sc.stream));
     SVDCHK(hipEventRecord(sc.e0, sc.stream));
-    const int nel = n_tau * n_omega;
-    hipLaunchKernelGGL(mxe::tau_kernel_fill, dim3((nel + 255) / 256), dim3(256), 0, sc.stream, dtau, dom, beta, n_tau, n_omega, dKt0);
+    fill(sc.stream, dgrid, dom, dKt0);
     SVDCHK(hipGetLastError());
     for (int ib = 0; ib < n_b; ++ib) {
         double* Ai = sp.A + (size_t)ib * n * m;
@@ -3285,7 +3287,7 @@ try {
             hipLaunchKernelGGL(mxe::preblur_rows, dim3(n_omega), dim3(256), 0, sc.stream, dom, ddel, b, n_omega, dr1);
             hipLaunchKernelGGL(mxe::preblur_cols, dim3(n_omega), dim3(256), 0, sc.stream, dom, ddel, b, n_omega, dr1, ddc);
             hipLaunchKernelGGL(mxe::preblur_matrix, dim3((n_omega * n_omega + 255) / 256), dim3(256), 0, sc.stream, dom, b, n_omega, dr1, ddc, dB);
-            hipLaunchKernelGGL(mxe::preblur_product, dim3(n_omega), dim3(256), n * 8, sc.stream, dKt0, ddel, dB, n_tau, n_omega, Ai);
+            hipLaunchKernelGGL(mxe::preblur_product, dim3(n_omega), dim3(256), n * 8, sc.stream, dKt0, ddel, dB, m_rows, n_omega, Ai);
             SVDCHK(hipGetLastError());
         } else {
             SVDCHK(hipMemcpyAsync(Ai, dKt0, n * m * 8, hipMemcpyDeviceToDevice, sc.stream));
@@ -3320,5 +3322,38 @@ try {
                 for (size_t i = 0; i < m; ++i)
                     out_K[((size_t)ib * m + i) * n + j] = hKt[((size_t)ib * n + j) * m + i];
     return rc;
+}
+} // namespace
+
+extern "C" int mxe_kernel_svd(int device, int n_tau, int n_omega, const double* tau, const double* omega,
+                              const double* delta, double beta, int n_b, const double* preblur_b,
+                              double threshold, int ns_max, double* out_K, double* out_U, double* out_S,
+                              double* out_V, int32_t* out_ns, int32_t* out_info, float* out_ms)
+try {
+    if (n_tau < 1 || n_omega < 1 || n_b < 1 || !tau || !omega || !delta || !preblur_b || !out_U || !out_S ||
+        !out_V || !out_ns || ns_max < 1 || ns_max > mxe::SVD_RCAP || !(threshold >= 0.0)) return MXE_ERR_ARG;
+    return kernel_svd_common(device, n_tau, n_tau, n_omega, tau, omega, delta, n_b, preblur_b, threshold, ns_max,
+                             out_K, out_U, out_S, out_V, out_ns, out_info, out_ms,
+                             [=](hipStream_t st, const double* dtau, const double* dom, double* dKt0) {
+        const int nel = n_tau * n_omega;
+        hipLaunchKernelGGL(mxe::tau_kernel_fill, dim3((nel + 255) / 256), dim3(256), 0, st, dtau, dom, beta, n_tau, n_omega, dKt0);
+    });
+}
+MXE_CATCH_ALL
+
+extern "C" int mxe_kernel_svd_iw(int device, int n_iw, int n_omega, const double* iomega, const double* omega,
+                                 const double* delta, int n_b, const double* preblur_b, double threshold, int ns_max,
+                                 double* out_K, double* out_U, double* out_S, double* out_V, int32_t* out_ns,
+                                 int32_t* out_info, float* out_ms)
+try {
+    if (n_iw < 1 || n_omega < 1 || n_b < 1 || !iomega || !omega || !delta || !preblur_b || !out_U || !out_S ||
+        !out_V || !out_ns || ns_max < 1 || ns_max > mxe::SVD_RCAP || !(threshold >= 0.0) ||
+        n_iw > (1 << 29) / n_omega) return MXE_ERR_ARG;
+    return kernel_svd_common(device, n_iw, 2 * n_iw, n_omega, iomega, omega, delta, n_b, preblur_b, threshold, ns_max,
+                             out_K, out_U, out_S, out_V, out_ns, out_info, out_ms,
+                             [=](hipStream_t st, const double* diw, const double* dom, double* dKt0) {
+        const int nel = n_iw * n_omega;
+        hipLaunchKernelGGL(mxe::iomega_kernel_fill, dim3((nel + 255) / 256), dim3(256), 0, st, diw, dom, n_iw, n_omega, dKt0);
+    });
 }
 MXE_CATCH_ALL

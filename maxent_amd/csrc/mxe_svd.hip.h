@@ -1,6 +1,7 @@
 // mxe_svd.hip.h -- kernel matrix staging on the device
 //
 //   TauKernel._fill_values      kernels.py:244-271   -> tau_kernel_fill
+//   IOmegaKernel._fill_values   kernels.py:312-331   -> iomega_kernel_fill  (stacked real [Re K ; Im K])
 //   get_preblur                 preblur.py:31-58     -> preblur_rows / preblur_cols / preblur_matrix
 //   PreblurKernel._fill_values  kernels.py:384-393   -> preblur_product   (K' = K diag(delta) B)
 //   KernelSVD.svd + reduce_singular_space kernels.py:53-122 -> svd_kernel
@@ -44,6 +45,25 @@ void tau_kernel_fill(const double* __restrict__ tau, const double* __restrict__ 
     // two algebraically equal forms, each overflow-free on its half-axis (kernels.py:256-263)
     Kt[idx] = (w >= 0.0) ? -exp(-w * t) / (exp(-beta * w) + 1.0)
                          : -exp(w * (beta - t)) / (1.0 + exp(beta * w));
+}
+
+// K^T[j][r] of IOmegaKernel, stacked real: K(i w_n, w) = 1 / (i w_n - w) = (-w - i w_n) / (w_n^2 + w^2),
+// rows r < n_iw the real parts -w / d, rows n_iw + r the imaginary parts -w_n / d, both from ONE
+// d = w_n^2 + w^2.  Column-major like tau_kernel_fill: column j is a contiguous run of 2 n_iw values.
+// One thread per (w_n, w) pair writes both parts.
+__global__ __launch_bounds__(256)
+void iomega_kernel_fill(const double* __restrict__ iomega, const double* __restrict__ omega,
+                        int n_iw, int n_omega, double* __restrict__ Kt)
+{
+#pragma clang fp contract(off)
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= n_iw * n_omega) return;
+    const int j = idx / n_iw, i = idx - j * n_iw;
+    const double w = omega[j], wn = iomega[i];
+    const double d = wn * wn + w * w;              // (not contracted to an fma: the host's rounding, bit for bit)
+    double* col = Kt + (size_t)j * 2 * n_iw;
+    col[i] = -w / d;
+    col[n_iw + i] = -wn / d;
 }
 
 __device__ __forceinline__ double gauss_blur(double wi, double wj, double b)

@@ -27,6 +27,11 @@ class MaxEntDeviceError(RuntimeError):
     pass
 
 
+_MXE_ERR_LIMIT = -5
+#: most rows of a kernel matrix the device SVD takes (mxe_kernel_svd*: the rows + 216 doubles of the decomposition's LDS <= 60 KB)
+SVD_MAX_ROWS = 60 * 1024 // 8 - 216
+
+
 class MxeOpts(ctypes.Structure):
     """mirror of ``struct mxe_opts`` (include/maxent_hip.h)."""
     _fields_ = [('maxiter', ctypes.c_int32),
@@ -125,6 +130,10 @@ SYMBOLS = [
                                       ctypes.c_double, ctypes.c_int, _dp, ctypes.c_double,
                                       ctypes.c_int, _dp, _dp, _dp, _dp, _ip, _ip,
                                       ctypes.POINTER(ctypes.c_float)]),
+    ('mxe_kernel_svd_iw', ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp,
+                                         ctypes.c_int, _dp, ctypes.c_double,
+                                         ctypes.c_int, _dp, _dp, _dp, _dp, _ip, _ip,
+                                         ctypes.POINTER(ctypes.c_float)]),
 ]
 
 
@@ -288,20 +297,43 @@ def kernel_svd(tau, omega, delta, beta, preblur_b=(0.0,), threshold=1.e-14,
     if device_count() < 1:
         raise MaxEntDeviceError('no HIP device visible; the device SVD has no CPU fallback')
     tau, omega, delta = _c(tau), _c(omega), _c(delta)
+    return _kernel_svd_call('mxe_kernel_svd', len(tau), (_p(tau),), (float(beta),), omega, delta, preblur_b,
+                            threshold, ns_max, want_K, device)
+
+
+def kernel_svd_iw(iomega, omega, delta, preblur_b=(0.0,), threshold=1.e-14, ns_max=128, want_K=False, device=0):
+    """``mxe_kernel_svd_iw``: IOmegaKernel (stacked real, 2 n_iw rows) and its PreblurKernels filled and
+    decomposed on the device; returns what :func:`kernel_svd` returns.  More rows than the decomposition's LDS
+    holds (2 n_iw > ``SVD_MAX_ROWS``) raise :class:`MaxEntDeviceError` -- the host SVD (``svd_backend='host'``) takes them."""
+    load_library()
+    if device_count() < 1:
+        raise MaxEntDeviceError('no HIP device visible; the device SVD has no CPU fallback')
+    iomega, omega, delta = _c(iomega), _c(omega), _c(delta)
+    return _kernel_svd_call('mxe_kernel_svd_iw', len(iomega), (_p(iomega),), (), omega, delta, preblur_b,
+                            threshold, ns_max, want_K, device, n_rows=2 * len(iomega))
+
+
+def _kernel_svd_call(name, n_grid, grid_args, scalar_args, omega, delta, preblur_b, threshold, ns_max, want_K, device,
+                     n_rows=None):
+    lib = load_library()
     bs = _c(np.atleast_1d(np.asarray(preblur_b, dtype=float)))
-    n_tau, n_w, n_b = len(tau), len(omega), len(bs)
-    K = np.empty((n_b, n_tau, n_w)) if want_K else None
-    U = np.empty((n_b, n_tau, ns_max))
+    n_rows = n_grid if n_rows is None else n_rows      # (rows of K: n_tau, or 2 n_iw)
+    n_w, n_b = len(omega), len(bs)
+    K = np.empty((n_b, n_rows, n_w)) if want_K else None
+    U = np.empty((n_b, n_rows, ns_max))
     S = np.empty((n_b, ns_max))
     V = np.empty((n_b, n_w, ns_max))
     ns = np.zeros(n_b, dtype=np.int32)
     info = np.zeros((n_b, 3), dtype=np.int32)
     ms = ctypes.c_float(0)
-    rc = lib.mxe_kernel_svd(int(device), n_tau, n_w, _p(tau), _p(omega), _p(delta), float(beta),
+    rc = getattr(lib, name)(int(device), n_grid, n_w, *grid_args, _p(omega), _p(delta), *scalar_args,
                             n_b, _p(bs), float(threshold), int(ns_max), _p(K), _p(U), _p(S), _p(V),
                             _p(ns), _p(info), ctypes.byref(ms))
+    if rc == _MXE_ERR_LIMIT and n_rows > SVD_MAX_ROWS:
+        raise MaxEntDeviceError('%s: %d rows of the kernel exceed the %d the device decomposition holds in LDS; '
+                                'svd_backend="host" takes them' % (name, n_rows, SVD_MAX_ROWS))
     if rc != 0:
-        raise MaxEntDeviceError('mxe_kernel_svd failed: ' + lib.mxe_strerror(rc).decode())
+        raise MaxEntDeviceError(name + ' failed: ' + lib.mxe_strerror(rc).decode())
     out = []
     for ib in range(n_b):
         k = int(ns[ib])

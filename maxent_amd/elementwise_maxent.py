@@ -22,6 +22,7 @@ from datetime import datetime
 
 import numpy as np
 
+from . import kernels
 from .default_models import DataDefaultModel
 from .logtaker import VerbosityFlags
 from .maxent_loop import solve_elements, select_params
@@ -691,10 +692,11 @@ class ElementwiseMaxEnt(object):
         omega, beta, no preblur on one side only) the second takes the SVD of the first instead of
         repeating it"""
         a, b = self.maxent_diagonal.K, self.maxent_offdiagonal.K
-        if a is b or type(a) is not type(b) or not hasattr(a, 'tau') or a.rotation is not None or b.rotation is not None:
+        if a is b or type(a) is not type(b) or not isinstance(a, (kernels.TauKernel, kernels.IOmegaKernel)) or \
+                a.rotation is not None or b.rotation is not None:
             return
         try:
-            same = (np.array_equal(np.asarray(a.tau), np.asarray(b.tau)) and
+            same = (np.array_equal(np.asarray(a.data_variable), np.asarray(b.data_variable)) and
                     np.array_equal(np.asarray(a.omega), np.asarray(b.omega)) and a.beta == b.beta and
                     a.svd_backend == b.svd_backend)
         except Exception:
@@ -827,6 +829,7 @@ class ElementwiseMaxEnt(object):
         self.determine_shape = determine_shape
         self.maxent_result = None
         object.__setattr__(self, '_array_input', False)
+        object.__setattr__(self, '_n_iw', None)
 
     def set_G_tau(self, *args, **kwargs):
         raise NotImplementedError('set_G_tau needs TRIQS Green functions; '
@@ -840,8 +843,39 @@ class ElementwiseMaxEnt(object):
             g = G_mat[1][elem]
             maxent.set_G_tau_data(G_mat[0], np.real(g) if re else np.imag(g),
                                   *args, **kwargs)
+        for worker in (self.maxent_diagonal, self.maxent_offdiagonal):
+            worker._use_tau_kernel(tau)
         self.set_G((tau, G_tau), feed, lambda G_mat: G_mat[1].shape[:2])
         object.__setattr__(self, '_array_input', not args and not kwargs)
+
+    def set_G_iw_data(self, iomega, G_iw, beta=None):
+        """``G_iw``: complex (M, N, n_iw) array of G_ij(i omega_n) on the real Matsubara frequencies ``iomega``
+        (:meth:`TauMaxEnt.set_G_iw_data`).  Element (i, j) is continued from the parts of G that belong to the real
+        and the imaginary part of A_ij: for a hermitian A(omega), (G_ij + G_ji) / 2 = K Re A_ij and
+        (G_ij - G_ji) / (2i) = K Im A_ij (the latter with ``use_complex``); a diagonal element is G_ii itself.
+        Every problem is the stacked real one of an IOmegaKernel, and all elements share its decomposition."""
+        iomega = np.asarray(iomega, dtype=float)
+        G_iw = np.asarray(G_iw)
+        if G_iw.ndim != 3 or G_iw.shape[0] != G_iw.shape[1] or G_iw.shape[2] != len(iomega):
+            raise AssertionError('G_iw must be (M, M, n_iw) with n_iw = len(iomega)')
+        Gt = G_iw.transpose(1, 0, 2)
+        re_part = 0.5 * (G_iw + Gt)                 # K Re A_ij
+        im_part = (G_iw - Gt) / 2j                  # K Im A_ij
+        # the stacked real data of the real-part problem in the real part, of the imaginary-part problem in the imaginary
+        # part: the feed and the arrays of _prepare_batch pick them the way they pick the parts of G(tau)
+        stacked = np.concatenate([re_part.real, re_part.imag], axis=-1) + \
+            1j * np.concatenate([im_part.real, im_part.imag], axis=-1)
+        n = len(iomega)
+
+        def feed(maxent, G_mat, elem, re):
+            x = G_mat[1][elem]
+            x = np.real(x) if re else np.imag(x)
+            maxent.set_G_iw_data(G_mat[0], x[:n] + 1j * x[n:], beta)
+        for worker in (self.maxent_diagonal, self.maxent_offdiagonal):
+            worker._use_iomega_kernel(iomega, beta)
+        self.set_G((iomega, stacked), feed, lambda G_mat: G_mat[1].shape[:2])
+        object.__setattr__(self, '_array_input', True)
+        object.__setattr__(self, '_n_iw', n)
 
     def set_G_tau_filename_pattern(self, filename, dimension, tau_col=0,
                                    G_col_re=1, G_col_im=2, *args, **kwargs):
@@ -870,8 +904,15 @@ class ElementwiseMaxEnt(object):
         if isinstance(self.error, float):
             return self.error
         if len(np.shape(self.error)) == self.error_dimension:
-            return self.error
-        return self.error[elem]
+            return self._stacked_error(self.error)
+        return self._stacked_error(self.error[elem])
+
+    def _stacked_error(self, err):
+        """Matsubara data: one error bar per frequency serves the real and the imaginary parts of the stacked data"""
+        n = self.__dict__.get('_n_iw')
+        if n is not None and self.error_dimension == 1 and np.shape(err) == (n,):
+            err = np.concatenate([err, err]).astype(float, copy=False)
+        return err
 
     def set_cov(self, cov):
         """(T, T) or (M, N, T, T) (reference elementwise_maxent.py:502-515)."""

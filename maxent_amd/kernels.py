@@ -5,7 +5,7 @@ filled and decomposed once on the host with numpy/LAPACK; the truncated
 factors ``U, S, V`` are what :class:`maxent_amd.device.DeviceContext` stages
 in HBM.  Public names and semantics follow the reference's ``kernels`` module
 (reference python/kernels.py:37-413): ``KernelSVD``, ``Kernel``,
-``DataKernel``, ``TauKernel``, ``PreblurKernel``.
+``DataKernel``, ``TauKernel``, ``IOmegaKernel``, ``PreblurKernel``.
 """
 
 import numpy as np
@@ -93,9 +93,9 @@ class KernelSVD(object):
     """
 
     #: 'host' (numpy / LAPACK, the reference's path) or 'device'
-    #: (``mxe_kernel_svd``: fill, preblur product and a preconditioned one-sided
-    #: Jacobi SVD on the GPU; kernels that know how they are filled -- TauKernel,
-    #: PreblurKernel of a TauKernel -- implement ``_device_svd``)
+    #: (``mxe_kernel_svd`` / ``mxe_kernel_svd_iw``: fill, preblur product and a preconditioned
+    #: one-sided Jacobi SVD on the GPU; kernels that know how they are filled -- TauKernel,
+    #: IOmegaKernel, a PreblurKernel of either -- implement ``_device_svd``)
     svd_backend = 'host'
 
     def __init__(self, K=None):
@@ -193,6 +193,15 @@ class Kernel(KernelSVD):
     def _fill_values(self):
         raise NotImplementedError('Use a subclass of Kernel')
 
+    def fold(self, x):
+        """a data-space vector or array (last axis = the rows of K) in the form of the data the kernel was made for;
+        identity here, complex for :class:`IOmegaKernel`, whose rows are the stacked real and imaginary parts"""
+        return x
+
+    def unfold(self, x):
+        """the inverse of :meth:`fold`"""
+        return x
+
     def transform(self, T_):
         """Left-multiply K (and U) by ``T_``, given as the absolute rotation
         with respect to the unrotated kernel; ``None`` undoes it."""
@@ -264,7 +273,7 @@ class TauKernel(Kernel):
         w = np.asarray(self.omega, dtype=float)
         beta = tau[-1] if self.beta is None else self.beta
         delta = np.asarray(self.omega.delta, dtype=float)
-        key = (tau.tobytes(), w.tobytes(), delta.tobytes(), float(beta))
+        key = ('tau', tau.tobytes(), w.tobytes(), delta.tobytes(), float(beta))
         hit = _recent_fill.get(key, lambda _: True)               # (the key IS the contents)
         if hit is not None:
             self._K, self._K_delta = hit
@@ -297,6 +306,99 @@ class TauKernel(Kernel):
         self.tau = value
 
 
+class IOmegaKernel(Kernel):
+    r"""Fermionic Matsubara kernel :math:`K(i\omega_n, \omega) = 1/(i\omega_n - \omega)` (reference
+    kernels.py:283-346), for a REAL spectral function: the complex rows become the stacked real matrix
+
+    .. math::
+
+        K = \begin{pmatrix} \mathrm{Re}\,K \\ \mathrm{Im}\,K \end{pmatrix}, \quad
+        \mathrm{Re}\,K = \frac{-\omega}{\omega_n^2 + \omega^2}, \quad
+        \mathrm{Im}\,K = \frac{-\omega_n}{\omega_n^2 + \omega^2}
+
+    of ``2 n_iw`` rows, with the data stacked the same way, ``[Re G ; Im G]``: chi2 over the complex
+    data is the ordinary chi2 of that real system, so the solver runs unchanged.  ``K``, ``K_delta``,
+    ``U``, ``S``, ``V`` belong to the stacked matrix (the reference's ``K`` is complex: it is
+    ``K_complex`` here).  ``iomega``: the real frequencies :math:`\omega_n`; ``beta`` defaults to
+    :math:`2\pi/(\omega_1 - \omega_0)` and does not enter K."""
+
+    def __init__(self, iomega, omega, beta=None, svd_backend='host'):
+        super(IOmegaKernel, self).__init__()
+        self.iomega = iomega
+        self.omega = omega
+        self.beta = beta
+        self.svd_backend = svd_backend
+        self._fill_values()
+
+    @property
+    def n_iw(self):
+        return len(self.iomega)
+
+    def get_beta(self):
+        if self._beta is None:
+            iw = np.asarray(self.iomega, dtype=float)
+            return 2 * np.pi / (iw[1] - iw[0])
+        return self._beta
+
+    def set_beta(self, beta):
+        self._beta = beta
+
+    beta = property(get_beta, set_beta)
+
+    @property
+    def K_complex(self):
+        """the reference's complex ``K`` (n_iw x n_omega), unrotated"""
+        n = self.n_iw
+        return self._K_stacked[:n] + 1j * self._K_stacked[n:]
+
+    def fold(self, x):
+        """``x[..., :n] + 1j x[..., n:]`` (n = n_iw): stacked real data-space values as complex G(i omega_n)"""
+        x = np.asarray(x)
+        n = self.n_iw
+        if x.shape[-1] != 2 * n:
+            raise ValueError('fold: the last axis has %d values, not 2 x %d' % (x.shape[-1], n))
+        return x[..., :n] + 1j * x[..., n:]
+
+    def unfold(self, z):
+        """complex G(i omega_n) (last axis n_iw) as the stacked real vector ``[Re ; Im]``"""
+        z = np.asarray(z)
+        return np.concatenate([z.real, z.imag], axis=-1).astype(float, copy=False)
+
+    def _device_svd(self, preblur_b=0.0):
+        """U, S, V of the UNROTATED stacked kernel from the device (``mxe_kernel_svd_iw``); see TauKernel._device_svd"""
+        from . import device
+        iw = np.asarray(self.iomega, dtype=float)
+        r = device.kernel_svd_iw(iw, np.asarray(self.omega, dtype=float), self.omega.delta, [preblur_b],
+                                 threshold=0.0)[0]
+        return r['U'], r['S'], r['V']
+
+    def _fill_values(self):
+        self._invalidate_svd()
+        iw = np.asarray(self.iomega, dtype=float)
+        w = np.asarray(self.omega, dtype=float)
+        delta = np.asarray(self.omega.delta, dtype=float)
+        key = ('iomega', iw.tobytes(), w.tobytes(), delta.tobytes())         # (the kind keeps a tau grid of the same values apart)
+        hit = _recent_fill.get(key, lambda _: True)
+        if hit is None:
+            d = iw[:, np.newaxis] ** 2 + w[np.newaxis, :] ** 2           # (one w_n^2 + w^2 for both parts, as the device fill)
+            K = np.concatenate([-w[np.newaxis, :] / d, -iw[:, np.newaxis] / d])
+            hit = (_frozen(K), _frozen(K * delta[np.newaxis, :]))
+            _recent_fill.put(key, None, hit)
+        self._K, self._K_delta = hit
+        self._K_stacked = hit[0]
+        T = self._T
+        self._T = None
+        self.transform(T)
+
+    @property
+    def data_variable(self):
+        return self.iomega
+
+    @data_variable.setter
+    def data_variable(self, value):
+        self.iomega = value
+
+
 class PreblurKernel(Kernel):
     """``K' = K diag(delta) B`` for the preblur formalism; ``K_delta`` stays
     un-blurred (reference kernels.py:349-413)."""
@@ -309,9 +411,15 @@ class PreblurKernel(Kernel):
         self.svd_backend = K.svd_backend if svd_backend is None else svd_backend
         self._fill_values()
 
+    def fold(self, x):
+        return self.kernel.fold(x)
+
+    def unfold(self, x):
+        return self.kernel.unfold(x)
+
     def _device_svd(self):
-        if not isinstance(self.kernel, TauKernel):
-            raise NotImplementedError('device SVD of a PreblurKernel needs a TauKernel inside')
+        if not isinstance(self.kernel, (TauKernel, IOmegaKernel)):
+            raise NotImplementedError('device SVD of a PreblurKernel needs a TauKernel or an IOmegaKernel inside')
         U, S, V = self.kernel._device_svd(preblur_b=self._b)
         T = self.kernel._T
         return (U if T is None else np.dot(T, U)), S, V

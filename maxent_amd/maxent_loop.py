@@ -33,17 +33,28 @@ from .probabilities import NormalLogProbability
 # --------------------------------------------------------------------------
 
 class _LazyProduct(object):
-    """``A @ K_delta.T`` (MaxEntResult.G_rec, reference maxent_result.py:908) evaluated on first use:
+    """``fold(A @ K_delta.T)`` (MaxEntResult.G_rec, reference maxent_result.py:908) evaluated on first use:
     a 10 MFLOP product per matrix element that most jobs never look at."""
 
-    def __init__(self, A, K_delta):
-        self._A, self._K, self._val = A, K_delta, None
+    def __init__(self, A, K_delta, fold=None):
+        self._A, self._K, self._fold, self._val = A, K_delta, fold, None
 
     def __array__(self, dtype=None, copy=None):
         if self._val is None:
             self._val = np.dot(np.asarray(self._A), self._K.T)
-            self._A = self._K = None
+            if self._fold is not None:
+                self._val = self._fold(self._val)
+            self._A = self._K = self._fold = None
         return self._val if dtype is None else self._val.astype(dtype, copy=False)
+
+
+def data_fields(K, G, G_orig, A):
+    """G, G_orig and G_rec of a result record in the form of the data: ``K.fold`` -- the identity, or for an IOmegaKernel
+    the stacked real data space back to complex G(i omega_n) (G itself only where it is not rotated into a covariance
+    eigenbasis).  The one place where a record's data-space fields are made."""
+    fold = K.fold
+    return dict(G=(fold(G) if K.rotation is None else G), G_orig=fold(G_orig),
+                G_rec=_LazyProduct(A, K.K_delta, fold))
 
 
 def solve_elements(K, specs, minimizer, device_id=0, waves_per_chain=0,
@@ -251,10 +262,8 @@ class MaxEntLoop(object):
             A = LazyA(sol['H'], self.A_of_H) if isinstance(sol['H'], LazyH) else self.A_of_H.f(sol['H'])
         rec = dict(sol)
         rec['A'] = A
-        rec['G'] = spec['G']
-        rec['G_orig'] = spec['G_orig']
+        rec.update(data_fields(self.K, spec['G'], spec['G_orig'], A))      # (G_rec = K_delta A, formed when it is looked at)
         rec['data_variable'] = spec['data_variable']
-        rec['G_rec'] = _LazyProduct(A, self.K.K_delta)      # K_delta A, formed when it is looked at
         rec['omega'] = self.omega
         X = len(sol['alpha'])
         if self.probability is not None and sol.get('logdet') is not None:
@@ -278,7 +287,7 @@ class MaxEntLoop(object):
         if self.probability is not None or any(sol.get('A') is not None for sol in sols):
             return [self.make_record(spec, sol) for spec, sol in zip(specs, sols)]
         from .batch_solver import LazyA, LazyH
-        A_of_H, K_delta, omega = self.A_of_H, self.K.K_delta, self.omega
+        A_of_H, K, omega = self.A_of_H, self.K, self.omega
         nans = {}
         out = []
         for spec, sol in zip(specs, sols):
@@ -290,8 +299,8 @@ class MaxEntLoop(object):
                 nan = nans[X] = np.full(X, np.nan)
                 nan.setflags(write=False)           # (one array for every scan of the launch)
             rec = dict(sol)
-            rec.update(A=A, G=spec['G'], G_orig=spec['G_orig'], data_variable=spec['data_variable'],
-                       G_rec=_LazyProduct(A, K_delta), omega=omega, probability=nan)
+            rec.update(A=A, data_variable=spec['data_variable'], omega=omega, probability=nan)
+            rec.update(data_fields(K, spec['G'], spec['G_orig'], A))
             out.append(rec)
         return out
 

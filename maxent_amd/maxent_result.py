@@ -5,6 +5,8 @@ reference's (reference python/maxent_result.py:157-188, 688-1081):
 
 scalar run          alpha (X,)  v (X,n_s)  A,H (X,n_omega)  chi2,S,Q,probability
                     (X,)  G,G_orig,data_variable (n_tau,)  G_rec (X,n_tau)
+                    (Matsubara data, IOmegaKernel: G, G_orig, G_rec complex of
+                    n_iw values, data_variable = iomega)
 element-wise run    the same with a prefix (M,N) or (M,N,2); NaN where an
                     element was not calculated; H and A of a missing (i,j)
                     are mirrored from (j,i) when ``use_hermiticity`` is set
@@ -442,13 +444,14 @@ class MaxEntResult(MaxEntResultData):
         self._last_add = now
         row = dict(alpha=float(q._alpha), v=np.array(q._x, dtype=float), H=H, A=A,
                    chi2=float(q.chi2.f()), S=float(q.S.f()), Q=float(q.f()),
-                   G_rec=np.dot(K.K_delta, A),
+                   G_rec=K.fold(np.dot(K.K_delta, A)),
                    probability=np.nan if log_probability is None else log_probability,
                    n_iter=0, converged=True, n_evals=0, run_times=now - last)
         rec = self._records.get(key)
         if rec is None:
             rec = dict((k, np.array([val])) for k, val in row.items())
-            rec.update(G=np.array(q.G), G_orig=np.array(q.G_orig), data_variable=np.array(K.data_variable), omega=q.omega)
+            rec.update(G=(K.fold(np.array(q.G)) if K.rotation is None else np.array(q.G)), G_orig=K.fold(np.array(q.G_orig)),
+                       data_variable=np.array(K.data_variable), omega=q.omega)
         else:
             rec = dict(rec)
             for k, val in row.items():
@@ -665,9 +668,11 @@ class MaxEntResult(MaxEntResultData):
             if fast is not None:
                 self._cache[name] = fast
                 return fast
-            arr = np.full(shape, np.nan)
+            # (the data-space fields of a Matsubara problem are complex: IOmegaKernel.fold)
+            dtype = complex if name in ('G', 'G_orig', 'G_rec') and np.iscomplexobj(np.asarray(ref[name])) else float
+            arr = np.full(shape, np.nan, dtype=dtype)
             for key, rec in self._records.items():
-                val = np.asarray(rec[name], dtype=float)
+                val = np.asarray(rec[name], dtype=dtype)
                 if per_alpha:
                     arr[key][:len(val)] = val
                 else:

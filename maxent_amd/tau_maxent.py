@@ -5,7 +5,9 @@ Keeps the reference's surface (reference python/tau_maxent.py:37-356): owns a
 ``tm.alpha_mesh = ...``), default 100-point hyperbolic omega mesh on
 [-10, 10] with a flat default model, setters for G(tau) from arrays or text
 files, scalar / per-tau errors and full covariance matrices (the problem is
-rotated into the covariance eigenbasis).  ``set_G_tau`` / ``set_G_iw`` need
+rotated into the covariance eigenbasis).  ``set_G_iw_data`` takes G(i omega_n)
+as arrays instead: the kernel becomes an :class:`IOmegaKernel` and the data
+its stacked real form ``[Re G ; Im G]``.  ``set_G_tau`` / ``set_G_iw`` need
 TRIQS Green-function objects and are not provided.
 """
 
@@ -84,17 +86,56 @@ class TauMaxEnt(object):
         else:
             self._rotate_to(T_)
 
+    def _iomega_kernel(self):
+        """the IOmegaKernel of a Matsubara problem (also inside a PreblurKernel), else None"""
+        K = self.K
+        K = getattr(K, 'kernel', K)
+        return K if isinstance(K, kernels.IOmegaKernel) else None
+
+    def _use_tau_kernel(self, tau):
+        """after Matsubara data: a TauKernel on ``tau`` again (same omega mesh and SVD backend)"""
+        if self._iomega_kernel() is not None:
+            self.K = kernels.TauKernel(np.asarray(tau, dtype=float), self.omega, svd_backend=self.K.svd_backend)
+
+    def _use_iomega_kernel(self, iomega, beta=None):
+        """an IOmegaKernel on ``iomega`` (same omega mesh and SVD backend); one that is there already -- also inside
+        a PreblurKernel -- is refilled only when the grid changes"""
+        K = self._iomega_kernel()
+        if K is not None:
+            self.tau = iomega
+            K.beta = beta
+        else:
+            self.K = kernels.IOmegaKernel(np.array(iomega, dtype=float), self.omega, beta=beta,
+                                          svd_backend=self.K.svd_backend)
+
     def set_G_tau_data(self, tau, G_tau):
         """G(tau) from arrays (reference tau_maxent.py:181-196)"""
         if len(tau) != len(G_tau):
             raise AssertionError("tau and G_tau don't have the same dimension")
+        self._use_tau_kernel(tau)
         self.tau, self.G = tau, G_tau
+        self._adopt_data()
+
+    def set_G_iw_data(self, iomega, G_iw, beta=None):
+        """G(i omega_n) from arrays: ``iomega`` the real Matsubara frequencies omega_n, ``G_iw`` the complex data
+        there; ``beta`` defaults to 2 pi / (omega_1 - omega_0).  The kernel becomes an :class:`IOmegaKernel` (the
+        reference's kernel, kernels.py:283-346, in its stacked real form) and ``G`` the stacked real vector
+        ``[Re G ; Im G]`` of 2 n_iw values, which ``scale_alpha='Ndata'`` counts; results give G, G_orig and G_rec
+        back as complex arrays of n_iw values.  (The reference's ``set_G_iw`` takes a TRIQS Green function and
+        Fourier-transforms it to tau first, tau_maxent.py:148-179.)"""
+        iomega = np.asarray(iomega, dtype=float)
+        G_iw = np.asarray(G_iw)
+        if iomega.ndim != 1 or G_iw.shape != iomega.shape:
+            raise AssertionError("iomega and G_iw don't have the same dimension")
+        self._use_iomega_kernel(iomega, beta)
+        self.G = self.K.unfold(G_iw)
         self._adopt_data()
 
     def set_G_tau_file(self, filename, tau_col=0, G_col=1, err_col=None):
         """G(tau), optionally with its error bar, from the columns of a text file
         (reference tau_maxent.py:198-225); a file that brings errors ends any rotation"""
         table = np.loadtxt(filename)
+        self._use_tau_kernel(table[:, tau_col])
         self.tau, self.G = table[:, tau_col], table[:, G_col]
         if err_col is not None:
             self.err = table[:, err_col]
@@ -102,11 +143,15 @@ class TauMaxEnt(object):
 
     def set_error(self, error):
         """one standard deviation for all tau or one per tau; ends a covariance rotation
-        (reference tau_maxent.py:227-251)"""
+        (reference tau_maxent.py:227-251).  Matsubara data: a scalar, one value per frequency (for the real and the
+        imaginary part alike) or one per stacked real value (2 n_iw: the real parts', then the imaginary parts')"""
         if not np.all(np.isreal(error)):
             raise Exception('complex error supplied, only real accepted')
         sigma = np.real(error) * np.ones(np.shape(self.G)) if np.ndim(error) == 0 \
             else np.asarray(np.real(error), dtype=float)
+        K = self._iomega_kernel()
+        if K is not None and sigma.shape == (K.n_iw,) and np.shape(self.G) == (2 * K.n_iw,):
+            sigma = np.concatenate([sigma, sigma])
         if sigma.shape != np.shape(self.G):
             raise Exception('Supply scalar error or with length of G_tau.')
         self.err = sigma
