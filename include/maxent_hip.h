@@ -38,6 +38,7 @@
  *     kernels.py:53-122,244-271,384-393                    |   numpy path stays the default)
  *   IOmegaKernel fill (stacked real [Re K ; Im K])         | mxe_kernel_svd_iw (the same, for
  *     + KernelSVD.svd   kernels.py:283-346                 |   Matsubara data)
+ *   get_G_w_from_A_w  maxent_util.py:43-132                | mxe_kramers_kronig
  *   the arrays of MaxEntResult (numpy allocations)         | mxe_host_alloc / mxe_host_free (optional:
  *     maxent_result.py:835-967                             |   page-locked destinations, one DMA per fetch)
  *
@@ -465,6 +466,20 @@ int  mxe_kernel_svd_iw(int device, int n_iw, int n_omega, const double* iomega,
                        int n_b, const double* preblur_b, double threshold, int ns_max,
                        double* out_K, double* out_U, double* out_S, double* out_V,
                        int32_t* out_ns, int32_t* out_info, float* out_ms);
+
+/* ---- Kramers-Kronig: G(w) from A(w) (get_G_w_from_A_w, maxent_util.py:43-132) ---- */
+/* The broadened Cauchy / Hilbert sum, for every spectrum s and output point o:
+ *     G[s][o] = sum_j A[s][j] * weight[j] / (w_out[o] - w[j] + i eta[j])
+ * w, weight, eta: n_w; w_out: n_out; A: n_spec x n_w (real; a complex spectrum is two rows, the caller
+ * recombines them); out_G: n_spec x n_out x 2 (interleaved complex), host, row-major.  get_G_w_from_A_w
+ * passes weight = the half-width of each point's neighbourhood and eta = broadening_factor * weight.
+ * The bits of one spectrum's G do not depend on n_spec or on its place in the batch: each sum runs over
+ * j in a fixed order (slices of 256 values, added in slice order), with no atomics.  out_ms: device
+ * time of the sum (may be NULL).  MXE_ERR_ARG also when n_spec * n_out or n_spec * n_w exceed 2^31 - 1,
+ * MXE_ERR_LIMIT when n_out > 65535 * 256. */
+int  mxe_kramers_kronig(int device, int n_w, const double* w, const double* weight, const double* eta,
+                        int n_out, const double* w_out, int n_spec, const double* A,
+                        double* out_G, float* out_ms);
 
 #ifdef __cplusplus
 }

@@ -36,6 +36,10 @@ from .tau_maxent import TauMaxEnt                   # noqa: F401
 from .elementwise_maxent import (ElementwiseMaxEnt, DiagonalMaxEnt,   # noqa: F401
                                  PoormanMaxEnt, PendingRun, run_many)
 from .device import MaxEntDeviceError, device_count  # noqa: F401
+from .maxent_util import (ArrayGf, get_G_w_from_A_w, get_G_tau_from_A_w,   # noqa: F401
+                          kramers_kronig)
+from .sigma_continuator import (SigmaContinuator, InversionSigmaContinuator,   # noqa: F401
+                                DirectSigmaContinuator)
 from . import _layout as _layout        # the reference's sub-module paths (analyzers.linefit_analyzer, ...)
 _layout.register(__name__)
 

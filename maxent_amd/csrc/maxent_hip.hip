@@ -3357,3 +3357,69 @@ try {
     });
 }
 MXE_CATCH_ALL
+
+// ---- the broadened Kramers-Kronig sum of get_G_w_from_A_w (mxe_kk.hip.h) -------------------
+#include "mxe_kk.hip.h"
+
+namespace {
+template <int TS>
+void kk_launch(hipStream_t st, const mxe::KKParams& p, int n_o_tiles, bool split)
+{
+    const dim3 grid((p.n_spec + TS - 1) / TS, n_o_tiles, split ? p.n_slice : 1);
+    if (split) hipLaunchKernelGGL((mxe::kk_partial<TS, false>), grid, dim3(mxe::KK_T), 0, st, p);
+    else       hipLaunchKernelGGL((mxe::kk_partial<TS, true>), grid, dim3(mxe::KK_T), 0, st, p);
+}
+} // namespace
+
+extern "C" int mxe_kramers_kronig(int device, int n_w, const double* w, const double* weight, const double* eta,
+                                  int n_out, const double* w_out, int n_spec, const double* A,
+                                  double* out_G, float* out_ms)
+try {
+    if (n_w < 1 || n_out < 1 || n_spec < 1 || !w || !weight || !eta || !w_out || !A || !out_G) return MXE_ERR_ARG;
+    if ((int64_t)n_spec * n_out > INT32_MAX || (int64_t)n_spec * n_w > INT32_MAX) return MXE_ERR_ARG;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return MXE_ERR_NODEVICE;
+    if (device < 0 || device >= ndev) return MXE_ERR_ARG;
+    SVDCHK(hipSetDevice(device));
+    const int TS = n_spec <= 2 ? 2 : n_spec <= 8 ? 8 : 16;        // spectra per workgroup tile
+    const int n_slice = (n_w + mxe::KK_SLICE - 1) / mxe::KK_SLICE;
+    const int n_o_tiles = (n_out + mxe::KK_T - 1) / mxe::KK_T;
+    const size_t n_res = (size_t)n_spec * n_out;                  // complex values of the result
+    // few workgroups without splitting (few spectra): one workgroup per j slice, the partials added by kk_combine
+    // (the same operations in the same order as one workgroup adding them as it goes: the same bits)
+    const int64_t wgs = (int64_t)((n_spec + TS - 1) / TS) * n_o_tiles;
+    const bool split = n_slice > 1 && n_slice <= 65535 && wgs < 1024 && (int64_t)n_slice * n_res * 16 <= ((int64_t)1 << 30);
+    if (n_o_tiles > 65535) return MXE_ERR_LIMIT;                   // (the grid's y extent)
+    SvdScratch sc;
+    SVDCHK(hipStreamCreateWithFlags(&sc.stream, hipStreamNonBlocking));
+    SVDCHK(hipEventCreate(&sc.e0));
+    SVDCHK(hipEventCreate(&sc.e1));
+    double *dw, *dwt, *deta, *dwo, *dA, *dG, *dP = nullptr;
+    SVDCHK(sc.alloc(&dw, n_w)); SVDCHK(sc.alloc(&dwt, n_w)); SVDCHK(sc.alloc(&deta, n_w));
+    SVDCHK(sc.alloc(&dwo, n_out)); SVDCHK(sc.alloc(&dA, (size_t)n_spec * n_w)); SVDCHK(sc.alloc(&dG, 2 * n_res));
+    if (split) SVDCHK(sc.alloc(&dP, 2 * n_res * n_slice));
+    SVDCHK(hipMemcpyAsync(dw, w, (size_t)n_w * 8, hipMemcpyHostToDevice, sc.stream));
+    SVDCHK(hipMemcpyAsync(dwt, weight, (size_t)n_w * 8, hipMemcpyHostToDevice, sc.stream));
+    SVDCHK(hipMemcpyAsync(deta, eta, (size_t)n_w * 8, hipMemcpyHostToDevice, sc.stream));
+    SVDCHK(hipMemcpyAsync(dwo, w_out, (size_t)n_out * 8, hipMemcpyHostToDevice, sc.stream));
+    SVDCHK(hipMemcpyAsync(dA, A, (size_t)n_spec * n_w * 8, hipMemcpyHostToDevice, sc.stream));
+    SVDCHK(hipEventRecord(sc.e0, sc.stream));
+    mxe::KKParams p;
+    p.w = dw; p.weight = dwt; p.eta = deta; p.w_out = dwo; p.A = dA; p.out = split ? dP : dG;
+    p.n_w = n_w; p.n_out = n_out; p.n_spec = n_spec; p.n_slice = n_slice;
+    if (TS == 2) kk_launch<2>(sc.stream, p, n_o_tiles, split);
+    else if (TS == 8) kk_launch<8>(sc.stream, p, n_o_tiles, split);
+    else kk_launch<16>(sc.stream, p, n_o_tiles, split);
+    SVDCHK(hipGetLastError());
+    if (split) {
+        hipLaunchKernelGGL(mxe::kk_combine, dim3((unsigned)((n_res + 255) / 256)), dim3(256), 0, sc.stream,
+                           (const double2*)dP, n_slice, n_res, (double2*)dG);
+        SVDCHK(hipGetLastError());
+    }
+    SVDCHK(hipEventRecord(sc.e1, sc.stream));
+    SVDCHK(hipMemcpyAsync(out_G, dG, 2 * n_res * 8, hipMemcpyDeviceToHost, sc.stream));
+    SVDCHK(hipStreamSynchronize(sc.stream));
+    if (out_ms) SVDCHK(hipEventElapsedTime(out_ms, sc.e0, sc.e1));
+    return MXE_OK;
+}
+MXE_CATCH_ALL

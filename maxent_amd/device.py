@@ -134,6 +134,8 @@ SYMBOLS = [
                                          ctypes.c_int, _dp, ctypes.c_double,
                                          ctypes.c_int, _dp, _dp, _dp, _dp, _ip, _ip,
                                          ctypes.POINTER(ctypes.c_float)]),
+    ('mxe_kramers_kronig', ctypes.c_int, [ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, ctypes.c_int, _dp,
+                                          ctypes.c_int, _dp, _dp, ctypes.POINTER(ctypes.c_float)]),
 ]
 
 
@@ -341,6 +343,54 @@ def _kernel_svd_call(name, n_grid, grid_args, scalar_args, omega, delta, preblur
                         K=(K[ib] if want_K else None), qr_rank=int(info[ib, 0]),
                         sweeps=int(info[ib, 1]), ms=float(ms.value)))
     return out
+
+
+#: most complex values of G one ``mxe_kramers_kronig`` launch writes (1 GiB of result on the device); more spectra are
+#: split into launches of fewer
+KK_MAX_VALUES = 1 << 26
+
+
+def kramers_kronig(w, weight, eta, w_out, A, device=0, max_spectra=None, timing=None):
+    """``mxe_kramers_kronig``: ``G[..., o] = sum_j A[..., j] weight[j] / (w_out[o] - w[j] + i eta[j])`` on the device.
+    ``A``: real or complex, shape ``(..., n_w)``; returns complex ``(..., n_out)``.  A complex ``A`` goes as two real
+    rows (its real and its imaginary part), recombined as ``G(Re A) + i G(Im A)``.  The spectra go in launches of at
+    most ``max_spectra`` rows (default: as many as keep a launch's result within ``KK_MAX_VALUES``); the bits of a
+    spectrum's G do not depend on the launch it is in.  ``timing``: a dict that receives the device time ``ms`` of the
+    sums (all launches) and the number of ``launches``."""
+    lib = load_library()
+    if device_count() < 1:
+        raise MaxEntDeviceError('no HIP device visible; the Kramers-Kronig transform has no CPU fallback')
+    w, weight, eta, w_out = (_c(np.ravel(a)) for a in (w, weight, eta, w_out))
+    A = np.asarray(A)
+    n_w, n_out = len(w), len(w_out)
+    if A.ndim < 1 or A.shape[-1] != n_w or len(weight) != n_w or len(eta) != n_w or n_out < 1 or n_w < 1:
+        raise ValueError('kramers_kronig: A (..., n_w) = %s, weight and eta of n_w = %d values, w_out not empty'
+                         % (A.shape, n_w))
+    lead = A.shape[:-1]
+    is_complex = np.iscomplexobj(A)
+    rows = A.reshape(-1, n_w)
+    rows = _c(np.stack([rows.real, rows.imag], axis=1).reshape(-1, n_w)) if is_complex else _c(rows)
+    cap = max(1, min(KK_MAX_VALUES // n_out, (2 ** 31 - 1) // max(n_out, n_w)))
+    if max_spectra is not None:
+        cap = max(1, min(cap, int(max_spectra)))
+    G = np.empty((rows.shape[0], n_out), dtype=complex)
+    ms_total, launches = 0.0, 0
+    for r0 in range(0, rows.shape[0], cap):
+        part = rows[r0:r0 + cap]
+        out = G[r0:r0 + len(part)]            # (a C-contiguous slice of rows: the library writes it in place)
+        ms = ctypes.c_float(0)
+        rc = lib.mxe_kramers_kronig(int(device), n_w, _p(w), _p(weight), _p(eta), n_out, _p(w_out), len(part),
+                                    _p(part), out.ctypes.data_as(_dp), ctypes.byref(ms))
+        if rc != 0:
+            raise MaxEntDeviceError('mxe_kramers_kronig failed: ' + lib.mxe_strerror(rc).decode())
+        ms_total += float(ms.value)
+        launches += 1
+    if timing is not None:
+        timing['ms'] = ms_total
+        timing['launches'] = launches
+    if is_complex:
+        G = G[0::2] + 1j * G[1::2]
+    return G.reshape(lead + (n_out,))
 
 
 def entropy(kind, H, D, device=0):
