@@ -38,7 +38,11 @@
  *     kernels.py:53-122,244-271,384-393                    |   numpy path stays the default)
  *   IOmegaKernel fill (stacked real [Re K ; Im K])         | mxe_kernel_svd_iw (the same, for
  *     + KernelSVD.svd   kernels.py:283-346                 |   Matsubara data)
- *   get_G_w_from_A_w  maxent_util.py:43-132                | mxe_kramers_kronig
+ *   BosonicTauKernel / BosonicIOmegaKernel fill + SVD      | mxe_kernel_svd_boson / mxe_kernel_svd_boson_iw
+ *     (chi(tau), chi(i nu_n); not in the reference)        |
+ *   DataKernel (a caller's matrix) + KernelSVD.svd         | mxe_kernel_svd_data
+ *     kernels.py:183-207                                   |
+ *   get_G_w_from_A_w  maxent_util.py:43-132                | mxe_kramers_kronig (also get_chi_w_from_A_w)
  *   the arrays of MaxEntResult (numpy allocations)         | mxe_host_alloc / mxe_host_free (optional:
  *     maxent_result.py:835-967                             |   page-locked destinations, one DMA per fetch)
  *
@@ -466,6 +470,38 @@ int  mxe_kernel_svd_iw(int device, int n_iw, int n_omega, const double* iomega,
                        int n_b, const double* preblur_b, double threshold, int ns_max,
                        double* out_K, double* out_U, double* out_S, double* out_V,
                        int32_t* out_ns, int32_t* out_info, float* out_ms);
+
+/* Bosonic kernels (no counterpart in the reference), for A(w) = Im chi(w) / (pi w):
+ *   mxe_kernel_svd_boson     K(tau, w) = w e^{-tau w} / (1 - e^{-beta w}), K(tau, 0) = 1/beta, n_tau rows.
+ *       symmetric != 0: K(tau, w) + K(tau, -w) = w (e^{-tau w} + e^{-(beta - tau) w}) / (1 - e^{-beta w}) on a mesh
+ *       w >= 0 (2/beta at w = 0).  Filled without overflow on either half-axis, by a series below
+ *       |beta w| = 1e-5, and with the rounding of the arguments of exp compensated: a few ulp everywhere.
+ *   mxe_kernel_svd_boson_iw  K(i nu_n, w) = w / (w - i nu_n), 1 at w = nu_n = 0, as the stacked real matrix of
+ *       2 n_inu rows: Re K = w^2 / (w^2 + nu_n^2) above Im K = w nu_n / (w^2 + nu_n^2) (the zero row Im K(i nu_0 = 0)
+ *       is kept).  symmetric != 0: the real 2 w^2 / (w^2 + nu_n^2) of n_inu rows (2 at w = nu_n = 0).
+ * inu: the n_inu real bosonic Matsubara frequencies nu_n.  A symmetric kernel on a mesh with a negative point is
+ * MXE_ERR_ARG.  Everything else -- preblur widths, threshold, ns_max, outputs, error codes, the LDS limit on the
+ * rows -- as mxe_kernel_svd / mxe_kernel_svd_iw. */
+int  mxe_kernel_svd_boson(int device, int n_tau, int n_omega, const double* tau,
+                          const double* omega, const double* delta, double beta, int symmetric,
+                          int n_b, const double* preblur_b, double threshold, int ns_max,
+                          double* out_K, double* out_U, double* out_S, double* out_V,
+                          int32_t* out_ns, int32_t* out_info, float* out_ms);
+int  mxe_kernel_svd_boson_iw(int device, int n_inu, int n_omega, const double* inu,
+                             const double* omega, const double* delta, int symmetric,
+                             int n_b, const double* preblur_b, double threshold, int ns_max,
+                             double* out_K, double* out_U, double* out_S, double* out_V,
+                             int32_t* out_ns, int32_t* out_info, float* out_ms);
+
+/* DataKernel (reference kernels.py:183-207): the same preblur products and decomposition for a matrix the caller
+ * filled.  K: n_rows x n_omega, host, row-major; it is transposed into the column-major working layout on the
+ * device.  omega and delta serve the preblur (and are required).  Outputs as mxe_kernel_svd with n_tau -> n_rows;
+ * MXE_ERR_LIMIT also when n_rows exceed the decomposition's LDS (n_rows > 7464). */
+int  mxe_kernel_svd_data(int device, int n_rows, int n_omega, const double* K,
+                         const double* omega, const double* delta,
+                         int n_b, const double* preblur_b, double threshold, int ns_max,
+                         double* out_K, double* out_U, double* out_S, double* out_V,
+                         int32_t* out_ns, int32_t* out_info, float* out_ms);
 
 /* ---- Kramers-Kronig: G(w) from A(w) (get_G_w_from_A_w, maxent_util.py:43-132) ---- */
 /* The broadened Cauchy / Hilbert sum, for every spectrum s and output point o:

@@ -3243,8 +3243,9 @@ MXE_CATCH_ALL
 
 
 namespace {
-// mxe_kernel_svd / mxe_kernel_svd_iw after their argument checks: ``fill(stream, dgrid, domega, dKt)`` writes the
-// unblurred K^T (n_omega columns of m_rows values) from the row grid (n_grid values: tau, or iomega); the preblur
+// mxe_kernel_svd and its siblings after their argument checks: ``fill(stream, dgrid, domega, dKt)`` writes the
+// unblurred K^T (n_omega columns of m_rows values) from the row grid (n_grid values: tau, iomega, or the rows of a
+// caller's matrix); the preblur
 // stages, the decomposition and the copy-out are the same for every kernel
 template <class Fill>
 int kernel_svd_common(int device, int n_grid, int m_rows, int n_omega, const double* grid, const double* omega,
@@ -3354,6 +3355,70 @@ try {
                              [=](hipStream_t st, const double* diw, const double* dom, double* dKt0) {
         const int nel = n_iw * n_omega;
         hipLaunchKernelGGL(mxe::iomega_kernel_fill, dim3((nel + 255) / 256), dim3(256), 0, st, diw, dom, n_iw, n_omega, dKt0);
+    });
+}
+MXE_CATCH_ALL
+
+// BosonicTauKernel: K(tau, w) = w e^{-tau w} / (1 - e^{-beta w}); symmetric != 0: K(tau, w) + K(tau, -w) on w >= 0
+extern "C" int mxe_kernel_svd_boson(int device, int n_tau, int n_omega, const double* tau, const double* omega,
+                                    const double* delta, double beta, int symmetric, int n_b, const double* preblur_b,
+                                    double threshold, int ns_max, double* out_K, double* out_U, double* out_S,
+                                    double* out_V, int32_t* out_ns, int32_t* out_info, float* out_ms)
+try {
+    if (n_tau < 1 || n_omega < 1 || n_b < 1 || !tau || !omega || !delta || !preblur_b || !out_U || !out_S ||
+        !out_V || !out_ns || ns_max < 1 || ns_max > mxe::SVD_RCAP || !(threshold >= 0.0) || !(beta > 0.0) ||
+        n_tau > (1 << 30) / n_omega) return MXE_ERR_ARG;
+    if (symmetric)
+        for (int j = 0; j < n_omega; ++j) if (!(omega[j] >= 0.0)) return MXE_ERR_ARG;
+    return kernel_svd_common(device, n_tau, n_tau, n_omega, tau, omega, delta, n_b, preblur_b, threshold, ns_max,
+                             out_K, out_U, out_S, out_V, out_ns, out_info, out_ms,
+                             [=](hipStream_t st, const double* dtau, const double* dom, double* dKt0) {
+        const int nel = n_tau * n_omega;
+        hipLaunchKernelGGL(mxe::boson_tau_kernel_fill, dim3((nel + 255) / 256), dim3(256), 0, st, dtau, dom, beta,
+                           symmetric ? 1 : 0, n_tau, n_omega, dKt0);
+    });
+}
+MXE_CATCH_ALL
+
+// BosonicIOmegaKernel: K(i nu_n, w) = w / (w - i nu_n), stacked real of 2 n_inu rows; symmetric != 0: the real
+// 2 w^2 / (w^2 + nu_n^2) of n_inu rows on w >= 0
+extern "C" int mxe_kernel_svd_boson_iw(int device, int n_inu, int n_omega, const double* inu, const double* omega,
+                                       const double* delta, int symmetric, int n_b, const double* preblur_b,
+                                       double threshold, int ns_max, double* out_K, double* out_U, double* out_S,
+                                       double* out_V, int32_t* out_ns, int32_t* out_info, float* out_ms)
+try {
+    if (n_inu < 1 || n_omega < 1 || n_b < 1 || !inu || !omega || !delta || !preblur_b || !out_U || !out_S ||
+        !out_V || !out_ns || ns_max < 1 || ns_max > mxe::SVD_RCAP || !(threshold >= 0.0) ||
+        n_inu > (1 << 29) / n_omega) return MXE_ERR_ARG;
+    if (symmetric)
+        for (int j = 0; j < n_omega; ++j) if (!(omega[j] >= 0.0)) return MXE_ERR_ARG;
+    return kernel_svd_common(device, n_inu, symmetric ? n_inu : 2 * n_inu, n_omega, inu, omega, delta, n_b, preblur_b,
+                             threshold, ns_max, out_K, out_U, out_S, out_V, out_ns, out_info, out_ms,
+                             [=](hipStream_t st, const double* dnu, const double* dom, double* dKt0) {
+        const int nel = n_inu * n_omega;
+        hipLaunchKernelGGL(mxe::boson_iomega_kernel_fill, dim3((nel + 255) / 256), dim3(256), 0, st, dnu, dom,
+                           symmetric ? 1 : 0, n_inu, n_omega, dKt0);
+    });
+}
+MXE_CATCH_ALL
+
+// DataKernel: the decomposition (and the preblur products) of a matrix the caller filled; K: n_rows x n_omega, host,
+// row-major.  It travels as the "row grid" of kernel_svd_common, and the fill is its transposition on the device.
+extern "C" int mxe_kernel_svd_data(int device, int n_rows, int n_omega, const double* K, const double* omega,
+                                   const double* delta, int n_b, const double* preblur_b, double threshold, int ns_max,
+                                   double* out_K, double* out_U, double* out_S, double* out_V, int32_t* out_ns,
+                                   int32_t* out_info, float* out_ms)
+try {
+    if (n_rows < 1 || n_omega < 1 || n_b < 1 || !K || !omega || !delta || !preblur_b || !out_U || !out_S ||
+        !out_V || !out_ns || ns_max < 1 || ns_max > mxe::SVD_RCAP || !(threshold >= 0.0) ||
+        n_rows > (1 << 30) / n_omega) return MXE_ERR_ARG;
+    // (before the matrix is copied: kernel_svd_common would refuse the same rows after its own check)
+    if (((size_t)n_rows + 16 + 8 + mxe::SVD_RCAP + mxe::SVD_RCAP / 2) * sizeof(double) > 60 * 1024) return MXE_ERR_LIMIT;
+    return kernel_svd_common(device, n_rows * n_omega, n_rows, n_omega, K, omega, delta, n_b, preblur_b, threshold,
+                             ns_max, out_K, out_U, out_S, out_V, out_ns, out_info, out_ms,
+                             [=](hipStream_t st, const double* dK, const double*, double* dKt0) {
+        hipLaunchKernelGGL(mxe::data_kernel_transpose, dim3((n_omega + 31) / 32, (n_rows + 31) / 32), dim3(32, 8), 0, st,
+                           dK, n_rows, n_omega, dKt0);
     });
 }
 MXE_CATCH_ALL

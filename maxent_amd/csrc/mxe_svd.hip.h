@@ -2,6 +2,8 @@
 //
 //   TauKernel._fill_values      kernels.py:244-271   -> tau_kernel_fill
 //   IOmegaKernel._fill_values   kernels.py:312-331   -> iomega_kernel_fill  (stacked real [Re K ; Im K])
+//   BosonicTauKernel, BosonicIOmegaKernel (no counterpart in the reference) -> boson_tau_kernel_fill, boson_iomega_kernel_fill
+//   DataKernel (a caller's matrix)  kernels.py:183-207 -> data_kernel_transpose
 //   get_preblur                 preblur.py:31-58     -> preblur_rows / preblur_cols / preblur_matrix
 //   PreblurKernel._fill_values  kernels.py:384-393   -> preblur_product   (K' = K diag(delta) B)
 //   KernelSVD.svd + reduce_singular_space kernels.py:53-122 -> svd_kernel
@@ -64,6 +66,110 @@ void iomega_kernel_fill(const double* __restrict__ iomega, const double* __restr
     double* col = Kt + (size_t)j * 2 * n_iw;
     col[i] = -w / d;
     col[n_iw + i] = -wn / d;
+}
+
+// exp(a * b) with the rounding of the product given back: p = fl(a b), e = a b - p exactly (one fma), and
+// exp(p + e) = exp(p) (1 + e) to first order in e (|e| <= ulp(p) / 2).  The error of the result is then a few ulp
+// whatever the size of the argument; a plain exp(a * b) is off by |a b| 2^-53 relative.  ``extra``: a further small
+// addend of the argument (the rounding of beta - tau times omega).
+__device__ __forceinline__ double exp_of_product(double a, double b, double extra)
+{
+    const double p = a * b;
+    const double e = fma(a, b, -p) + extra;
+    const double x = exp(p);
+    return fma(x, e, x);
+}
+
+// Series cut of the bosonic tau kernel: below |beta omega| = BOSON_SERIES_CUT the factor (beta omega) / (1 - e^{-beta omega})
+// is 1 + x/2 + x^2/12 (next term x^4/720 < 2e-23); this also covers omega = 0 exactly (K = 1/beta) and products
+// beta omega that underflow.
+constexpr double BOSON_SERIES_CUT = 1.0e-5;
+
+// K^T[j][i] of BosonicTauKernel, K(tau, omega) = omega e^{-tau omega} / (1 - e^{-beta omega}), K(tau, 0) = 1/beta,
+// column-major like tau_kernel_fill.  The branches of the host fill (kernels.py, BosonicTauKernel._fill_values):
+//   |beta omega| < cut : (1/beta) (1 + x/2 + x^2/12) e^{-tau omega}
+//   omega > 0          : omega e^{-tau omega} / (-expm1(-beta omega))
+//   omega < 0          : omega e^{(beta - tau) omega} / expm1(beta omega)       (no overflow on either half-axis)
+// symmetric (omega >= 0 only): K(tau, omega) + K(tau, -omega)
+//   = omega (e^{-tau omega} + e^{-(beta - tau) omega}) / (-expm1(-beta omega)),  2/beta at omega = 0.
+__global__ __launch_bounds__(256)
+void boson_tau_kernel_fill(const double* __restrict__ tau, const double* __restrict__ omega, double beta,
+                           int symmetric, int n_tau, int n_omega, double* __restrict__ Kt)
+{
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= n_tau * n_omega) return;
+    const int j = idx / n_tau, i = idx - j * n_tau;
+    const double w = omega[j], t = tau[i];
+    const double x = beta * w;
+    // beta - tau = bt + bt_lo exactly (two-sum)
+    const double bt = beta - t;
+    const double bb = bt - beta;
+    const double bt_lo = (beta - (bt - bb)) + (-t - bb);
+    double val;
+    if (fabs(x) < BOSON_SERIES_CUT) {
+        const double ep = exp_of_product(-t, w, 0.0);
+        const double sp = 1.0 + 0.5 * x + x * x / 12.0;
+        if (symmetric) {
+            const double em = exp_of_product(t, w, 0.0);
+            const double sn = 1.0 - 0.5 * x + x * x / 12.0;
+            val = sp * ep / beta + sn * em / beta;
+        } else {
+            val = sp * ep / beta;
+        }
+    } else if (symmetric) {
+        const double ep = exp_of_product(-t, w, 0.0);
+        const double em = exp_of_product(-bt, w, -bt_lo * w);
+        val = w * (ep + em) / (-expm1(-x));
+    } else if (w > 0.0) {
+        val = w * exp_of_product(-t, w, 0.0) / (-expm1(-x));
+    } else {
+        val = w * exp_of_product(bt, w, bt_lo * w) / expm1(x);
+    }
+    Kt[idx] = val;
+}
+
+// K^T of BosonicIOmegaKernel, K(i nu_n, w) = w / (w - i nu_n) = (w^2 + i w nu_n) / (w^2 + nu_n^2), 1 at w = nu_n = 0.
+// Stacked (symmetric = 0): 2 n_inu rows, Re K = w^2 / d above Im K = w nu_n / d, both from ONE d = nu_n^2 + w^2 with
+// contraction off (the host's rounding, bit for bit), as iomega_kernel_fill.  symmetric: n_inu rows of
+// K(i nu_n, w) + K(i nu_n, -w) = 2 w^2 / d (real; 2 at w = nu_n = 0).
+__global__ __launch_bounds__(256)
+void boson_iomega_kernel_fill(const double* __restrict__ inu, const double* __restrict__ omega, int symmetric,
+                              int n_inu, int n_omega, double* __restrict__ Kt)
+{
+#pragma clang fp contract(off)
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= n_inu * n_omega) return;
+    const int j = idx / n_inu, i = idx - j * n_inu;
+    const double w = omega[j], nu = inu[i];
+    const double w2 = w * w;
+    const double d = nu * nu + w2;
+    const bool origin = !(d > 0.0);                 // (w = nu_n = 0, or both squares underflow)
+    if (symmetric) {
+        Kt[(size_t)j * n_inu + i] = origin ? 2.0 : 2.0 * w2 / d;
+    } else {
+        double* col = Kt + (size_t)j * 2 * n_inu;
+        col[i] = origin ? 1.0 : w2 / d;
+        col[n_inu + i] = origin ? 0.0 : w * nu / d;
+    }
+}
+
+// K^T[j][i] = K[i][j]: a caller-supplied matrix (row-major, n_rows x n_omega) into the column-major working layout of
+// the decomposition (mxe_kernel_svd_data).  32 x 32 tiles through the LDS (33 columns: no bank conflicts), reads and
+// writes both along the fast index; grid = (ceil(n_omega / 32), ceil(n_rows / 32)), block = (32, 8).
+__global__ __launch_bounds__(256)
+void data_kernel_transpose(const double* __restrict__ K, int n_rows, int n_omega, double* __restrict__ Kt)
+{
+    __shared__ double tile[32][33];
+    const int j0 = blockIdx.x * 32, i0 = blockIdx.y * 32;
+    for (int r = threadIdx.y; r < 32; r += 8) {
+        const int i = i0 + r, j = j0 + threadIdx.x;
+        if (i < n_rows && j < n_omega) tile[r][threadIdx.x] = K[(size_t)i * n_omega + j];
+    }
+    __syncthreads();
+    for (int r = threadIdx.y; r < 32; r += 8) {
+        const int j = j0 + r, i = i0 + threadIdx.x;
+        if (i < n_rows && j < n_omega) Kt[(size_t)j * n_rows + i] = tile[threadIdx.x][r];
+    }
 }
 
 __device__ __forceinline__ double gauss_blur(double wi, double wj, double b)

@@ -134,6 +134,18 @@ SYMBOLS = [
                                          ctypes.c_int, _dp, ctypes.c_double,
                                          ctypes.c_int, _dp, _dp, _dp, _dp, _ip, _ip,
                                          ctypes.POINTER(ctypes.c_float)]),
+    ('mxe_kernel_svd_boson', ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp,
+                                            ctypes.c_double, ctypes.c_int, ctypes.c_int, _dp, ctypes.c_double,
+                                            ctypes.c_int, _dp, _dp, _dp, _dp, _ip, _ip,
+                                            ctypes.POINTER(ctypes.c_float)]),
+    ('mxe_kernel_svd_boson_iw', ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp,
+                                               ctypes.c_int, ctypes.c_int, _dp, ctypes.c_double,
+                                               ctypes.c_int, _dp, _dp, _dp, _dp, _ip, _ip,
+                                               ctypes.POINTER(ctypes.c_float)]),
+    ('mxe_kernel_svd_data', ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp,
+                                           ctypes.c_int, _dp, ctypes.c_double,
+                                           ctypes.c_int, _dp, _dp, _dp, _dp, _ip, _ip,
+                                           ctypes.POINTER(ctypes.c_float)]),
     ('mxe_kramers_kronig', ctypes.c_int, [ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, ctypes.c_int, _dp,
                                           ctypes.c_int, _dp, _dp, ctypes.POINTER(ctypes.c_float)]),
 ]
@@ -313,6 +325,46 @@ def kernel_svd_iw(iomega, omega, delta, preblur_b=(0.0,), threshold=1.e-14, ns_m
     iomega, omega, delta = _c(iomega), _c(omega), _c(delta)
     return _kernel_svd_call('mxe_kernel_svd_iw', len(iomega), (_p(iomega),), (), omega, delta, preblur_b,
                             threshold, ns_max, want_K, device, n_rows=2 * len(iomega))
+
+
+def kernel_svd_boson(tau, omega, delta, beta, symmetric=False, preblur_b=(0.0,), threshold=1.e-14, ns_max=128,
+                     want_K=False, device=0):
+    """``mxe_kernel_svd_boson``: BosonicTauKernel (``symmetric``: its half-axis form) and its PreblurKernels filled
+    and decomposed on the device; returns what :func:`kernel_svd` returns."""
+    load_library()
+    if device_count() < 1:
+        raise MaxEntDeviceError('no HIP device visible; the device SVD has no CPU fallback')
+    tau, omega, delta = _c(tau), _c(omega), _c(delta)
+    return _kernel_svd_call('mxe_kernel_svd_boson', len(tau), (_p(tau),), (float(beta), 1 if symmetric else 0), omega,
+                            delta, preblur_b, threshold, ns_max, want_K, device)
+
+
+def kernel_svd_boson_iw(inu, omega, delta, symmetric=False, preblur_b=(0.0,), threshold=1.e-14, ns_max=128,
+                        want_K=False, device=0):
+    """``mxe_kernel_svd_boson_iw``: BosonicIOmegaKernel -- stacked real of 2 n rows, or with ``symmetric`` the real
+    half-axis form of n rows -- and its PreblurKernels filled and decomposed on the device; returns what
+    :func:`kernel_svd` returns.  Too many rows for the decomposition's LDS: as :func:`kernel_svd_iw`."""
+    load_library()
+    if device_count() < 1:
+        raise MaxEntDeviceError('no HIP device visible; the device SVD has no CPU fallback')
+    inu, omega, delta = _c(inu), _c(omega), _c(delta)
+    return _kernel_svd_call('mxe_kernel_svd_boson_iw', len(inu), (_p(inu),), (1 if symmetric else 0,), omega, delta,
+                            preblur_b, threshold, ns_max, want_K, device,
+                            n_rows=len(inu) if symmetric else 2 * len(inu))
+
+
+def kernel_svd_data(K, omega, delta, preblur_b=(0.0,), threshold=1.e-14, ns_max=128, want_K=False, device=0):
+    """``mxe_kernel_svd_data``: the decomposition (and the preblur products, one per entry of ``preblur_b`` > 0) of a
+    matrix the caller filled, ``K`` of shape (n_rows, n_omega); returns what :func:`kernel_svd` returns.  More rows
+    than the decomposition's LDS holds (``SVD_MAX_ROWS``) raise :class:`MaxEntDeviceError` -- the host SVD takes them."""
+    load_library()
+    if device_count() < 1:
+        raise MaxEntDeviceError('no HIP device visible; the device SVD has no CPU fallback')
+    K, omega, delta = _c(K), _c(omega), _c(delta)
+    if K.ndim != 2 or K.shape[1] != len(omega) or len(delta) != len(omega):
+        raise ValueError('kernel_svd_data: K (n_rows, n_omega) = %s on an omega mesh of %d points' % (K.shape, len(omega)))
+    return _kernel_svd_call('mxe_kernel_svd_data', K.shape[0], (_p(K),), (), omega, delta, preblur_b, threshold, ns_max,
+                            want_K, device)
 
 
 def _kernel_svd_call(name, n_grid, grid_args, scalar_args, omega, delta, preblur_b, threshold, ns_max, want_K, device,

@@ -692,8 +692,11 @@ class ElementwiseMaxEnt(object):
         omega, beta, no preblur on one side only) the second takes the SVD of the first instead of
         repeating it"""
         a, b = self.maxent_diagonal.K, self.maxent_offdiagonal.K
-        if a is b or type(a) is not type(b) or not isinstance(a, (kernels.TauKernel, kernels.IOmegaKernel)) or \
-                a.rotation is not None or b.rotation is not None:
+        if a is b or type(a) is not type(b) or \
+                not isinstance(a, (kernels.TauKernel, kernels.IOmegaKernel, kernels.BosonicTauKernel,
+                                   kernels.BosonicIOmegaKernel)) or \
+                a.rotation is not None or b.rotation is not None or \
+                getattr(a, 'symmetric', None) != getattr(b, 'symmetric', None):
             return
         try:
             same = (np.array_equal(np.asarray(a.data_variable), np.asarray(b.data_variable)) and
@@ -876,6 +879,51 @@ class ElementwiseMaxEnt(object):
         self.set_G((iomega, stacked), feed, lambda G_mat: G_mat[1].shape[:2])
         object.__setattr__(self, '_array_input', True)
         object.__setattr__(self, '_n_iw', n)
+
+    def set_chi_tau_data(self, tau, chi, beta=None, symmetric=False):
+        """``chi``: (M, N, T) array of bosonic chi_ij(tau) (:meth:`TauMaxEnt.set_chi_tau_data`); the real part of an
+        element is continued to Re A_ij, with ``use_complex`` the imaginary part to Im A_ij, as for G(tau)."""
+        tau = np.asarray(tau, dtype=float)
+        chi = np.asarray(chi)
+        if chi.ndim != 3 or chi.shape[2] != len(tau):
+            raise AssertionError('chi must be (M, N, n_tau) with n_tau = len(tau)')
+
+        def feed(maxent, G_mat, elem, re):
+            g = G_mat[1][elem]
+            maxent.set_chi_tau_data(G_mat[0], np.real(g) if re else np.imag(g), beta, symmetric)
+        for worker in (self.maxent_diagonal, self.maxent_offdiagonal):
+            worker._use_bosonic_kernel(kernels.BosonicTauKernel, tau, beta, symmetric)
+        self.set_G((tau, chi), feed, lambda G_mat: G_mat[1].shape[:2])
+        object.__setattr__(self, '_array_input', True)
+
+    def set_chi_iw_data(self, inu, chi_iw, beta=None, symmetric=False):
+        """``chi_iw``: complex (M, M, n) array of bosonic chi_ij(i nu_n) (:meth:`TauMaxEnt.set_chi_iw_data`).  The
+        hermitian split of :meth:`set_G_iw_data` applies: (chi_ij + chi_ji) / 2 = K Re A_ij and
+        (chi_ij - chi_ji) / (2i) = K Im A_ij (the latter with ``use_complex``).  ``symmetric``: the real parts of
+        these (n values per element) are the data of the real half-axis kernel."""
+        inu = np.asarray(inu, dtype=float)
+        chi_iw = np.asarray(chi_iw)
+        if chi_iw.ndim != 3 or chi_iw.shape[0] != chi_iw.shape[1] or chi_iw.shape[2] != len(inu):
+            raise AssertionError('chi_iw must be (M, M, n) with n = len(inu)')
+        Gt = chi_iw.transpose(1, 0, 2)
+        re_part = 0.5 * (chi_iw + Gt)               # K Re A_ij
+        im_part = (chi_iw - Gt) / 2j                # K Im A_ij
+        n = len(inu)
+        if symmetric:
+            data = re_part.real + 1j * im_part.real
+        else:
+            data = np.concatenate([re_part.real, re_part.imag], axis=-1) + \
+                1j * np.concatenate([im_part.real, im_part.imag], axis=-1)
+
+        def feed(maxent, G_mat, elem, re):
+            x = G_mat[1][elem]
+            x = np.real(x) if re else np.imag(x)
+            maxent.set_chi_iw_data(G_mat[0], x if symmetric else x[:n] + 1j * x[n:], beta, symmetric)
+        for worker in (self.maxent_diagonal, self.maxent_offdiagonal):
+            worker._use_bosonic_kernel(kernels.BosonicIOmegaKernel, inu, beta, symmetric)
+        self.set_G((inu, data), feed, lambda G_mat: G_mat[1].shape[:2])
+        object.__setattr__(self, '_array_input', True)
+        object.__setattr__(self, '_n_iw', None if symmetric else n)
 
     def set_G_tau_filename_pattern(self, filename, dimension, tau_col=0,
                                    G_col_re=1, G_col_im=2, *args, **kwargs):

@@ -5,7 +5,8 @@ filled and decomposed once on the host with numpy/LAPACK; the truncated
 factors ``U, S, V`` are what :class:`maxent_amd.device.DeviceContext` stages
 in HBM.  Public names and semantics follow the reference's ``kernels`` module
 (reference python/kernels.py:37-413): ``KernelSVD``, ``Kernel``,
-``DataKernel``, ``TauKernel``, ``IOmegaKernel``, ``PreblurKernel``.
+``DataKernel``, ``TauKernel``, ``IOmegaKernel``, ``PreblurKernel``.  ``BosonicTauKernel`` and
+``BosonicIOmegaKernel`` (susceptibilities: chi(tau), chi(i nu_n)) have no counterpart there.
 """
 
 import numpy as np
@@ -93,9 +94,9 @@ class KernelSVD(object):
     """
 
     #: 'host' (numpy / LAPACK, the reference's path) or 'device'
-    #: (``mxe_kernel_svd`` / ``mxe_kernel_svd_iw``: fill, preblur product and a preconditioned
-    #: one-sided Jacobi SVD on the GPU; kernels that know how they are filled -- TauKernel,
-    #: IOmegaKernel, a PreblurKernel of either -- implement ``_device_svd``)
+    #: (``mxe_kernel_svd`` and its siblings: fill, preblur product and a preconditioned
+    #: one-sided Jacobi SVD on the GPU; every kernel of this module implements ``_device_svd`` --
+    #: the ones that know how they are filled are filled there, a DataKernel's matrix is sent)
     svd_backend = 'host'
 
     def __init__(self, K=None):
@@ -107,8 +108,8 @@ class KernelSVD(object):
         self._U = self._S = self._V = None
 
     def _device_svd(self):
-        raise NotImplementedError('svd_backend="device" needs a kernel that can be '
-                                  'filled on the device (TauKernel, PreblurKernel)')
+        raise NotImplementedError('svd_backend="device" needs a Kernel of this module '
+                                  '(a bare KernelSVD has no omega mesh)')
 
     def svd(self):
         if self._U is None:
@@ -228,16 +229,28 @@ class Kernel(KernelSVD):
 class DataKernel(Kernel):
     """Kernel given as a matrix (reference kernels.py:183-207)."""
 
-    def __init__(self, data_variable, omega, K):
+    def __init__(self, data_variable, omega, K, svd_backend='host'):
         super(DataKernel, self).__init__()
         self._data_variable = data_variable
         self.omega = omega
         self._K = K
         self._K_delta = K * omega.delta[np.newaxis, :]
+        self.svd_backend = svd_backend
 
     @property
     def data_variable(self):
         return self._data_variable
+
+    def _device_svd(self, preblur_b=0.0):
+        """U, S, V of the matrix as it stands (``mxe_kernel_svd_data``); with ``preblur_b`` > 0, of the UNROTATED
+        blurred matrix -- the blur acts from the right, so the rotation is taken off the rows first"""
+        from . import device
+        K = np.asarray(self._K, dtype=float)
+        if preblur_b > 0.0 and self._T is not None:
+            K = np.dot(self._T.conjugate().transpose(), K)
+        r = device.kernel_svd_data(K, np.asarray(self.omega, dtype=float), self.omega.delta, [preblur_b],
+                                   threshold=0.0)[0]
+        return r['U'], r['S'], r['V']
 
 
 class TauKernel(Kernel):
@@ -399,6 +412,237 @@ class IOmegaKernel(Kernel):
         self.iomega = value
 
 
+def _exp_of_product(a, b, extra=0.0):
+    """``exp(a * b)`` with the rounding of the product given back: p = fl(a b), e = a b - p exactly (Dekker's product
+    of Veltkamp halves), exp(p + e + extra) = exp(p) (1 + e + extra) to first order.  A plain ``exp(a * b)`` is off by
+    |a b| 2^-53 relative -- 4e-14 at tau omega = 400; this is a few ulp whatever the argument."""
+    a, b = np.broadcast_arrays(np.asarray(a, dtype=float), np.asarray(b, dtype=float))
+    p = a * b
+    ca, cb = 134217729.0 * a, 134217729.0 * b
+    ah = ca - (ca - a)
+    bh = cb - (cb - b)
+    al, bl = a - ah, b - bh
+    e = ((ah * bh - p) + ah * bl + al * bh) + al * bl
+    x = np.exp(p)
+    return x + x * (e + extra)
+
+
+def _require_half_axis(omega, name):
+    if np.any(np.asarray(omega, dtype=float) < 0.0):
+        raise ValueError('%s(symmetric=True) needs a mesh on omega >= 0: A(omega) = A(-omega) is continued on the '
+                         'half-axis' % name)
+
+
+#: below |beta omega| = this the factor beta omega / (1 - e^{-beta omega}) of the bosonic tau kernel is its series
+#: 1 + x/2 + x^2/12 (next term x^4/720 < 2e-23); it covers omega = 0 exactly and products that underflow
+BOSON_SERIES_CUT = 1.0e-5
+
+
+class BosonicTauKernel(Kernel):
+    r"""Bosonic imaginary-time kernel for :math:`A(\omega) = \mathrm{Im}\,\chi(\omega)/(\pi\omega)`:
+    :math:`\chi(\tau) = \int d\omega\, K(\tau,\omega) A(\omega)`,
+
+    .. math:: K(\tau,\omega) = \frac{\omega e^{-\tau\omega}}{1 - e^{-\beta\omega}}, \quad K(\tau, 0) = 1/\beta
+
+    (positive: no sign as in the fermionic :class:`TauKernel`).  ``symmetric=True``: :math:`A(\omega) = A(-\omega)`
+    on a mesh :math:`\omega \ge 0`, :math:`K_s(\tau,\omega) = K(\tau,\omega) + K(\tau,-\omega)`, 2/beta at 0.
+    ``beta`` defaults to ``tau[-1]``.  Not in the reference (its FAQ anticipates it).
+
+    The fill has no overflow on either half-axis (:math:`e^{-(\beta-\tau)|\omega|}` for negative omega), uses
+    ``expm1`` for the denominator and a short series below ``BOSON_SERIES_CUT``, and compensates the rounding of the
+    arguments of ``exp``: every entry is good to a few ulp."""
+
+    def __init__(self, tau, omega, beta=None, symmetric=False, svd_backend='host'):
+        super(BosonicTauKernel, self).__init__()
+        self.tau = tau
+        self.omega = omega
+        self.beta = beta
+        self.symmetric = bool(symmetric)
+        self.svd_backend = svd_backend
+        self._fill_values()
+
+    def _device_args(self):
+        tau = np.asarray(self.tau, dtype=float)
+        beta = tau[-1] if self.beta is None else self.beta
+        return tau, np.asarray(self.omega, dtype=float), self.omega.delta, beta
+
+    def _device_svd(self, preblur_b=0.0):
+        """U, S, V of the UNROTATED kernel from the device (``mxe_kernel_svd_boson``); see TauKernel._device_svd"""
+        from . import device
+        tau, w, delta, beta = self._device_args()
+        r = device.kernel_svd_boson(tau, w, delta, beta, self.symmetric, [preblur_b], threshold=0.0)[0]
+        return r['U'], r['S'], r['V']
+
+    @staticmethod
+    def _values(tau, w, beta, symmetric):
+        t = tau[:, np.newaxis] * np.ones((1, len(w)))
+        ww = w[np.newaxis, :] * np.ones((len(tau), 1))
+        x = beta * ww
+        # beta - tau = bt + bt_lo exactly (two-sum)
+        bt = beta - t
+        bb = bt - beta
+        bt_lo = (beta - (bt - bb)) + (-t - bb)
+        K = np.empty(ww.shape)
+        small = np.abs(x) < BOSON_SERIES_CUT
+        s = small
+        sp = 1.0 + 0.5 * x[s] + x[s] * x[s] / 12.0
+        if symmetric:
+            sn = 1.0 - 0.5 * x[s] + x[s] * x[s] / 12.0
+            K[s] = sp * _exp_of_product(-t[s], ww[s]) / beta + sn * _exp_of_product(t[s], ww[s]) / beta
+            r = np.logical_not(small)
+            K[r] = ww[r] * (_exp_of_product(-t[r], ww[r]) + _exp_of_product(-bt[r], ww[r], -bt_lo[r] * ww[r])) / \
+                (-np.expm1(-x[r]))
+            return K
+        K[s] = sp * _exp_of_product(-t[s], ww[s]) / beta
+        # two algebraically equal forms, each overflow-free on its half-axis
+        pos = np.logical_and(np.logical_not(small), ww > 0.0)
+        K[pos] = ww[pos] * _exp_of_product(-t[pos], ww[pos]) / (-np.expm1(-x[pos]))
+        neg = np.logical_and(np.logical_not(small), ww < 0.0)
+        K[neg] = ww[neg] * _exp_of_product(bt[neg], ww[neg], bt_lo[neg] * ww[neg]) / np.expm1(x[neg])
+        return K
+
+    def _fill_values(self):
+        self._invalidate_svd()
+        tau = np.asarray(self.tau, dtype=float)
+        w = np.asarray(self.omega, dtype=float)
+        if self.symmetric:
+            _require_half_axis(w, 'BosonicTauKernel')
+        beta = float(tau[-1] if self.beta is None else self.beta)
+        delta = np.asarray(self.omega.delta, dtype=float)
+        key = ('boson_tau', self.symmetric, tau.tobytes(), w.tobytes(), delta.tobytes(), beta)
+        hit = _recent_fill.get(key, lambda _: True)               # (the key IS the contents)
+        if hit is None:
+            with np.errstate(under='ignore'):
+                K = self._values(tau, w, beta, self.symmetric)
+            hit = (_frozen(K), _frozen(K * delta[np.newaxis, :]))
+            _recent_fill.put(key, None, hit)
+        self._K, self._K_delta = hit
+        T = self._T
+        self._T = None
+        self.transform(T)
+
+    @property
+    def data_variable(self):
+        return self.tau
+
+    @data_variable.setter
+    def data_variable(self, value):
+        self.tau = value
+
+
+class BosonicIOmegaKernel(Kernel):
+    r"""Bosonic Matsubara kernel :math:`K(i\nu_n, \omega) = \omega/(\omega - i\nu_n)
+    = (\omega^2 + i\omega\nu_n)/(\omega^2 + \nu_n^2)`, 1 at :math:`\omega = \nu_n = 0`, for
+    :math:`A(\omega) = \mathrm{Im}\,\chi(\omega)/(\pi\omega)`; held like :class:`IOmegaKernel` as the stacked real
+    matrix ``[Re K ; Im K]`` of ``2 n`` rows with ``K_complex``, ``fold``, ``unfold`` (the zero row
+    Im K(i nu_0 = 0) is kept: the layout stays 2 n).  ``symmetric=True``: :math:`A(\omega) = A(-\omega)` on a mesh
+    :math:`\omega \ge 0`, the real kernel :math:`2\omega^2/(\omega^2 + \nu_n^2)` of ``n`` rows (2 at the origin) for
+    the data Re chi(i nu_n); ``fold`` / ``unfold`` are then the identity.  ``inu``: the real frequencies
+    :math:`\nu_n = 2\pi n/\beta`; ``beta`` defaults to :math:`2\pi/(\nu_1 - \nu_0)` and does not enter K."""
+
+    def __init__(self, inu, omega, beta=None, symmetric=False, svd_backend='host'):
+        super(BosonicIOmegaKernel, self).__init__()
+        self.inu = inu
+        self.omega = omega
+        self.beta = beta
+        self.symmetric = bool(symmetric)
+        self.svd_backend = svd_backend
+        self._fill_values()
+
+    @property
+    def n_iw(self):
+        return len(self.inu)
+
+    @property
+    def stacked(self):
+        """whether the rows are ``[Re K ; Im K]`` (2 n of them) and the data complex"""
+        return not self.symmetric
+
+    def get_beta(self):
+        if self._beta is None:
+            nu = np.asarray(self.inu, dtype=float)
+            return 2 * np.pi / (nu[1] - nu[0])
+        return self._beta
+
+    def set_beta(self, beta):
+        self._beta = beta
+
+    beta = property(get_beta, set_beta)
+
+    @property
+    def K_complex(self):
+        """the complex ``K`` (n x n_omega), unrotated; real-valued (but complex dtype) for a symmetric kernel"""
+        n = self.n_iw
+        if self.symmetric:
+            return self._K_plain + 0j
+        return self._K_plain[:n] + 1j * self._K_plain[n:]
+
+    def fold(self, x):
+        """``x[..., :n] + 1j x[..., n:]``: stacked real data-space values as complex chi(i nu_n); the identity for
+        a symmetric kernel"""
+        if self.symmetric:
+            return x
+        x = np.asarray(x)
+        n = self.n_iw
+        if x.shape[-1] != 2 * n:
+            raise ValueError('fold: the last axis has %d values, not 2 x %d' % (x.shape[-1], n))
+        return x[..., :n] + 1j * x[..., n:]
+
+    def unfold(self, z):
+        """complex chi(i nu_n) (last axis n) as the stacked real vector ``[Re ; Im]``; the real part for a symmetric
+        kernel, whose data are Re chi(i nu_n)"""
+        if self.symmetric:
+            return z if not np.iscomplexobj(z) else np.asarray(z).real.astype(float, copy=False)
+        z = np.asarray(z)
+        return np.concatenate([z.real, z.imag], axis=-1).astype(float, copy=False)
+
+    def _device_svd(self, preblur_b=0.0):
+        """U, S, V of the UNROTATED kernel from the device (``mxe_kernel_svd_boson_iw``); see TauKernel._device_svd"""
+        from . import device
+        r = device.kernel_svd_boson_iw(np.asarray(self.inu, dtype=float), np.asarray(self.omega, dtype=float),
+                                       self.omega.delta, self.symmetric, [preblur_b], threshold=0.0)[0]
+        return r['U'], r['S'], r['V']
+
+    def _fill_values(self):
+        self._invalidate_svd()
+        nu = np.asarray(self.inu, dtype=float)
+        w = np.asarray(self.omega, dtype=float)
+        if self.symmetric:
+            _require_half_axis(w, 'BosonicIOmegaKernel')
+        delta = np.asarray(self.omega.delta, dtype=float)
+        key = ('boson_iomega', self.symmetric, nu.tobytes(), w.tobytes(), delta.tobytes())
+        hit = _recent_fill.get(key, lambda _: True)
+        if hit is None:
+            w2 = (w * w)[np.newaxis, :]
+            d = nu[:, np.newaxis] ** 2 + w2                  # (one nu_n^2 + w^2 for both parts, as the device fill)
+            origin = np.logical_not(d > 0.0)                 # (w = nu_n = 0: K = 1)
+            with np.errstate(invalid='ignore', divide='ignore', under='ignore'):
+                if self.symmetric:
+                    K = np.where(origin, 2.0, 2.0 * w2 / d)
+                else:
+                    K = np.concatenate([np.where(origin, 1.0, w2 / d),
+                                        np.where(origin, 0.0, w[np.newaxis, :] * nu[:, np.newaxis] / d)])
+            hit = (_frozen(K), _frozen(K * delta[np.newaxis, :]))
+            _recent_fill.put(key, None, hit)
+        self._K, self._K_delta = hit
+        self._K_plain = hit[0]
+        T = self._T
+        self._T = None
+        self.transform(T)
+
+    @property
+    def data_variable(self):
+        return self.inu
+
+    @data_variable.setter
+    def data_variable(self, value):
+        self.inu = value
+
+
+#: the kernels a PreblurKernel can hand to the device: each has ``_device_svd(preblur_b)``
+_DEVICE_KERNELS = (TauKernel, IOmegaKernel, BosonicTauKernel, BosonicIOmegaKernel, DataKernel)
+
+
 class PreblurKernel(Kernel):
     """``K' = K diag(delta) B`` for the preblur formalism; ``K_delta`` stays
     un-blurred (reference kernels.py:349-413)."""
@@ -418,8 +662,8 @@ class PreblurKernel(Kernel):
         return self.kernel.unfold(x)
 
     def _device_svd(self):
-        if not isinstance(self.kernel, (TauKernel, IOmegaKernel)):
-            raise NotImplementedError('device SVD of a PreblurKernel needs a TauKernel or an IOmegaKernel inside')
+        if not isinstance(self.kernel, _DEVICE_KERNELS):
+            raise NotImplementedError('device SVD of a PreblurKernel needs a kernel of this module inside')
         U, S, V = self.kernel._device_svd(preblur_b=self._b)
         T = self.kernel._T
         return (U if T is None else np.dot(T, U)), S, V
@@ -427,12 +671,16 @@ class PreblurKernel(Kernel):
     @classmethod
     def scan(cls, K, b_values, threshold=1.e-14):
         """The kernels of a b-scan (reference doc/guide/preblur_example.py:49-56) with
-        their truncated SVDs from ONE batched device launch (``mxe_kernel_svd``)."""
+        their truncated SVDs from ONE batched device launch (``mxe_kernel_svd``, or ``mxe_kernel_svd_boson``
+        for a BosonicTauKernel)."""
         from . import device
-        if not isinstance(K, TauKernel) or K._T is not None:
-            raise NotImplementedError('PreblurKernel.scan needs an unrotated TauKernel')
+        if not isinstance(K, (TauKernel, BosonicTauKernel)) or K._T is not None:
+            raise NotImplementedError('PreblurKernel.scan needs an unrotated TauKernel or BosonicTauKernel')
         tau, w, delta, beta = K._device_args()
-        res = device.kernel_svd(tau, w, delta, beta, list(b_values), threshold=threshold)
+        if isinstance(K, BosonicTauKernel):
+            res = device.kernel_svd_boson(tau, w, delta, beta, K.symmetric, list(b_values), threshold=threshold)
+        else:
+            res = device.kernel_svd(tau, w, delta, beta, list(b_values), threshold=threshold)
         out = []
         for b, r in zip(b_values, res):
             Kb = cls(K, b, svd_backend='device')

@@ -1,5 +1,5 @@
 """Helpers around a continuation (the reference's python/maxent_util.py): G(w) from A(w) by Kramers-Kronig and
-G(tau) from A(w).
+G(tau) from A(w); chi(w) from the A(w) = Im chi(w) / (pi w) of a bosonic continuation (not in the reference).
 
 The reference returns TRIQS Green functions (``GfReFreq``, ``GfImTime``); here :class:`ArrayGf` takes their place: a
 mesh array and a data array in TRIQS's layout ``(n_points, n, n)``, so ``g.data[:, 0, 0]`` and
@@ -13,7 +13,7 @@ from . import device
 from .kernels import TauKernel
 from .omega_meshes import DataOmegaMesh
 
-__all__ = ['ArrayGf', 'get_G_w_from_A_w', 'get_G_tau_from_A_w', 'kramers_kronig']
+__all__ = ['ArrayGf', 'get_G_w_from_A_w', 'get_chi_w_from_A_w', 'get_G_tau_from_A_w', 'kramers_kronig']
 
 
 class ArrayGf(object):
@@ -58,10 +58,13 @@ def _kk_weights(w_points, broadening_factor):
     return w, delta, broadening_factor * delta
 
 
-def _kk_rows(rows_list, w_points, w_out, broadening_factor):
+def _kk_rows(rows_list, w_points, w_out, broadening_factor, bosonic=False):
     """one device launch for a list of spectra arrays ``(..., n_w)`` on the same grid; returns their G, complex
-    ``(..., n_out)`` each.  A complex spectrum goes as its real and imaginary rows, recombined as G(Re A) + i G(Im A)."""
+    ``(..., n_out)`` each.  A complex spectrum goes as its real and imaginary rows, recombined as G(Re A) + i G(Im A).
+    ``bosonic``: weight_j -> -w_j weight_j, the sum of :func:`get_chi_w_from_A_w` (the broadening stays)."""
     w, weight, eta = _kk_weights(w_points, broadening_factor)
+    if bosonic:
+        weight = -w * weight
     n_w = len(w)
     real_rows, plan = [], []
     for A in rows_list:
@@ -180,6 +183,40 @@ def get_G_w_from_A_w(A_w, w_points, np_interp_A=None, np_omega=2000, w_min=-10, 
         complex ``(np_omega, n, n)`` (n = 1 for a 1-D A_w).
     """
     return _get_G_w_from_A_w_many([A_w], w_points, np_interp_A, np_omega, w_min, w_max, broadening_factor)[0]
+
+
+def _mirror_half_axis(A_w, w_points):
+    """a spectrum given on w >= 0 with A(w) = A(-w) on the whole axis: (A, w) with the mirrored points in front (a
+    point w = 0 is not doubled)"""
+    w = np.asarray(w_points, dtype=float).ravel()
+    A_w = np.asarray(A_w)
+    if len(w) < 1 or np.any(w < 0.0) or np.any(np.diff(w) <= 0.0):
+        raise Exception('symmetric: w_points must be increasing and >= 0')
+    if A_w.shape[-1] != len(w):
+        raise Exception('A_w does not end in the %d points of w_points' % len(w))
+    k = 1 if w[0] == 0.0 else 0
+    return (np.concatenate([A_w[..., :k - 1 if k else None:-1], A_w], axis=-1),
+            np.concatenate([-w[:k - 1 if k else None:-1], w]))
+
+
+def get_chi_w_from_A_w(A_w, w_points, np_interp_A=None, np_omega=2000, w_min=-10, w_max=10, broadening_factor=1.0,
+                       symmetric=False):
+    r"""The retarded bosonic correlator :math:`\chi(\omega + i0)` from the spectral function
+    :math:`A(\omega) = \mathrm{Im}\,\chi(\omega)/(\pi\omega)` of a bosonic continuation
+    (:meth:`TauMaxEnt.set_chi_tau_data`, :meth:`TauMaxEnt.set_chi_iw_data`):
+
+    .. math:: \chi(\omega) = \sum_j \omega_j A(\omega_j) \Delta\omega_j / (\omega_j - \omega - i\, bf \Delta\omega_j)
+
+    so that :math:`\mathrm{Im}\,\chi(\omega) = \pi\omega A(\omega)` and :math:`\mathrm{Re}\,\chi(0) = \int A`.  It is
+    the sum of :func:`get_G_w_from_A_w` with the weight :math:`-\omega_j\Delta\omega_j`, on the device
+    (``mxe_kramers_kronig``).  Parameters and return value as :func:`get_G_w_from_A_w`; ``symmetric``: ``A_w`` is given
+    on ``w_points`` >= 0 only and mirrored, A(-w) = A(w), before anything else."""
+    _check_A_w(A_w, w_min, w_max)
+    if symmetric:
+        A_w, w_points = _mirror_half_axis(A_w, w_points)
+    A_w, w = _interp_A_w(A_w, w_points, np_interp_A)
+    w_out = np.linspace(w_min, w_max, np_omega)
+    return _to_array_gf(_kk_rows([A_w], w, w_out, broadening_factor, bosonic=True)[0], w_out)
 
 
 def get_G_tau_from_A_w(A_w, w_points, beta, np_tau):

@@ -7,8 +7,10 @@ Keeps the reference's surface (reference python/tau_maxent.py:37-356): owns a
 files, scalar / per-tau errors and full covariance matrices (the problem is
 rotated into the covariance eigenbasis).  ``set_G_iw_data`` takes G(i omega_n)
 as arrays instead: the kernel becomes an :class:`IOmegaKernel` and the data
-its stacked real form ``[Re G ; Im G]``.  ``set_G_tau`` / ``set_G_iw`` need
-TRIQS Green-function objects and are not provided.
+its stacked real form ``[Re G ; Im G]``.  ``set_chi_tau_data`` / ``set_chi_iw_data``
+take bosonic data (susceptibilities) the same way, with a
+:class:`BosonicTauKernel` / :class:`BosonicIOmegaKernel`.  ``set_G_tau`` /
+``set_G_iw`` need TRIQS Green-function objects and are not provided.
 """
 
 from copy import deepcopy
@@ -86,16 +88,45 @@ class TauMaxEnt(object):
         else:
             self._rotate_to(T_)
 
+    def _inner_kernel(self):
+        """the kernel of the problem, looked up inside a PreblurKernel"""
+        K = self.K
+        return getattr(K, 'kernel', K)
+
     def _iomega_kernel(self):
         """the IOmegaKernel of a Matsubara problem (also inside a PreblurKernel), else None"""
-        K = self.K
-        K = getattr(K, 'kernel', K)
+        K = self._inner_kernel()
         return K if isinstance(K, kernels.IOmegaKernel) else None
 
+    def _stacked_kernel(self):
+        """the kernel whose rows are ``[Re K ; Im K]`` -- an IOmegaKernel, or a BosonicIOmegaKernel that is not
+        symmetric -- (also inside a PreblurKernel), else None"""
+        K = self._inner_kernel()
+        if isinstance(K, kernels.IOmegaKernel) or (isinstance(K, kernels.BosonicIOmegaKernel) and K.stacked):
+            return K
+        return None
+
     def _use_tau_kernel(self, tau):
-        """after Matsubara data: a TauKernel on ``tau`` again (same omega mesh and SVD backend)"""
-        if self._iomega_kernel() is not None:
+        """after Matsubara or bosonic data: a TauKernel on ``tau`` again (same omega mesh and SVD backend)"""
+        if isinstance(self._inner_kernel(), (kernels.IOmegaKernel, kernels.BosonicTauKernel,
+                                             kernels.BosonicIOmegaKernel)):
             self.K = kernels.TauKernel(np.asarray(tau, dtype=float), self.omega, svd_backend=self.K.svd_backend)
+
+    def _use_bosonic_kernel(self, cls, grid, beta, symmetric):
+        """a bosonic kernel of class ``cls`` on ``grid`` (same omega mesh and SVD backend); one of the same class and
+        symmetry that is there already -- also inside a PreblurKernel -- is refilled only when grid or beta change"""
+        K = self._inner_kernel()
+        if type(K) is cls and K.symmetric == bool(symmetric):
+            if cls is kernels.BosonicTauKernel and K.beta != beta:
+                K.beta = beta
+                self.K.parameter_change()
+                self.K = self.K
+            elif cls is kernels.BosonicIOmegaKernel:
+                K.beta = beta
+            self.tau = grid
+        else:
+            self.K = cls(np.array(grid, dtype=float), self.omega, beta=beta, symmetric=symmetric,
+                         svd_backend=self.K.svd_backend)
 
     def _use_iomega_kernel(self, iomega, beta=None):
         """an IOmegaKernel on ``iomega`` (same omega mesh and SVD backend); one that is there already -- also inside
@@ -131,6 +162,35 @@ class TauMaxEnt(object):
         self.G = self.K.unfold(G_iw)
         self._adopt_data()
 
+    def set_chi_tau_data(self, tau, chi, beta=None, symmetric=False):
+        """Bosonic chi(tau) from arrays, continued to A(omega) = Im chi(omega) / (pi omega): the kernel becomes a
+        :class:`BosonicTauKernel` (``beta`` defaults to ``tau[-1]``).  ``symmetric``: A(omega) = A(-omega), the omega
+        mesh holds omega >= 0 only.  Not in the reference."""
+        tau = np.asarray(tau, dtype=float)
+        chi = np.asarray(chi)
+        if tau.ndim != 1 or chi.shape != tau.shape:
+            raise AssertionError("tau and chi don't have the same dimension")
+        if np.iscomplexobj(chi):
+            raise AssertionError('chi(tau) must be real')
+        self._use_bosonic_kernel(kernels.BosonicTauKernel, tau, beta, symmetric)
+        self.G = np.asarray(chi, dtype=float)
+        self._adopt_data()
+
+    def set_chi_iw_data(self, inu, chi_iw, beta=None, symmetric=False):
+        """Bosonic chi(i nu_n) from arrays: ``inu`` the real Matsubara frequencies nu_n = 2 pi n / beta (nu_0 = 0
+        included if it is there), ``chi_iw`` the data; ``beta`` defaults to 2 pi / (nu_1 - nu_0).  The kernel becomes
+        a :class:`BosonicIOmegaKernel` and ``G`` the stacked real vector ``[Re chi ; Im chi]`` of 2 n values, which
+        ``scale_alpha='Ndata'`` counts; results give G, G_orig and G_rec back complex.  ``symmetric``:
+        A(omega) = A(-omega) on a mesh omega >= 0, chi(i nu_n) is real: ``G`` holds the n values Re chi(i nu_n) (an
+        imaginary part of the data is dropped), and the results are real."""
+        inu = np.asarray(inu, dtype=float)
+        chi_iw = np.asarray(chi_iw)
+        if inu.ndim != 1 or chi_iw.shape != inu.shape:
+            raise AssertionError("inu and chi_iw don't have the same dimension")
+        self._use_bosonic_kernel(kernels.BosonicIOmegaKernel, inu, beta, symmetric)
+        self.G = np.asarray(self._inner_kernel().unfold(chi_iw), dtype=float)
+        self._adopt_data()
+
     def set_G_tau_file(self, filename, tau_col=0, G_col=1, err_col=None):
         """G(tau), optionally with its error bar, from the columns of a text file
         (reference tau_maxent.py:198-225); a file that brings errors ends any rotation"""
@@ -149,7 +209,7 @@ class TauMaxEnt(object):
             raise Exception('complex error supplied, only real accepted')
         sigma = np.real(error) * np.ones(np.shape(self.G)) if np.ndim(error) == 0 \
             else np.asarray(np.real(error), dtype=float)
-        K = self._iomega_kernel()
+        K = self._stacked_kernel()
         if K is not None and sigma.shape == (K.n_iw,) and np.shape(self.G) == (2 * K.n_iw,):
             sigma = np.concatenate([sigma, sigma])
         if sigma.shape != np.shape(self.G):
