@@ -71,7 +71,7 @@ extern "C" {
 #define MXE_ERR_LIMIT       -5   /* n_s > 128 (fp32: > 64); mxe_eval_batch / mxe_audit: w and H of a problem
                                      exceed the LDS (n_omega > ~7900); the alpha scans themselves take any
                                      n_omega (state in device memory where the LDS does not hold it) */
-#define MXE_ERR_NUMERIC     -6   /* whitening failed (non-positive error bar) / SVD sweeps exhausted */
+#define MXE_ERR_NUMERIC     -6   /* whitening failed (non-positive error bar) / SVD sweeps exhausted or matrix not finite */
 #define MXE_ERR_NOMEM       -7   /* host allocation failed                     */
 
 #define MXE_PRECISION_F64      0 /* all arithmetic IEEE binary64 (default)      */
@@ -449,10 +449,16 @@ int  mxe_apply_output_map(mxe_ctx* ctx, const double* B, double* out_A);
  *   out_K [ib][n_tau][n_omega]   the (blurred) kernel matrix; may be NULL
  *   out_U [ib][n_tau][ns_max], out_S [ib][ns_max], out_V [ib][n_omega][ns_max]
  *         (columns >= out_ns[ib] are zero), out_ns [ib]
- *   out_info [ib][3]: rank kept by the QR stage, Jacobi sweeps, status (may be NULL)
+ *   out_info [ib][3]: rank kept by the QR stage, Jacobi sweeps, status (may be NULL); status: 0 ok,
+ *         1 Jacobi sweeps exhausted or a matrix that is not finite, 2 more than ns_max values pass
+ *         the threshold, 3 the QR stage kept its 128 rows and columns above its stop cut
+ *         (eps x the largest column norm) were left: K has more than 128 significant directions
+ *         and U, S, V are those of a rank-128 approximation, not the leading triplets of K
  *   out_ms: device time of the whole batch (may be NULL)
- * Returns MXE_ERR_LIMIT if more than ns_max singular values pass the threshold,
- * MXE_ERR_NUMERIC if the Jacobi sweeps did not converge. */
+ * Returns MXE_ERR_LIMIT if more than ns_max singular values pass the threshold (status 2) or
+ * the numerical rank of K is above 128 (status 3: only a host SVD decomposes such a matrix),
+ * MXE_ERR_NUMERIC if the Jacobi sweeps did not converge, if K holds a NaN or an Inf or its
+ * squared column norms overflow (status 1), or if a NaN came out in out_S. */
 int  mxe_kernel_svd(int device, int n_tau, int n_omega, const double* tau,
                     const double* omega, const double* delta, double beta,
                     int n_b, const double* preblur_b, double threshold, int ns_max,
@@ -496,7 +502,9 @@ int  mxe_kernel_svd_boson_iw(int device, int n_inu, int n_omega, const double* i
 /* DataKernel (reference kernels.py:183-207): the same preblur products and decomposition for a matrix the caller
  * filled.  K: n_rows x n_omega, host, row-major; it is transposed into the column-major working layout on the
  * device.  omega and delta serve the preblur (and are required).  Outputs as mxe_kernel_svd with n_tau -> n_rows;
- * MXE_ERR_LIMIT also when n_rows exceed the decomposition's LDS (n_rows > 7464). */
+ * MXE_ERR_LIMIT also when n_rows exceed the decomposition's LDS (n_rows > 7464).  A matrix with a NaN or an Inf is
+ * refused before anything is launched (MXE_ERR_NUMERIC); a well-conditioned matrix of more than 128 rows and columns
+ * is MXE_ERR_LIMIT (status 3 above). */
 int  mxe_kernel_svd_data(int device, int n_rows, int n_omega, const double* K,
                          const double* omega, const double* delta,
                          int n_b, const double* preblur_b, double threshold, int ns_max,

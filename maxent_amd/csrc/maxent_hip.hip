@@ -532,8 +532,8 @@ const char* mxe_strerror(int code)
         case MXE_ERR_HIP: return "HIP runtime error (see mxe_last_hip_error)";
         case MXE_ERR_NODEVICE: return "no usable HIP device";
         case MXE_ERR_STATE: return "call order violated";
-        case MXE_ERR_LIMIT: return "problem exceeds kernel limits (n_s <= 128, 160 KB LDS per chain)";
-        case MXE_ERR_NUMERIC: return "numerical failure (whitening: error bars must be finite and > 0; device SVD: Jacobi sweeps exhausted)";
+        case MXE_ERR_LIMIT: return "problem exceeds kernel limits (n_s <= 128, 160 KB LDS per chain; device SVD: more singular values above the threshold than ns_max, or a matrix with more than 128 significant directions, which svd_backend=\"host\" takes)";
+        case MXE_ERR_NUMERIC: return "numerical failure (whitening: error bars must be finite and > 0; device SVD: Jacobi sweeps exhausted, or a matrix that is not finite or whose squares overflow)";
         case MXE_ERR_NOMEM: return "out of host memory";
         default: return "unknown error";
     }
@@ -3314,8 +3314,13 @@ int kernel_svd_common(int device, int n_grid, int m_rows, int n_omega, const dou
     for (int ib = 0; ib < n_b; ++ib) {
         out_ns[ib] = hinfo[(size_t)ib * 4];
         if (out_info) { out_info[ib * 3] = hinfo[(size_t)ib * 4 + 1]; out_info[ib * 3 + 1] = hinfo[(size_t)ib * 4 + 2]; out_info[ib * 3 + 2] = hinfo[(size_t)ib * 4 + 3]; }
-        if (hinfo[(size_t)ib * 4 + 3] == 2) rc = MXE_ERR_LIMIT;
-        else if (hinfo[(size_t)ib * 4 + 3] == 1 && rc == MXE_OK) rc = MXE_ERR_NUMERIC;
+        const int status = hinfo[(size_t)ib * 4 + 3];
+        if (status == 2 || status == 3) rc = MXE_ERR_LIMIT;       // (3: more than SVD_RCAP significant directions)
+        else if (status == 1 && rc == MXE_OK) rc = MXE_ERR_NUMERIC;
+        // a NaN that entered with the grids or the matrix passes every comparison of the decomposition as "false"
+        // and comes out in S: never MXE_OK
+        for (int k = 0; k < ns_max && rc == MXE_OK; ++k)
+            if (std::isnan(out_S[(size_t)ib * ns_max + k])) rc = MXE_ERR_NUMERIC;
     }
     if (out_K)
         for (int ib = 0; ib < n_b; ++ib)
@@ -3414,6 +3419,8 @@ try {
         n_rows > (1 << 30) / n_omega) return MXE_ERR_ARG;
     // (before the matrix is copied: kernel_svd_common would refuse the same rows after its own check)
     if (((size_t)n_rows + 16 + 8 + mxe::SVD_RCAP + mxe::SVD_RCAP / 2) * sizeof(double) > 60 * 1024) return MXE_ERR_LIMIT;
+    // a caller's matrix may hold anything: NaN and Inf are refused before the launch
+    for (size_t i = 0, nel = (size_t)n_rows * n_omega; i < nel; ++i) if (!std::isfinite(K[i])) return MXE_ERR_NUMERIC;
     return kernel_svd_common(device, n_rows * n_omega, n_rows, n_omega, K, omega, delta, n_b, preblur_b, threshold,
                              ns_max, out_K, out_U, out_S, out_V, out_ns, out_info, out_ms,
                              [=](hipStream_t st, const double* dK, const double*, double* dKt0) {

@@ -264,7 +264,9 @@ struct SvdParams {
     double* out_U;      // [m][ns_max]
     double* out_S;      // [ns_max]
     double* out_V;      // [n][ns_max]
-    int* out_info;      // [4]: n_s, rank of the QR stage, Jacobi sweeps, status (0 ok, 1 sweeps exhausted, 2 n_s > ns_max)
+    int* out_info;      // [4]: n_s, rank of the QR stage, Jacobi sweeps, status (0 ok, 1 sweeps exhausted, 2 n_s > ns_max,
+                        //      3 the QR stage reached SVD_RCAP rows with columns left above its stop cut: the numerical
+                        //      rank of K exceeds SVD_RCAP and U, S, V are those of a rank-SVD_RCAP approximation, not of K)
 };
 
 __global__ __launch_bounds__(SVD_T)
@@ -305,8 +307,11 @@ void svd_kernel(const SvdParams p)
 
     // ---- 1. Householder QR with column pivoting, early stop ----
     const int kmax = min(min(m, n), SVD_RCAP);
-    int r = 0;
-    for (int k = 0; k < kmax; ++k) {
+    // a matrix with more rows and columns than SVD_RCAP gets one more pivot search after the last step: columns
+    // still above the stop cut mean that R (SVD_RCAP rows) is not K to rounding, and its singular triplets not K's
+    const int ksearch = kmax + ((kmax < min(m, n)) ? 1 : 0);
+    int r = 0, capped = 0;
+    for (int k = 0; k < ksearch; ++k) {
         // pivot = argmax_{j >= k} cn2[j] (lowest index on ties)
         double best = -1.0; int bi = k;
         for (int j = k + tid; j < n; j += SVD_T) { const double c = cn2[j]; if (c > best) { best = c; bi = j; } }
@@ -328,6 +333,7 @@ void svd_kernel(const SvdParams p)
         }
         __syncthreads();
         if (sh_stop) break;
+        if (k == kmax) { capped = 1; break; }
         const int piv = sh_piv;
         if (piv != k) {
             for (int i = tid; i < m; i += SVD_T) {
@@ -482,6 +488,13 @@ void svd_kernel(const SvdParams p)
     int ns = 0;
     for (int kk = 0; kk < rr; ++kk) if (sqrt(s2[order[kk]]) >= p.threshold && s2[order[kk]] > 0.0) ns = kk + 1; else break;
     if (ns > p.ns_max) { ns = p.ns_max; status = 2; }
+    if (capped) status = 3;
+    // non-finite input: a NaN is never the pivot, spreads over its column of R and makes every comparison above false
+    // (``order`` is then not a permutation); an Inf, or squares that overflow, stop the QR stage at its first step.
+    // Nothing is returned for such a matrix.
+    bool bad = !(sh_nrm0 >= 0.0 && sh_nrm0 <= 1.7976931348623157e308);
+    for (int kk = 0; kk < rr; ++kk) if (s2[kk] != s2[kk]) bad = true;
+    if (bad) { ns = 0; status = 1; }
 
     // Q = H_0 ... H_{r-1} [I_r ; 0], columns in Qc[l][i]
     for (int idx = tid; idx < r * m; idx += SVD_T) {

@@ -30,6 +30,9 @@ class MaxEntDeviceError(RuntimeError):
 _MXE_ERR_LIMIT = -5
 #: most rows of a kernel matrix the device SVD takes (mxe_kernel_svd*: the rows + 216 doubles of the decomposition's LDS <= 60 KB)
 SVD_MAX_ROWS = 60 * 1024 // 8 - 216
+#: most significant directions (rows of R the pivoted QR keeps, SVD_RCAP of mxe_svd.hip.h) of a matrix the device SVD
+#: decomposes; a matrix of higher numerical rank raises MaxEntDeviceError
+SVD_MAX_RANK = 128
 
 
 class MxeOpts(ctypes.Structure):
@@ -363,6 +366,8 @@ def kernel_svd_data(K, omega, delta, preblur_b=(0.0,), threshold=1.e-14, ns_max=
     K, omega, delta = _c(K), _c(omega), _c(delta)
     if K.ndim != 2 or K.shape[1] != len(omega) or len(delta) != len(omega):
         raise ValueError('kernel_svd_data: K (n_rows, n_omega) = %s on an omega mesh of %d points' % (K.shape, len(omega)))
+    if not np.all(np.isfinite(K)):
+        raise ValueError('kernel_svd_data: K holds %d values that are not finite' % int((~np.isfinite(K)).sum()))
     return _kernel_svd_call('mxe_kernel_svd_data', K.shape[0], (_p(K),), (), omega, delta, preblur_b, threshold, ns_max,
                             want_K, device)
 
@@ -386,6 +391,10 @@ def _kernel_svd_call(name, n_grid, grid_args, scalar_args, omega, delta, preblur
     if rc == _MXE_ERR_LIMIT and n_rows > SVD_MAX_ROWS:
         raise MaxEntDeviceError('%s: %d rows of the kernel exceed the %d the device decomposition holds in LDS; '
                                 'svd_backend="host" takes them' % (name, n_rows, SVD_MAX_ROWS))
+    if rc == _MXE_ERR_LIMIT and np.any(info[:, 2] == 3):
+        raise MaxEntDeviceError('%s: the matrix (%d x %d) has more than %d significant directions (its pivoted QR still '
+                                'had columns above eps x the largest after %d steps), and the device decomposition '
+                                'keeps no more; svd_backend="host" takes it' % (name, n_rows, n_w, SVD_MAX_RANK, SVD_MAX_RANK))
     if rc != 0:
         raise MaxEntDeviceError(name + ' failed: ' + lib.mxe_strerror(rc).decode())
     out = []

@@ -298,6 +298,7 @@ def check_svd(r, Kh, what):
     assert len(S) >= k and d_abs < 1e-12 and d_rel < 1e-12
     assert np.abs((U * S) @ V.T - Kh).max() < 1e-13 * nrm
     assert np.abs(U.T @ U - np.eye(len(S))).max() < 1e-12
+    assert np.abs(V.T @ V - np.eye(len(S))).max() < 1e-12
 
 
 @pytest.mark.parametrize('name', sorted(CASES))

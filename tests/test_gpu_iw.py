@@ -231,6 +231,7 @@ def test_device_fill_and_svd_of_the_stacked_kernel(g):
         assert len(S) >= k and d_abs < 1e-12 and d_rel < 1e-12
         assert np.abs((U * S) @ V.T - Kh).max() < 1e-13 * nrm
         assert np.abs(U.T @ U - np.eye(len(S))).max() < 1e-12
+        assert np.abs(V.T @ V - np.eye(len(S))).max() < 1e-12
     # the facade with the device decomposition meets the gate
     tm = iw_tm(g, svd_backend='device')
     out = tm.run()
