@@ -43,6 +43,8 @@
  *   DataKernel (a caller's matrix) + KernelSVD.svd         | mxe_kernel_svd_data
  *     kernels.py:183-207                                   |
  *   get_G_w_from_A_w  maxent_util.py:43-132                | mxe_kramers_kronig (also get_chi_w_from_A_w)
+ *   (nothing: the reference gives no error bars)           | mxe_posterior_var (posterior variances of
+ *                                                          |   integrated quantities, diagonal of the covariance)
  *   the arrays of MaxEntResult (numpy allocations)         | mxe_host_alloc / mxe_host_free (optional:
  *     maxent_result.py:835-967                             |   page-locked destinations, one DMA per fetch)
  *
@@ -357,6 +359,30 @@ int  mxe_eval_batch(mxe_ctx* ctx, int P, const int32_t* elem_of_problem, const d
                     double* out_Q, double* out_chi2, double* out_S,
                     double* out_H, double* out_u, double* out_w, double* out_q,
                     double* out_h, double* out_g, double* out_W, double* out_W2);
+/* Posterior error bars in the Gaussian approximation around the minimiser (Bryan 1990; Jarrell & Gubernatis 1996,
+ * section 5).  Replaces nothing of the reference, which offers none.  With w = H (normal entropy) or sqrt(H^2 + 4 D^2)
+ * (plus-minus), the whitened basis K^T Sigma^-1 K = V' c^2 V'^T and a = alpha~ / eta the covariance of H is
+ *   Gamma = (eta K^T Sigma^-1 K + alpha~ diag(1/w))^-1 = (1/alpha~) [diag(w) - diag(w) V' c B^-1 c V'^T diag(w)],
+ *   B = c W c + a I,  W = V'^T diag(w) V',  B = L L^T  (the matrix and the factor of mxe_logdet), so that
+ *   out_var[p][j]   = f_j^T Gamma f_j = (1/alpha~) [sum_i w_i f_ji^2 - |L^-1 y|^2],  y = c o V'^T (w o f_j)
+ *   out_prior[p][j] = f_j^T diag(w) f_j / alpha~     (what the entropy alone would leave: var <= prior)
+ *   out_diag[p][i]  = Gamma_ii = (w_i / alpha~) [1 - w_i |L^-1 (c o V'_i)|^2]
+ * for P problems on the staged elements of ctx (data set, entropy and D of elem_of_problem[p], as mxe_eval_batch) at
+ * alpha_scaled[p] > 0 and the hidden images
+ *   H != NULL:  H [P][n_omega], host (results outlive launches);
+ *   H == NULL:  rows of the last launch, read where they lie on the device: row problem_index[p] = chain * n_alpha +
+ *               alpha index (problem_index == NULL: row p).  MXE_ERR_STATE when nothing was launched.
+ * F: n_f x n_omega weights on H (host, finite; n_f may be 0 with F == NULL when only out_diag is wanted); out_prior and
+ * out_diag may be NULL.  The differences are formed as written, never through B^-1; one that rounding makes negative
+ * is returned as 0 (a NaN stays a NaN).  A problem whose H row is not finite or whose B is not positive definite gets NaN in all its
+ * outputs, the others are not touched by it and the call returns MXE_OK.  The bits of a value do not depend on the
+ * other problems or functionals of the call (fixed summation order, no atomics).  out_ms: device time of the kernel
+ * (may be NULL).  MXE_ERR_LIMIT when B and w exceed 160 KB of LDS (n_omega > 15872 with n_s <= 64,
+ * > 3584 with n_s <= 128; the right-hand sides live in the part of B that its factor leaves free). */
+int  mxe_posterior_var(mxe_ctx* ctx, int P, const int32_t* elem_of_problem, const double* alpha_scaled,
+                       const double* H, const int32_t* problem_index, double chi2_factor,
+                       int n_f, const double* F, double* out_var, double* out_diag, double* out_prior,
+                       float* out_ms);
 /* NormalEntropy / PlusMinusEntropy as functions of a hidden image given directly (functions.py:508-520,
  * 544-564): S, dS/dH and the diagonal of d2S/dH2 for P images H [P][n_omega] and one default model D
  * [n_omega] (including delta-omega).  No context needed; outputs may be NULL. */

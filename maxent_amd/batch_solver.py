@@ -849,6 +849,31 @@ class BatchSolver(object):
                           np.ascontiguousarray(full(staged['v0'])), opts)
         held[id(ctx)] = staged
 
+    @classmethod
+    def staged_context_for(cls, K, specs, dev):
+        """(context, solver) of a one-device solver of ``K`` on device ``dev`` that holds exactly the elements of ``specs``
+        staged (:meth:`_stage`: same data sets, default models and entropies in the same order; all singular directions) and
+        has no batch in flight -- for calls that work on staged elements without solving (``mxe_posterior_var``); the
+        caller takes ``solver._lock`` around its call.  (None, None) when there is none: the caller stages its own."""
+        for s in list((K.__dict__.get('_batch_solvers') or {}).values()):
+            if s._keep is not None or s._busy or s.device_ids != (int(dev),) or not s.ctxs[0]._h or \
+                    not cls._same_token(s._token, cls._kernel_token(K)):
+                continue
+            ctx = s.ctxs[0]
+            old = s.__dict__.get('_staged', {}).get(id(ctx))
+            n = len(specs)
+            if old is None or old['err'] is None or old['n'] != n or old['rotated'] != (K.rotation is not None):
+                continue
+            full = lambda a: np.broadcast_to(a, (n, a.shape[1]))
+            errs, Ds = full(old['err']), full(old['D'])
+            if all(a is b.get('U_rot') for a, b in zip(old['U_rot'], specs)) and \
+                    np.array_equal(old['kinds'], np.array([b['kind'] for b in specs])) and \
+                    all(Ds[i].shape == np.shape(b['D']) and np.array_equal(Ds[i], b['D']) and
+                        np.array_equal(errs[i], np.asarray(b['err'], dtype=float) * np.ones(len(b['G'])))
+                        for i, b in enumerate(specs)):
+                return ctx, s
+        return None, None
+
     def _on_devices(self, fn, ranks, wait=True):
         """fn(rank) for every rank: in this thread for one device, one thread per device otherwise (``wait=False``:
         returns the function that joins them)"""

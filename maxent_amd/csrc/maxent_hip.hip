@@ -307,6 +307,9 @@ struct mxe_ctx {
     // mxe_eval_batch / mxe_audit scratch
     DevBuf<double> ev_x, ev_alpha, ev_scal, ev_vecw, ev_vecs, ev_mat;
     DevBuf<int> ev_elem;
+    // mxe_posterior_var scratch: alpha | H rows | F | var | prior | diag;  elem | row
+    DevBuf<double> pv_d;
+    DevBuf<int> pv_i;
     DevBuf<double> rows_out;        // mxe_fetch_rows: the selected rows, gathered on the device
     DevBuf<int> rows_idx;
     double chi2_factor = 1.0;     // of the staged chains (mxe_opts.chi2_factor)
@@ -617,6 +620,7 @@ void mxe_ctx_destroy(mxe_ctx* ctx)
     ctx->rows_out.release(); ctx->rows_idx.release();
     ctx->ev_x.release(); ctx->ev_alpha.release(); ctx->ev_scal.release(); ctx->ev_vecw.release(); ctx->ev_vecs.release();
     ctx->ev_mat.release(); ctx->ev_elem.release();
+    ctx->pv_d.release(); ctx->pv_i.release();
     if (ctx->ev0) hipEventDestroy(ctx->ev0);
     if (ctx->ev1) hipEventDestroy(ctx->ev1);
     if (ctx->ev_mark) hipEventDestroy(ctx->ev_mark);
@@ -2706,6 +2710,88 @@ try {
         if (out_g) vec_out(hg, out_g);
         if (wantW) mat_out(hW, out_W);
         if (wantW2) mat_out(hW2, out_W2);
+    }
+    return MXE_OK;
+}
+MXE_CATCH_ALL
+
+// ---- posterior variances of linear functionals of H, and the diagonal of the covariance (mxe_postvar.hip.h) ----
+#include "mxe_postvar.hip.h"
+
+extern "C" int mxe_posterior_var(mxe_ctx* ctx, int P, const int32_t* elem_of_problem, const double* alpha_scaled,
+                                 const double* H, const int32_t* problem_index, double chi2_factor,
+                                 int n_f, const double* F, double* out_var, double* out_diag, double* out_prior,
+                                 float* out_ms)
+try {
+    if (!ctx || P < 1 || !elem_of_problem || !alpha_scaled || n_f < 0 || (n_f > 0 && (!F || !out_var))) return MXE_ERR_ARG;
+    if (n_f == 0 && !out_diag) return MXE_ERR_ARG;
+    if (out_prior && n_f == 0) return MXE_ERR_ARG;
+    if (ctx->n_elem < 1) return MXE_ERR_STATE;
+    if (!H && !ctx->launched) return MXE_ERR_STATE;
+    if (!(chi2_factor > 0.0) || !std::isfinite(chi2_factor)) return MXE_ERR_ARG;
+    const int NP = ctx->NP, nw = ctx->n_omega;
+    if ((size_t)P * (size_t)std::max(n_f, 1) > 0x7fffffffull || (size_t)P * nw > 0x7fffffffull || (size_t)n_f * nw > 0x7fffffffull)
+        return MXE_ERR_ARG;
+    const size_t lds = mxe::postvar_lds_bytes(NP, ctx->nwp);
+    if (lds > 160 * 1024) return MXE_ERR_LIMIT;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (ctx->ds_dirty) { int rc = upload_bases(ctx); if (rc != MXE_OK) return rc; }
+    const size_t n_last = (size_t)ctx->n_chain * ctx->n_alpha;
+    std::vector<double> ha(P);
+    std::vector<int> hi((size_t)2 * P);
+    for (int p = 0; p < P; ++p) {
+        const int e = elem_of_problem[p];
+        if (e < 0 || e >= ctx->n_elem) return MXE_ERR_ARG;
+        if (!(alpha_scaled[p] > 0.0) || !std::isfinite(alpha_scaled[p])) return MXE_ERR_ARG;
+        ha[p] = alpha_scaled[p] / chi2_factor;
+        hi[p] = e;
+        int row = p;
+        if (!H) {
+            row = problem_index ? problem_index[p] : p;
+            if (row < 0 || (size_t)row >= n_last) return MXE_ERR_ARG;
+        }
+        hi[(size_t)P + p] = row;
+    }
+    for (size_t i = 0; i < (size_t)n_f * nw; ++i) if (!std::isfinite(F[i])) return MXE_ERR_ARG;
+    // one block of doubles: alpha [P] | H [P][nw] (when handed in) | F [n_f][nw] | var [P][n_f] | prior [P][n_f] | diag [P][nw]
+    const size_t oH = (size_t)P, oF = oH + (H ? (size_t)P * nw : 0), oV = oF + (size_t)n_f * nw, oP = oV + (size_t)P * n_f,
+                 oD = oP + (out_prior ? (size_t)P * n_f : 0), total = oD + (out_diag ? (size_t)P * nw : 0);
+    HIPCHK(ctx, ctx->pv_d.ensure(total));
+    HIPCHK(ctx, ctx->pv_i.ensure((size_t)2 * P));
+    double* d = ctx->pv_d.p;
+    HIPCHK(ctx, hipMemcpyAsync(d, ha.data(), (size_t)P * 8, hipMemcpyHostToDevice, ctx->stream));
+    if (H) HIPCHK(ctx, hipMemcpyAsync(d + oH, H, (size_t)P * nw * 8, hipMemcpyHostToDevice, ctx->stream));
+    if (n_f) HIPCHK(ctx, hipMemcpyAsync(d + oF, F, (size_t)n_f * nw * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->pv_i.p, hi.data(), hi.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    mxe::PostVarParams pp;
+    pp.V = ctx->dV.p; pp.c = ctx->dc.p; pp.elem_ds = ctx->delem_ds.p; pp.elem_kind = ctx->delem_kind.p; pp.D = ctx->dD.p;
+    pp.elem = ctx->pv_i.p; pp.alpha = d;
+    pp.H = H ? d + oH : ctx->dout_H.p; pp.row = H ? nullptr : ctx->pv_i.p + P;
+    pp.F = n_f ? d + oF : nullptr;
+    pp.out_var = d + oV; pp.out_prior = out_prior ? d + oP : nullptr; pp.out_diag = out_diag ? d + oD : nullptr;
+    pp.nw = nw; pp.nwp = ctx->nwp; pp.ns = ctx->n_s; pp.n_f = n_f;
+    SvdScratch sc;                    // (the two events of the timing, released on every path)
+    if (out_ms) {
+        HIPCHK(ctx, hipEventCreate(&sc.e0)); HIPCHK(ctx, hipEventCreate(&sc.e1));
+        HIPCHK(ctx, hipEventRecord(sc.e0, ctx->stream));
+    }
+    hipError_t e;
+#define MXE_LAUNCH_POSTVAR(NT_) do { \
+        e = hipFuncSetAttribute((const void*)mxe::postvar_kernel<NT_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+        if (e == hipSuccess) { hipLaunchKernelGGL((mxe::postvar_kernel<NT_>), dim3((unsigned)P), dim3(256), lds, ctx->stream, pp); \
+                               e = hipGetLastError(); } } while (0)
+    if (NP == 64) MXE_LAUNCH_POSTVAR(4); else MXE_LAUNCH_POSTVAR(8);
+#undef MXE_LAUNCH_POSTVAR
+    HIPCHK(ctx, e);
+    if (out_ms) HIPCHK(ctx, hipEventRecord(sc.e1, ctx->stream));
+    if (n_f) HIPCHK(ctx, hipMemcpyAsync(out_var, d + oV, (size_t)P * n_f * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (out_prior) HIPCHK(ctx, hipMemcpyAsync(out_prior, d + oP, (size_t)P * n_f * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (out_diag) HIPCHK(ctx, hipMemcpyAsync(out_diag, d + oD, (size_t)P * nw * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, stream_wait(ctx->stream));
+    if (out_ms) HIPCHK(ctx, hipEventElapsedTime(out_ms, sc.e0, sc.e1));
+    if (chi2_factor != 1.0) {         // Gamma(eta, alpha~) = Gamma(1, alpha~ / eta) / eta
+        for (size_t i = 0; i < (size_t)P * n_f; ++i) { out_var[i] /= chi2_factor; if (out_prior) out_prior[i] /= chi2_factor; }
+        if (out_diag) for (size_t i = 0; i < (size_t)P * nw; ++i) out_diag[i] /= chi2_factor;
     }
     return MXE_OK;
 }

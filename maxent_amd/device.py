@@ -110,6 +110,8 @@ SYMBOLS = [
     ('mxe_launch_depth', ctypes.c_int, [_vp, _ip, _dp]),
     ('mxe_schedule_info', ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
     ('mxe_eval_batch', ctypes.c_int, [_vp, ctypes.c_int, _ip, _dp, _dp, ctypes.c_int, ctypes.c_double] + [_dp] * 11),
+    ('mxe_posterior_var', ctypes.c_int, [_vp, ctypes.c_int, _ip, _dp, _dp, _ip, ctypes.c_double, ctypes.c_int, _dp, _dp, _dp, _dp,
+                                         ctypes.POINTER(ctypes.c_float)]),
     ('mxe_entropy', ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, _dp, _dp]),
     ('mxe_audit', ctypes.c_int, [_vp, _dp, _dp]),
     ('mxe_select_launch', ctypes.c_int, [_vp, ctypes.c_int]),
@@ -733,6 +735,51 @@ class DeviceContext(object):
         args = [_p(out.get(k)) for k in ('Q', 'chi2', 'S', 'H', 'u', 'w', 'q', 'h', 'g', 'W', 'W2')]
         self._check(self._lib.mxe_eval_batch(self._h, P, _p(el), _p(al), _p(x), int(bool(input_is_H)),
                                              float(chi2_factor), *args), 'mxe_eval_batch')
+        return out
+
+    def posterior_var(self, elem_of_problem, alpha_scaled, H=None, problem_index=None, F=None, chi2_factor=1.0,
+                      want_diag=False, timing=None):
+        """``mxe_posterior_var``: Gaussian posterior variances around the minimiser, on the staged elements.
+        ``H``: (P, n_omega) hidden images, or None for rows ``problem_index`` (chain * n_alpha + alpha index) of the last
+        launch, read on the device.  ``F``: (n_f, n_omega) weights on H.  Returns a dict: ``var`` and ``prior`` (P, n_f) --
+        f^T Gamma f and f^T diag(w) f / alpha~ -- and, with ``want_diag``, ``diag`` (P, n_omega) = Gamma_ii.  A problem whose
+        H row is not finite or whose curvature matrix is not positive definite has NaN everywhere.  ``timing``: a dict that
+        receives the device time ``ms`` of the kernel."""
+        if self._n_s_dev < self.n_s:
+            raise MaxEntDeviceError('posterior_var on a context that keeps %d of %d singular directions' % (self._n_s_dev, self.n_s))
+        el = _c(np.atleast_1d(elem_of_problem), np.int32)
+        P = len(el)
+        al = _c(np.broadcast_to(np.asarray(alpha_scaled, dtype=float), (P,)))
+        if not np.all(al > 0) or not np.all(np.isfinite(al)):
+            raise ValueError('posterior_var: every alpha must be positive and finite')
+        if H is not None:
+            H = _c(H).reshape(P, self.n_omega)
+            pi = None
+        else:
+            pi = _c(np.arange(P) if problem_index is None else np.atleast_1d(problem_index), np.int32)
+            if len(pi) != P or (P and (pi.min() < 0 or pi.max() >= self._n_chain * self._n_alpha)):
+                raise ValueError('posterior_var: problem_index must name %d problems of the last launch (%d x %d)'
+                                 % (P, self._n_chain, self._n_alpha))
+        if F is not None:
+            F = _c(np.atleast_2d(F))
+            if F.shape[1] != self.n_omega:
+                raise ValueError('posterior_var: F has %d columns, the omega mesh %d points' % (F.shape[1], self.n_omega))
+            if not np.all(np.isfinite(F)):
+                raise ValueError('posterior_var: F holds values that are not finite')
+        n_f = 0 if F is None else F.shape[0]
+        if n_f == 0 and not want_diag:
+            raise ValueError('posterior_var: neither functionals nor the diagonal asked for')
+        var, prior = np.empty((P, n_f)), np.empty((P, n_f))
+        diag = np.empty((P, self.n_omega)) if want_diag else None
+        ms = ctypes.c_float(0)
+        self._check(self._lib.mxe_posterior_var(self._h, P, _p(el), _p(al), _p(H), _p(pi), float(chi2_factor), n_f,
+                                                _p(F) if n_f else None, _p(var) if n_f else None, _p(diag),
+                                                _p(prior) if n_f else None, ctypes.byref(ms)), 'mxe_posterior_var')
+        if timing is not None:
+            timing['ms'] = float(ms.value)
+        out = dict(var=var, prior=prior)
+        if want_diag:
+            out['diag'] = diag
         return out
 
     def audit(self):

@@ -681,6 +681,90 @@ class ElementwiseMaxEnt(object):
                                         [b['worker'].maxent_loop.A_of_H for b in live], which_of, settle))
         return True
 
+    # ---- error bars ------------------------------------------------------------
+    def _posterior_models(self, jobs, result):
+        """default models of the off-diagonal jobs when they are not the worker's own (PoormanMaxEnt), else None"""
+        return None
+
+    def posterior_errors(self, result=None, alpha=None, windows=None, functionals=None, pointwise=False, timing=None):
+        """:meth:`TauMaxEnt.posterior_errors` for every matrix element of ``result`` (default: the last result of this
+        object): all elements of a worker -- the diagonal ones, the off-diagonal ones with their plus-minus entropy -- in
+        ONE call of ``mxe_posterior_var`` per device, each with its own error bars or covariance.  Returns a dict of arrays
+        shaped like the result's fields (matrix indices, then the complex index with ``use_complex``, then what
+        :meth:`TauMaxEnt.posterior_errors` returns); elements that were not computed (below the threshold) hold NaN,
+        those that follow from hermiticity are filled from their partners.  ``info``: per computed element its
+        ``nan_rows``."""
+        from . import posterior
+        res = self.maxent_result if result is None else result
+        if res is None:
+            raise ValueError('no result: run() first or hand one in')
+        zero = set(tuple(z) for z in res.zero_elements)
+        phases = [(self.maxent_diagonal, self._diag_jobs(), None)]
+        if not isinstance(self, DiagonalMaxEnt):
+            off = self._offdiag_jobs()
+            phases.append((self.maxent_offdiagonal, off, self._posterior_models(off, res)))
+        ids = self.device_ids if self.device_ids else (self.maxent_diagonal.maxent_loop.device_id,)
+        collected, ms = [], 0.0
+        for worker, jobs, models in phases:
+            loop = worker.maxent_loop
+            items, keys = [], []
+            for n, (element, re) in enumerate(jobs):
+                cidx = 0 if re else 1
+                key = tuple(element) + ((cidx,) if self.use_complex else ())
+                if key in zero:
+                    continue
+                try:
+                    H = np.asarray(res.element_array('H', key), dtype=float)
+                except (KeyError, IndexError, AttributeError, AssertionError):
+                    continue
+                if H.ndim != 2 or H.shape[0] == 0:
+                    continue
+                if models is not None:
+                    worker.set_D(models[n])
+                self._load_element(worker, element, re)
+                spec = loop.make_spec()
+                posterior.check_alpha(spec, res.alpha)
+                logp = np.asarray(res.element_array('probability', key), dtype=float)
+                ana = res.analyzer_results
+                for i in key:
+                    ana = ana[i]
+                items.append(dict(spec=spec, H=H, alpha=np.asarray(res.alpha, dtype=float), analysis=ana,
+                                  probability=None if np.all(np.isnan(logp)) else logp, B=loop.A_of_H.matrix()))
+                keys.append(key)
+            if not items:
+                continue
+            t = {}
+            outs = posterior.element_errors(worker.K, worker.omega, items, alpha=alpha, windows=windows,
+                                            functionals=functionals, pointwise=pointwise,
+                                            default_name=res.default_analyzer_name,
+                                            chi2_factor=loop.cost_function.chi2_factor, device_ids=ids,
+                                            bryan=posterior.find_bryan(loop.analyzers), timing=t)
+            ms += t.get('ms', 0.0)
+            collected.extend(zip(keys, outs))
+        if timing is not None:
+            timing['ms'] = ms
+        if not collected:
+            raise ValueError('the result holds no element to compute errors for')
+        struct = tuple(self.shape) + ((2,) if self.use_complex else ())
+        out = dict(info={})
+        for key, o in collected:
+            out['info'][key] = o['info']
+            for name, val in o.items():
+                if name == 'info':
+                    continue
+                val = np.asarray(val)
+                if name not in out:
+                    out[name] = np.full(struct + val.shape, np.nan) if val.dtype.kind == 'f' else \
+                        np.full(struct + val.shape, -1, dtype=val.dtype)
+                if out[name].shape[len(struct):] != val.shape:
+                    raise ValueError('{}: the elements chose different numbers of alphas; use alpha= indices'.format(name))
+                out[name][key] = val
+                if self.use_hermiticity and key[0] != key[1]:
+                    # G_ji = conj(G_ij): the same errors; the imaginary part's values change sign
+                    flip = -1.0 if (len(key) == 3 and key[2] == 1 and name in ('window_weight', 'functional_value', 'A')) else 1.0
+                    out[name][(key[1], key[0]) + key[2:]] = val * flip if val.dtype.kind == 'f' else val
+        return out
+
     def _direct_input(self, worker):
         """G(tau) came as one array and the errors are plain (no covariance): specs can be cut from the
         arrays without sending every element through the worker's setters"""
@@ -1010,6 +1094,15 @@ class PoormanMaxEnt(ElementwiseMaxEnt):
         super(PoormanMaxEnt, self).__init__(*args, **kwargs)
         self.analyzer_offdiag_D = analyzer_offdiag_D
         self.D_add_constant = D_add_constant
+
+    def _posterior_models(self, jobs, result):
+        ar = result.analyzer_results
+        models = []
+        for (i, j), re in jobs:
+            A1 = (ar[i][i][0] if self.use_complex else ar[i][i])[self.analyzer_offdiag_D]['A_out']
+            A2 = (ar[j][j][0] if self.use_complex else ar[j][j])[self.analyzer_offdiag_D]['A_out']
+            models.append(DataDefaultModel(np.sqrt(A1 * A2) + self.D_add_constant, self.omega))
+        return models
 
     def run_offdiagonal(self):
         self.prepare_maxent_result(overwrite=False)

@@ -253,6 +253,37 @@ class TauMaxEnt(object):
     def set_cov_file(self, filename):
         self.set_cov(np.loadtxt(filename))
 
+    # ---- error bars ------------------------------------------------------------
+    def posterior_errors(self, result, alpha=None, windows=None, functionals=None, pointwise=False, timing=None):
+        """Posterior error bars of ``result`` (made by this object: its kernel, errors, default model and alpha mesh
+        are used) in the Gaussian approximation around the minimiser, computed on the device (``mxe_posterior_var``).
+        Not in the reference.
+
+        ``alpha``: an analyzer name (default: the result's default analyzer), an index, a sequence of indices,
+        ``'all'``, or ``'bryan'`` (the mixture over alpha with the weights of ``BryanAnalyzer``: mean
+        ``sum p_a x_a``, variance ``sum p_a [var_a + (x_a - mean)^2]``; needs the probability).
+        ``windows=[(lo, hi), ...]`` -> ``window_weight`` (the sum of H over the mesh points inside: the integral of
+        A) and ``window_err``; ``functionals=F`` (n_f, n_omega: weights on ``A delta_omega``) -> ``functional_value``,
+        ``functional_err``; ``pointwise=True`` -> ``A_err``, the standard deviation of A(omega_i) -- large and strongly
+        correlated between neighbouring points: only integrated quantities have meaningful errors.  Always there:
+        ``prior_err`` (windows, then functionals; also ``window_prior_err``, ``functional_prior_err``,
+        ``A_prior_err``), the error the default model alone would leave, ``alpha``, ``alpha_index`` and ``info``
+        (``nan_rows``: alphas whose H is not finite).  A sequence of alphas or ``'all'`` keeps an alpha axis in front.
+        With a ``PreblurKernel`` everything refers to A = B H."""
+        from . import posterior
+        loop = self.maxent_loop
+        spec = loop.make_spec()
+        posterior.check_alpha(spec, result.alpha)
+        H = np.asarray(result.element_array('H'))
+        logp = np.asarray(result.element_array('probability'), dtype=float)
+        item = dict(spec=spec, H=H, alpha=np.asarray(result.alpha, dtype=float), analysis=result.analyzer_results,
+                    probability=None if np.all(np.isnan(logp)) else logp, B=loop.A_of_H.matrix())
+        ids = loop.device_ids if loop.device_ids else (loop.device_id,)
+        return posterior.element_errors(self.K, self.omega, [item], alpha=alpha, windows=windows, functionals=functionals,
+                                        pointwise=pointwise, default_name=result.default_analyzer_name,
+                                        chi2_factor=loop.cost_function.chi2_factor, device_ids=ids[:1],
+                                        bryan=posterior.find_bryan(loop.analyzers), timing=timing)[0]
+
     # ---- tau ----------------------------------------------------------------
     def get_tau(self):
         return self.maxent_loop.get_data_variable()
