@@ -551,6 +551,27 @@ int  mxe_kramers_kronig(int device, int n_w, const double* w, const double* weig
                         int n_out, const double* w_out, int n_spec, const double* A,
                         double* out_G, float* out_ms);
 
+/* ---- binned Monte Carlo data: the covariance eigenbasis of every set (no counterpart in the reference) ---- */
+/* bins: n_sets x n_bins x n_data, host, C order: n_bins independent estimates of the n_data values of each set.  Per
+ * set, all sets in one launch (one workgroup each): the mean over the bins (double-double sums in a fixed order: the
+ * error does not grow with n_bins), X = (bins - mean) / sqrt(n_bins (n_bins - 1)), and the eigen-decomposition of the
+ * covariance of the mean C = X^T X as the one-sided Jacobi SVD of X (pivoted Householder QR first when
+ * n_bins > n_data; the n_bins rows of X themselves otherwise) -- C is never formed, eigenvalues are resolved down to
+ * (eps s_max)^2 instead of eps lambda_max.
+ *   threshold   absolute cut on the eigenvalues (cov_threshold).  Kept: lambda_k >= threshold and
+ *               lambda_k > (max(n_bins, n_data) eps)^2 lambda_max (the noise floor of a null direction).
+ *   out_mean    n_sets x n_data
+ *   out_var     n_sets x n_data: the kept eigenvalues, ASCENDING like eigh, in the first out_rank[s] entries (0 behind)
+ *   out_T       n_sets x n_data x n_data: row k = the eigenvector of out_var[k], its component of largest magnitude
+ *               (lowest index on ties) positive (zero rows behind the kept ones)
+ *   out_rank    n_sets: eigenvalues kept;  out_sweeps  n_sets: Jacobi sweeps taken
+ * A set's output does not depend on the other sets of the launch and repeats bit for bit.  MXE_ERR_ARG: n_sets < 1,
+ * n_bins < 2, n_data < 1 or > 512, n_bins * n_data > 2^31 - 1, a threshold that is negative or not finite, a NaN or an
+ * Inf anywhere in bins (nothing is launched in any of these cases); MXE_ERR_NUMERIC: a set whose Jacobi iteration did
+ * not converge in 60 sweeps, or whose squares overflow. */
+int  mxe_bins_eig(int device, int n_sets, int n_bins, int n_data, const double* bins, double threshold,
+                  double* out_mean, double* out_var, double* out_T, int32_t* out_rank, int32_t* out_sweeps);
+
 #ifdef __cplusplus
 }
 #endif

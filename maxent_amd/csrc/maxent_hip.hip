@@ -3581,3 +3581,62 @@ try {
     return MXE_OK;
 }
 MXE_CATCH_ALL
+
+// ---- binned Monte Carlo data: mean and covariance eigenbasis of every set in one launch (mxe_bins.hip.h) ----
+#include "mxe_bins.hip.h"
+
+extern "C" int mxe_bins_eig(int device, int n_sets, int n_bins, int n_data, const double* bins, double threshold,
+                            double* out_mean, double* out_var, double* out_T, int32_t* out_rank, int32_t* out_sweeps)
+try {
+    if (n_sets < 1 || n_bins < 2 || n_data < 1 || n_data > mxe::BINS_NMAX || !bins || !out_mean || !out_var || !out_T ||
+        !out_rank || !out_sweeps || !(threshold >= 0.0) || !std::isfinite(threshold)) return MXE_ERR_ARG;
+    if ((int64_t)n_bins * n_data > INT32_MAX) return MXE_ERR_ARG;
+    const size_t m = n_bins, n = n_data, ns = n_sets, nel = ns * m * n;
+    {   // a NaN or an Inf anywhere: x - x is then NaN (eight independent chains)
+        double acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        size_t i = 0;
+        for (; i + 8 <= nel; i += 8)
+            for (int q = 0; q < 8; ++q) acc[q] += bins[i + q] - bins[i + q];
+        for (; i < nel; ++i) acc[0] += bins[i] - bins[i];
+        for (int q = 0; q < 8; ++q) if (acc[q] != 0.0) return MXE_ERR_ARG;
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return MXE_ERR_NODEVICE;
+    if (device < 0 || device >= ndev) return MXE_ERR_ARG;
+    SVDCHK(hipSetDevice(device));
+    SvdScratch sc;
+    SVDCHK(hipStreamCreateWithFlags(&sc.stream, hipStreamNonBlocking));
+    mxe::BinsParams p;
+    p.m = n_bins; p.n = n_data;
+    p.rcap = (std::min(n_bins, n_data) + 1) & ~1;
+    p.scale = 1.0 / std::sqrt((double)n_bins * (double)(n_bins - 1));
+    p.threshold = threshold;
+    const double floor1 = (double)std::max(n_bins, n_data) * 2.220446049250313e-16;
+    p.floor2 = floor1 * floor1;
+    double* dbins;
+    SVDCHK(sc.alloc(&dbins, nel));
+    p.bins = dbins;
+    SVDCHK(sc.alloc(&p.A, (n_bins > n_data) ? nel : 1));
+    SVDCHK(sc.alloc(&p.Rm, ns * p.rcap * n)); SVDCHK(sc.alloc(&p.vk, ns * m));
+    SVDCHK(sc.alloc(&p.part, ns * mxe::BINS_NWAVE * n * 2)); SVDCHK(sc.alloc(&p.cn2, ns * n));
+    SVDCHK(sc.alloc(&p.perm, ns * n));
+    SVDCHK(sc.alloc(&p.out_mean, ns * n)); SVDCHK(sc.alloc(&p.out_var, ns * n));
+    SVDCHK(sc.alloc(&p.out_T, ns * n * n)); SVDCHK(sc.alloc(&p.out_info, ns * 4));
+    SVDCHK(hipMemcpyAsync(dbins, bins, nel * 8, hipMemcpyHostToDevice, sc.stream));
+    hipLaunchKernelGGL(mxe::bins_eig_kernel, dim3(n_sets), dim3(mxe::BINS_T), 0, sc.stream, p);
+    SVDCHK(hipGetLastError());
+    std::vector<int> hinfo(ns * 4);
+    SVDCHK(hipMemcpyAsync(out_mean, p.out_mean, ns * n * 8, hipMemcpyDeviceToHost, sc.stream));
+    SVDCHK(hipMemcpyAsync(out_var, p.out_var, ns * n * 8, hipMemcpyDeviceToHost, sc.stream));
+    SVDCHK(hipMemcpyAsync(out_T, p.out_T, ns * n * n * 8, hipMemcpyDeviceToHost, sc.stream));
+    SVDCHK(hipMemcpyAsync(hinfo.data(), p.out_info, hinfo.size() * 4, hipMemcpyDeviceToHost, sc.stream));
+    SVDCHK(hipStreamSynchronize(sc.stream));
+    int rc = MXE_OK;
+    for (size_t s = 0; s < ns; ++s) {
+        out_rank[s] = hinfo[s * 4];
+        out_sweeps[s] = hinfo[s * 4 + 2];
+        if (hinfo[s * 4 + 3] != 0) rc = MXE_ERR_NUMERIC;      // (Jacobi sweeps exhausted, or squares that overflow)
+    }
+    return rc;
+}
+MXE_CATCH_ALL

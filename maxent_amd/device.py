@@ -27,7 +27,9 @@ class MaxEntDeviceError(RuntimeError):
     pass
 
 
+_MXE_ERR_ARG = -1
 _MXE_ERR_LIMIT = -5
+_MXE_ERR_NUMERIC = -6
 #: most rows of a kernel matrix the device SVD takes (mxe_kernel_svd*: the rows + 216 doubles of the decomposition's LDS <= 60 KB)
 SVD_MAX_ROWS = 60 * 1024 // 8 - 216
 #: most significant directions (rows of R the pivoted QR keeps, SVD_RCAP of mxe_svd.hip.h) of a matrix the device SVD
@@ -153,6 +155,8 @@ SYMBOLS = [
                                            ctypes.POINTER(ctypes.c_float)]),
     ('mxe_kramers_kronig', ctypes.c_int, [ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, ctypes.c_int, _dp,
                                           ctypes.c_int, _dp, _dp, ctypes.POINTER(ctypes.c_float)]),
+    ('mxe_bins_eig', ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, ctypes.c_double,
+                                    _dp, _dp, _dp, _ip, _ip]),
 ]
 
 
@@ -454,6 +458,64 @@ def kramers_kronig(w, weight, eta, w_out, A, device=0, max_spectra=None, timing=
     if is_complex:
         G = G[0::2] + 1j * G[1::2]
     return G.reshape(lead + (n_out,))
+
+
+#: most data points of a set ``mxe_bins_eig`` takes (``BINS_NMAX``)
+BINS_MAX_DATA = 512
+
+
+def bins_keep(var, threshold, n_bins, n_data):
+    """The selection rule of ``mxe_bins_eig`` on a spectrum ``var`` of covariance eigenvalues: kept are those
+    ``>= threshold`` and ``> (max(n_bins, n_data) eps)^2 max(var)`` -- the second bound is the noise floor of a
+    singular value of the centred bins, which separates a null direction from a small eigenvalue.  Returns a mask."""
+    var = np.asarray(var, dtype=float)
+    if var.size == 0:
+        return np.zeros(0, dtype=bool)
+    floor = (max(int(n_bins), int(n_data)) * np.finfo(float).eps) ** 2
+    return (var >= threshold) & (var > floor * var.max()) & (var > 0.0)
+
+
+def bins_eig(bins, threshold, device=0):
+    """``mxe_bins_eig``: ``bins`` of shape (n_sets, n_bins, n_data) or (n_bins, n_data) -- independent estimates of
+    the data -- into the mean over the bins and the eigenbasis of the covariance of that mean, every set in one launch.
+    Returns one dict per set (one dict for 2-d ``bins``): ``mean`` (n_data), ``sigma`` (the square roots of the kept
+    eigenvalues, ascending), ``T`` (rank x n_data, row k the eigenvector of ``sigma[k]``), ``rank``, ``sweeps`` (Jacobi
+    sweeps taken)."""
+    lib = load_library()
+    b = np.asarray(bins)
+    single = b.ndim == 2
+    if single:
+        b = b[None]
+    if b.ndim != 3 or np.iscomplexobj(b):
+        raise ValueError('bins_eig: bins must be real, (n_sets, n_bins, n_data) or (n_bins, n_data); got %s' % (np.shape(bins),))
+    b = _c(b)
+    n_sets, n_bins, n_data = b.shape
+    if n_sets < 1 or n_bins < 2:
+        raise ValueError('bins_eig: at least one set and two bins are needed; got %d set(s) of %d bin(s)' % (n_sets, n_bins))
+    if n_data < 1 or n_data > BINS_MAX_DATA:
+        raise MaxEntDeviceError('mxe_bins_eig: %d data points per set; the device decomposition takes 1 to %d'
+                                % (n_data, BINS_MAX_DATA))
+    if device_count() < 1:
+        raise MaxEntDeviceError('no HIP device visible; the covariance eigenbasis of bins has no CPU fallback')
+    mean = np.empty((n_sets, n_data))
+    var = np.empty((n_sets, n_data))
+    T = np.empty((n_sets, n_data, n_data))
+    rank = np.zeros(n_sets, dtype=np.int32)
+    sweeps = np.zeros(n_sets, dtype=np.int32)
+    rc = lib.mxe_bins_eig(int(device), n_sets, n_bins, n_data, _p(b), float(threshold), _p(mean), _p(var), _p(T),
+                          _p(rank), _p(sweeps))
+    if rc == _MXE_ERR_NUMERIC:
+        raise MaxEntDeviceError('mxe_bins_eig: the Jacobi iteration of set(s) %s did not converge (sweeps %s), or the '
+                                'squares of the bins overflow' % (np.nonzero(sweeps >= 60)[0].tolist(), int(sweeps.max())))
+    if rc == _MXE_ERR_ARG:           # (sizes were checked above: what the library refuses here is a NaN or an Inf, before any launch)
+        raise ValueError('bins_eig: bins hold %d values that are not finite' % int((~np.isfinite(b)).sum()))
+    if rc != 0:
+        raise MaxEntDeviceError('mxe_bins_eig failed: ' + lib.mxe_strerror(rc).decode())
+    out = []
+    for s in range(n_sets):
+        k = int(rank[s])
+        out.append(dict(mean=mean[s].copy(), sigma=np.sqrt(var[s, :k]), T=T[s, :k].copy(), rank=k, sweeps=int(sweeps[s])))
+    return out[0] if single else out
 
 
 def entropy(kind, H, D, device=0):

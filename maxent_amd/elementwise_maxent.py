@@ -295,7 +295,10 @@ class ElementwiseMaxEnt(object):
         i, j = element
         self.set_G_element(worker, self.G_mat, (i, j),
                            True if i == j else re)
-        self.put_error(worker, self.get_error((i, j)))
+        err = self.get_error((i, j))
+        if self.__dict__.get('_errors_from_bins'):
+            err = err[0 if (re or i == j) else 1]       # (real and imaginary part have eigenbases of their own)
+        self.put_error(worker, err)
 
     def run_element(self, element, re=True):
         """one matrix element, like the reference's ``run_element``
@@ -952,6 +955,10 @@ class ElementwiseMaxEnt(object):
         # part: the feed and the arrays of _prepare_batch pick them the way they pick the parts of G(tau)
         stacked = np.concatenate([re_part.real, re_part.imag], axis=-1) + \
             1j * np.concatenate([im_part.real, im_part.imag], axis=-1)
+        self._set_G_iw_stacked(iomega, stacked, beta)
+
+    def _set_G_iw_stacked(self, iomega, stacked, beta):
+        """the tail of :meth:`set_G_iw_data`: ``stacked`` (M, M, 2 n_iw) as described there"""
         n = len(iomega)
 
         def feed(maxent, G_mat, elem, re):
@@ -1030,6 +1037,7 @@ class ElementwiseMaxEnt(object):
         """float, (T,) or (M, N, T) (reference elementwise_maxent.py:472-487)."""
         self.error = error
         self.error_dimension = 1
+        object.__setattr__(self, '_errors_from_bins', False)
         self.put_error = lambda maxent, err: maxent.set_error(err)
 
     def get_error(self, elem):
@@ -1050,7 +1058,109 @@ class ElementwiseMaxEnt(object):
         """(T, T) or (M, N, T, T) (reference elementwise_maxent.py:502-515)."""
         self.error_dimension = 2
         self.error = cov
+        object.__setattr__(self, '_errors_from_bins', False)
         self.put_error = lambda maxent, err: maxent.set_cov(err)
+
+    # ---- bins: all sets of the run through ONE mxe_bins_eig call ----------------------------------------
+    def _bins_eig(self, shape, sets_of, n_bins):
+        """``sets_of(i, j)``: the real bins (n_bins, n_data) of the real-part problem of element (i, j) and of its
+        imaginary-part problem (None: there is none).  Every set the run needs -- with ``use_hermiticity`` only
+        i <= j, imaginary parts only with ``use_complex`` and off the diagonal -- goes down in one call, on the first
+        of ``device_ids`` (the preparation is not sharded: the elements' solves are).  Returns
+        {(i, j): [statistics of the real part, of the imaginary part or None]}."""
+        from . import device
+        M, N = shape
+        where, sets = [], []
+        for i in range(M):
+            for j in range(N):
+                if self.use_hermiticity and i > j:
+                    continue
+                re_set, im_set = sets_of(i, j)
+                where.append((i, j, 0))
+                sets.append(re_set)
+                if self.use_complex and i != j and im_set is not None:
+                    where.append((i, j, 1))
+                    sets.append(im_set)
+        stack = np.ascontiguousarray(np.stack(sets), dtype=float)
+        self.maxent_diagonal._warn_few_bins(n_bins, stack.shape[-1])
+        ids = self.device_ids if self.device_ids else (self.maxent_diagonal._device_for_bins(),)
+        stats = device.bins_eig(stack, self.cov_threshold, device=ids[0])
+        table, public = {}, {}
+        for (i, j, c), st in zip(where, stats):
+            st = dict(st, n_bins=n_bins)
+            if st['rank'] == 0 and np.any(st['mean'] != 0.0):
+                raise AssertionError('bins of element {} {}: no eigenvalue of the covariance of the mean is above '
+                                     'cov_threshold = {}'.format(i, j, self.cov_threshold))
+            table.setdefault((i, j), [None, None])[c] = st if st['rank'] > 0 else None
+            public[(i, j, c) if self.use_complex else (i, j)] = st
+        object.__setattr__(self, 'bin_statistics', public)
+        return table
+
+    def _means_of_bins(self, table, shape, n_data):
+        """the (M, N, n_data) array of the means: real parts' + 1j imaginary parts' with ``use_complex``"""
+        G = np.zeros(tuple(shape) + (n_data,), dtype=complex if self.use_complex else float)
+        for (i, j), (st_re, st_im) in table.items():
+            if st_re is not None:
+                G[i, j] = G[i, j] + st_re['mean']
+            if st_im is not None:
+                G[i, j] = G[i, j] + 1j * st_im['mean']
+        return G
+
+    def _put_eigenbases(self, table):
+        """errors from bins: ``get_error`` gives the element's pair of statistics, ``_load_element`` picks the part that
+        is loaded and ``put_error`` hands the worker its precomputed (sigma, T), where ``set_cov`` would decompose a matrix"""
+        def put(maxent, st):
+            if st is None:
+                maxent.set_error(1.0)        # (a part without data -- all bins zero --: below G_threshold, nothing is solved)
+            else:
+                maxent._set_eigenbasis(st['sigma'], st['T'])
+        self.error_dimension = 2
+        self.error = table                   # (get_error(elem) -> table[elem])
+        self.put_error = put
+        object.__setattr__(self, '_errors_from_bins', True)
+
+    def set_G_tau_bins(self, tau, bins):
+        """``bins``: (n_bins, M, N, n_tau) array of independent estimates of G_ij(tau) (:meth:`TauMaxEnt.set_G_tau_bins`),
+        complex with ``use_complex``: real and imaginary parts are then sets of their own, each with the covariance of
+        its own mean.  The eigenbases of all elements the run needs come from one ``mxe_bins_eig`` call;
+        ``bin_statistics[(i, j)]`` (``[(i, j, c)]`` with ``use_complex``) holds ``mean``, ``sigma``, ``T``, ``rank`` and
+        ``n_bins``.  Not in the reference."""
+        tau = np.asarray(tau, dtype=float)
+        bins = TauMaxEnt._check_bins(tau, bins, 'G(tau) bins')
+        if bins.ndim != 4:
+            raise AssertionError('G(tau) bins must be (n_bins, M, N, n_tau); their shape is {}'.format(bins.shape))
+        cplx = np.iscomplexobj(bins)
+        if cplx and not self.use_complex:
+            raise AssertionError('complex G(tau) bins need use_complex=True')
+
+        def sets_of(i, j):
+            b = bins[:, i, j, :]
+            return b.real, (b.imag if cplx else None)
+        table = self._bins_eig(bins.shape[1:3], sets_of, bins.shape[0])
+        self.set_G_tau_data(tau, self._means_of_bins(table, bins.shape[1:3], len(tau)))
+        self._put_eigenbases(table)
+
+    def set_G_iw_bins(self, iomega, bins, beta=None):
+        """``bins``: complex (n_bins, M, M, n_iw) array of independent estimates of G_ij(i omega_n).  Every bin is split
+        as in :meth:`set_G_iw_data` -- (G_ij + G_ji) / 2 = K Re A_ij, (G_ij - G_ji) / (2i) = K Im A_ij (the latter with
+        ``use_complex``) -- and unfolded to stacked real values, whose mean and covariance enter as in
+        :meth:`set_G_tau_bins`."""
+        iomega = np.asarray(iomega, dtype=float)
+        bins = TauMaxEnt._check_bins(iomega, bins, 'G(i omega_n) bins', per_point=2)
+        if bins.ndim != 4 or bins.shape[1] != bins.shape[2]:
+            raise AssertionError('G(i omega_n) bins must be (n_bins, M, M, n_iw); their shape is {}'.format(bins.shape))
+
+        def sets_of(i, j):
+            a, b = bins[:, i, j, :], bins[:, j, i, :]
+            re_part = 0.5 * (a + b)
+            re_set = np.concatenate([re_part.real, re_part.imag], axis=-1)
+            if not self.use_complex or i == j:
+                return re_set, None
+            im_part = (a - b) / 2j
+            return re_set, np.concatenate([im_part.real, im_part.imag], axis=-1)
+        table = self._bins_eig(bins.shape[1:3], sets_of, bins.shape[0])
+        self._set_G_iw_stacked(iomega, self._means_of_bins(table, bins.shape[1:3], 2 * len(iomega)), beta)
+        self._put_eigenbases(table)
 
     def get_tau(self):
         d = self.maxent_diagonal.get_data_variable()

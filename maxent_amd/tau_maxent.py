@@ -253,6 +253,91 @@ class TauMaxEnt(object):
     def set_cov_file(self, filename):
         self.set_cov(np.loadtxt(filename))
 
+    # ---- bins: mean, covariance of the mean and its eigenbasis from the device ------------------------------
+    @staticmethod
+    def _check_bins(grid, bins, what, per_point=1):
+        """``bins`` as an array whose first axis are the bins and whose last the grid; raises like the other setters"""
+        bins = np.asarray(bins)
+        n = len(grid)
+        if bins.ndim < 2 or bins.shape[-1] != n:
+            raise AssertionError("{0} must have the bins on its first and the {1} values of the grid on its last axis; "
+                                 "its shape is {2}".format(what, n, bins.shape))
+        if bins.shape[0] < 2:
+            raise AssertionError('{0}: {1} bin(s); a covariance needs at least two'.format(what, bins.shape[0]))
+        if not np.all(np.isfinite(bins)):
+            raise AssertionError('{0} hold {1} values that are not finite'.format(what, int((~np.isfinite(bins)).sum())))
+        from . import device
+        if per_point * n > device.BINS_MAX_DATA:
+            raise AssertionError('{0}: {1} data values per set; the device decomposition takes at most {2} '
+                                 '(set_cov takes a covariance matrix of any size)'.format(what, per_point * n,
+                                                                                       device.BINS_MAX_DATA))
+        return bins
+
+    def _warn_few_bins(self, n_bins, n_data):
+        if n_bins <= n_data:
+            self.logtaker.error_message(
+                '{} bins for {} data values: the covariance of the mean is rank-deficient, at most {} directions of the '
+                'data are kept.', n_bins, n_data, n_bins - 1)
+
+    def _device_for_bins(self):
+        loop = self.maxent_loop
+        return loop.device_ids[0] if getattr(loop, 'device_ids', None) else getattr(loop, 'device_id', 0)
+
+    def _set_eigenbasis(self, sigma, T, mean=None):
+        """the job a fresh object holds after ``set_G_*_data`` of ``mean`` (default: the data as supplied last) and
+        ``set_cov`` of a covariance with the eigenvalues ``sigma**2`` and the eigenvectors ``T`` (rows): data and kernel
+        are rotated by ``T`` alone, whatever rotation there was (no hop from the previous one as in :meth:`set_cov`)"""
+        self.err = None              # no chi2 with stale errors while data and kernel change
+        self.G = self.cost_function._G_orig if mean is None else mean
+        self._transform(T, G_original_basis=True)
+        self.err = sigma
+
+    def _bins_eig(self, stacked_bins):
+        """mean and covariance eigenbasis of real ``stacked_bins`` (n_bins, n_data) from the device; changes nothing"""
+        from . import device
+        n_bins, n_data = stacked_bins.shape
+        self._warn_few_bins(n_bins, n_data)
+        st = device.bins_eig(stacked_bins, self.cov_threshold, device=self._device_for_bins())
+        if st['rank'] == 0:
+            raise AssertionError('no eigenvalue of the covariance of the mean is above cov_threshold = {}'.format(
+                self.cov_threshold))
+        return dict(st, n_bins=n_bins)
+
+    def _adopt_bins(self, st):
+        object.__setattr__(self, 'bin_statistics', st)
+        self._set_eigenbasis(st['sigma'], st['T'], mean=st['mean'])
+
+    def set_G_tau_bins(self, tau, bins):
+        """G(tau) as ``bins`` of shape (n_bins, n_tau): independent estimates (Monte Carlo bins).  The data become their
+        mean, the errors those of the covariance of the mean C = X^T X, X = (bins - mean) / sqrt(n_bins (n_bins - 1)):
+        the job is the one of ``set_G_tau_data(tau, mean)`` and ``set_cov(C)`` on a fresh object, with ``cov_threshold``
+        as the cut.  Mean and eigenbasis come from the device (``mxe_bins_eig``: the singular value decomposition of X;
+        C is never formed, and small eigenvalues keep their relative accuracy); ``bin_statistics`` holds ``mean``,
+        ``sigma``, ``T``, ``rank`` and ``n_bins``.  Bins that are refused leave the object as it was.  Not in the
+        reference."""
+        tau = np.asarray(tau, dtype=float)
+        bins = self._check_bins(tau, bins, 'G(tau) bins')
+        if bins.ndim != 2:
+            raise AssertionError('G(tau) bins must be (n_bins, n_tau); their shape is {}'.format(bins.shape))
+        if np.iscomplexobj(bins):
+            raise AssertionError('G(tau) bins must be real')
+        st = self._bins_eig(np.asarray(bins, dtype=float))
+        self._use_tau_kernel(tau)
+        self.tau = tau
+        self._adopt_bins(st)
+
+    def set_G_iw_bins(self, iomega, bins, beta=None):
+        """G(i omega_n) as complex ``bins`` of shape (n_bins, n_iw), see :meth:`set_G_tau_bins` and
+        :meth:`set_G_iw_data`: every bin is unfolded to the stacked real vector ``[Re G ; Im G]``, mean and covariance
+        are those of the 2 n_iw stacked values."""
+        iomega = np.asarray(iomega, dtype=float)
+        bins = self._check_bins(iomega, bins, 'G(i omega_n) bins', per_point=2)
+        if bins.ndim != 2:
+            raise AssertionError('G(i omega_n) bins must be (n_bins, n_iw); their shape is {}'.format(bins.shape))
+        st = self._bins_eig(kernels.IOmegaKernel.unfold(None, bins))       # (every bin as [Re ; Im]; needs no kernel object)
+        self._use_iomega_kernel(iomega, beta)
+        self._adopt_bins(st)
+
     # ---- error bars ------------------------------------------------------------
     def posterior_errors(self, result, alpha=None, windows=None, functionals=None, pointwise=False, timing=None):
         """Posterior error bars of ``result`` (made by this object: its kernel, errors, default model and alpha mesh
