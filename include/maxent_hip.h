@@ -45,6 +45,10 @@
  *   get_G_w_from_A_w  maxent_util.py:43-132                | mxe_kramers_kronig (also get_chi_w_from_A_w)
  *   (nothing: the reference gives no error bars)           | mxe_posterior_var (posterior variances of
  *                                                          |   integrated quantities, diagonal of the covariance)
+ *   (nothing: users loop run() over their resamples)       | mxe_bins_resample (the rotated data of every
+ *                                                          |   jackknife / bootstrap resample of the bins),
+ *                                                          |   mxe_resample_reduce (mean, spread and functional
+ *                                                          |   covariances of the H rows they were continued to)
  *   the arrays of MaxEntResult (numpy allocations)         | mxe_host_alloc / mxe_host_free (optional:
  *     maxent_result.py:835-967                             |   page-locked destinations, one DMA per fetch)
  *
@@ -571,6 +575,51 @@ int  mxe_kramers_kronig(int device, int n_w, const double* w, const double* weig
  * not converge in 60 sweeps, or whose squares overflow. */
 int  mxe_bins_eig(int device, int n_sets, int n_bins, int n_data, const double* bins, double threshold,
                   double* out_mean, double* out_var, double* out_T, int32_t* out_rank, int32_t* out_sweeps);
+
+/* ---- jackknife / bootstrap resampling of the bins (no counterpart in the reference) ---- */
+/* The rotated data of every resample of every set, one launch (one workgroup per set).
+ *   bins        n_sets x n_bins x n_data, as for mxe_bins_eig
+ *   counts      n_res x n_bins: counts[r][b] >= 0 is the multiplicity of bin b in resample r, N_r = sum_b counts[r][b] > 0.
+ *               One table for every set of the call: bins are joint measurements, all sets see the same resample.
+ *   T, rank     n_sets x n_data x n_data and n_sets: out_T and out_rank of mxe_bins_eig
+ *   out_mean    n_sets x n_data: the mean over the bins, formed by the code mxe_bins_eig runs -- the same bits
+ *   out_dev     n_sets x n_res x n_data (may be NULL): out_dev[r][k] = sum_j T[k][j] D[r][j] with the deviation of the
+ *               resampled mean D[r] = sum_b counts[r][b] (bins[b] - mean) / N_r.  A resampled mean is never formed as a
+ *               sum of raw bins: the deviations are ~1/n_bins of the data and keep their own relative accuracy.
+ *   out_G       n_sets x n_res x n_data: out_G[r][k] = sum_j T[k][j] mean[j] + out_dev[r][k], the data of resample r in
+ *               the eigenbasis.  Rows k >= rank of out_G and out_dev are zeros.
+ *   out_ms      device time of the kernel (may be NULL)
+ * Both products run as v_mfma_f64_16x16x4_f64 tiles, every sum over all bins (all data points) in index order inside one
+ * wavefront: no atomics, a set's output does not depend on the other sets and repeats bit for bit.  MXE_ERR_ARG (nothing
+ * is launched): what mxe_bins_eig refuses in its sizes and bins, n_res < 1, n_res * n_bins or n_res * n_data > 2^31 - 1, a
+ * negative count, a row of counts that sums to 0, a rank outside 0 .. n_data, a NaN or an Inf in bins or T. */
+int  mxe_bins_resample(int device, int n_sets, int n_bins, int n_data, const double* bins,
+                       int n_res, const int32_t* counts, const double* T, const int32_t* rank,
+                       double* out_mean, double* out_G, double* out_dev, float* out_ms);
+
+/* Mean, spread and functional covariances of groups of hidden images (the resamples of one matrix element each), one
+ * launch (one workgroup per group).  Group g owns the rows group_offset[g] .. group_offset[g + 1] - 1 (group_offset[0] = 0,
+ * not decreasing; a group may be empty), rows = group_offset[n_groups].
+ *   H           rows x n_omega on the host, or NULL: row r is problem problem_index[r] (chain * n_alpha + alpha index; NULL:
+ *               r itself) of the last launch on ctx, read where it lies on the device -- no H row crosses to the host
+ *   scale       n_groups: the factor on the centred sums of squares ((n - 1) / n jackknife, 1 / (n - 1) bootstrap)
+ *   F           n_f x n_omega weights on H (n_f may be 0)
+ *   out_fval    rows x n_f: F H_row of every row
+ *   out_used    n_groups: the rows of the group that are finite.  A failed alpha leaves H = NaN; such a row is left out of
+ *               everything below.
+ *   out_mean    n_groups x n_omega: the mean over the used rows, added in row order
+ *   out_var     n_groups x n_omega: scale * sum (H_r - mean)^2, a second pass in row order
+ *   out_fmean   n_groups x n_f, out_fcov n_groups x n_f x n_f: the same of the functional values (scaled centred covariance)
+ *   out_ms      device time of the kernel (may be NULL)
+ * Every output pointer may be NULL.  A group with fewer than two used rows has NaN in out_var and out_fcov (and in its means
+ * when it has none); the other groups are not touched by it.  Fixed summation order, no atomics: a group's bits do not depend
+ * on the other groups and repeat.  MXE_ERR_STATE: H == NULL and nothing was launched.  MXE_ERR_ARG: n_groups < 1, offsets
+ * that decrease or do not start at 0, a problem_index outside the last launch, a scale or an F that is not finite, sizes
+ * whose products exceed 2^31 - 1. */
+int  mxe_resample_reduce(mxe_ctx* ctx, int n_groups, const int32_t* group_offset, const double* H,
+                         const int32_t* problem_index, const double* scale, int n_f, const double* F,
+                         double* out_mean, double* out_var, double* out_fval, double* out_fmean, double* out_fcov,
+                         int32_t* out_used, float* out_ms);
 
 #ifdef __cplusplus
 }

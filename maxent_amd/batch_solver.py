@@ -436,10 +436,12 @@ class BatchSolver(object):
         the results then come as a :class:`LazySols` (per-scan dicts built when asked for), nothing per scan is done here.
         ``specs``: dicts with G, err, U_rot (or None), D, kind, v0, alpha (equal lengths).  Returns
         (list of per-spec result dicts in the order of ``specs``, info).  ``want_H``: 'lazy' (default),
-        True (fetched now) or False.  ``select`` = (linefit_deg, gamma[, default]): the three default analyzers' alphas are
+        True (fetched now) or False.  ``select`` = (linefit_deg, gamma[, default[, rows]]): the three default analyzers' alphas are
         picked on the device behind the solve (``mxe_select3_launch``) and come back as ``device_select`` of every result
         -- the indices of all three and the H rows of analyzer ``default`` (0 line fit, 1 chi2 curvature, 2 entropy: the one
-        ``result.A_out`` shows) at once, the rows of the other two when somebody looks at them; None: not.
+        ``result.A_out`` shows) at once, the rows of the other two when somebody looks at them; ``rows`` given and false: only
+        the indices come over, every picked row stays on the device (a caller that works on them there: ``mxe_resample_reduce``);
+        None: not.
         ``while_waiting(results)``: called while the kernel runs, with the result dicts complete but for their VALUES (the
         arrays are there and are filled behind it) -- a caller builds its records from them then; only with one device and
         neither ``want_logdet`` nor ``output_map`` (which add keys later): who passes it checks that it was called."""
@@ -480,6 +482,9 @@ class BatchSolver(object):
         picks = [None] * N
         conv = {}
         eager = int(select[2]) if select is not None and len(select) > 2 else 0
+        # (a fourth entry that is false: only the indices of the picks come over, their rows stay on the device for a caller that
+        #  works on them there -- mxe_resample_reduce)
+        pick_rows = not (select is not None and len(select) > 3 and not select[3])
         sel_params = (int(select[0]), float(select[1])) if select is not None else None
 
         def begin(r):
@@ -498,11 +503,12 @@ class BatchSolver(object):
                 outs[r] = c.result_arrays()
                 conv[r] = np.empty(outs[r]['converged'].shape, dtype=bool)
             if select is not None:
-                idx, row = c.select3_arrays(1)
+                idx, row = c.select3_arrays(1) if pick_rows else (np.empty((3, c._n_chain), dtype=np.int32), None)
                 rows = [LazyRows(self, r, w, c._n_chain, self.n_omega) for w in range(3)]
-                rows[eager]._val = row[0]
+                if pick_rows:
+                    rows[eager]._val = row[0]
                 for w in range(3):
-                    if w != eager:
+                    if w != eager or not pick_rows:
                         self._pending.append(weakref.ref(rows[w]))
                 picks[r] = (idx, rows, row)
 
@@ -521,7 +527,7 @@ class BatchSolver(object):
             if select is not None:
                 # (the indices of all three analyzers and the rows of the result's default analyzer; the rows of the other two when
                 #  somebody looks at them)
-                c.select3_fetch_rows(first=eager, count=1, idx=picks[r][0], rows=picks[r][2])
+                c.select3_fetch_rows(first=eager, count=1 if pick_rows else 0, idx=picks[r][0], rows=picks[r][2])
 
         def skeleton():
             # what of the results does not wait for the device: built while the kernel runs

@@ -310,6 +310,9 @@ struct mxe_ctx {
     // mxe_posterior_var scratch: alpha | H rows | F | var | prior | diag;  elem | row
     DevBuf<double> pv_d;
     DevBuf<int> pv_i;
+    // mxe_resample_reduce scratch: scale | H rows | F | fval | mean | var | fmean | fcov;  offsets | flags | used | rows
+    DevBuf<double> rr_d;
+    DevBuf<int> rr_i;
     DevBuf<double> rows_out;        // mxe_fetch_rows: the selected rows, gathered on the device
     DevBuf<int> rows_idx;
     double chi2_factor = 1.0;     // of the staged chains (mxe_opts.chi2_factor)
@@ -621,6 +624,7 @@ void mxe_ctx_destroy(mxe_ctx* ctx)
     ctx->ev_x.release(); ctx->ev_alpha.release(); ctx->ev_scal.release(); ctx->ev_vecw.release(); ctx->ev_vecs.release();
     ctx->ev_mat.release(); ctx->ev_elem.release();
     ctx->pv_d.release(); ctx->pv_i.release();
+    ctx->rr_d.release(); ctx->rr_i.release();
     if (ctx->ev0) hipEventDestroy(ctx->ev0);
     if (ctx->ev1) hipEventDestroy(ctx->ev1);
     if (ctx->ev_mark) hipEventDestroy(ctx->ev_mark);
@@ -3638,5 +3642,146 @@ try {
         if (hinfo[s * 4 + 3] != 0) rc = MXE_ERR_NUMERIC;      // (Jacobi sweeps exhausted, or squares that overflow)
     }
     return rc;
+}
+MXE_CATCH_ALL
+
+// ---- resampling of the bins: the rotated data of every jackknife / bootstrap resample, and the reduction of the
+// ---- H rows they were continued to (mxe_resample.hip.h) ----
+#include "mxe_resample.hip.h"
+
+namespace {
+// a NaN or an Inf anywhere: x - x is then NaN (eight independent chains)
+bool all_finite(const double* x, size_t nel)
+{
+    double acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    size_t i = 0;
+    for (; i + 8 <= nel; i += 8)
+        for (int q = 0; q < 8; ++q) acc[q] += x[i + q] - x[i + q];
+    for (; i < nel; ++i) acc[0] += x[i] - x[i];
+    for (int q = 0; q < 8; ++q) if (acc[q] != 0.0) return false;
+    return true;
+}
+} // namespace
+
+extern "C" int mxe_bins_resample(int device, int n_sets, int n_bins, int n_data, const double* bins,
+                                 int n_res, const int32_t* counts, const double* T, const int32_t* rank,
+                                 double* out_mean, double* out_G, double* out_dev, float* out_ms)
+try {
+    if (n_sets < 1 || n_bins < 2 || n_data < 1 || n_data > mxe::BINS_NMAX || !bins || n_res < 1 || !counts || !T || !rank ||
+        !out_mean || !out_G) return MXE_ERR_ARG;
+    if ((int64_t)n_bins * n_data > INT32_MAX || (int64_t)n_res * n_bins > INT32_MAX || (int64_t)n_res * n_data > INT32_MAX)
+        return MXE_ERR_ARG;
+    const size_t m = n_bins, n = n_data, ns = n_sets, nr = n_res, nel = ns * m * n;
+    std::vector<double> hNr(nr);
+    for (size_t r = 0; r < nr; ++r) {
+        int64_t s = 0;
+        for (size_t b = 0; b < m; ++b) {
+            const int32_t c = counts[r * m + b];
+            if (c < 0) return MXE_ERR_ARG;
+            s += c;
+        }
+        if (s <= 0) return MXE_ERR_ARG;
+        hNr[r] = (double)s;
+    }
+    for (size_t s = 0; s < ns; ++s) if (rank[s] < 0 || rank[s] > n_data) return MXE_ERR_ARG;
+    if (!all_finite(bins, nel) || !all_finite(T, ns * n * n)) return MXE_ERR_ARG;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return MXE_ERR_NODEVICE;
+    if (device < 0 || device >= ndev) return MXE_ERR_ARG;
+    SVDCHK(hipSetDevice(device));
+    SvdScratch sc;
+    SVDCHK(hipStreamCreateWithFlags(&sc.stream, hipStreamNonBlocking));
+    mxe::ResampleParams p;
+    p.m = n_bins; p.n = n_data; p.n_res = n_res;
+    double *dbins, *dNr, *dT;
+    int *dcounts, *drank;
+    SVDCHK(sc.alloc(&dbins, nel)); SVDCHK(sc.alloc(&dcounts, nr * m)); SVDCHK(sc.alloc(&dNr, nr));
+    SVDCHK(sc.alloc(&dT, ns * n * n)); SVDCHK(sc.alloc(&drank, ns));
+    SVDCHK(sc.alloc(&p.part, ns * mxe::BINS_NWAVE * n * 2)); SVDCHK(sc.alloc(&p.D, ns * nr * n));
+    SVDCHK(sc.alloc(&p.out_mean, ns * n)); SVDCHK(sc.alloc(&p.out_G, ns * nr * n)); SVDCHK(sc.alloc(&p.out_dev, ns * nr * n));
+    p.bins = dbins; p.counts = dcounts; p.Nr = dNr; p.T = dT; p.rank = drank;
+    SVDCHK(hipMemcpyAsync(dbins, bins, nel * 8, hipMemcpyHostToDevice, sc.stream));
+    SVDCHK(hipMemcpyAsync(dcounts, counts, nr * m * 4, hipMemcpyHostToDevice, sc.stream));
+    SVDCHK(hipMemcpyAsync(dNr, hNr.data(), nr * 8, hipMemcpyHostToDevice, sc.stream));
+    SVDCHK(hipMemcpyAsync(dT, T, ns * n * n * 8, hipMemcpyHostToDevice, sc.stream));
+    SVDCHK(hipMemcpyAsync(drank, rank, ns * 4, hipMemcpyHostToDevice, sc.stream));
+    if (out_ms) {
+        SVDCHK(hipEventCreate(&sc.e0)); SVDCHK(hipEventCreate(&sc.e1));
+        SVDCHK(hipEventRecord(sc.e0, sc.stream));
+    }
+    hipLaunchKernelGGL(mxe::bins_resample_kernel, dim3(n_sets), dim3(mxe::BINS_T), 0, sc.stream, p);
+    SVDCHK(hipGetLastError());
+    if (out_ms) SVDCHK(hipEventRecord(sc.e1, sc.stream));
+    SVDCHK(hipMemcpyAsync(out_mean, p.out_mean, ns * n * 8, hipMemcpyDeviceToHost, sc.stream));
+    SVDCHK(hipMemcpyAsync(out_G, p.out_G, ns * nr * n * 8, hipMemcpyDeviceToHost, sc.stream));
+    if (out_dev) SVDCHK(hipMemcpyAsync(out_dev, p.out_dev, ns * nr * n * 8, hipMemcpyDeviceToHost, sc.stream));
+    SVDCHK(hipStreamSynchronize(sc.stream));
+    if (out_ms) SVDCHK(hipEventElapsedTime(out_ms, sc.e0, sc.e1));
+    return MXE_OK;
+}
+MXE_CATCH_ALL
+
+extern "C" int mxe_resample_reduce(mxe_ctx* ctx, int n_groups, const int32_t* group_offset, const double* H,
+                                   const int32_t* problem_index, const double* scale, int n_f, const double* F,
+                                   double* out_mean, double* out_var, double* out_fval, double* out_fmean, double* out_fcov,
+                                   int32_t* out_used, float* out_ms)
+try {
+    if (!ctx || n_groups < 1 || !group_offset || !scale || n_f < 0 || (n_f > 0 && !F)) return MXE_ERR_ARG;
+    if (group_offset[0] != 0) return MXE_ERR_ARG;
+    for (int g = 0; g < n_groups; ++g) {
+        if (group_offset[g + 1] < group_offset[g]) return MXE_ERR_ARG;
+        if (!std::isfinite(scale[g])) return MXE_ERR_ARG;
+    }
+    if (!H && !ctx->launched) return MXE_ERR_STATE;
+    const size_t rows = (size_t)group_offset[n_groups], nw = ctx->n_omega, nf = n_f, ng = n_groups;
+    if (rows * nw > 0x7fffffffull || rows * std::max<size_t>(nf, 1) > 0x7fffffffull || nf * nw > 0x7fffffffull ||
+        ng * nw > 0x7fffffffull || ng * nf * nf > 0x7fffffffull) return MXE_ERR_ARG;
+    const size_t n_last = (size_t)ctx->n_chain * ctx->n_alpha;
+    // integers: offsets [ng + 1] | scratch flags [rows] | used [ng] | rows of the launch [rows] (H == NULL)
+    std::vector<int> hi(group_offset, group_offset + ng + 1);
+    const size_t iO = 0, iK = iO + ng + 1, iU = iK + rows, iR = iU + ng, itotal = iR + (H ? 0 : rows);
+    hi.resize(itotal, 0);
+    if (!H)
+        for (size_t r = 0; r < rows; ++r) {
+            const int row = problem_index ? problem_index[r] : (int)r;
+            if (row < 0 || (size_t)row >= n_last) return MXE_ERR_ARG;
+            hi[iR + r] = row;
+        }
+    if (nf && !all_finite(F, nf * nw)) return MXE_ERR_ARG;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    // doubles: scale [ng] | H [rows][nw] (when handed in) | F [nf][nw] | fval [rows][nf] | mean, var [ng][nw] | fmean [ng][nf] | fcov [ng][nf][nf]
+    const size_t oH = ng, oF = oH + (H ? rows * nw : 0), oV = oF + nf * nw, oM = oV + rows * nf, oS = oM + ng * nw,
+                 oFm = oS + ng * nw, oFc = oFm + ng * nf, total = oFc + ng * nf * nf;
+    HIPCHK(ctx, ctx->rr_d.ensure(total));
+    HIPCHK(ctx, ctx->rr_i.ensure(itotal));
+    double* d = ctx->rr_d.p;
+    int* di = ctx->rr_i.p;
+    HIPCHK(ctx, hipMemcpyAsync(d, scale, ng * 8, hipMemcpyHostToDevice, ctx->stream));
+    if (H && rows) HIPCHK(ctx, hipMemcpyAsync(d + oH, H, rows * nw * 8, hipMemcpyHostToDevice, ctx->stream));
+    if (nf) HIPCHK(ctx, hipMemcpyAsync(d + oF, F, nf * nw * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(di, hi.data(), itotal * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    mxe::ReduceParams rp;
+    rp.H = H ? d + oH : ctx->dout_H.p; rp.row = H ? nullptr : di + iR;
+    rp.off = di + iO; rp.scale = d; rp.F = d + oF; rp.nw = (int)nw; rp.n_f = n_f;
+    rp.ok = di + iK; rp.fval = d + oV; rp.mean = d + oM; rp.var = d + oS; rp.fmean = d + oFm; rp.fcov = d + oFc; rp.used = di + iU;
+    SvdScratch sc;                    // (the two events of the timing, released on every path)
+    if (out_ms) {
+        HIPCHK(ctx, hipEventCreate(&sc.e0)); HIPCHK(ctx, hipEventCreate(&sc.e1));
+        HIPCHK(ctx, hipEventRecord(sc.e0, ctx->stream));
+    }
+    hipLaunchKernelGGL(mxe::resample_reduce_kernel, dim3((unsigned)n_groups), dim3(256), 0, ctx->stream, rp);
+    HIPCHK(ctx, hipGetLastError());
+    if (out_ms) HIPCHK(ctx, hipEventRecord(sc.e1, ctx->stream));
+    if (out_mean) HIPCHK(ctx, hipMemcpyAsync(out_mean, d + oM, ng * nw * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (out_var) HIPCHK(ctx, hipMemcpyAsync(out_var, d + oS, ng * nw * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (out_fval && rows * nf) HIPCHK(ctx, hipMemcpyAsync(out_fval, d + oV, rows * nf * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (out_fmean && nf) HIPCHK(ctx, hipMemcpyAsync(out_fmean, d + oFm, ng * nf * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (out_fcov && nf) HIPCHK(ctx, hipMemcpyAsync(out_fcov, d + oFc, ng * nf * nf * 8, hipMemcpyDeviceToHost, ctx->stream));
+    std::vector<int> hused(ng);
+    if (out_used) HIPCHK(ctx, hipMemcpyAsync(hused.data(), di + iU, ng * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, stream_wait(ctx->stream));
+    if (out_used) for (size_t g = 0; g < ng; ++g) out_used[g] = hused[g];
+    if (out_ms) HIPCHK(ctx, hipEventElapsedTime(out_ms, sc.e0, sc.e1));
+    return MXE_OK;
 }
 MXE_CATCH_ALL

@@ -72,34 +72,14 @@ __device__ __forceinline__ void bins_two_sum(double a, double b, double& s, doub
     e = (a - (s - bb)) + (b - bb);
 }
 
-__global__ __launch_bounds__(BINS_T)
-void bins_eig_kernel(const BinsParams p)
+// The mean over the m bins of one set (n columns), by the whole workgroup of BINS_T threads: wavefront w sums the rows
+// of chunk w serially in double-double, lanes over the columns; the BINS_NWAVE partial sums are added in chunk order and
+// divided in double-double.  ``part``: [BINS_NWAVE][n][2] of device memory, ``meanv``: [n] of LDS; both hold the result
+// (and ``out_mean``) behind the barrier this ends with.  Shared by bins_eig_kernel and bins_resample_kernel
+// (mxe_resample.hip.h): their means are the same bits.
+__device__ __forceinline__ void bins_mean(const double* bins, int m, int n, double* part, double* meanv, double* out_mean)
 {
-    const int set = blockIdx.x;
-    const int m = p.m, n = p.n;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const double* bins = p.bins + (size_t)set * m * n;
-    double* A = p.A + ((m > n) ? (size_t)set * n * m : 0);
-    double* Rm = p.Rm + (size_t)set * p.rcap * n;
-    double* vk = p.vk + (size_t)set * m;
-    double* part = p.part + (size_t)set * BINS_NWAVE * n * 2;
-    double* cn2 = p.cn2 + (size_t)set * n;
-    int* perm = p.perm + (size_t)set * n;
-    double* out_mean = p.out_mean + (size_t)set * n;
-    double* out_var = p.out_var + (size_t)set * n;
-    double* out_T = p.out_T + (size_t)set * n * n;
-    int* out_info = p.out_info + (size_t)set * 4;
-
-    __shared__ double tile[64][65];
-    __shared__ double meanv[BINS_NMAX];
-    __shared__ double s2[BINS_NMAX];
-    __shared__ int order[BINS_NMAX];
-    __shared__ double redv[BINS_NWAVE];
-    __shared__ int redi[BINS_NWAVE];
-    __shared__ int sh_piv, sh_stop, sh_rot;
-    __shared__ double sh_nrm0;
-
-    // ---- 1. mean: wavefront w sums the rows of chunk w, lanes over the columns ----
     {
         const int ch = (m + BINS_NWAVE - 1) / BINS_NWAVE;
         const int i0 = min(wave * ch, m), i1 = min(i0 + ch, m);
@@ -133,6 +113,37 @@ void bins_eig_kernel(const BinsParams p)
         out_mean[j] = mean;
     }
     __syncthreads();
+}
+
+__global__ __launch_bounds__(BINS_T)
+void bins_eig_kernel(const BinsParams p)
+{
+    const int set = blockIdx.x;
+    const int m = p.m, n = p.n;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const double* bins = p.bins + (size_t)set * m * n;
+    double* A = p.A + ((m > n) ? (size_t)set * n * m : 0);
+    double* Rm = p.Rm + (size_t)set * p.rcap * n;
+    double* vk = p.vk + (size_t)set * m;
+    double* part = p.part + (size_t)set * BINS_NWAVE * n * 2;
+    double* cn2 = p.cn2 + (size_t)set * n;
+    int* perm = p.perm + (size_t)set * n;
+    double* out_mean = p.out_mean + (size_t)set * n;
+    double* out_var = p.out_var + (size_t)set * n;
+    double* out_T = p.out_T + (size_t)set * n * n;
+    int* out_info = p.out_info + (size_t)set * 4;
+
+    __shared__ double tile[64][65];
+    __shared__ double meanv[BINS_NMAX];
+    __shared__ double s2[BINS_NMAX];
+    __shared__ int order[BINS_NMAX];
+    __shared__ double redv[BINS_NWAVE];
+    __shared__ int redi[BINS_NWAVE];
+    __shared__ int sh_piv, sh_stop, sh_rot;
+    __shared__ double sh_nrm0;
+
+    // ---- 1. mean ----
+    bins_mean(bins, m, n, part, meanv, out_mean);
 
     // ---- 2. X = (bins - mean) * scale ----
     int r = 0;

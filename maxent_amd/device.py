@@ -157,6 +157,10 @@ SYMBOLS = [
                                           ctypes.c_int, _dp, _dp, ctypes.POINTER(ctypes.c_float)]),
     ('mxe_bins_eig', ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, ctypes.c_double,
                                     _dp, _dp, _dp, _ip, _ip]),
+    ('mxe_bins_resample', ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, ctypes.c_int, _ip, _dp, _ip,
+                                         _dp, _dp, _dp, ctypes.POINTER(ctypes.c_float)]),
+    ('mxe_resample_reduce', ctypes.c_int, [_vp, ctypes.c_int, _ip, _dp, _ip, _dp, ctypes.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _ip,
+                                           ctypes.POINTER(ctypes.c_float)]),
 ]
 
 
@@ -518,6 +522,55 @@ def bins_eig(bins, threshold, device=0):
     return out[0] if single else out
 
 
+
+def bins_resample(bins, counts, T, rank, device=0, want_dev=True, timing=None):
+    """``mxe_bins_resample``: the rotated data of every resample of every set, one launch.  ``bins``: (n_sets, n_bins,
+    n_data) or (n_bins, n_data); ``counts``: (n_res, n_bins) multiplicities, one table for all sets; ``T``: (n_sets, n_data,
+    n_data) eigenvector rows as ``mxe_bins_eig`` writes them (zero rows behind the kept ones), ``rank``: (n_sets,).  Returns
+    a dict: ``mean`` (n_sets, n_data) -- the bits of ``bins_eig`` --, ``G`` (n_sets, n_res, n_data) = T mean + dev, ``dev``
+    (the rotated deviations of the resampled means, with ``want_dev``); rows k >= rank are zeros.  2-d ``bins``: without
+    the leading axis.  ``timing``: a dict that receives the device time ``ms`` of the kernel."""
+    lib = load_library()
+    b = np.asarray(bins)
+    single = b.ndim == 2
+    if single:
+        b = b[None]
+    if b.ndim != 3 or np.iscomplexobj(b):
+        raise ValueError('bins_resample: bins must be real, (n_sets, n_bins, n_data) or (n_bins, n_data); got %s' % (np.shape(bins),))
+    b = _c(b)
+    n_sets, n_bins, n_data = b.shape
+    cnt = np.asarray(counts)
+    if cnt.ndim != 2 or cnt.shape[1] != n_bins or cnt.shape[0] < 1 or cnt.dtype.kind not in 'iu':
+        raise ValueError('bins_resample: counts must be integers of shape (n_res >= 1, n_bins = %d); got %s %s'
+                         % (n_bins, cnt.dtype, cnt.shape))
+    cnt = _c(cnt, np.int32)
+    n_res = cnt.shape[0]
+    Tm = _c(np.asarray(T, dtype=float).reshape(n_sets, n_data, n_data))
+    rk = _c(np.asarray(rank).reshape(n_sets), np.int32)
+    if device_count() < 1:
+        raise MaxEntDeviceError('no HIP device visible; the resampling of bins has no CPU fallback')
+    mean = np.empty((n_sets, n_data))
+    G = np.empty((n_sets, n_res, n_data))
+    dev = np.empty((n_sets, n_res, n_data)) if want_dev else None
+    ms = ctypes.c_float(0)
+    rc = lib.mxe_bins_resample(int(device), n_sets, n_bins, n_data, _p(b), n_res, _p(cnt), _p(Tm), _p(rk), _p(mean), _p(G),
+                               _p(dev), ctypes.byref(ms))
+    if rc == _MXE_ERR_ARG:
+        raise ValueError('mxe_bins_resample refused its arguments: %d set(s) of %d bins x %d values (2 bins and 1 to %d values are '
+                         'needed), %d resample(s), counts that are negative or a row of them that sums to 0, a rank outside '
+                         '0..n_data, or values of bins or T that are not finite' % (n_sets, n_bins, n_data, BINS_MAX_DATA, n_res))
+    if rc != 0:
+        raise MaxEntDeviceError('mxe_bins_resample failed: ' + lib.mxe_strerror(rc).decode())
+    if timing is not None:
+        timing['ms'] = float(ms.value)
+    out = dict(mean=mean, G=G)
+    if want_dev:
+        out['dev'] = dev
+    if single:
+        out = dict((k, v[0]) for k, v in out.items())
+    return out
+
+
 def entropy(kind, H, D, device=0):
     """``mxe_entropy``: S, dS/dH and diag(d2S/dH2) of hidden images given directly; ``H``: (P, n) or (n,)."""
     lib = load_library()
@@ -842,6 +895,57 @@ class DeviceContext(object):
         out = dict(var=var, prior=prior)
         if want_diag:
             out['diag'] = diag
+        return out
+
+    def resample_reduce(self, group_offset, scale, H=None, problem_index=None, F=None, want=('mean', 'var', 'fval', 'fmean', 'fcov'),
+                        timing=None):
+        """``mxe_resample_reduce``: mean, spread and functional covariances of groups of hidden images.  Group g owns the
+        rows ``group_offset[g] .. group_offset[g + 1] - 1``; ``H``: (rows, n_omega) on the host, or None for the rows
+        ``problem_index`` (chain * n_alpha + alpha index) of the last launch, read on the device.  ``scale``: (n_groups,),
+        the factor on the centred sums of squares.  ``F``: (n_f, n_omega) weights on H.  Returns a dict with ``used``
+        (n_groups: finite rows -- the others are left out) and what ``want`` names: ``mean``, ``var`` (n_groups, n_omega),
+        ``fval`` (rows, n_f), ``fmean`` (n_groups, n_f), ``fcov`` (n_groups, n_f, n_f).  A group with fewer than two used
+        rows has NaN variances.  ``timing``: a dict that receives the device time ``ms`` of the kernel."""
+        off = _c(np.atleast_1d(group_offset), np.int32)
+        ng = len(off) - 1
+        if ng < 1 or off[0] != 0 or np.any(np.diff(off) < 0):
+            raise ValueError('resample_reduce: group_offset must start at 0, not decrease and name at least one group')
+        rows = int(off[-1])
+        sc = _c(np.broadcast_to(np.asarray(scale, dtype=float), (ng,)))
+        if not np.all(np.isfinite(sc)):
+            raise ValueError('resample_reduce: every scale must be finite')
+        pi = None
+        if H is not None:
+            H = _c(H).reshape(rows, self.n_omega)
+        else:
+            pi = _c(np.arange(rows) if problem_index is None else np.atleast_1d(problem_index), np.int32)
+            n_last = self._n_chain * self._n_alpha           # (0: nothing was staged -- the library answers MXE_ERR_STATE)
+            if len(pi) != rows or (rows and n_last and (pi.min() < 0 or pi.max() >= n_last)):
+                raise ValueError('resample_reduce: problem_index must name %d problems of the last launch (%d x %d)'
+                                 % (rows, self._n_chain, self._n_alpha))
+        n_f = 0
+        if F is not None and len(F):
+            F = _c(np.atleast_2d(F))
+            if F.shape[1] != self.n_omega:
+                raise ValueError('resample_reduce: F has %d columns, the omega mesh %d points' % (F.shape[1], self.n_omega))
+            if not np.all(np.isfinite(F)):
+                raise ValueError('resample_reduce: F holds values that are not finite')
+            n_f = F.shape[0]
+        shapes = dict(mean=(ng, self.n_omega), var=(ng, self.n_omega), fval=(rows, n_f), fmean=(ng, n_f), fcov=(ng, n_f, n_f))
+        out = {}
+        for k in want:
+            if k not in shapes:
+                raise TypeError('unknown output {!r}'.format(k))
+            out[k] = np.empty(shapes[k])
+        used = np.zeros(ng, dtype=np.int32)
+        ms = ctypes.c_float(0)
+        self._check(self._lib.mxe_resample_reduce(self._h, ng, _p(off), _p(H), _p(pi), _p(sc), n_f, _p(F) if n_f else None,
+                                                  _p(out.get('mean')), _p(out.get('var')), _p(out.get('fval')),
+                                                  _p(out.get('fmean')), _p(out.get('fcov')), _p(used), ctypes.byref(ms)),
+                    'mxe_resample_reduce')
+        if timing is not None:
+            timing['ms'] = float(ms.value)
+        out['used'] = used
         return out
 
     def audit(self):

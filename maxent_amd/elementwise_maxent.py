@@ -768,6 +768,22 @@ class ElementwiseMaxEnt(object):
                     out[name][(key[1], key[0]) + key[2:]] = val * flip if val.dtype.kind == 'f' else val
         return out
 
+    def resample_errors(self, bins, method='jackknife', block=1, n_resamples=None, seed=None, alpha=None,
+                        alpha_mode='per_resample', windows=None, functionals=None, pointwise=True, keep_samples=False,
+                        timing=None):
+        """:meth:`TauMaxEnt.resample_errors` for every matrix element: ``bins`` are those the last ``set_G_tau_bins`` /
+        ``set_G_iw_bins`` call received; all elements see the same resamples (bins are joint measurements).  The rotated
+        data of all sets come from one ``mxe_bins_resample`` call on the first device, every phase is one launch per
+        device for all elements and resamples, each element with ONE data set.  Returns a dict of arrays laid out like
+        :meth:`posterior_errors`' (matrix indices, then the complex index with ``use_complex``; elements that were not
+        computed hold NaN, those that follow from hermiticity are filled from their partners); ``info['n_datasets']``
+        and ``info['n_elements']`` per phase."""
+        from . import resampling
+        return resampling.elementwise_resample_errors(self, bins, method=method, block=block, n_resamples=n_resamples,
+                                                      seed=seed, alpha=alpha, alpha_mode=alpha_mode, windows=windows,
+                                                      functionals=functionals, pointwise=pointwise,
+                                                      keep_samples=keep_samples, timing=timing)
+
     def _direct_input(self, worker):
         """G(tau) came as one array and the errors are plain (no covariance): specs can be cut from the
         arrays without sending every element through the worker's setters"""
@@ -1213,6 +1229,12 @@ class PoormanMaxEnt(ElementwiseMaxEnt):
             A2 = (ar[j][j][0] if self.use_complex else ar[j][j])[self.analyzer_offdiag_D]['A_out']
             models.append(DataDefaultModel(np.sqrt(A1 * A2) + self.D_add_constant, self.omega))
         return models
+
+    def resample_errors(self, *args, **kwargs):
+        raise NotImplementedError('PoormanMaxEnt.resample_errors: the default model of an off-diagonal element is built from '
+                                  'the diagonal results, so every resample would need the diagonal results of that resample '
+                                  'first -- two dependent launches per resample, which this driver does not do; use '
+                                  'ElementwiseMaxEnt or DiagonalMaxEnt')
 
     def run_offdiagonal(self):
         self.prepare_maxent_result(overwrite=False)

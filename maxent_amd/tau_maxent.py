@@ -369,6 +369,34 @@ class TauMaxEnt(object):
                                         chi2_factor=loop.cost_function.chi2_factor, device_ids=ids[:1],
                                         bryan=posterior.find_bryan(loop.analyzers), timing=timing)[0]
 
+    def resample_errors(self, bins, method='jackknife', block=1, n_resamples=None, seed=None, alpha=None,
+                        alpha_mode='per_resample', windows=None, functionals=None, pointwise=True, keep_samples=False,
+                        timing=None):
+        """Jackknife or bootstrap error bars from the Monte Carlo ``bins`` the last ``set_G_tau_bins`` / ``set_G_iw_bins``
+        call of this object received: every resample of the bins is continued with the covariance of the full sample (one
+        launch for all of them, :mod:`maxent_amd.resampling`) and the spread of the results is taken on the device.  The
+        object is not changed.  Not in the reference.
+
+        ``method='jackknife'``: ``n_bins // block`` leave-one-block-out resamples; ``'bootstrap'``: ``n_resamples`` draws
+        with ``numpy.random.default_rng(seed)`` (``seed`` is required).  ``alpha``: the analyzer whose alpha is taken
+        (``'LineFitAnalyzer'``, ``'Chi2CurvatureAnalyzer'``, ``'EntropyAnalyzer'``; default: the first analyzer of this
+        object, if it is one of them), or one index.  ``alpha_mode='per_resample'``: every resample at the alpha the
+        analyzer picks for its own scan -- the uncertainty of the alpha selection is inside the error --;
+        ``'full_sample'``: all at the alpha of the full sample.  ``windows``, ``functionals``, ``pointwise`` as in
+        :meth:`posterior_errors` (with a ``PreblurKernel`` they refer to A = B H).
+
+        Returns a dict: ``A``, ``alpha``, ``alpha_index`` (the full sample at its alpha); ``A_mean``, ``A_err`` (and
+        ``A_bias`` = (n_used - 1) (A_mean - A), jackknife only) with ``pointwise``; ``window_weight`` (the mean over the
+        resamples), ``window_err``, ``window_full`` (the full sample's); ``functional_value``, ``functional_err``,
+        ``functional_cov``, ``functional_full``; ``alpha_index_samples`` (n_res); ``n_used`` (a resample whose chosen
+        alpha failed is left out), ``n_resamples``, ``method``; ``info`` (kernel times, launches, ``n_datasets``,
+        ``left_out``); with ``keep_samples`` ``samples['H']`` (n_res, n_omega) and ``samples['functional']``
+        (n_res, windows then functionals) for anything nonlinear downstream."""
+        from . import resampling
+        return resampling.tau_resample_errors(self, bins, method=method, block=block, n_resamples=n_resamples, seed=seed,
+                                              alpha=alpha, alpha_mode=alpha_mode, windows=windows, functionals=functionals,
+                                              pointwise=pointwise, keep_samples=keep_samples, timing=timing)
+
     # ---- tau ----------------------------------------------------------------
     def get_tau(self):
         return self.maxent_loop.get_data_variable()
