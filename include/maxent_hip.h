@@ -40,6 +40,7 @@
  *     + KernelSVD.svd   kernels.py:283-346                 |   Matsubara data)
  *   BosonicTauKernel / BosonicIOmegaKernel fill + SVD      | mxe_kernel_svd_boson / mxe_kernel_svd_boson_iw
  *     (chi(tau), chi(i nu_n); not in the reference)        |
+ *   LegendreKernel fill + SVD (G_l; not in the reference)  | mxe_kernel_svd_legendre
  *   DataKernel (a caller's matrix) + KernelSVD.svd         | mxe_kernel_svd_data
  *     kernels.py:183-207                                   |
  *   get_G_w_from_A_w  maxent_util.py:43-132                | mxe_kramers_kronig (also get_chi_w_from_A_w)
@@ -540,6 +541,22 @@ int  mxe_kernel_svd_data(int device, int n_rows, int n_omega, const double* K,
                          int n_b, const double* preblur_b, double threshold, int ns_max,
                          double* out_K, double* out_U, double* out_S, double* out_V,
                          int32_t* out_ns, int32_t* out_info, float* out_ms);
+
+/* LegendreKernel (no counterpart in the reference; its documentation anticipates it): G given as Legendre coefficients
+ * in TRIQS's GfLegendre normalisation, G(tau) = sum_l sqrt(2l+1)/beta P_l(2 tau/beta - 1) G_l, G_l = int dw K(l, w) A(w),
+ *     K(l, w) = -beta sqrt(2l+1) (-sgn w)^l i_l(beta |w| / 2) / (2 cosh(beta w / 2))
+ * (i_l: modified spherical Bessel function of the first kind): K(0, w) = -tanh(beta w / 2) / w; at w = 0 the row l = 0
+ * is -beta/2 and every other row 0.  Real, n_l rows.  l: the n_l orders as integer-valued doubles, in any order (a
+ * subset is fine); beta is required.  Filled column by column from the ratios i_{k+1}/i_k (backward recurrence) and the
+ * scaled e^{-a} i_0(a), a = beta |w| / 2: no positive exponent, no overflow for any beta w, small entries underflow
+ * to 0; relative error below (8 + l) 2^-52.  MXE_ERR_ARG, before anything is launched: an order that is negative, not
+ * integer-valued, above 4096 or there twice; beta <= 0 or not finite; beta |w| / 2 above 1e6 or a NaN in omega (the work of a column
+ * grows like max(l_max, beta |w| / 2)).  Everything else as mxe_kernel_svd, with n_tau -> n_l. */
+int  mxe_kernel_svd_legendre(int device, int n_l, int n_omega, const double* l,
+                             const double* omega, const double* delta, double beta,
+                             int n_b, const double* preblur_b, double threshold, int ns_max,
+                             double* out_K, double* out_U, double* out_S, double* out_V,
+                             int32_t* out_ns, int32_t* out_info, float* out_ms);
 
 /* ---- Kramers-Kronig: G(w) from A(w) (get_G_w_from_A_w, maxent_util.py:43-132) ---- */
 /* The broadened Cauchy / Hilbert sum, for every spectrum s and output point o:

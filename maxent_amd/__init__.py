@@ -14,7 +14,7 @@ from .default_models import *          # noqa: F401,F403
 from .preblur import get_preblur       # noqa: F401
 from .kernels import (KernelSVD, Kernel, DataKernel, TauKernel,   # noqa: F401
                       IOmegaKernel, PreblurKernel, BosonicTauKernel,
-                      BosonicIOmegaKernel)
+                      BosonicIOmegaKernel, LegendreKernel)
 from .functions import (GenericFunction, DoublyDerivableFunction, cached,   # noqa: F401
                         NormalChi2, NormalEntropy, PlusMinusEntropy,
                         NormalH_of_v, PlusMinusH_of_v, IdentityA_of_H,
@@ -38,7 +38,8 @@ from .elementwise_maxent import (ElementwiseMaxEnt, DiagonalMaxEnt,   # noqa: F4
                                  PoormanMaxEnt, PendingRun, run_many)
 from .device import MaxEntDeviceError, device_count  # noqa: F401
 from .maxent_util import (ArrayGf, get_G_w_from_A_w, get_G_tau_from_A_w,   # noqa: F401
-                          get_chi_w_from_A_w, kramers_kronig)
+                          get_chi_w_from_A_w, get_G_l_from_A_w, get_G_tau_from_G_l,
+                          kramers_kronig)
 from .sigma_continuator import (SigmaContinuator, InversionSigmaContinuator,   # noqa: F401
                                 DirectSigmaContinuator)
 from . import _layout as _layout        # the reference's sub-module paths (analyzers.linefit_analyzer, ...)

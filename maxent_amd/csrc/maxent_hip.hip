@@ -3497,6 +3497,40 @@ try {
 }
 MXE_CATCH_ALL
 
+// LegendreKernel: K(l, w) = -beta sqrt(2l+1) (-sgn w)^l i_l(beta |w| / 2) / (2 cosh(beta w / 2)), n_l rows.  The orders
+// travel as the "row grid" of kernel_svd_common, followed by the row indices sorted by ascending order (the fill walks
+// the orders downwards and upwards).  Everything the fill's loops depend on is checked here, before any launch.
+extern "C" int mxe_kernel_svd_legendre(int device, int n_l, int n_omega, const double* l, const double* omega,
+                                       const double* delta, double beta, int n_b, const double* preblur_b,
+                                       double threshold, int ns_max, double* out_K, double* out_U, double* out_S,
+                                       double* out_V, int32_t* out_ns, int32_t* out_info, float* out_ms)
+try {
+    if (n_l < 1 || n_omega < 1 || n_b < 1 || !l || !omega || !delta || !preblur_b || !out_U || !out_S ||
+        !out_V || !out_ns || ns_max < 1 || ns_max > mxe::SVD_RCAP || !(threshold >= 0.0) ||
+        !(beta > 0.0) || !std::isfinite(beta) || n_l > (1 << 29) / n_omega) return MXE_ERR_ARG;
+    int l_max = 0;
+    for (int i = 0; i < n_l; ++i) {
+        if (!(l[i] >= 0.0) || !(l[i] <= (double)mxe::LEGENDRE_L_MAX) || l[i] != std::floor(l[i])) return MXE_ERR_ARG;
+        l_max = std::max(l_max, (int)l[i]);
+    }
+    for (int j = 0; j < n_omega; ++j)
+        if (!(beta * std::fabs(omega[j]) / 2.0 <= mxe::LEGENDRE_A_MAX)) return MXE_ERR_ARG;      // (also a NaN)
+    std::vector<int> order(n_l);
+    for (int i = 0; i < n_l; ++i) order[i] = i;
+    std::stable_sort(order.begin(), order.end(), [l](int x, int y) { return l[x] < l[y]; });
+    for (int i = 1; i < n_l; ++i)
+        if (l[order[i]] == l[order[i - 1]]) return MXE_ERR_ARG;                                  // (an order twice)
+    std::vector<double> lgrid((size_t)2 * n_l);
+    for (int i = 0; i < n_l; ++i) { lgrid[i] = l[i]; lgrid[(size_t)n_l + i] = (double)order[i]; }
+    return kernel_svd_common(device, 2 * n_l, n_l, n_omega, lgrid.data(), omega, delta, n_b, preblur_b, threshold, ns_max,
+                             out_K, out_U, out_S, out_V, out_ns, out_info, out_ms,
+                             [=](hipStream_t st, const double* dl, const double* dom, double* dKt0) {
+        hipLaunchKernelGGL(mxe::legendre_kernel_fill, dim3((n_omega + 255) / 256), dim3(256), 0, st, dl, dom, beta,
+                           l_max, n_l, n_omega, dKt0);
+    });
+}
+MXE_CATCH_ALL
+
 // DataKernel: the decomposition (and the preblur products) of a matrix the caller filled; K: n_rows x n_omega, host,
 // row-major.  It travels as the "row grid" of kernel_svd_common, and the fill is its transposition on the device.
 extern "C" int mxe_kernel_svd_data(int device, int n_rows, int n_omega, const double* K, const double* omega,

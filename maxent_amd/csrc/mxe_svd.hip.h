@@ -3,6 +3,7 @@
 //   TauKernel._fill_values      kernels.py:244-271   -> tau_kernel_fill
 //   IOmegaKernel._fill_values   kernels.py:312-331   -> iomega_kernel_fill  (stacked real [Re K ; Im K])
 //   BosonicTauKernel, BosonicIOmegaKernel (no counterpart in the reference) -> boson_tau_kernel_fill, boson_iomega_kernel_fill
+//   LegendreKernel (G_l; no counterpart in the reference) -> legendre_kernel_fill
 //   DataKernel (a caller's matrix)  kernels.py:183-207 -> data_kernel_transpose
 //   get_preblur                 preblur.py:31-58     -> preblur_rows / preblur_cols / preblur_matrix
 //   PreblurKernel._fill_values  kernels.py:384-393   -> preblur_product   (K' = K diag(delta) B)
@@ -150,6 +151,75 @@ void boson_iomega_kernel_fill(const double* __restrict__ inu, const double* __re
         double* col = Kt + (size_t)j * 2 * n_inu;
         col[i] = origin ? 1.0 : w2 / d;
         col[n_inu + i] = origin ? 0.0 : w * nu / d;
+    }
+}
+
+// LegendreKernel (not in the reference): the cuts of the host fill (kernels.py, LEGENDRE_*).
+// Below a = beta |omega| / 2 = LEGENDRE_SERIES_CUT the scaled e^{-a} i_0(a) = (1 - e^{-2a}) / (2a) is its series
+// 1 - a + 2 a^2 / 3 (next term a^3 / 3 < 4e-19); it covers omega = 0 exactly (no 0 / 0).  The backward recurrence of the
+// ratios starts at L = m + LEGENDRE_START_PAD + floor(LEGENDRE_START_SQRT sqrt(m)), m = max(l_max, floor(a)): the wrong
+// start r_L = 0 reaches order l multiplied by prod r_{k-1} r_k over k = l+1..L, below e^-72 for the sqrt term alone and
+// below 2^-80 for the constant alone (kernels.py, _legendre_start).  LEGENDRE_L_MAX, LEGENDRE_A_MAX: the largest order and
+// the largest a the entry takes (the work of a column grows like max(l_max, a)).
+constexpr double LEGENDRE_SERIES_CUT = 1.0e-6;
+constexpr double LEGENDRE_START_PAD = 40.0;
+constexpr double LEGENDRE_START_SQRT = 6.0;
+constexpr int LEGENDRE_L_MAX = 4096;
+constexpr double LEGENDRE_A_MAX = 1.0e6;
+
+// K^T[j][i] of LegendreKernel, K(l, omega) = -beta sqrt(2l+1) (-sgn omega)^l i_l(a) / (2 cosh a), a = beta |omega| / 2
+// (i_l: modified spherical Bessel function of the first kind), column-major like tau_kernel_fill.  One thread owns a
+// column and runs the host's recurrences (kernels.py, LegendreKernel._scaled_bessel) with contraction off:
+//   down:  r_{k-1} = a / (2k + 1 + a r_k) from r_L = 0                     (r_k = i_{k+1} / i_k; a = 0 gives 0, no 0 / 0)
+//   s_0 = e^{-a} i_0(a) = -expm1(-2a) / (2a), its series below the cut
+//   up:    s_{k+1} = s_k r_k,   K = -beta sqrt(2l+1) (-sgn omega)^l s_l / (1 + e^{-2a})
+// No exponent is positive: nothing overflows, small entries underflow to 0.  The column itself is the only storage: on
+// the way down the slot of the q-th smallest order lam_q receives the product of the ratios r_k, lam_{q-1} <= k < lam_q
+// (lam_{-1} = 0), on the way up s is multiplied by it and the slot receives K.  For l = 0..n-1 in any order every
+// product is ONE ratio and the operations are the host's, one for one; a subset multiplies the same ratios in groups.
+// lgrid: the n_l orders (integer-valued, 0 <= l <= l_max), then the n_l row indices sorted by ascending order.
+__global__ __launch_bounds__(256)
+void legendre_kernel_fill(const double* __restrict__ lgrid, const double* __restrict__ omega, double beta,
+                          int l_max, int n_l, int n_omega, double* __restrict__ Kt)
+{
+#pragma clang fp contract(off)
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n_omega) return;
+    const double* order = lgrid + n_l;
+    double* col = Kt + (size_t)j * n_l;
+    const double w = omega[j];
+    const double a = beta * fabs(w) / 2.0;
+    const double mm = fmax((double)l_max, floor(a));
+    const int L = (int)(mm + LEGENDRE_START_PAD + floor(LEGENDRE_START_SQRT * sqrt(mm)));
+    // down: group q holds the ratios r_k, lo <= k < hi
+    int q = n_l - 1;
+    int slot = (int)order[q];
+    int hi = (int)lgrid[slot];
+    int lo = q > 0 ? (int)lgrid[(int)order[q - 1]] : 0;
+    double r = 0.0, prod = 1.0;
+    for (int k = L; k >= 1 && q >= 0; --k) {
+        r = a / ((double)(2 * k + 1) + a * r);              // r_{k-1}
+        const int kk = k - 1;
+        if (kk < hi) prod = prod * r;
+        while (q >= 0 && kk == lo) {                        // (more than once: an order given twice has an empty group)
+            col[slot] = prod;
+            prod = 1.0;
+            if (--q >= 0) {
+                slot = (int)order[q];
+                hi = lo;
+                lo = q > 0 ? (int)lgrid[(int)order[q - 1]] : 0;
+            }
+        }
+    }
+    // up
+    double s = (a < LEGENDRE_SERIES_CUT) ? 1.0 - a + 2.0 * a * a / 3.0 : -expm1(-2.0 * a) / (2.0 * a);
+    const double den = 1.0 + exp(-2.0 * a);
+    for (q = 0; q < n_l; ++q) {
+        slot = (int)order[q];
+        const double l = lgrid[slot];
+        s = s * col[slot];
+        const double v = -beta * sqrt(2.0 * l + 1.0) * s / den;
+        col[slot] = (((int)l & 1) && w > 0.0) ? -v : v;    // (-sgn omega)^l
     }
 }
 

@@ -149,6 +149,10 @@ SYMBOLS = [
                                                ctypes.c_int, ctypes.c_int, _dp, ctypes.c_double,
                                                ctypes.c_int, _dp, _dp, _dp, _dp, _ip, _ip,
                                                ctypes.POINTER(ctypes.c_float)]),
+    ('mxe_kernel_svd_legendre', ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp,
+                                               ctypes.c_double, ctypes.c_int, _dp, ctypes.c_double,
+                                               ctypes.c_int, _dp, _dp, _dp, _dp, _ip, _ip,
+                                               ctypes.POINTER(ctypes.c_float)]),
     ('mxe_kernel_svd_data', ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp,
                                            ctypes.c_int, _dp, ctypes.c_double,
                                            ctypes.c_int, _dp, _dp, _dp, _dp, _ip, _ip,
@@ -364,6 +368,19 @@ def kernel_svd_boson_iw(inu, omega, delta, symmetric=False, preblur_b=(0.0,), th
     return _kernel_svd_call('mxe_kernel_svd_boson_iw', len(inu), (_p(inu),), (1 if symmetric else 0,), omega, delta,
                             preblur_b, threshold, ns_max, want_K, device,
                             n_rows=len(inu) if symmetric else 2 * len(inu))
+
+
+def kernel_svd_legendre(l, omega, delta, beta, preblur_b=(0.0,), threshold=1.e-14, ns_max=128, want_K=False, device=0):
+    """``mxe_kernel_svd_legendre``: LegendreKernel (orders ``l``: non-negative integers in any order) and its
+    PreblurKernels filled and decomposed on the device; returns what :func:`kernel_svd` returns.  An order that is
+    negative, not an integer or too large, or ``beta`` <= 0, is refused by the library before anything is launched
+    (:class:`MaxEntDeviceError`)."""
+    load_library()
+    if device_count() < 1:
+        raise MaxEntDeviceError('no HIP device visible; the device SVD has no CPU fallback')
+    l, omega, delta = _c(l), _c(omega), _c(delta)
+    return _kernel_svd_call('mxe_kernel_svd_legendre', len(l), (_p(l),), (float(beta),), omega, delta, preblur_b,
+                            threshold, ns_max, want_K, device)
 
 
 def kernel_svd_data(K, omega, delta, preblur_b=(0.0,), threshold=1.e-14, ns_max=128, want_K=False, device=0):

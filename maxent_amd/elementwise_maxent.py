@@ -797,7 +797,7 @@ class ElementwiseMaxEnt(object):
         a, b = self.maxent_diagonal.K, self.maxent_offdiagonal.K
         if a is b or type(a) is not type(b) or \
                 not isinstance(a, (kernels.TauKernel, kernels.IOmegaKernel, kernels.BosonicTauKernel,
-                                   kernels.BosonicIOmegaKernel)) or \
+                                   kernels.BosonicIOmegaKernel, kernels.LegendreKernel)) or \
                 a.rotation is not None or b.rotation is not None or \
                 getattr(a, 'symmetric', None) != getattr(b, 'symmetric', None):
             return
@@ -1032,6 +1032,23 @@ class ElementwiseMaxEnt(object):
         object.__setattr__(self, '_array_input', True)
         object.__setattr__(self, '_n_iw', None if symmetric else n)
 
+    def set_G_l_data(self, G_l, beta, l=None):
+        """``G_l``: (M, N, n_l) array of Legendre coefficients of G_ij (:meth:`TauMaxEnt.set_G_l_data`; ``l`` defaults to
+        0..n_l-1); the real part of an element is continued to Re A_ij, with ``use_complex`` the imaginary part to
+        Im A_ij, as for G(tau)."""
+        G_l = np.asarray(G_l)
+        if G_l.ndim != 3:
+            raise AssertionError('G_l must be (M, N, n_l)')
+        l = TauMaxEnt._legendre_orders(l, G_l.shape[2])
+
+        def feed(maxent, G_mat, elem, re):
+            g = G_mat[1][elem]
+            maxent.set_G_l_data(np.real(g) if re else np.imag(g), beta, G_mat[0])
+        for worker in (self.maxent_diagonal, self.maxent_offdiagonal):
+            worker._use_legendre_kernel(l, beta)
+        self.set_G((l, G_l), feed, lambda G_mat: G_mat[1].shape[:2])
+        object.__setattr__(self, '_array_input', True)
+
     def set_G_tau_filename_pattern(self, filename, dimension, tau_col=0,
                                    G_col_re=1, G_col_im=2, *args, **kwargs):
         """one file per element, name with ``{i}`` and ``{j}``
@@ -1176,6 +1193,25 @@ class ElementwiseMaxEnt(object):
             return re_set, np.concatenate([im_part.real, im_part.imag], axis=-1)
         table = self._bins_eig(bins.shape[1:3], sets_of, bins.shape[0])
         self._set_G_iw_stacked(iomega, self._means_of_bins(table, bins.shape[1:3], 2 * len(iomega)), beta)
+        self._put_eigenbases(table)
+
+    def set_G_l_bins(self, bins, beta, l=None):
+        """``bins``: (n_bins, M, N, n_l) array of independent estimates of the Legendre coefficients of G_ij
+        (:meth:`TauMaxEnt.set_G_l_bins`), complex with ``use_complex``; everything else as :meth:`set_G_tau_bins`."""
+        bins = np.asarray(bins)
+        if bins.ndim != 4:
+            raise AssertionError('G_l bins must be (n_bins, M, N, n_l); their shape is {}'.format(bins.shape))
+        l = TauMaxEnt._legendre_orders(l, bins.shape[-1])
+        bins = TauMaxEnt._check_bins(l, bins, 'G_l bins')
+        cplx = np.iscomplexobj(bins)
+        if cplx and not self.use_complex:
+            raise AssertionError('complex G_l bins need use_complex=True')
+
+        def sets_of(i, j):
+            b = bins[:, i, j, :]
+            return b.real, (b.imag if cplx else None)
+        table = self._bins_eig(bins.shape[1:3], sets_of, bins.shape[0])
+        self.set_G_l_data(self._means_of_bins(table, bins.shape[1:3], len(l)), beta, l)
         self._put_eigenbases(table)
 
     def get_tau(self):

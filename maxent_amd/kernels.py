@@ -6,7 +6,8 @@ factors ``U, S, V`` are what :class:`maxent_amd.device.DeviceContext` stages
 in HBM.  Public names and semantics follow the reference's ``kernels`` module
 (reference python/kernels.py:37-413): ``KernelSVD``, ``Kernel``,
 ``DataKernel``, ``TauKernel``, ``IOmegaKernel``, ``PreblurKernel``.  ``BosonicTauKernel`` and
-``BosonicIOmegaKernel`` (susceptibilities: chi(tau), chi(i nu_n)) have no counterpart there.
+``BosonicIOmegaKernel`` (susceptibilities: chi(tau), chi(i nu_n)) and ``LegendreKernel`` (Legendre coefficients G_l)
+have no counterpart there.
 """
 
 import numpy as np
@@ -169,6 +170,10 @@ class Kernel(KernelSVD):
     """Kernel on an omega mesh with an optional left rotation ``T``
     (covariance eigenbasis; reference kernels.py:125-180)."""
 
+    #: the matrix has been taken out of a rotation with fewer rows than columns by ``transform``: it is a projection
+    #: of what its rotation says (``refill_unrotated`` mends it)
+    _projected = False
+
     def __init__(self):
         super(Kernel, self).__init__()
         self.omega = None
@@ -194,6 +199,13 @@ class Kernel(KernelSVD):
     def _fill_values(self):
         raise NotImplementedError('Use a subclass of Kernel')
 
+    def refill_unrotated(self):
+        """the unrotated matrix again, filled afresh: the way out of a rotation with fewer rows than columns, which
+        ``transform(None)`` cannot undo (T^H T is a projection then)"""
+        self._T = None
+        self._projected = False
+        self._fill_values()
+
     def fold(self, x):
         """a data-space vector or array (last axis = the rows of K) in the form of the data the kernel was made for;
         identity here, complex for :class:`IOmegaKernel`, whose rows are the stacked real and imaginary parts"""
@@ -209,6 +221,8 @@ class Kernel(KernelSVD):
         T = self._relative_rotation(T_, self._T)
         if T is None:
             return
+        if self._T is not None and self._T.shape[0] != self._T.shape[1]:
+            self._projected = True       # (T_old^H T_old is a projection: what follows is T_ times a projected K)
         self._T = T_
         self._U = np.dot(T, self.U)
         self._K = np.dot(T, self._K)
@@ -240,6 +254,18 @@ class DataKernel(Kernel):
     @property
     def data_variable(self):
         return self._data_variable
+
+    def transform(self, T_):
+        if self._T is None and not self._projected:
+            self._K_unrotated = self._K          # (the matrix as it was given: transform assigns a new one)
+        super(DataKernel, self).transform(T_)
+
+    def refill_unrotated(self):
+        if self._T is not None or self._projected:
+            self._T = None
+            self._projected = False
+            self._invalidate_svd()
+            self._K = self._K_unrotated
 
     def _device_svd(self, preblur_b=0.0):
         """U, S, V of the matrix as it stands (``mxe_kernel_svd_data``); with ``preblur_b`` > 0, of the UNROTATED
@@ -639,8 +665,155 @@ class BosonicIOmegaKernel(Kernel):
         self.inu = value
 
 
+#: below a = beta |omega| / 2 = this the scaled e^{-a} i_0(a) = (1 - e^{-2a}) / (2a) of the Legendre kernel is its series
+#: 1 - a + 2 a^2 / 3 (next term a^3 / 3 < 4e-19); it covers omega = 0 exactly (no 0 / 0) and products that underflow
+LEGENDRE_SERIES_CUT = 1.0e-6
+#: the backward recurrence of the ratios starts at L = m + LEGENDRE_START_PAD + floor(LEGENDRE_START_SQRT sqrt(m)),
+#: m = max(l_max, floor(a)); see :func:`_legendre_start`
+LEGENDRE_START_PAD = 40
+LEGENDRE_START_SQRT = 6.0
+#: largest order l a LegendreKernel (and ``mxe_kernel_svd_legendre``) takes
+LEGENDRE_L_MAX = 4096
+#: largest a = beta |omega| / 2 they take: the work of a column grows like max(l_max, a)
+LEGENDRE_A_MAX = 1.0e6
+
+
+def _legendre_start(l_max, a):
+    """The order L at which the backward recurrence of the ratios r_k = i_{k+1}(a) / i_k(a) starts with r_L = 0.
+
+    An error e_k of r_k becomes e_{k-1} = -r_{k-1}^2 e_k one step down (differentiate r_{k-1} = a / (2k + 1 + a r_k)), so
+    the wrong start (relative error 1) arrives at order l multiplied by prod_{k=l+1..L} r_{k-1} r_k.  Above the turning
+    point k ~ a the ratios fall like r_k < a / (2k + 3): with m = max(l, a) and k = m + d, r_k < 1 / (1 + 2d / m)
+    ~ exp(-2d / m) for d << m, the product over d = 1..D is below exp(-2 D^2 / m), and D = 6 sqrt(m) alone gives
+    e^-72 ~ 5e-32; for d >~ m every factor is below 1/2 and 40 further steps give 2^-80 for small m, where sqrt(m) is
+    no measure.  Either term suffices on its side; their sum is used for all m, far below 2^-53 everywhere."""
+    m = np.maximum(float(l_max), np.floor(a))
+    return (m + LEGENDRE_START_PAD + np.floor(LEGENDRE_START_SQRT * np.sqrt(m))).astype(np.int64)
+
+
+class LegendreKernel(Kernel):
+    r"""Fermionic kernel for G given as Legendre coefficients :math:`G_l` in TRIQS's ``GfLegendre`` normalisation,
+    :math:`G(\tau) = \sum_l \sqrt{2l+1}/\beta\; P_l(x(\tau))\, G_l`, :math:`x(\tau) = 2\tau/\beta - 1`:
+    :math:`G_l = \int d\omega\, K(l,\omega) A(\omega)` with
+
+    .. math:: K(l,\omega) = -\beta\sqrt{2l+1}\,(-\mathrm{sgn}\,\omega)^l\,
+              \frac{i_l(\beta|\omega|/2)}{2\cosh(\beta\omega/2)}
+
+    (:math:`i_l`: the modified spherical Bessel function of the first kind); :math:`K(0,\omega) =
+    -\tanh(\beta\omega/2)/\omega`, and at :math:`\omega = 0` the row l = 0 is :math:`-\beta/2`, every other row 0.
+    ``l``: distinct non-negative integers in any order (a subset such as the even l is fine); ``beta`` is required.
+    The matrix is real with ``len(l)`` rows.  Not in the reference (its documentation anticipates it).
+
+    The fill runs column by column in :math:`a = \beta|\omega|/2`: the ratios :math:`r_{k-1} = i_k/i_{k-1} =
+    a/(2k+1+a r_k)` backwards from :math:`r_L = 0` (:func:`_legendre_start`), the scaled :math:`s_0 = e^{-a} i_0(a) =
+    -\mathrm{expm1}(-2a)/(2a)` (a series below ``LEGENDRE_SERIES_CUT``), :math:`s_{k+1} = s_k r_k` forwards, and
+    :math:`K = -\beta\sqrt{2l+1}(-\mathrm{sgn}\,\omega)^l s_l/(1+e^{-2a})`.  No exponent is positive: nothing
+    overflows for any :math:`\beta\omega`, small entries underflow to 0.  The work per column grows like
+    :math:`\max(l_{max}, a)`."""
+
+    def __init__(self, l, omega, beta=None, svd_backend='host'):
+        super(LegendreKernel, self).__init__()
+        self._checked_beta(beta)
+        self.l = self._checked_l(l)
+        self.omega = omega
+        self.beta = beta
+        self.svd_backend = svd_backend
+        self._fill_values()
+
+    @staticmethod
+    def _checked_beta(beta):
+        """raises ValueError naming ``beta`` unless it is a positive finite number"""
+        if beta is None:
+            raise ValueError('LegendreKernel: beta is required (it is not in the grid l)')
+        if not (float(beta) > 0.0 and np.isfinite(float(beta))):
+            raise ValueError('LegendreKernel: beta must be positive and finite, not %r' % (beta,))
+        return beta
+
+    @staticmethod
+    def _checked_l(l):
+        """``l`` as an int64 array; raises ValueError naming ``l`` for anything but distinct non-negative integers"""
+        a = np.asarray(l)
+        if a.ndim != 1 or a.size < 1:
+            raise ValueError('LegendreKernel: l must be a 1-D array of orders, not of shape %s' % (a.shape,))
+        if a.dtype.kind not in 'iuf' or not np.all(np.isfinite(a)) or np.any(a != np.floor(a)):
+            raise ValueError('LegendreKernel: l must hold integers')
+        if np.any(a < 0):
+            raise ValueError('LegendreKernel: l must not be negative')
+        if np.any(a > LEGENDRE_L_MAX):
+            raise ValueError('LegendreKernel: l must not exceed %d' % LEGENDRE_L_MAX)
+        a = a.astype(np.int64)
+        if len(np.unique(a)) != len(a):
+            raise ValueError('LegendreKernel: l holds duplicates')
+        return a
+
+    def _device_svd(self, preblur_b=0.0):
+        """U, S, V of the UNROTATED kernel from the device (``mxe_kernel_svd_legendre``); see TauKernel._device_svd"""
+        from . import device
+        r = device.kernel_svd_legendre(self.l, np.asarray(self.omega, dtype=float), self.omega.delta, float(self.beta),
+                                       [preblur_b], threshold=0.0)[0]
+        return r['U'], r['S'], r['V']
+
+    def _device_args(self):
+        return self.l, np.asarray(self.omega, dtype=float), self.omega.delta, float(self.beta)
+
+    @staticmethod
+    def _scaled_bessel(l_max, a):
+        """s_k = e^{-a} i_k(a) for k = 0..l_max and every a >= 0 of the array ``a``: (l_max + 1, len(a))"""
+        L = _legendre_start(l_max, a)
+        r = np.zeros(len(a))
+        ratios = np.empty((l_max + 1, len(a)))
+        for k in range(int(L.max()), 0, -1):
+            # r holds r_k (0 where k >= L: the recurrence of that column has not started)
+            r = np.where(k <= L, a / ((2 * k + 1) + a * r), 0.0)
+            if k - 1 <= l_max:
+                ratios[k - 1] = r
+        small = a < LEGENDRE_SERIES_CUT
+        s = np.empty((l_max + 1, len(a)))
+        s[0] = np.where(small, 1.0 - a + 2.0 * a * a / 3.0, -np.expm1(-2.0 * a) / np.where(small, 1.0, 2.0 * a))
+        for k in range(l_max):
+            s[k + 1] = s[k] * ratios[k]
+        return s
+
+    @classmethod
+    def _values(cls, l, w, beta):
+        a = beta * np.abs(w) / 2.0
+        s = cls._scaled_bessel(int(l.max()), a)[l]
+        c = -beta * np.sqrt(2.0 * l + 1.0)
+        # (-sgn omega)^l: -1 for odd l on omega > 0, +1 otherwise
+        sign = np.where((l[:, np.newaxis] % 2 == 1) & (w[np.newaxis, :] > 0.0), -1.0, 1.0)
+        return sign * (c[:, np.newaxis] * s / (1.0 + np.exp(-2.0 * a))[np.newaxis, :])
+
+    def _fill_values(self):
+        self._invalidate_svd()
+        l = self._checked_l(self.l)
+        w = np.asarray(self.omega, dtype=float)
+        beta = float(self.beta)
+        delta = np.asarray(self.omega.delta, dtype=float)
+        if not np.all(beta * np.abs(w) / 2.0 <= LEGENDRE_A_MAX):                # (also a NaN)
+            raise ValueError('LegendreKernel: beta |omega| / 2 must not exceed %g' % LEGENDRE_A_MAX)
+        key = ('legendre', l.tobytes(), w.tobytes(), delta.tobytes(), beta)
+        hit = _recent_fill.get(key, lambda _: True)               # (the key IS the contents)
+        if hit is None:
+            with np.errstate(under='ignore'):
+                K = self._values(l, w, beta)
+            hit = (_frozen(K), _frozen(K * delta[np.newaxis, :]))
+            _recent_fill.put(key, None, hit)
+        self._K, self._K_delta = hit
+        T = self._T
+        self._T = None
+        self.transform(T)
+
+    @property
+    def data_variable(self):
+        return self.l
+
+    @data_variable.setter
+    def data_variable(self, value):
+        self.l = self._checked_l(value)
+
+
 #: the kernels a PreblurKernel can hand to the device: each has ``_device_svd(preblur_b)``
-_DEVICE_KERNELS = (TauKernel, IOmegaKernel, BosonicTauKernel, BosonicIOmegaKernel, DataKernel)
+_DEVICE_KERNELS = (TauKernel, IOmegaKernel, BosonicTauKernel, BosonicIOmegaKernel, LegendreKernel, DataKernel)
 
 
 class PreblurKernel(Kernel):
@@ -671,13 +844,15 @@ class PreblurKernel(Kernel):
     @classmethod
     def scan(cls, K, b_values, threshold=1.e-14):
         """The kernels of a b-scan (reference doc/guide/preblur_example.py:49-56) with
-        their truncated SVDs from ONE batched device launch (``mxe_kernel_svd``, or ``mxe_kernel_svd_boson``
-        for a BosonicTauKernel)."""
+        their truncated SVDs from ONE batched device launch (``mxe_kernel_svd``, ``mxe_kernel_svd_boson``
+        for a BosonicTauKernel, ``mxe_kernel_svd_legendre`` for a LegendreKernel)."""
         from . import device
-        if not isinstance(K, (TauKernel, BosonicTauKernel)) or K._T is not None:
-            raise NotImplementedError('PreblurKernel.scan needs an unrotated TauKernel or BosonicTauKernel')
+        if not isinstance(K, (TauKernel, BosonicTauKernel, LegendreKernel)) or K._T is not None:
+            raise NotImplementedError('PreblurKernel.scan needs an unrotated TauKernel, BosonicTauKernel or LegendreKernel')
         tau, w, delta, beta = K._device_args()
-        if isinstance(K, BosonicTauKernel):
+        if isinstance(K, LegendreKernel):
+            res = device.kernel_svd_legendre(tau, w, delta, beta, list(b_values), threshold=threshold)
+        elif isinstance(K, BosonicTauKernel):
             res = device.kernel_svd_boson(tau, w, delta, beta, K.symmetric, list(b_values), threshold=threshold)
         else:
             res = device.kernel_svd(tau, w, delta, beta, list(b_values), threshold=threshold)
@@ -691,6 +866,10 @@ class PreblurKernel(Kernel):
 
     def parameter_change(self):
         self.kernel.parameter_change()
+        self._fill_values()
+
+    def refill_unrotated(self):
+        self.kernel.refill_unrotated()
         self._fill_values()
 
     def _fill_values(self):

@@ -1,5 +1,6 @@
 """Helpers around a continuation (the reference's python/maxent_util.py): G(w) from A(w) by Kramers-Kronig and
-G(tau) from A(w); chi(w) from the A(w) = Im chi(w) / (pi w) of a bosonic continuation (not in the reference).
+G(tau) from A(w); chi(w) from the A(w) = Im chi(w) / (pi w) of a bosonic continuation, Legendre coefficients G_l from
+A(w) and G(tau) from G_l (not in the reference).
 
 The reference returns TRIQS Green functions (``GfReFreq``, ``GfImTime``); here :class:`ArrayGf` takes their place: a
 mesh array and a data array in TRIQS's layout ``(n_points, n, n)``, so ``g.data[:, 0, 0]`` and
@@ -10,10 +11,11 @@ mesh array and a data array in TRIQS's layout ``(n_points, n, n)``, so ``g.data[
 import numpy as np
 
 from . import device
-from .kernels import TauKernel
+from .kernels import LegendreKernel, TauKernel
 from .omega_meshes import DataOmegaMesh
 
-__all__ = ['ArrayGf', 'get_G_w_from_A_w', 'get_chi_w_from_A_w', 'get_G_tau_from_A_w', 'kramers_kronig']
+__all__ = ['ArrayGf', 'get_G_w_from_A_w', 'get_chi_w_from_A_w', 'get_G_tau_from_A_w', 'get_G_l_from_A_w',
+           'get_G_tau_from_G_l', 'kramers_kronig']
 
 
 class ArrayGf(object):
@@ -228,3 +230,28 @@ def get_G_tau_from_A_w(A_w, w_points, beta, np_tau):
     tau = np.linspace(0.0, beta, np_tau)
     K = TauKernel(tau=tau, omega=w_points, beta=beta)
     return ArrayGf(tau, np.dot(np.asarray(K.K_delta), A_w)[:, None, None])
+
+
+def get_G_l_from_A_w(A_w, w_points, l, beta):
+    r"""The Legendre coefficients :math:`G_l` (TRIQS's ``GfLegendre`` normalisation) of the G that belongs to
+    :math:`A(\omega)`: ``LegendreKernel(l, w_points, beta).K_delta @ A_w``.  ``w_points``: an array or an omega mesh;
+    ``l``: the orders.  Returns an array of ``len(l)`` values.  Not in the reference."""
+    if not hasattr(w_points, 'delta'):
+        w_points = DataOmegaMesh(w_points)
+    K = LegendreKernel(l, w_points, beta=beta)
+    return np.dot(np.asarray(K.K_delta), A_w)
+
+
+def get_G_tau_from_G_l(G_l, l, tau, beta):
+    r""":math:`G(\tau) = \sum_l \sqrt{2l+1}/\beta\; P_l(2\tau/\beta - 1)\, G_l` at the points ``tau`` (an array) from the
+    Legendre coefficients ``G_l`` (last axis) of the orders ``l``.  Returns an array ``(..., len(tau))``.  Not in the
+    reference."""
+    l = LegendreKernel._checked_l(l)
+    G_l = np.asarray(G_l)
+    if G_l.shape[-1] != len(l):
+        raise ValueError('G_l does not end in the %d orders of l' % len(l))
+    c = np.zeros(G_l.shape[:-1] + (int(l.max()) + 1,), dtype=G_l.dtype if np.iscomplexobj(G_l) else float)
+    c[..., l] = np.sqrt(2.0 * l + 1.0) / beta * G_l
+    x = 2.0 * np.asarray(tau, dtype=float) / beta - 1.0
+    # legval takes the coefficients on the FIRST axis and returns (..., len(x))
+    return np.polynomial.legendre.legval(x, np.moveaxis(c, -1, 0))

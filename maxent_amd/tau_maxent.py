@@ -9,7 +9,8 @@ rotated into the covariance eigenbasis).  ``set_G_iw_data`` takes G(i omega_n)
 as arrays instead: the kernel becomes an :class:`IOmegaKernel` and the data
 its stacked real form ``[Re G ; Im G]``.  ``set_chi_tau_data`` / ``set_chi_iw_data``
 take bosonic data (susceptibilities) the same way, with a
-:class:`BosonicTauKernel` / :class:`BosonicIOmegaKernel`.  ``set_G_tau`` /
+:class:`BosonicTauKernel` / :class:`BosonicIOmegaKernel`, ``set_G_l_data``
+takes Legendre coefficients with a :class:`LegendreKernel`.  ``set_G_tau`` /
 ``set_G_iw`` need TRIQS Green-function objects and are not provided.
 """
 
@@ -107,9 +108,9 @@ class TauMaxEnt(object):
         return None
 
     def _use_tau_kernel(self, tau):
-        """after Matsubara or bosonic data: a TauKernel on ``tau`` again (same omega mesh and SVD backend)"""
+        """after Matsubara, bosonic or Legendre data: a TauKernel on ``tau`` again (same omega mesh and SVD backend)"""
         if isinstance(self._inner_kernel(), (kernels.IOmegaKernel, kernels.BosonicTauKernel,
-                                             kernels.BosonicIOmegaKernel)):
+                                             kernels.BosonicIOmegaKernel, kernels.LegendreKernel)):
             self.K = kernels.TauKernel(np.asarray(tau, dtype=float), self.omega, svd_backend=self.K.svd_backend)
 
     def _use_bosonic_kernel(self, cls, grid, beta, symmetric):
@@ -127,6 +128,22 @@ class TauMaxEnt(object):
         else:
             self.K = cls(np.array(grid, dtype=float), self.omega, beta=beta, symmetric=symmetric,
                          svd_backend=self.K.svd_backend)
+
+    def _use_legendre_kernel(self, l, beta):
+        """a LegendreKernel on the orders ``l`` (same omega mesh and SVD backend); one that is there already -- also
+        inside a PreblurKernel -- is refilled only when ``l`` or ``beta`` change"""
+        K = self._inner_kernel()
+        l = kernels.LegendreKernel._checked_l(l)
+        kernels.LegendreKernel._checked_beta(beta)          # (before anything is changed)
+        if isinstance(K, kernels.LegendreKernel):
+            if K.beta != beta:
+                K.beta = beta
+                if np.array_equal(K.l, l):
+                    self.K.parameter_change()
+                    self.K = self.K
+            self.tau = l
+        else:
+            self.K = kernels.LegendreKernel(l, self.omega, beta=beta, svd_backend=self.K.svd_backend)
 
     def _use_iomega_kernel(self, iomega, beta=None):
         """an IOmegaKernel on ``iomega`` (same omega mesh and SVD backend); one that is there already -- also inside
@@ -189,6 +206,28 @@ class TauMaxEnt(object):
             raise AssertionError("inu and chi_iw don't have the same dimension")
         self._use_bosonic_kernel(kernels.BosonicIOmegaKernel, inu, beta, symmetric)
         self.G = np.asarray(self._inner_kernel().unfold(chi_iw), dtype=float)
+        self._adopt_data()
+
+    @staticmethod
+    def _legendre_orders(l, n):
+        """the orders of ``n`` Legendre coefficients: ``l``, or 0..n-1"""
+        l = np.arange(n) if l is None else np.asarray(l)
+        if l.ndim != 1 or len(l) != n:
+            raise AssertionError("l and G_l don't have the same dimension")
+        return l
+
+    def set_G_l_data(self, G_l, beta, l=None):
+        """G as Legendre coefficients G_l in TRIQS's ``GfLegendre`` normalisation, G(tau) = sum_l sqrt(2l+1)/beta
+        P_l(2 tau/beta - 1) G_l (what continuous-time Monte Carlo solvers measure): the kernel becomes a
+        :class:`LegendreKernel` on the orders ``l`` (default 0..n-1; any distinct non-negative integers, such as the
+        even orders only).  ``beta`` is required; the coefficients are real.  Not in the reference."""
+        G_l = np.asarray(G_l)
+        if G_l.ndim != 1:
+            raise AssertionError('G_l must be one-dimensional')
+        if np.iscomplexobj(G_l):
+            raise AssertionError('G_l must be real')
+        self._use_legendre_kernel(self._legendre_orders(l, len(G_l)), beta)
+        self.G = np.asarray(G_l, dtype=float)
         self._adopt_data()
 
     def set_G_tau_file(self, filename, tau_col=0, G_col=1, err_col=None):
@@ -289,8 +328,20 @@ class TauMaxEnt(object):
         are rotated by ``T`` alone, whatever rotation there was (no hop from the previous one as in :meth:`set_cov`)"""
         self.err = None              # no chi2 with stale errors while data and kernel change
         self.G = self.cost_function._G_orig if mean is None else mean
+        self._leave_truncated_rotation()
         self._transform(T, G_original_basis=True)
         self.err = sigma
+
+    def _leave_truncated_rotation(self):
+        """A rotation that dropped directions (fewer bins than data values, or eigenvalues below ``cov_threshold``) has
+        fewer rows than columns, and the hop of ``Kernel.transform`` cannot leave it: T_new T_old^H T_old K is T_new
+        applied to a projection of K, not to K.  The kernel is filled again unrotated (from the cache of recent fills)
+        so that the next rotation is applied to K itself -- the second matrix element of an element-wise job on such
+        bins got the projected kernel.  A square rotation is left by the hop as before."""
+        inner = self._inner_kernel()
+        T = inner.rotation
+        if inner._projected or (T is not None and T.shape[0] != T.shape[1]):
+            self.K.refill_unrotated()
 
     def _bins_eig(self, stacked_bins):
         """mean and covariance eigenbasis of real ``stacked_bins`` (n_bins, n_data) from the device; changes nothing"""
@@ -336,6 +387,21 @@ class TauMaxEnt(object):
             raise AssertionError('G(i omega_n) bins must be (n_bins, n_iw); their shape is {}'.format(bins.shape))
         st = self._bins_eig(kernels.IOmegaKernel.unfold(None, bins))       # (every bin as [Re ; Im]; needs no kernel object)
         self._use_iomega_kernel(iomega, beta)
+        self._adopt_bins(st)
+
+    def set_G_l_bins(self, bins, beta, l=None):
+        """Legendre coefficients as ``bins`` of shape (n_bins, n_l), see :meth:`set_G_tau_bins` and
+        :meth:`set_G_l_data`: the job is the one of ``set_G_l_data(mean, beta, l)`` and ``set_cov(C)`` on a fresh
+        object."""
+        bins = np.asarray(bins)
+        if bins.ndim != 2:
+            raise AssertionError('G_l bins must be (n_bins, n_l); their shape is {}'.format(bins.shape))
+        l = self._legendre_orders(l, bins.shape[-1])
+        bins = self._check_bins(l, bins, 'G_l bins')
+        if np.iscomplexobj(bins):
+            raise AssertionError('G_l bins must be real')
+        st = self._bins_eig(np.asarray(bins, dtype=float))
+        self._use_legendre_kernel(l, beta)
         self._adopt_bins(st)
 
     # ---- error bars ------------------------------------------------------------
