@@ -46,6 +46,8 @@
  *   get_G_w_from_A_w  maxent_util.py:43-132                | mxe_kramers_kronig (also get_chi_w_from_A_w)
  *   (nothing: the reference gives no error bars)           | mxe_posterior_var (posterior variances of
  *                                                          |   integrated quantities, diagonal of the covariance)
+ *   (nothing: the reference draws no spectra)              | mxe_posterior_sample (draws of H from the same
+ *                                                          |   Gaussian posterior), mxe_normals (its generator)
  *   (nothing: users loop run() over their resamples)       | mxe_bins_resample (the rotated data of every
  *                                                          |   jackknife / bootstrap resample of the bins),
  *                                                          |   mxe_resample_reduce (mean, spread and functional
@@ -388,6 +390,34 @@ int  mxe_posterior_var(mxe_ctx* ctx, int P, const int32_t* elem_of_problem, cons
                        const double* H, const int32_t* problem_index, double chi2_factor,
                        int n_f, const double* F, double* out_var, double* out_diag, double* out_prior,
                        float* out_ms);
+/* Draws from the Gaussian posterior that mxe_posterior_var integrates, for error bars of what is not linear in A (a peak
+ * position, a gap edge, Sigma(omega)).  Replaces nothing of the reference.  In the notation above (w, V', c, a = alpha~ /
+ * eta, B = c W c + a I = L L^T), with z1 [n_omega] and z2 [n_s] independent standard normals:
+ *   q_i     = sqrt(a w_i) z1_i + w_i V'_i . (c o z2)        (q = w o r, cov r = a diag(1/w) + V' c^2 V'^T; no division by w)
+ *   y       = c o V'^T q
+ *   x       = L^-T L^-1 y                                     (forward, then backward substitution; B^-1 is never formed)
+ *   delta_i = (1/a) [q_i - w_i V'_i . (c o x)] / sqrt(eta)
+ * so that cov delta = Gamma exactly; w_i = 0 gives delta_i = 0.  out_dH [P][n_samples][n_omega] (host) receives delta:
+ * a sample of H is the minimiser plus its row.  elem_of_problem, alpha_scaled, H, problem_index and chi2_factor as in
+ * mxe_posterior_var (also the rows of the last launch with H == NULL, and MXE_ERR_STATE).
+ *   z == NULL:  the normals are generated on the device, see mxe_normals: problem p draws from (seed, stream[p]), its
+ *               sample s uses the normals 0 .. n_omega-1 as z1 and n_omega .. n_omega+n_s-1 as z2 (n_s: the kept rank);
+ *   z != NULL:  z [P][n_samples][n_omega + n_s] on the host, finite, used as given (seed and stream are ignored).
+ * A problem whose H row is not finite or whose B is not positive definite gets NaN in all its samples, the others are
+ * not touched and the call returns MXE_OK.  No atomics, fixed summation order: the bits of sample s of a problem depend on
+ * neither the other problems of the call nor on n_samples.  MXE_ERR_ARG: n_samples < 1, P n_samples (n_omega + n_s) >
+ * 2^31 - 1, a z that is not finite.  MXE_ERR_LIMIT as mxe_posterior_var.  out_ms: device time (may be NULL). */
+int  mxe_posterior_sample(mxe_ctx* ctx, int P, const int32_t* elem_of_problem, const double* alpha_scaled,
+                          const double* H, const int32_t* problem_index, double chi2_factor,
+                          int n_samples, uint64_t seed, const uint64_t* stream, const double* z,
+                          double* out_dH, float* out_ms);
+/* The standard normals of mxe_posterior_sample, out_z [n_samples][n] (host), by the same device function.  Philox4x32-10
+ * (Salmon et al. 2011; multipliers 0xD2511F53, 0xCD9E8D57, Weyl constants 0x9E3779B9, 0xBB67AE85) with the key (seed low,
+ * seed high) and the counter (j, s, stream low, stream high): s the sample, j the pair of normals.  From the output
+ * words x0..x3:  u1 = (((x0 2^32 + x1) >> 11) + 0.5) 2^-53, u2 likewise from x2, x3,
+ *   z_2j = sqrt(-2 ln u1) cos(2 pi u2),  z_2j+1 = sqrt(-2 ln u1) sin(2 pi u2)      (|z| < 8.7).
+ * A sample's normals depend on (seed, stream, s) alone.  maxent_amd.posterior.sample_normals is the host mirror. */
+int  mxe_normals(int device, uint64_t seed, uint64_t stream, int n_samples, int n, double* out_z);
 /* NormalEntropy / PlusMinusEntropy as functions of a hidden image given directly (functions.py:508-520,
  * 544-564): S, dS/dH and the diagonal of d2S/dH2 for P images H [P][n_omega] and one default model D
  * [n_omega] (including delta-omega).  No context needed; outputs may be NULL. */

@@ -310,6 +310,8 @@ struct mxe_ctx {
     // mxe_posterior_var scratch: alpha | H rows | F | var | prior | diag;  elem | row
     DevBuf<double> pv_d;
     DevBuf<int> pv_i;
+    // mxe_posterior_sample scratch: alpha | stream ids | H rows | normals | samples  (elem | row in pv_i)
+    DevBuf<double> ps_d;
     // mxe_resample_reduce scratch: scale | H rows | F | fval | mean | var | fmean | fcov;  offsets | flags | used | rows
     DevBuf<double> rr_d;
     DevBuf<int> rr_i;
@@ -2797,6 +2799,107 @@ try {
         for (size_t i = 0; i < (size_t)P * n_f; ++i) { out_var[i] /= chi2_factor; if (out_prior) out_prior[i] /= chi2_factor; }
         if (out_diag) for (size_t i = 0; i < (size_t)P * nw; ++i) out_diag[i] /= chi2_factor;
     }
+    return MXE_OK;
+}
+MXE_CATCH_ALL
+
+// ---- draws from the Gaussian posterior of H (mxe_postsample.hip.h) ---------------------------------------------------
+#include "mxe_postsample.hip.h"
+
+extern "C" int mxe_posterior_sample(mxe_ctx* ctx, int P, const int32_t* elem_of_problem, const double* alpha_scaled,
+                                    const double* H, const int32_t* problem_index, double chi2_factor,
+                                    int n_samples, uint64_t seed, const uint64_t* stream, const double* z,
+                                    double* out_dH, float* out_ms)
+try {
+    if (!ctx || P < 1 || !elem_of_problem || !alpha_scaled || !out_dH || n_samples < 1 || (!z && !stream)) return MXE_ERR_ARG;
+    if (ctx->n_elem < 1) return MXE_ERR_STATE;
+    if (!H && !ctx->launched) return MXE_ERR_STATE;
+    if (!(chi2_factor > 0.0) || !std::isfinite(chi2_factor)) return MXE_ERR_ARG;
+    const int NP = ctx->NP, nw = ctx->n_omega, nz = nw + ctx->n_s;
+    if ((size_t)P * (size_t)n_samples * (size_t)nz > 0x7fffffffull) return MXE_ERR_ARG;
+    const size_t lds = mxe::postsample_lds_bytes(NP, ctx->nwp);
+    if (lds > 160 * 1024) return MXE_ERR_LIMIT;
+    const size_t n_z = (size_t)P * n_samples * nz, n_out = (size_t)P * n_samples * nw;
+    if (z) for (size_t i = 0; i < n_z; ++i) if (!std::isfinite(z[i])) return MXE_ERR_ARG;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (ctx->ds_dirty) { int rc = upload_bases(ctx); if (rc != MXE_OK) return rc; }
+    const size_t n_last = (size_t)ctx->n_chain * ctx->n_alpha;
+    std::vector<double> ha(P);
+    std::vector<int> hi((size_t)2 * P);
+    for (int p = 0; p < P; ++p) {
+        const int e = elem_of_problem[p];
+        if (e < 0 || e >= ctx->n_elem) return MXE_ERR_ARG;
+        if (!(alpha_scaled[p] > 0.0) || !std::isfinite(alpha_scaled[p])) return MXE_ERR_ARG;
+        ha[p] = alpha_scaled[p] / chi2_factor;
+        hi[p] = e;
+        int row = p;
+        if (!H) {
+            row = problem_index ? problem_index[p] : p;
+            if (row < 0 || (size_t)row >= n_last) return MXE_ERR_ARG;
+        }
+        hi[(size_t)P + p] = row;
+    }
+    // one block of doubles: alpha [P] | stream ids [P] (64-bit words) | H [P][nw] (when handed in) | z | samples
+    const size_t oS = (size_t)P, oH = oS + (size_t)P, oZ = oH + (H ? (size_t)P * nw : 0), oO = oZ + n_z, total = oO + n_out;
+    HIPCHK(ctx, ctx->ps_d.ensure(total));
+    HIPCHK(ctx, ctx->pv_i.ensure((size_t)2 * P));
+    double* d = ctx->ps_d.p;
+    HIPCHK(ctx, hipMemcpyAsync(d, ha.data(), (size_t)P * 8, hipMemcpyHostToDevice, ctx->stream));
+    if (H) HIPCHK(ctx, hipMemcpyAsync(d + oH, H, (size_t)P * nw * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->pv_i.p, hi.data(), hi.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    if (z) HIPCHK(ctx, hipMemcpyAsync(d + oZ, z, n_z * 8, hipMemcpyHostToDevice, ctx->stream));
+    else HIPCHK(ctx, hipMemcpyAsync(d + oS, stream, (size_t)P * 8, hipMemcpyHostToDevice, ctx->stream));
+    mxe::PostSampleParams pp;
+    pp.V = ctx->dV.p; pp.c = ctx->dc.p; pp.elem_ds = ctx->delem_ds.p; pp.elem_kind = ctx->delem_kind.p; pp.D = ctx->dD.p;
+    pp.elem = ctx->pv_i.p; pp.alpha = d;
+    pp.H = H ? d + oH : ctx->dout_H.p; pp.row = H ? nullptr : ctx->pv_i.p + P;
+    pp.z = d + oZ; pp.out = d + oO; pp.scale = 1.0 / std::sqrt(chi2_factor);
+    pp.nw = nw; pp.nwp = ctx->nwp; pp.ns = ctx->n_s; pp.n_samples = n_samples;
+    SvdScratch sc;                    // (the two events of the timing, released on every path)
+    if (out_ms) {
+        HIPCHK(ctx, hipEventCreate(&sc.e0)); HIPCHK(ctx, hipEventCreate(&sc.e1));
+        HIPCHK(ctx, hipEventRecord(sc.e0, ctx->stream));
+    }
+    if (!z) {
+        const size_t per = (size_t)n_samples * ((nz + 1) / 2);
+        const unsigned gx = (unsigned)std::min<size_t>((per + 255) / 256, 1024), gy = (unsigned)std::min(P, 65535);
+        hipLaunchKernelGGL(mxe::normals_kernel, dim3(gx, gy), dim3(256), 0, ctx->stream, seed, (const uint64_t*)(d + oS),
+                           (uint64_t)0, P, n_samples, nz, d + oZ);
+        HIPCHK(ctx, hipGetLastError());
+    }
+    hipError_t e;
+#define MXE_LAUNCH_POSTSAMPLE(NT_) do { \
+        e = hipFuncSetAttribute((const void*)mxe::postsample_kernel<NT_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+        if (e == hipSuccess) { hipLaunchKernelGGL((mxe::postsample_kernel<NT_>), dim3((unsigned)P), dim3(256), lds, ctx->stream, pp); \
+                               e = hipGetLastError(); } } while (0)
+    if (NP == 64) MXE_LAUNCH_POSTSAMPLE(4); else MXE_LAUNCH_POSTSAMPLE(8);
+#undef MXE_LAUNCH_POSTSAMPLE
+    HIPCHK(ctx, e);
+    if (out_ms) HIPCHK(ctx, hipEventRecord(sc.e1, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(out_dH, d + oO, n_out * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, stream_wait(ctx->stream));
+    if (out_ms) HIPCHK(ctx, hipEventElapsedTime(out_ms, sc.e0, sc.e1));
+    return MXE_OK;
+}
+MXE_CATCH_ALL
+
+extern "C" int mxe_normals(int device, uint64_t seed, uint64_t stream, int n_samples, int n, double* out_z)
+try {
+    if (n_samples < 1 || n < 1 || !out_z || (size_t)n_samples * (size_t)n > 0x7fffffffull) return MXE_ERR_ARG;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return MXE_ERR_NODEVICE;
+    if (device < 0 || device >= ndev) return MXE_ERR_ARG;
+    SvdScratch sc;                    // stream + buffer released on every path
+    SVDCHK(hipSetDevice(device));
+    SVDCHK(hipStreamCreateWithFlags(&sc.stream, hipStreamNonBlocking));
+    double* dz;
+    SVDCHK(sc.alloc(&dz, (size_t)n_samples * n));
+    const size_t per = (size_t)n_samples * ((n + 1) / 2);
+    hipLaunchKernelGGL(mxe::normals_kernel, dim3((unsigned)std::min<size_t>((per + 255) / 256, 1024), 1), dim3(256), 0, sc.stream,
+                       seed, (const uint64_t*)nullptr, stream, 1, n_samples, n, dz);
+    SVDCHK(hipGetLastError());
+    SVDCHK(hipMemcpyAsync(out_z, dz, (size_t)n_samples * n * 8, hipMemcpyDeviceToHost, sc.stream));
+    SVDCHK(hipStreamSynchronize(sc.stream));
     return MXE_OK;
 }
 MXE_CATCH_ALL

@@ -114,6 +114,9 @@ SYMBOLS = [
     ('mxe_eval_batch', ctypes.c_int, [_vp, ctypes.c_int, _ip, _dp, _dp, ctypes.c_int, ctypes.c_double] + [_dp] * 11),
     ('mxe_posterior_var', ctypes.c_int, [_vp, ctypes.c_int, _ip, _dp, _dp, _ip, ctypes.c_double, ctypes.c_int, _dp, _dp, _dp, _dp,
                                          ctypes.POINTER(ctypes.c_float)]),
+    ('mxe_posterior_sample', ctypes.c_int, [_vp, ctypes.c_int, _ip, _dp, _dp, _ip, ctypes.c_double, ctypes.c_int, ctypes.c_uint64,
+                                            ctypes.POINTER(ctypes.c_uint64), _dp, _dp, ctypes.POINTER(ctypes.c_float)]),
+    ('mxe_normals', ctypes.c_int, [ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int, ctypes.c_int, _dp]),
     ('mxe_entropy', ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, _dp, _dp]),
     ('mxe_audit', ctypes.c_int, [_vp, _dp, _dp]),
     ('mxe_select_launch', ctypes.c_int, [_vp, ctypes.c_int]),
@@ -605,6 +608,21 @@ def entropy(kind, H, D, device=0):
     return S, dS, ddS
 
 
+def normals(seed, stream, n_samples, n, device=0):
+    """``mxe_normals``: the standard normals (n_samples, n) of the stream ``(seed, stream)``, by the device function
+    ``mxe_posterior_sample`` draws with; :func:`maxent_amd.posterior.sample_normals` is the host mirror."""
+    lib = load_library()
+    if device_count() < 1:
+        raise MaxEntDeviceError('no HIP device visible; mxe_normals has no CPU fallback (posterior.sample_normals is the host mirror)')
+    if int(n_samples) < 1 or int(n) < 1:
+        raise ValueError('normals: n_samples and n must be at least 1')
+    z = np.empty((int(n_samples), int(n)))
+    rc = lib.mxe_normals(int(device), int(seed) & (2 ** 64 - 1), int(stream) & (2 ** 64 - 1), int(n_samples), int(n), _p(z))
+    if rc != 0:
+        raise MaxEntDeviceError('mxe_normals failed: ' + lib.mxe_strerror(rc).decode())
+    return z
+
+
 class DeviceContext(object):
     """One solver context on one GPU: holds the truncated SVD of the kernel.
 
@@ -912,6 +930,60 @@ class DeviceContext(object):
         out = dict(var=var, prior=prior)
         if want_diag:
             out['diag'] = diag
+        return out
+
+    def posterior_sample(self, elem_of_problem, alpha_scaled, H=None, problem_index=None, chi2_factor=1.0, n_samples=1, seed=0,
+                         stream=None, z=None, timing=None):
+        """``mxe_posterior_sample``: draws ``delta`` (P, n_samples, n_omega) from the Gaussian posterior N(0, Gamma) around
+        the minimiser, on the staged elements; a sample of H is the minimiser plus its row.  ``H``, ``problem_index`` and
+        ``chi2_factor`` as in :meth:`posterior_var`.  ``z=None``: problem p draws from the counter-based stream
+        ``(seed, stream[p])`` (``stream``: P 64-bit ids, default 0 .. P-1; see :func:`normals`); else ``z``
+        (P, n_samples, n_omega + n_s) standard normals that are used as given.  A problem whose H row is not finite or whose
+        curvature matrix is not positive definite has NaN in all its samples.  ``timing``: a dict that receives the device
+        time ``ms``."""
+        if self._n_s_dev < self.n_s:
+            raise MaxEntDeviceError('posterior_sample on a context that keeps %d of %d singular directions' % (self._n_s_dev, self.n_s))
+        el = _c(np.atleast_1d(elem_of_problem), np.int32)
+        P = len(el)
+        al = _c(np.broadcast_to(np.asarray(alpha_scaled, dtype=float), (P,)))
+        if not np.all(al > 0) or not np.all(np.isfinite(al)):
+            raise ValueError('posterior_sample: every alpha must be positive and finite')
+        n_samples = int(n_samples)
+        if n_samples < 1:
+            raise ValueError('posterior_sample: n_samples must be at least 1')
+        nz = self.n_omega + self.n_s
+        if P * n_samples * nz > 2 ** 31 - 1:
+            raise ValueError('posterior_sample: P n_samples (n_omega + n_s) = %d exceeds 2^31 - 1; draw in several calls'
+                             % (P * n_samples * nz))
+        if H is not None:
+            H = _c(H).reshape(P, self.n_omega)
+            pi = None
+        else:
+            pi = _c(np.arange(P) if problem_index is None else np.atleast_1d(problem_index), np.int32)
+            n_last = self._n_chain * self._n_alpha           # (0: nothing launched, the library answers MXE_ERR_STATE)
+            if len(pi) != P or (n_last and P and (pi.min() < 0 or pi.max() >= n_last)):
+                raise ValueError('posterior_sample: problem_index must name %d problems of the last launch (%d x %d)'
+                                 % (P, self._n_chain, self._n_alpha))
+        st = None
+        if z is not None:
+            z = _c(z)
+            if z.shape != (P, n_samples, nz):
+                raise ValueError('posterior_sample: z must have the shape (P, n_samples, n_omega + n_s) = %r, got %r'
+                                 % ((P, n_samples, nz), z.shape))
+            if not np.all(np.isfinite(z)):
+                raise ValueError('posterior_sample: z holds values that are not finite')
+        else:
+            st = np.ascontiguousarray(np.arange(P) if stream is None else np.atleast_1d(stream), dtype=np.uint64)
+            if st.shape != (P,):
+                raise ValueError('posterior_sample: stream must hold one id per problem')
+        out = np.empty((P, n_samples, self.n_omega))
+        ms = ctypes.c_float(0)
+        self._check(self._lib.mxe_posterior_sample(
+            self._h, P, _p(el), _p(al), _p(H), _p(pi), float(chi2_factor), n_samples, int(seed) & (2 ** 64 - 1),
+            None if st is None else st.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), _p(z), _p(out), ctypes.byref(ms)),
+            'mxe_posterior_sample')
+        if timing is not None:
+            timing['ms'] = float(ms.value)
         return out
 
     def resample_reduce(self, group_offset, scale, H=None, problem_index=None, F=None, want=('mean', 'var', 'fval', 'fmean', 'fcov'),

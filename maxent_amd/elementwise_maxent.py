@@ -768,6 +768,90 @@ class ElementwiseMaxEnt(object):
                     out[name][(key[1], key[0]) + key[2:]] = val * flip if val.dtype.kind == 'f' else val
         return out
 
+    def posterior_samples(self, result=None, n_samples=100, seed=0, alpha=None, transform='linear', z=None, timing=None):
+        """:meth:`TauMaxEnt.posterior_samples` for every matrix element of ``result`` (default: the last result of this
+        object): all elements of a worker in ONE call of ``mxe_posterior_sample`` per device.  The stream of an element is
+        ((flat matrix index) * 2 + complex index) * n_alpha + alpha index, so an element draws the same spectra alone and
+        inside a matrix, and different elements draw independently.  ``z`` is used for every element alike.  Returns a dict of arrays laid out like
+        :meth:`posterior_errors`' (elements that were not computed hold NaN; those that follow from hermiticity are
+        filled from their partners, the imaginary part's spectra with the other sign).  ``transform='log'`` raises
+        ``ValueError`` when plus-minus (off-diagonal) elements are among them."""
+        from . import posterior
+        res = self.maxent_result if result is None else result
+        if res is None:
+            raise ValueError('no result: run() first or hand one in')
+        if int(n_samples) < 1:
+            raise ValueError('n_samples must be at least 1, got {}'.format(n_samples))
+        if transform not in posterior.TRANSFORMS:
+            raise ValueError('transform={!r}: one of {} is needed'.format(transform, posterior.TRANSFORMS))
+        zero = set(tuple(z0) for z0 in res.zero_elements)
+        phases = [(self.maxent_diagonal, self._diag_jobs(), None)]
+        if not isinstance(self, DiagonalMaxEnt):
+            off = self._offdiag_jobs()
+            phases.append((self.maxent_offdiagonal, off, self._posterior_models(off, res)))
+        ids = self.device_ids if self.device_ids else (self.maxent_diagonal.maxent_loop.device_id,)
+        collected, ms = [], 0.0
+        for worker, jobs, models in phases:
+            loop = worker.maxent_loop
+            items, keys = [], []
+            for n, (element, re) in enumerate(jobs):
+                cidx = 0 if re else 1
+                key = tuple(element) + ((cidx,) if self.use_complex else ())
+                if key in zero:
+                    continue
+                try:
+                    H = np.asarray(res.element_array('H', key), dtype=float)
+                except (KeyError, IndexError, AttributeError, AssertionError):
+                    continue
+                if H.ndim != 2 or H.shape[0] == 0:
+                    continue
+                if models is not None:
+                    worker.set_D(models[n])
+                self._load_element(worker, element, re)
+                spec = loop.make_spec()
+                posterior.check_alpha(spec, res.alpha)
+                logp = np.asarray(res.element_array('probability', key), dtype=float)
+                ana = res.analyzer_results
+                for i in key:
+                    ana = ana[i]
+                flat = int(np.ravel_multi_index(tuple(element), tuple(self.shape)))
+                items.append(dict(spec=spec, H=H, alpha=np.asarray(res.alpha, dtype=float), analysis=ana,
+                                  probability=None if np.all(np.isnan(logp)) else logp, B=loop.A_of_H.matrix(),
+                                  stream=flat * 2 + cidx))
+                keys.append(key)
+            if not items:
+                continue
+            t = {}
+            outs = posterior.element_samples(worker.K, worker.omega, items, n_samples=n_samples, seed=seed, alpha=alpha,
+                                             transform=transform, z=z, default_name=res.default_analyzer_name,
+                                             chi2_factor=loop.cost_function.chi2_factor, device_ids=ids,
+                                             bryan=posterior.find_bryan(loop.analyzers), timing=t)
+            ms += t.get('ms', 0.0)
+            collected.extend(zip(keys, outs))
+        if timing is not None:
+            timing['ms'] = ms
+        if not collected:
+            raise ValueError('the result holds no element to draw samples for')
+        struct = tuple(self.shape) + ((2,) if self.use_complex else ())
+        out = dict(info={}, seed=int(seed))
+        for key, o in collected:
+            out['info'][key] = o['info']
+            for name, val in o.items():
+                if name in ('info', 'seed'):
+                    continue
+                val = np.asarray(val)
+                if name not in out:
+                    out[name] = np.full(struct + val.shape, np.nan) if val.dtype.kind == 'f' else \
+                        np.full(struct + val.shape, -1, dtype=val.dtype)
+                if out[name].shape[len(struct):] != val.shape:
+                    raise ValueError('{}: the elements chose different numbers of alphas; use alpha= indices'.format(name))
+                out[name][key] = val
+                if self.use_hermiticity and key[0] != key[1]:
+                    # G_ji = conj(G_ij): the same spectra; the imaginary part's change sign
+                    flip = -1.0 if (len(key) == 3 and key[2] == 1 and name in ('H', 'H_samples', 'A_samples')) else 1.0
+                    out[name][(key[1], key[0]) + key[2:]] = val * flip if val.dtype.kind == 'f' else val
+        return out
+
     def resample_errors(self, bins, method='jackknife', block=1, n_resamples=None, seed=None, alpha=None,
                         alpha_mode='per_resample', windows=None, functionals=None, pointwise=True, keep_samples=False,
                         timing=None):

@@ -12,6 +12,10 @@ point-wise error ``A_err`` is there for completeness; it is large and strongly c
 The variances come from ``mxe_posterior_var`` (one call per device for all matrix elements and alphas); this module is
 the host glue: which alphas, which rows of weights on H, the mixture over alpha, the shape of what is returned.
 There is no CPU path: without the library and a GPU :class:`maxent_amd.device.MaxEntDeviceError` is raised.
+
+``posterior_samples`` draws spectra from the same Gaussian (``mxe_posterior_sample``) for error bars of what is not linear
+in A.  The standard normals behind a draw come from a counter-based generator (Philox4x32-10 + Box-Muller) that
+:func:`philox4x32_10` and :func:`sample_normals` mirror on the host, so a draw can be reproduced off the device.
 """
 
 import numpy as np
@@ -123,6 +127,67 @@ def entropy_weights(H, D, kind):
     if kind == device.ENTROPY_NORMAL:
         return H
     return np.sqrt(H * H + 4.0 * np.asarray(D, dtype=float) ** 2)
+
+
+# ---- the generator of mxe_normals / mxe_posterior_sample, mirrored in numpy ----------------------------------------
+
+_PHILOX_M0, _PHILOX_M1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57)
+_PHILOX_W0, _PHILOX_W1 = 0x9E3779B9, 0xBB67AE85
+_M32 = np.uint64(0xFFFFFFFF)
+
+
+def philox4x32_10(counter, key):
+    """Philox4x32-10 (Salmon et al. 2011, the Random123 constants): ``counter`` (..., 4) and ``key`` (..., 2) 32-bit words
+    (broadcast against each other) -> (..., 4) uint32"""
+    c = np.asarray(counter, dtype=np.uint64) & _M32
+    k = np.asarray(key, dtype=np.uint64) & _M32
+    shape = np.broadcast_shapes(c.shape[:-1], k.shape[:-1])
+    c0, c1, c2, c3 = (np.broadcast_to(c[..., i], shape).copy() for i in range(4))
+    k0, k1 = (np.broadcast_to(k[..., i], shape).copy() for i in range(2))
+    for r in range(10):
+        p0, p1 = _PHILOX_M0 * c0, _PHILOX_M1 * c2                    # (32 x 32 -> 64 bits: no overflow)
+        c0, c1, c2, c3 = (p1 >> np.uint64(32)) ^ c1 ^ k0, p1 & _M32, (p0 >> np.uint64(32)) ^ c3 ^ k1, p0 & _M32
+        k0, k1 = (k0 + np.uint64(_PHILOX_W0)) & _M32, (k1 + np.uint64(_PHILOX_W1)) & _M32
+    return np.stack([c0, c1, c2, c3], axis=-1).astype(np.uint32)
+
+
+def sample_normals(seed, stream, n_samples, n):
+    """the standard normals (n_samples, n) that ``mxe_normals`` gives for ``(seed, stream)``: key (seed low, seed high),
+    counter (j, s, stream low, stream high) for the pair j of sample s; u = (((x0 2^32 + x1) >> 11) + 0.5) 2^-53 from each
+    half of the output, z_2j = sqrt(-2 ln u1) cos(2 pi u2), z_2j+1 = sqrt(-2 ln u1) sin(2 pi u2).  Row s depends on
+    (seed, stream, s) alone."""
+    seed, stream = int(seed) & (2 ** 64 - 1), int(stream) & (2 ** 64 - 1)
+    n_samples, n = int(n_samples), int(n)
+    if n_samples < 1 or n < 1:
+        raise ValueError('sample_normals: n_samples and n must be at least 1')
+    npair = (n + 1) // 2
+    ctr = np.empty((n_samples, npair, 4), dtype=np.uint64)
+    ctr[..., 0] = np.arange(npair, dtype=np.uint64)[np.newaxis, :]
+    ctr[..., 1] = np.arange(n_samples, dtype=np.uint64)[:, np.newaxis]
+    ctr[..., 2], ctr[..., 3] = stream & 0xFFFFFFFF, stream >> 32
+    x = philox4x32_10(ctr, np.array([seed & 0xFFFFFFFF, seed >> 32], dtype=np.uint64)).astype(np.uint64)
+    u1 = ((((x[..., 0] << np.uint64(32)) | x[..., 1]) >> np.uint64(11)).astype(np.float64) + 0.5) * 2.0 ** -53
+    u2 = ((((x[..., 2] << np.uint64(32)) | x[..., 3]) >> np.uint64(11)).astype(np.float64) + 0.5) * 2.0 ** -53
+    r, t = np.sqrt(-2.0 * np.log(u1)), 6.283185307179586 * u2
+    z = np.empty((n_samples, 2 * npair))
+    z[:, 0::2], z[:, 1::2] = r * np.cos(t), r * np.sin(t)
+    return np.ascontiguousarray(z[:, :n])
+
+
+def stream_id(flat_element, complex_index, n_alpha, alpha_index):
+    """the 64-bit stream of one (element, alpha): an element draws the same spectra alone and inside a matrix"""
+    return (int(flat_element) * 2 + int(complex_index)) * int(n_alpha) + int(alpha_index)
+
+
+def bryan_allotment(p, n_samples, seed, stream_base=0):
+    """for every sample the index (into ``p``) of its alpha, drawn with the Bryan weights ``p`` from
+    ``np.random.Generator(np.random.Philox(seed))`` (counter word 3 = ``stream_base``: elements draw independently)"""
+    n_samples = int(n_samples)
+    if n_samples < 1:
+        raise ValueError('n_samples must be at least 1')
+    p = np.asarray(p, dtype=float)
+    rng = np.random.Generator(np.random.Philox(key=int(seed) & (2 ** 64 - 1), counter=[0, 0, 0, int(stream_base)]))
+    return rng.choice(len(p), size=n_samples, p=p / p.sum())
 
 
 # ---- the device part ------------------------------------------------------------------------------------------------
@@ -288,6 +353,144 @@ def element_errors(K, omega, items, alpha=None, windows=None, functionals=None, 
             out['functional_prior_err'] = perr[..., n_win:n_win + n_fun]
         if pointwise:
             out['A'], out['A_err'], out['A_prior_err'] = A_val, np.sqrt(A_var), np.sqrt(A_prior)
+        outs.append(out)
+    return outs
+
+
+# ---- samples ---------------------------------------------------------------------------------------------------------
+
+TRANSFORMS = ('linear', 'log')
+
+
+def device_samples(K, specs, H_rows, alpha_rows, stream_rows, n_samples, seed, z_rows=None, chi2_factor=1.0, device_ids=None,
+                   timing=None):
+    """``mxe_posterior_sample`` for the elements ``specs`` of the kernel ``K`` (as :func:`device_variances`; the devices are
+    visited one after the other).  Returns per element ``delta`` (n_e, n_samples, n_omega)."""
+    device_ids = tuple(device_ids) if device_ids else (0,)
+    n = len(specs)
+    out = [None] * n
+    ms, reused = 0.0, 0
+    for r, dev in enumerate(device_ids):
+        mine = list(range(r, n, len(device_ids)))
+        if not mine:
+            continue
+        sub = [specs[e] for e in mine]
+        from .batch_solver import BatchSolver
+        ctx, solver = BatchSolver.staged_context_for(K, sub, dev) if len(device_ids) == 1 else (None, None)
+        own = ctx is None
+        reused += 0 if own else 1
+        if own:
+            ctx = _stage(K, sub, dev)
+        try:
+            el = np.concatenate([np.full(len(alpha_rows[e]), k, dtype=np.int32) for k, e in enumerate(mine)])
+            al = np.concatenate([np.asarray(alpha_rows[e], dtype=float) for e in mine])
+            Hs = np.concatenate([np.asarray(H_rows[e], dtype=float).reshape(len(alpha_rows[e]), -1) for e in mine])
+            st = np.concatenate([np.asarray(stream_rows[e], dtype=np.uint64) for e in mine])
+            zz = None if z_rows is None else np.concatenate([np.asarray(z_rows[e], dtype=float) for e in mine])
+            t = {}
+            kw = dict(H=Hs, chi2_factor=chi2_factor, n_samples=n_samples, seed=seed, stream=st, z=zz, timing=t)
+            if solver is not None:
+                with solver._lock:
+                    got = ctx.posterior_sample(el, al, **kw)
+            else:
+                got = ctx.posterior_sample(el, al, **kw)
+            ms += t.get('ms', 0.0)
+        finally:
+            if own:
+                ctx.close()
+        pos = 0
+        for e in mine:
+            k = len(alpha_rows[e])
+            out[e] = got[pos:pos + k]
+            pos += k
+    if timing is not None:
+        timing['ms'] = ms
+        timing['reused_contexts'] = reused
+    return out
+
+
+def apply_transform(H, delta, transform):
+    """a sample of H from the minimiser ``H`` (..., n_omega) and the Gaussian draw ``delta`` (..., n_samples, n_omega):
+    ``'linear'`` H + delta; ``'log'`` H exp(delta / H), positive and equal to first order (normal entropy)"""
+    H = np.asarray(H, dtype=float)[..., np.newaxis, :]
+    if transform == 'linear':
+        return H + delta
+    with np.errstate(divide='ignore', invalid='ignore', over='ignore'):
+        return np.where(H > 0, H * np.exp(delta / np.where(H > 0, H, 1.0)), H + delta)
+
+
+def element_samples(K, omega, items, n_samples=100, seed=0, alpha=None, transform='linear', z=None, default_name=None,
+                    chi2_factor=1.0, device_ids=None, bryan=None, timing=None):
+    """Draws from the Gaussian posterior of the elements ``items`` of one kernel.  An item: as in :func:`element_errors`,
+    with ``stream`` = (flat element index) * 2 + complex index.  Returns a list of dicts, one per item (see
+    ``TauMaxEnt.posterior_samples``)."""
+    n_samples = int(n_samples)
+    if n_samples < 1:
+        raise ValueError('n_samples must be at least 1, got {}'.format(n_samples))
+    if transform not in TRANSFORMS:
+        raise ValueError('transform={!r}: one of {} is needed'.format(transform, TRANSFORMS))
+    if transform == 'log' and any(it['spec']['kind'] != device.ENTROPY_NORMAL for it in items):
+        raise ValueError("transform='log' needs the normal entropy (a positive H); plus-minus elements take 'linear'")
+    delta = np.asarray(omega.delta, dtype=float)
+    n_omega, nz = len(delta), len(delta) + len(np.array(K.S))
+    B = items[0].get('B')
+    picks, hows, allot = [], [], []
+    for it in items:
+        n_alpha = len(it['alpha'])
+        idx, how = choose_alpha(alpha, n_alpha, it.get('analysis'), default_name)
+        p = who = None
+        if how == 'bryan':
+            logp = it.get('probability')
+            if logp is None:
+                raise ValueError('Probability not calculated. Cannot use BryanAnalyzer.')
+            average = bool(bryan.average_by_integration) if bryan is not None else False
+            good, p = bryan_weights(logp, it['alpha'], average)
+            who = np.nonzero(good)[0][bryan_allotment(p, n_samples, seed, it.get('stream', 0))]
+            idx = sorted(set(int(i) for i in who))               # (only the alphas that own a sample are drawn from)
+        picks.append(idx)
+        hows.append((how, p))
+        allot.append(who)
+    z_rows = None
+    if z is not None:
+        if any(h == 'bryan' for h, _ in hows):
+            raise ValueError("z= cannot be combined with alpha='bryan' (the allotment decides which normals are used)")
+        z = np.asarray(z, dtype=float)
+        z_rows = []
+        for idx in picks:
+            if z.shape not in ((n_samples, nz), (len(idx), n_samples, nz)):
+                raise ValueError('z: the shape (n_samples, n_omega + n_s) = {} or ({}, n_samples, n_omega + n_s) is needed, '
+                                 'got {}'.format((n_samples, nz), len(idx), z.shape))
+            z_rows.append(np.broadcast_to(z, (len(idx), n_samples, nz)))
+        if not np.all(np.isfinite(z)):
+            raise ValueError('z holds values that are not finite')
+    H_rows = [np.asarray(it['H'], dtype=float)[idx] for it, idx in zip(items, picks)]
+    al_rows = [np.asarray(it['alpha'], dtype=float)[idx] for it, idx in zip(items, picks)]
+    st_rows = [[it.get('stream', 0) * len(it['alpha']) + i for i in idx] for it, idx in zip(items, picks)]
+    # with 'bryan' sample s takes the draw s of its alpha's stream: n_samples draws of every alpha that owns one
+    deltas = device_samples(K, [it['spec'] for it in items], H_rows, al_rows, st_rows, n_samples, seed, z_rows=z_rows,
+                            chi2_factor=chi2_factor, device_ids=device_ids, timing=timing)
+    outs = []
+    for n, it in enumerate(items):
+        Hn, an, dn = H_rows[n], al_rows[n], deltas[n]
+        how, p = hows[n]
+        bad = np.nonzero(np.any(np.isnan(dn), axis=(1, 2)))[0]
+        out = dict(alpha_index=np.array(picks[n]), alpha=an, seed=int(seed),
+                   info=dict(nan_rows=[int(picks[n][b]) for b in bad]))
+        Hs = apply_transform(Hn, dn, transform)                 # (n_e, n_samples, n_omega)
+        if how == 'bryan':
+            pos = np.searchsorted(np.array(picks[n]), allot[n])
+            Hs = Hs[pos, np.arange(n_samples)]
+            good = np.logical_not(np.isnan(np.asarray(it['probability'], dtype=float)))
+            out['H'] = np.dot(p, np.asarray(it['H'], dtype=float)[good])
+            out['alpha_index_samples'], out['weights'] = np.asarray(allot[n]), p
+            out['alpha_index'], out['alpha'] = np.nonzero(good)[0], np.asarray(it['alpha'], dtype=float)[good]
+        elif how == 'one':
+            Hs, out['H'] = Hs[0], Hn[0]
+            out['alpha_index'], out['alpha'] = out['alpha_index'][0], out['alpha'][0]
+        else:
+            out['H'] = Hn
+        out['H_samples'] = Hs
+        out['A_samples'] = Hs / delta if B is None else np.dot(Hs, np.asarray(B, dtype=float).T)
         outs.append(out)
     return outs
 

@@ -435,6 +435,41 @@ class TauMaxEnt(object):
                                         chi2_factor=loop.cost_function.chi2_factor, device_ids=ids[:1],
                                         bryan=posterior.find_bryan(loop.analyzers), timing=timing)[0]
 
+    def posterior_samples(self, result=None, n_samples=100, seed=0, alpha=None, transform='linear', z=None, timing=None):
+        """Spectra drawn from the Gaussian posterior around the minimiser that :meth:`posterior_errors` integrates
+        (``mxe_posterior_sample``), for error bars of what is not linear in A: a peak position or width, a gap edge, a
+        quasi-particle weight, Sigma(omega) after ``set_Gaux_w_from_Aaux_w``.  Evaluate the quantity on every row of
+        ``A_samples`` and take the spread.  Not in the reference.
+
+        ``result``: a result of this object (required: a ``TauMaxEnt`` keeps none).  ``alpha`` as in
+        :meth:`posterior_errors`; with ``'bryan'`` every sample's alpha is allotted with the ``BryanAnalyzer`` weights from
+        ``np.random.Generator(np.random.Philox(seed))`` and returned as ``alpha_index_samples``.  ``seed``: the draw is a
+        function of (seed, element, alpha, sample index) alone (a counter-based generator,
+        :func:`maxent_amd.posterior.sample_normals` mirrors it), so more samples extend a draw and never change it.
+        ``z``: standard normals (n_samples, n_omega + n_s) -- or one such block per chosen alpha -- used instead of the
+        generator's.  ``transform='linear'``: H + delta, the Gaussian itself, consistent with :meth:`posterior_errors` (tail
+        points can go negative); ``'log'``: H exp(delta / H), positive and equal to first order (normal entropy only).
+
+        Returns a dict: ``H`` (the minimiser), ``H_samples`` (n_samples, n_omega), ``A_samples`` (H / delta_omega, or B H
+        with a ``PreblurKernel``), ``alpha_index``, ``alpha``, ``seed``, ``info`` (``nan_rows``: alphas whose H is not
+        finite or whose curvature is not positive definite: their samples are NaN).  A sequence of alphas or ``'all'``
+        keeps an alpha axis in front."""
+        from . import posterior
+        if result is None:
+            raise ValueError('no result: hand in the result of run()')
+        loop = self.maxent_loop
+        spec = loop.make_spec()
+        posterior.check_alpha(spec, result.alpha)
+        H = np.asarray(result.element_array('H'))
+        logp = np.asarray(result.element_array('probability'), dtype=float)
+        item = dict(spec=spec, H=H, alpha=np.asarray(result.alpha, dtype=float), analysis=result.analyzer_results,
+                    probability=None if np.all(np.isnan(logp)) else logp, B=loop.A_of_H.matrix(), stream=0)
+        ids = loop.device_ids if loop.device_ids else (loop.device_id,)
+        return posterior.element_samples(self.K, self.omega, [item], n_samples=n_samples, seed=seed, alpha=alpha,
+                                         transform=transform, z=z, default_name=result.default_analyzer_name,
+                                         chi2_factor=loop.cost_function.chi2_factor, device_ids=ids[:1],
+                                         bryan=posterior.find_bryan(loop.analyzers), timing=timing)[0]
+
     def resample_errors(self, bins, method='jackknife', block=1, n_resamples=None, seed=None, alpha=None,
                         alpha_mode='per_resample', windows=None, functionals=None, pointwise=True, keep_samples=False,
                         timing=None):
