@@ -137,7 +137,8 @@ typedef struct mxe_opts {
                                 saves the last, verifying iteration; 0: tol_h is applied to
                                 the correction just taken only                              */
     int32_t precision;       /* MXE_PRECISION_F64 (default) or MXE_PRECISION_F32: V, u = V v, w, H,
-                                exp, h = V^T H and the Gram matrix in binary32 (fp32 MFMA); the
+                                exp, h = V^T H and the Gram matrix in binary32 (the Gram matrix by split-f16
+                                MFMA in the lock-step kernel, from V^T in the LDS as binary32 in chain_kernel_lv); the
                                 n_act x n_act Newton system, the residual and all scalars stay
                                 binary64.  An alpha also stops when its Newton correction has
                                 reached the rounding floor (it no longer shrinks).  n_s <= 64.

@@ -2433,110 +2433,20 @@ extern "C" int mxe_prof_fetch(mxe_ctx* ctx, long long* out /*[n_sub + 8192][8]*/
 }
 #endif
 
-// ---- log det(I + M W / alpha) of every problem of the last launch ------------
-namespace mxe {
-// One workgroup (4 waves) per problem.  In the whitened basis M = diag(c^2), so
-// det(I + M W / a) = det(c W c + a I) / a^n_s with W = V^T diag(w) V over ALL n_s
-// kept directions (no active-subspace cut here).  w is rebuilt from the stored H
-// (normal: w = H; plusminus: w = sqrt(H^2 + 4 D^2), free of cancellation).
-//   1. W by v_mfma_f64_16x16x4_f64, the omega rows split over the waves, the
-//      upper-triangular 16x16 tiles (mt <= nt) of one tile row per sweep of V;
-//   2. B = c W c + a I, Cholesky in LDS (right-looking, all threads);
-//   3. log det = 2 sum log L_jj - n_s log a.
-template <int NT>
-__global__ __launch_bounds__(256)
-void logdet_kernel(const double* __restrict__ Vall, const double* __restrict__ call,
-                   const int* __restrict__ elem_ds, const int* __restrict__ elem_kind,
-                   const double* __restrict__ Dall, const int* __restrict__ elem_of_chain,
-                   const double* __restrict__ alpha, const double* __restrict__ H,
-                   double* __restrict__ out, int n_alpha, int nw, int nwp, int ns)
+// ---- the kernels that factorise B = c W c + a I per problem (mxe_factor.hip.h): logdet, posterior variances, samples ----
+#include "mxe_factor.hip.h"
+
+// one workgroup per problem with lds bytes of dynamic LDS; k4 / k8: the 64-row and the 128-row build of the kernel
+template <typename... KArgs, typename... Args>
+static hipError_t launch_factor_kernel(void (*k4)(KArgs...), void (*k8)(KArgs...), const mxe_ctx* ctx, size_t P, size_t lds,
+                                       Args... args)
 {
-    typedef double d4 __attribute__((ext_vector_type(4)));
-    constexpr int NP = 16 * NT, LD = NP + 1;
-    extern __shared__ double sm[];
-    double* Bm = sm;                 // [NP][LD]
-    double* wsh = Bm + NP * LD;      // [nwp]
-    double* red = wsh + nwp;         // [4]
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const size_t prob = blockIdx.x;
-    const int e = elem_of_chain[prob / n_alpha];
-    const int ds = elem_ds[e], kind = elem_kind[e];
-    const double a = alpha[prob];
-    const double* V = Vall + (size_t)ds * nwp * NP;
-    const double* cc = call + (size_t)ds * NP;
-    const double* Hp = H + prob * nw;
-    const double* Dp = Dall + (size_t)e * nwp;
-    for (int i = tid; i < nwp; i += 256) {
-        double w = 0.0;
-        if (i < nw) {
-            const double h = Hp[i];
-            if (kind == 0) w = h;
-            else { const double d2 = 2.0 * Dp[i]; w = sqrt(fma(h, h, d2 * d2)); }
-        }
-        wsh[i] = w;
-    }
-    for (int i = tid; i < NP * LD; i += 256) Bm[i] = 0.0;
-    __syncthreads();
-    const int kq = lane >> 4, cn = lane & 15;
-    const int n_groups = nwp >> 2;
-    const int ntile = (ns + 15) >> 4;            // tile rows / columns that hold data
-    for (int mt = 0; mt < ntile; ++mt) {
-        d4 acc[NT];
-#pragma unroll
-        for (int t = 0; t < NT; ++t) acc[t] = d4{0.0, 0.0, 0.0, 0.0};
-        for (int g = wave; g < n_groups; g += 4) {
-            const double* row = V + (size_t)(4 * g + kq) * NP + cn;
-            const double wq = wsh[4 * g + kq];
-            const double am = row[16 * mt] * wq;
-#pragma unroll
-            for (int t = 0; t < NT; ++t)
-                if (t >= mt && t < ntile) acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(am, row[16 * t], acc[t], 0, 0, 0);
-        }
-        // the four waves add their partial tiles one after the other (fixed order)
-        for (int ph = 0; ph < 4; ++ph) {
-            if (wave == ph) {
-#pragma unroll
-                for (int t = 0; t < NT; ++t)
-                    if (t >= mt && t < ntile) {
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) Bm[(16 * mt + kq + 4 * r) * LD + 16 * t + cn] += acc[t][r];
-                    }
-            }
-            __syncthreads();
-        }
-    }
-    // B = c W c + a I on the upper triangle (row <= col), mirrored to the lower one
-    for (int idx = tid; idx < ns * ns; idx += 256) {
-        const int i = idx / ns, j = idx % ns;
-        if (i <= j) {
-            double b = cc[i] * Bm[i * LD + j] * cc[j];
-            if (i == j) b += a;
-            Bm[j * LD + i] = b;          // lower triangle: row j >= col i
-        }
-    }
-    __syncthreads();
-    // right-looking Cholesky on the lower triangle
-    double logsum = 0.0;
-    bool ok = true;
-    for (int j = 0; j < ns; ++j) {
-        const double piv = Bm[j * LD + j];
-        if (!(piv > 0.0)) ok = false;
-        const double d = sqrt(piv);
-        logsum += log(d);
-        __syncthreads();                         // everybody has read the pivot
-        for (int i = j + 1 + tid; i < ns; i += 256) Bm[i * LD + j] /= d;
-        __syncthreads();
-        const int m = ns - j - 1;
-        for (int idx = tid; idx < m * m; idx += 256) {
-            const int i = j + 1 + idx / m, k = j + 1 + idx % m;
-            if (k <= i) Bm[i * LD + k] = fma(-Bm[i * LD + j], Bm[k * LD + j], Bm[i * LD + k]);
-        }
-        __syncthreads();
-    }
-    if (tid == 0) out[prob] = ok ? 2.0 * logsum - ns * log(a) : __builtin_nan("");
-    (void)red;
+    void (*k)(KArgs...) = ctx->NP == 64 ? k4 : k8;
+    hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k, dim3((unsigned)P), dim3(256), lds, ctx->stream, args...);
+    return hipGetLastError();
 }
-} // namespace mxe
 
 extern "C" int mxe_logdet(mxe_ctx* ctx, double* out_logdet)
 try {
@@ -2544,22 +2454,15 @@ try {
     if (!ctx->launched) return MXE_ERR_STATE;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const size_t P = (size_t)ctx->n_chain * ctx->n_alpha;
-    const int NP = ctx->NP;
     HIPCHK(ctx, ctx->dlogdet.ensure(P));
     HIPCHK(ctx, ctx->dparent_elem.ensure(ctx->chain_elem.size()));
     HIPCHK(ctx, hipMemcpyAsync(ctx->dparent_elem.p, ctx->chain_elem.data(), ctx->chain_elem.size() * sizeof(int),
                                hipMemcpyHostToDevice, ctx->stream));
-    const size_t lds = ((size_t)NP * (NP + 1) + ctx->nwp + 4) * sizeof(double);
+    const size_t lds = mxe::logdet_lds_bytes(ctx->NP, ctx->nwp);
     if (lds > 160 * 1024) return MXE_ERR_LIMIT;
-    hipError_t e;
-#define MXE_LAUNCH_LOGDET(NT_) do { \
-        e = hipFuncSetAttribute((const void*)mxe::logdet_kernel<NT_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        if (e == hipSuccess) { hipLaunchKernelGGL((mxe::logdet_kernel<NT_>), dim3((unsigned)P), dim3(256), lds, ctx->stream, \
-            ctx->dV.p, ctx->dc.p, ctx->delem_ds.p, ctx->delem_kind.p, ctx->dD.p, ctx->dparent_elem.p, ctx->dalpha.p, \
-            ctx->dout_H.p, ctx->dlogdet.p, ctx->n_alpha, ctx->n_omega, ctx->nwp, ctx->n_s); e = hipGetLastError(); } } while (0)
-    if (NP == 64) MXE_LAUNCH_LOGDET(4); else MXE_LAUNCH_LOGDET(8);
-#undef MXE_LAUNCH_LOGDET
-    HIPCHK(ctx, e);
+    HIPCHK(ctx, launch_factor_kernel(mxe::logdet_kernel<4>, mxe::logdet_kernel<8>, ctx, P, lds,
+                                     ctx->dV.p, ctx->dc.p, ctx->delem_ds.p, ctx->delem_kind.p, ctx->dD.p, ctx->dparent_elem.p,
+                                     ctx->dalpha.p, ctx->dout_H.p, ctx->dlogdet.p, ctx->n_alpha, ctx->n_omega, ctx->nwp, ctx->n_s));
     HIPCHK(ctx, hipMemcpyAsync(out_logdet, ctx->dlogdet.p, P * 8, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, stream_wait(ctx->stream));
     return MXE_OK;
@@ -2721,8 +2624,67 @@ try {
 }
 MXE_CATCH_ALL
 
-// ---- posterior variances of linear functionals of H, and the diagonal of the covariance (mxe_postvar.hip.h) ----
+// ---- posterior variances of linear functionals of H and draws from the posterior (mxe_postvar.hip.h, mxe_postsample.hip.h) ----
 #include "mxe_postvar.hip.h"
+#include "mxe_postsample.hip.h"
+
+namespace {
+// the problems of a posterior call as they go to the device
+struct PostStage {
+    size_t lds = 0;
+    std::vector<double> ha;     // [P] alpha~ / eta
+    std::vector<int> hi;        // [P] element | [P] row of H
+};
+
+// Checks the state and the problems (elem, alpha, chi2_factor, row) of mxe_posterior_var / mxe_posterior_sample and fills
+// st; uploads the bases when they are stale.  n_max: the largest element count among the call's arrays; z: n_z host values
+// (or NULL) that must be finite before the device is touched.
+int stage_posterior(mxe_ctx* ctx, int P, const int32_t* elem_of_problem, const double* alpha_scaled, const double* H,
+                    const int32_t* problem_index, double chi2_factor, size_t n_max, const double* z, size_t n_z, PostStage& st)
+{
+    if (ctx->n_elem < 1) return MXE_ERR_STATE;
+    if (!H && !ctx->launched) return MXE_ERR_STATE;
+    if (!(chi2_factor > 0.0) || !std::isfinite(chi2_factor)) return MXE_ERR_ARG;
+    if (n_max > 0x7fffffffull) return MXE_ERR_ARG;
+    st.lds = mxe::postvar_lds_bytes(ctx->NP, ctx->nwp);
+    if (st.lds > 160 * 1024) return MXE_ERR_LIMIT;
+    if (z) for (size_t i = 0; i < n_z; ++i) if (!std::isfinite(z[i])) return MXE_ERR_ARG;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (ctx->ds_dirty) { int rc = upload_bases(ctx); if (rc != MXE_OK) return rc; }
+    const size_t n_last = (size_t)ctx->n_chain * ctx->n_alpha;
+    st.ha.resize(P);
+    st.hi.resize((size_t)2 * P);
+    for (int p = 0; p < P; ++p) {
+        const int e = elem_of_problem[p];
+        if (e < 0 || e >= ctx->n_elem) return MXE_ERR_ARG;
+        if (!(alpha_scaled[p] > 0.0) || !std::isfinite(alpha_scaled[p])) return MXE_ERR_ARG;
+        st.ha[p] = alpha_scaled[p] / chi2_factor;
+        st.hi[p] = e;
+        int row = p;
+        if (!H) {
+            row = problem_index ? problem_index[p] : p;
+            if (row < 0 || (size_t)row >= n_last) return MXE_ERR_ARG;
+        }
+        st.hi[(size_t)P + p] = row;
+    }
+    return MXE_OK;
+}
+
+// st and the H rows (when handed in) into the block d (alpha first, H at oH) and pv_i; fp: what the kernels share
+int upload_posterior(mxe_ctx* ctx, const PostStage& st, int P, const double* H, double* d, size_t oH, mxe::FactorParams& fp)
+{
+    const int nw = ctx->n_omega;
+    HIPCHK(ctx, ctx->pv_i.ensure((size_t)2 * P));
+    HIPCHK(ctx, hipMemcpyAsync(d, st.ha.data(), (size_t)P * 8, hipMemcpyHostToDevice, ctx->stream));
+    if (H) HIPCHK(ctx, hipMemcpyAsync(d + oH, H, (size_t)P * nw * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->pv_i.p, st.hi.data(), st.hi.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    fp.V = ctx->dV.p; fp.c = ctx->dc.p; fp.elem_ds = ctx->delem_ds.p; fp.elem_kind = ctx->delem_kind.p; fp.D = ctx->dD.p;
+    fp.elem = ctx->pv_i.p; fp.alpha = d;
+    fp.H = H ? d + oH : ctx->dout_H.p; fp.row = H ? nullptr : ctx->pv_i.p + P;
+    fp.nw = nw; fp.nwp = ctx->nwp; fp.ns = ctx->n_s;
+    return MXE_OK;
+}
+} // namespace
 
 extern "C" int mxe_posterior_var(mxe_ctx* ctx, int P, const int32_t* elem_of_problem, const double* alpha_scaled,
                                  const double* H, const int32_t* problem_index, double chi2_factor,
@@ -2732,63 +2694,31 @@ try {
     if (!ctx || P < 1 || !elem_of_problem || !alpha_scaled || n_f < 0 || (n_f > 0 && (!F || !out_var))) return MXE_ERR_ARG;
     if (n_f == 0 && !out_diag) return MXE_ERR_ARG;
     if (out_prior && n_f == 0) return MXE_ERR_ARG;
-    if (ctx->n_elem < 1) return MXE_ERR_STATE;
-    if (!H && !ctx->launched) return MXE_ERR_STATE;
-    if (!(chi2_factor > 0.0) || !std::isfinite(chi2_factor)) return MXE_ERR_ARG;
-    const int NP = ctx->NP, nw = ctx->n_omega;
-    if ((size_t)P * (size_t)std::max(n_f, 1) > 0x7fffffffull || (size_t)P * nw > 0x7fffffffull || (size_t)n_f * nw > 0x7fffffffull)
-        return MXE_ERR_ARG;
-    const size_t lds = mxe::postvar_lds_bytes(NP, ctx->nwp);
-    if (lds > 160 * 1024) return MXE_ERR_LIMIT;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    if (ctx->ds_dirty) { int rc = upload_bases(ctx); if (rc != MXE_OK) return rc; }
-    const size_t n_last = (size_t)ctx->n_chain * ctx->n_alpha;
-    std::vector<double> ha(P);
-    std::vector<int> hi((size_t)2 * P);
-    for (int p = 0; p < P; ++p) {
-        const int e = elem_of_problem[p];
-        if (e < 0 || e >= ctx->n_elem) return MXE_ERR_ARG;
-        if (!(alpha_scaled[p] > 0.0) || !std::isfinite(alpha_scaled[p])) return MXE_ERR_ARG;
-        ha[p] = alpha_scaled[p] / chi2_factor;
-        hi[p] = e;
-        int row = p;
-        if (!H) {
-            row = problem_index ? problem_index[p] : p;
-            if (row < 0 || (size_t)row >= n_last) return MXE_ERR_ARG;
-        }
-        hi[(size_t)P + p] = row;
-    }
+    const int nw = ctx->n_omega;
+    PostStage st;
+    // n_max bounds what the kernel indexes with 32 bits: var / prior [P][n_f], diag [P][nw] and F [n_f][nw]
+    const size_t n_max = std::max({(size_t)P * (size_t)std::max(n_f, 1), (size_t)P * nw, (size_t)n_f * nw});
+    int rc = stage_posterior(ctx, P, elem_of_problem, alpha_scaled, H, problem_index, chi2_factor, n_max, nullptr, 0, st);
+    if (rc != MXE_OK) return rc;
     for (size_t i = 0; i < (size_t)n_f * nw; ++i) if (!std::isfinite(F[i])) return MXE_ERR_ARG;
     // one block of doubles: alpha [P] | H [P][nw] (when handed in) | F [n_f][nw] | var [P][n_f] | prior [P][n_f] | diag [P][nw]
     const size_t oH = (size_t)P, oF = oH + (H ? (size_t)P * nw : 0), oV = oF + (size_t)n_f * nw, oP = oV + (size_t)P * n_f,
                  oD = oP + (out_prior ? (size_t)P * n_f : 0), total = oD + (out_diag ? (size_t)P * nw : 0);
     HIPCHK(ctx, ctx->pv_d.ensure(total));
-    HIPCHK(ctx, ctx->pv_i.ensure((size_t)2 * P));
     double* d = ctx->pv_d.p;
-    HIPCHK(ctx, hipMemcpyAsync(d, ha.data(), (size_t)P * 8, hipMemcpyHostToDevice, ctx->stream));
-    if (H) HIPCHK(ctx, hipMemcpyAsync(d + oH, H, (size_t)P * nw * 8, hipMemcpyHostToDevice, ctx->stream));
-    if (n_f) HIPCHK(ctx, hipMemcpyAsync(d + oF, F, (size_t)n_f * nw * 8, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->pv_i.p, hi.data(), hi.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
     mxe::PostVarParams pp;
-    pp.V = ctx->dV.p; pp.c = ctx->dc.p; pp.elem_ds = ctx->delem_ds.p; pp.elem_kind = ctx->delem_kind.p; pp.D = ctx->dD.p;
-    pp.elem = ctx->pv_i.p; pp.alpha = d;
-    pp.H = H ? d + oH : ctx->dout_H.p; pp.row = H ? nullptr : ctx->pv_i.p + P;
+    rc = upload_posterior(ctx, st, P, H, d, oH, pp);
+    if (rc != MXE_OK) return rc;
+    if (n_f) HIPCHK(ctx, hipMemcpyAsync(d + oF, F, (size_t)n_f * nw * 8, hipMemcpyHostToDevice, ctx->stream));
     pp.F = n_f ? d + oF : nullptr;
     pp.out_var = d + oV; pp.out_prior = out_prior ? d + oP : nullptr; pp.out_diag = out_diag ? d + oD : nullptr;
-    pp.nw = nw; pp.nwp = ctx->nwp; pp.ns = ctx->n_s; pp.n_f = n_f;
+    pp.n_f = n_f;
     SvdScratch sc;                    // (the two events of the timing, released on every path)
     if (out_ms) {
         HIPCHK(ctx, hipEventCreate(&sc.e0)); HIPCHK(ctx, hipEventCreate(&sc.e1));
         HIPCHK(ctx, hipEventRecord(sc.e0, ctx->stream));
     }
-    hipError_t e;
-#define MXE_LAUNCH_POSTVAR(NT_) do { \
-        e = hipFuncSetAttribute((const void*)mxe::postvar_kernel<NT_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        if (e == hipSuccess) { hipLaunchKernelGGL((mxe::postvar_kernel<NT_>), dim3((unsigned)P), dim3(256), lds, ctx->stream, pp); \
-                               e = hipGetLastError(); } } while (0)
-    if (NP == 64) MXE_LAUNCH_POSTVAR(4); else MXE_LAUNCH_POSTVAR(8);
-#undef MXE_LAUNCH_POSTVAR
-    HIPCHK(ctx, e);
+    HIPCHK(ctx, launch_factor_kernel(mxe::postvar_kernel<4>, mxe::postvar_kernel<8>, ctx, (size_t)P, st.lds, pp));
     if (out_ms) HIPCHK(ctx, hipEventRecord(sc.e1, ctx->stream));
     if (n_f) HIPCHK(ctx, hipMemcpyAsync(out_var, d + oV, (size_t)P * n_f * 8, hipMemcpyDeviceToHost, ctx->stream));
     if (out_prior) HIPCHK(ctx, hipMemcpyAsync(out_prior, d + oP, (size_t)P * n_f * 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -2803,58 +2733,29 @@ try {
 }
 MXE_CATCH_ALL
 
-// ---- draws from the Gaussian posterior of H (mxe_postsample.hip.h) ---------------------------------------------------
-#include "mxe_postsample.hip.h"
-
 extern "C" int mxe_posterior_sample(mxe_ctx* ctx, int P, const int32_t* elem_of_problem, const double* alpha_scaled,
                                     const double* H, const int32_t* problem_index, double chi2_factor,
                                     int n_samples, uint64_t seed, const uint64_t* stream, const double* z,
                                     double* out_dH, float* out_ms)
 try {
     if (!ctx || P < 1 || !elem_of_problem || !alpha_scaled || !out_dH || n_samples < 1 || (!z && !stream)) return MXE_ERR_ARG;
-    if (ctx->n_elem < 1) return MXE_ERR_STATE;
-    if (!H && !ctx->launched) return MXE_ERR_STATE;
-    if (!(chi2_factor > 0.0) || !std::isfinite(chi2_factor)) return MXE_ERR_ARG;
-    const int NP = ctx->NP, nw = ctx->n_omega, nz = nw + ctx->n_s;
-    if ((size_t)P * (size_t)n_samples * (size_t)nz > 0x7fffffffull) return MXE_ERR_ARG;
-    const size_t lds = mxe::postsample_lds_bytes(NP, ctx->nwp);
-    if (lds > 160 * 1024) return MXE_ERR_LIMIT;
+    const int nw = ctx->n_omega, nz = nw + ctx->n_s;
     const size_t n_z = (size_t)P * n_samples * nz, n_out = (size_t)P * n_samples * nw;
-    if (z) for (size_t i = 0; i < n_z; ++i) if (!std::isfinite(z[i])) return MXE_ERR_ARG;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    if (ctx->ds_dirty) { int rc = upload_bases(ctx); if (rc != MXE_OK) return rc; }
-    const size_t n_last = (size_t)ctx->n_chain * ctx->n_alpha;
-    std::vector<double> ha(P);
-    std::vector<int> hi((size_t)2 * P);
-    for (int p = 0; p < P; ++p) {
-        const int e = elem_of_problem[p];
-        if (e < 0 || e >= ctx->n_elem) return MXE_ERR_ARG;
-        if (!(alpha_scaled[p] > 0.0) || !std::isfinite(alpha_scaled[p])) return MXE_ERR_ARG;
-        ha[p] = alpha_scaled[p] / chi2_factor;
-        hi[p] = e;
-        int row = p;
-        if (!H) {
-            row = problem_index ? problem_index[p] : p;
-            if (row < 0 || (size_t)row >= n_last) return MXE_ERR_ARG;
-        }
-        hi[(size_t)P + p] = row;
-    }
+    PostStage st;
+    // n_max = n_z bounds the kernel's 32-bit indices: z [P][n_samples][nz] is the largest array of the call
+    int rc = stage_posterior(ctx, P, elem_of_problem, alpha_scaled, H, problem_index, chi2_factor, n_z, z, n_z, st);
+    if (rc != MXE_OK) return rc;
     // one block of doubles: alpha [P] | stream ids [P] (64-bit words) | H [P][nw] (when handed in) | z | samples
     const size_t oS = (size_t)P, oH = oS + (size_t)P, oZ = oH + (H ? (size_t)P * nw : 0), oO = oZ + n_z, total = oO + n_out;
     HIPCHK(ctx, ctx->ps_d.ensure(total));
-    HIPCHK(ctx, ctx->pv_i.ensure((size_t)2 * P));
     double* d = ctx->ps_d.p;
-    HIPCHK(ctx, hipMemcpyAsync(d, ha.data(), (size_t)P * 8, hipMemcpyHostToDevice, ctx->stream));
-    if (H) HIPCHK(ctx, hipMemcpyAsync(d + oH, H, (size_t)P * nw * 8, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->pv_i.p, hi.data(), hi.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    mxe::PostSampleParams pp;
+    rc = upload_posterior(ctx, st, P, H, d, oH, pp);
+    if (rc != MXE_OK) return rc;
     if (z) HIPCHK(ctx, hipMemcpyAsync(d + oZ, z, n_z * 8, hipMemcpyHostToDevice, ctx->stream));
     else HIPCHK(ctx, hipMemcpyAsync(d + oS, stream, (size_t)P * 8, hipMemcpyHostToDevice, ctx->stream));
-    mxe::PostSampleParams pp;
-    pp.V = ctx->dV.p; pp.c = ctx->dc.p; pp.elem_ds = ctx->delem_ds.p; pp.elem_kind = ctx->delem_kind.p; pp.D = ctx->dD.p;
-    pp.elem = ctx->pv_i.p; pp.alpha = d;
-    pp.H = H ? d + oH : ctx->dout_H.p; pp.row = H ? nullptr : ctx->pv_i.p + P;
     pp.z = d + oZ; pp.out = d + oO; pp.scale = 1.0 / std::sqrt(chi2_factor);
-    pp.nw = nw; pp.nwp = ctx->nwp; pp.ns = ctx->n_s; pp.n_samples = n_samples;
+    pp.n_samples = n_samples;
     SvdScratch sc;                    // (the two events of the timing, released on every path)
     if (out_ms) {
         HIPCHK(ctx, hipEventCreate(&sc.e0)); HIPCHK(ctx, hipEventCreate(&sc.e1));
@@ -2867,14 +2768,7 @@ try {
                            (uint64_t)0, P, n_samples, nz, d + oZ);
         HIPCHK(ctx, hipGetLastError());
     }
-    hipError_t e;
-#define MXE_LAUNCH_POSTSAMPLE(NT_) do { \
-        e = hipFuncSetAttribute((const void*)mxe::postsample_kernel<NT_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        if (e == hipSuccess) { hipLaunchKernelGGL((mxe::postsample_kernel<NT_>), dim3((unsigned)P), dim3(256), lds, ctx->stream, pp); \
-                               e = hipGetLastError(); } } while (0)
-    if (NP == 64) MXE_LAUNCH_POSTSAMPLE(4); else MXE_LAUNCH_POSTSAMPLE(8);
-#undef MXE_LAUNCH_POSTSAMPLE
-    HIPCHK(ctx, e);
+    HIPCHK(ctx, launch_factor_kernel(mxe::postsample_kernel<4>, mxe::postsample_kernel<8>, ctx, (size_t)P, st.lds, pp));
     if (out_ms) HIPCHK(ctx, hipEventRecord(sc.e1, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(out_dH, d + oO, n_out * 8, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, stream_wait(ctx->stream));

@@ -20,15 +20,14 @@
 // terms and is formed as written.
 //
 // One workgroup (4 waves) per problem:
-//   1. w, W, B and the Cholesky factor in LDS: the steps of postvar_kernel, operation for operation (repeated, not shared:
-//      that kernel's code and time stay as they are);
+//   1. w, W, B and the Cholesky factor in LDS: factor_B (mxe_factor.hip.h), shared with logdet_kernel and postvar_kernel;
 //   2. the samples in blocks of 16; the block of right-hand sides lives where postvar_kernel keeps its Y block (pv_y).
 //      Three sweeps over the omega rows of V' by v_mfma_f64_16x16x4_f64, a tile of 16 samples x 16 omega points each:
-//        a. c o z2 into the block; q, written to the output rows themselves as scratch (a tile row belongs to one wave);
+//        a. c o z2 into the block; q (block_times_Vt), written to the output rows themselves as scratch (a tile row belongs to one wave);
 //        b. y = c o V'^T q: the omega rows go to the four waves round-robin in groups of 4, the waves' partial tiles
 //           are added in wave order;
 //        c. after the blocked forward substitution of postvar_kernel and a blocked backward substitution with L^T,
-//           c o x in the block; delta overwrites q (every lane reads back what it wrote itself in sweep a).
+//           c o x in the block; delta (block_times_Vt again) overwrites q (every lane reads back what it wrote itself in sweep a).
 // The normals are read from device memory ([P][n_samples][n_omega + n_s]): handed in by the caller, or filled before the
 // launch by normals_kernel with the generator below, so both ways run the same code on the same numbers.
 //
@@ -85,144 +84,35 @@ void normals_kernel(uint64_t seed, const uint64_t* stream, uint64_t stream0, int
         }
 }
 
-struct PostSampleParams {
-    const double* V;            // [n_ds][nwp][NP]
-    const double* c;            // [n_ds][NP]
-    const int* elem_ds;         // [n_elem]
-    const int* elem_kind;       // [n_elem]
-    const double* D;            // [n_elem][nwp]
-    const int* elem;            // [P] element of a problem
-    const double* alpha;        // [P] alpha~ / eta
-    const double* H;            // rows of n_omega values
-    const int* row;             // [P] row of H that belongs to a problem, or NULL: row p
+struct PostSampleParams : FactorParams {
     const double* z;            // [P][n_samples][nw + ns]
     double* out;                // [P][n_samples][nw]
     double scale;               // 1 / sqrt(eta)
-    int nw, nwp, ns, n_samples;
+    int n_samples;
 };
-
-inline size_t postsample_lds_bytes(int NP, int nwp) { return postvar_lds_bytes(NP, nwp); }
-
-// L^T X = Z for the block of 16 right-hand sides (pv_y), in place
-template <int NP>
-__device__ inline void ps_backward_solve(double* Bm, int ns, int tid)
-{
-    constexpr int LD = NP + 1;
-    const int ntile = (ns + 15) >> 4;
-    for (int J = ntile - 1; J >= 0; --J) {
-        const int k0 = 16 * J, k1 = min(k0 + 16, ns);
-        if (tid < 16) {
-            for (int k = k1 - 1; k >= k0; --k) {
-                double s = Bm[pv_y<NP>(k, tid)];
-                for (int m = k1 - 1; m > k; --m) s = fma(-Bm[m * LD + k], Bm[pv_y<NP>(m, tid)], s);
-                s /= Bm[k * LD + k];
-                Bm[pv_y<NP>(k, tid)] = s;
-            }
-        }
-        __syncthreads();
-        const int nb = k1 - k0;                      // (the last tile row, the first one here, may be short)
-        for (int idx = tid; idx < k0 * 16; idx += 256) {
-            const int m = idx >> 4, j = idx & 15;
-            double s = Bm[pv_y<NP>(m, j)];
-            for (int kk = nb - 1; kk >= 0; --kk) s = fma(-Bm[(k0 + kk) * LD + m], Bm[pv_y<NP>(k0 + kk, j)], s);
-            Bm[pv_y<NP>(m, j)] = s;
-        }
-        __syncthreads();
-    }
-}
 
 template <int NT>
 __global__ __launch_bounds__(256)
 void postsample_kernel(PostSampleParams p)
 {
-    typedef double d4 __attribute__((ext_vector_type(4)));
-    constexpr int NP = 16 * NT, LD = NP + 1;
+    constexpr int NP = 16 * NT;
     extern __shared__ double sm[];
-    double* Bm = sm;                     // [NP][LD]
-    double* wsh = Bm + NP * LD;          // [nwp]
+    double* Bm = sm;                     // [NP][NP + 1]
+    double* wsh = Bm + NP * (NP + 1);    // [nwp]
     double* fsh = wsh + p.nwp + 256;     // [16] unused | [16] flag (the places of postvar_kernel)
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int nw = p.nw, nwp = p.nwp, ns = p.ns, n_samples = p.n_samples;
+    const int nw = p.nw, ns = p.ns, n_samples = p.n_samples;
     const size_t prob = blockIdx.x;
-    const int e = p.elem[prob];
-    const int ds = p.elem_ds[e], kind = p.elem_kind[e];
-    const double a = p.alpha[prob];
-    const double* V = p.V + (size_t)ds * nwp * NP;
-    const double* cc = p.c + (size_t)ds * NP;
-    const double* Hp = p.H + (size_t)(p.row ? p.row[prob] : (int)prob) * nw;
-    const double* Dp = p.D + (size_t)e * nwp;
-    if (tid == 0) fsh[16] = 0.0;
-    __syncthreads();
-    bool finite = true;
-    for (int i = tid; i < nwp; i += 256) {
-        double w = 0.0;
-        if (i < nw) {
-            const double h = Hp[i];
-            if (kind == 0) w = h;
-            else { const double d2 = 2.0 * Dp[i]; w = sqrt(fma(h, h, d2 * d2)); }
-            if (!(fabs(w) <= 1.79769313486231570815e308)) finite = false;
-        }
-        wsh[i] = w;
-    }
-    if (!finite) fsh[16] = 1.0;          // (every writer writes the same value)
-    for (int i = tid; i < NP * LD; i += 256) Bm[i] = 0.0;
-    __syncthreads();
-    bool ok = fsh[16] == 0.0;
+    const FactorProblem fp = resolve_problem<NP>(p, prob);
+    const double* V = fp.V;
+    const double* cc = fp.cc;
+    const double a = fp.a;
+    const bool ok = factor_B<NT>(fp, nw, p.nwp, ns, Bm, wsh, fsh + 16);
     const int kq = lane >> 4, cn = lane & 15;
     const int n_groups = (nw + 3) >> 2;          // (the rows of V' behind n_omega are zero)
     const int ntile = (ns + 15) >> 4;
-    if (ok) {
-        for (int mt = 0; mt < ntile; ++mt) {
-            d4 acc[NT];
-#pragma unroll
-            for (int t = 0; t < NT; ++t) acc[t] = d4{0.0, 0.0, 0.0, 0.0};
-            for (int g = wave; g < n_groups; g += 4) {
-                const double* row = V + (size_t)(4 * g + kq) * NP + cn;
-                const double wq = wsh[4 * g + kq];
-                const double am = row[16 * mt] * wq;
-#pragma unroll
-                for (int t = 0; t < NT; ++t)
-                    if (t >= mt && t < ntile) acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(am, row[16 * t], acc[t], 0, 0, 0);
-            }
-            for (int ph = 0; ph < 4; ++ph) {         // the four waves add their partial tiles one after the other
-                if (wave == ph) {
-#pragma unroll
-                    for (int t = 0; t < NT; ++t)
-                        if (t >= mt && t < ntile) {
-#pragma unroll
-                            for (int r = 0; r < 4; ++r) Bm[(16 * mt + kq + 4 * r) * LD + 16 * t + cn] += acc[t][r];
-                        }
-                }
-                __syncthreads();
-            }
-        }
-        for (int idx = tid; idx < ns * ns; idx += 256) {
-            const int i = idx / ns, j = idx % ns;
-            if (i <= j) {
-                double b = cc[i] * Bm[i * LD + j] * cc[j];
-                if (i == j) b += a;
-                Bm[j * LD + i] = b;
-            }
-        }
-        __syncthreads();
-        for (int j = 0; j < ns; ++j) {               // right-looking Cholesky on the lower triangle
-            const double piv = Bm[j * LD + j];
-            if (!(piv > 0.0) || !(piv <= 1.79769313486231570815e308)) ok = false;
-            const double d = sqrt(piv);
-            __syncthreads();
-            for (int i = j + 1 + tid; i < ns; i += 256) Bm[i * LD + j] /= d;
-            if (tid == 0) Bm[j * LD + j] = d;
-            __syncthreads();
-            const int m = ns - j - 1;
-            for (int idx = tid; idx < m * m; idx += 256) {
-                const int i = j + 1 + idx / m, k = j + 1 + idx % m;
-                if (k <= i) Bm[i * LD + k] = fma(-Bm[i * LD + j], Bm[k * LD + j], Bm[i * LD + k]);
-            }
-            __syncthreads();
-        }
-    }
     double* out = p.out + prob * (size_t)n_samples * nw;
-    if (!ok) {                                       // (uniform: every thread saw the same pivots and the same flag)
+    if (!ok) {                                       // (uniform)
         const double nan = __builtin_nan("");
         for (size_t i = tid; i < (size_t)n_samples * nw; i += 256) out[i] = nan;
         return;
@@ -244,10 +134,7 @@ void postsample_kernel(PostSampleParams p)
         for (int T = wave; T < n_wtiles; T += 4) {
             const int i = 16 * T + cn;               // this lane's omega point; its samples are s0 + kq + 4 r
             const bool iv = i < nw;
-            const double* vrow = V + (size_t)(iv ? i : 0) * NP + kq;
-            d4 acc = d4{0.0, 0.0, 0.0, 0.0};
-            for (int g = 0; g < kgroups; ++g)
-                acc = __builtin_amdgcn_mfma_f64_16x16x4f64(Bm[pv_y<NP>(4 * g + kq, cn)], iv ? vrow[4 * g] : 0.0, acc, 0, 0, 0);
+            const d4 acc = block_times_Vt<NP>(Bm, V, i, iv, kgroups, kq, cn);
             if (iv) {
                 const double w = wsh[i], sw = sqrt(a * w);
 #pragma unroll
@@ -276,17 +163,7 @@ void postsample_kernel(PostSampleParams p)
                     if (t < ntile) acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(row[16 * t], b, acc[t], 0, 0, 0);
             }
             __syncthreads();
-            for (int ph = 0; ph < 4; ++ph) {
-                if (wave == ph) {
-#pragma unroll
-                    for (int t = 0; t < NT; ++t)
-                        if (t < ntile) {
-#pragma unroll
-                            for (int r = 0; r < 4; ++r) Bm[pv_y<NP>(16 * t + kq + 4 * r, cn)] += acc[t][r];
-                        }
-                }
-                __syncthreads();
-            }
+            add_tiles_in_wave_order<NT>(Bm, acc, 0, ntile, wave, [=](int t, int r) { return pv_y<NP>(16 * t + kq + 4 * r, cn); });
         }
         for (int idx = tid; idx < ntile * 256; idx += 256) {         // (rows behind n_s stay zero whatever V' holds there)
             const int k = idx >> 4;
@@ -301,10 +178,7 @@ void postsample_kernel(PostSampleParams p)
         for (int T = wave; T < n_wtiles; T += 4) {
             const int i = 16 * T + cn;
             const bool iv = i < nw;
-            const double* vrow = V + (size_t)(iv ? i : 0) * NP + kq;
-            d4 acc = d4{0.0, 0.0, 0.0, 0.0};
-            for (int g = 0; g < kgroups; ++g)
-                acc = __builtin_amdgcn_mfma_f64_16x16x4f64(Bm[pv_y<NP>(4 * g + kq, cn)], iv ? vrow[4 * g] : 0.0, acc, 0, 0, 0);
+            const d4 acc = block_times_Vt<NP>(Bm, V, i, iv, kgroups, kq, cn);
             if (iv) {
                 const double w = wsh[i];
 #pragma unroll

@@ -15,48 +15,32 @@
 // non-negative terms; B^-1 is never formed.  For eta != 1 the caller divides the result by eta.
 //
 // One workgroup (4 waves) per problem:
-//   1. w from the H row, W by v_mfma_f64_16x16x4_f64, B and its Cholesky factor in LDS: the steps of logdet_kernel
-//      (maxent_hip.hip), operation for operation;
+//   1. w from the H row, W by v_mfma_f64_16x16x4_f64, B and its Cholesky factor in LDS: factor_B (mxe_factor.hip.h),
+//      shared with logdet_kernel and postsample_kernel;
 //   2. the functionals in blocks of 16 (F is streamed from device memory, never held): Y = c o V'^T (w o F^T) as one
 //      sweep of f64 MFMAs over the omega rows (one 16 x 16 tile of Y per tile row of V'), the prior sums
 //      sum_i w_i f_i^2, then the blocked forward substitution L Z = Y in LDS -- the 16 x 16 diagonal block of a tile
 //      row by one thread per functional, the rows below it by all threads -- and |z|^2;
 //   3. for the diagonal the same substitution on blocks of 16 columns c o V'_i, loaded as they are.
 // No column of Y lives in registers, so the 128-row build needs no more of them than the 64-row one.  A block of 16
-// right-hand sides lives in LDS that B leaves free: once B is mirrored to its lower triangle, the rows 0 .. NP/2-1 of the
-// columns NP/2 .. NP-1 (all strictly above the diagonal) are dead, NP^2/4 >= 16 NP doubles; row k of Y is the 16 doubles
-// at row k/2, column NP/2 + 16 (k mod 2).  The kernel so needs logdet_kernel's LDS plus 2.3 KB and keeps its four
-// workgroups per CU at NP = 64.
-//
-// Steps 1 repeats logdet_kernel instead of sharing a device function with it: that kernel's code and time were to stay
-// exactly as they are in this change; folding both onto one helper is a follow-up.
+// right-hand sides lives in LDS that B leaves free (pv_y, mxe_factor.hip.h).  The kernel so needs logdet_kernel's LDS
+// plus 2.3 KB and keeps its four workgroups per CU at NP = 64.
 //
 // Bits do not depend on the batch, on n_f or on a functional's place in F: the omega rows go to the four waves
 // round-robin and the waves' partial tiles are added in wave order; every other sum runs in index order in one thread.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "mxe_factor.hip.h"
 
 namespace mxe {
 
-// element (k, j) of a block of 16 right-hand sides inside B's dead upper-right block (see above)
-template <int NP> __device__ __forceinline__ int pv_y(int k, int j) { return (k >> 1) * (NP + 1) + NP / 2 + ((k & 1) << 4) + j; }
-
-struct PostVarParams {
-    const double* V;            // [n_ds][nwp][NP]
-    const double* c;            // [n_ds][NP]
-    const int* elem_ds;         // [n_elem]
-    const int* elem_kind;       // [n_elem]
-    const double* D;            // [n_elem][nwp]
-    const int* elem;            // [P] element of a problem
-    const double* alpha;        // [P] alpha~ / eta
-    const double* H;            // rows of n_omega values
-    const int* row;             // [P] row of H that belongs to a problem, or NULL: row p
+struct PostVarParams : FactorParams {
     const double* F;            // [n_f][n_omega], may be NULL with n_f == 0
     double* out_var;            // [P][n_f]
     double* out_prior;          // [P][n_f] or NULL
     double* out_diag;           // [P][n_omega] or NULL
-    int nw, nwp, ns, n_f;
+    int n_f;
 };
 
 inline size_t postvar_lds_bytes(int NP, int nwp)
@@ -64,131 +48,29 @@ inline size_t postvar_lds_bytes(int NP, int nwp)
     return ((size_t)NP * (NP + 1) + (size_t)nwp + 256 + 32) * sizeof(double);
 }
 
-// L Z = Y for the block of 16 right-hand sides (pv_y), in place; returns (to threads 0..15) |z_j|^2 of column j = tid
-template <int NP>
-__device__ inline double pv_forward_solve(double* Bm, int ns, int tid)
-{
-    constexpr int LD = NP + 1;
-    double q = 0.0;
-    const int ntile = (ns + 15) >> 4;
-    for (int J = 0; J < ntile; ++J) {
-        const int k0 = 16 * J, k1 = min(k0 + 16, ns);
-        if (tid < 16) {
-            for (int k = k0; k < k1; ++k) {
-                double s = Bm[pv_y<NP>(k, tid)];
-                for (int m = k0; m < k; ++m) s = fma(-Bm[k * LD + m], Bm[pv_y<NP>(m, tid)], s);
-                s /= Bm[k * LD + k];
-                Bm[pv_y<NP>(k, tid)] = s;
-                q = fma(s, s, q);
-            }
-        }
-        __syncthreads();
-        const int below = ns - k1;
-        for (int idx = tid; idx < below * 16; idx += 256) {
-            const int m = k1 + (idx >> 4), j = idx & 15;
-            double s = Bm[pv_y<NP>(m, j)];
-#pragma unroll
-            for (int kk = 0; kk < 16; ++kk) s = fma(-Bm[m * LD + k0 + kk], Bm[pv_y<NP>(k0 + kk, j)], s);   // (rows below exist: the block is full)
-            Bm[pv_y<NP>(m, j)] = s;
-        }
-        __syncthreads();
-    }
-    return q;
-}
-
 template <int NT>
 __global__ __launch_bounds__(256)
 void postvar_kernel(PostVarParams p)
 {
-    typedef double d4 __attribute__((ext_vector_type(4)));
-    constexpr int NP = 16 * NT, LD = NP + 1;
+    constexpr int NP = 16 * NT;
     extern __shared__ double sm[];
-    double* Bm = sm;                     // [NP][LD]
-    double* wsh = Bm + NP * LD;          // [nwp]
+    double* Bm = sm;                     // [NP][NP + 1]
+    double* wsh = Bm + NP * (NP + 1);    // [nwp]
     double* part = wsh + p.nwp;          // [16][16] partial prior sums
     double* fsh = part + 256;            // [16] prior sums | [16] flag
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int nw = p.nw, nwp = p.nwp, ns = p.ns, n_f = p.n_f;
+    const int nw = p.nw, ns = p.ns, n_f = p.n_f;
     const size_t prob = blockIdx.x;
-    const int e = p.elem[prob];
-    const int ds = p.elem_ds[e], kind = p.elem_kind[e];
-    const double a = p.alpha[prob];
-    const double* V = p.V + (size_t)ds * nwp * NP;
-    const double* cc = p.c + (size_t)ds * NP;
-    const double* Hp = p.H + (size_t)(p.row ? p.row[prob] : (int)prob) * nw;
-    const double* Dp = p.D + (size_t)e * nwp;
-    if (tid == 0) fsh[16] = 0.0;
-    __syncthreads();
-    bool finite = true;
-    for (int i = tid; i < nwp; i += 256) {
-        double w = 0.0;
-        if (i < nw) {
-            const double h = Hp[i];
-            if (kind == 0) w = h;
-            else { const double d2 = 2.0 * Dp[i]; w = sqrt(fma(h, h, d2 * d2)); }
-            if (!(fabs(w) <= 1.79769313486231570815e308)) finite = false;
-        }
-        wsh[i] = w;
-    }
-    if (!finite) fsh[16] = 1.0;          // (every writer writes the same value)
-    for (int i = tid; i < NP * LD; i += 256) Bm[i] = 0.0;
-    __syncthreads();
-    bool ok = fsh[16] == 0.0;
+    const FactorProblem fp = resolve_problem<NP>(p, prob);
+    const double* V = fp.V;
+    const double* cc = fp.cc;
+    const double a = fp.a;
+    const bool ok = factor_B<NT>(fp, nw, p.nwp, ns, Bm, wsh, fsh + 16);
     const int kq = lane >> 4, cn = lane & 15;
     const int n_groups = (nw + 3) >> 2;          // (the rows of V' behind n_omega are zero)
     const int ntile = (ns + 15) >> 4;
-    if (ok) {
-        for (int mt = 0; mt < ntile; ++mt) {
-            d4 acc[NT];
-#pragma unroll
-            for (int t = 0; t < NT; ++t) acc[t] = d4{0.0, 0.0, 0.0, 0.0};
-            for (int g = wave; g < n_groups; g += 4) {
-                const double* row = V + (size_t)(4 * g + kq) * NP + cn;
-                const double wq = wsh[4 * g + kq];
-                const double am = row[16 * mt] * wq;
-#pragma unroll
-                for (int t = 0; t < NT; ++t)
-                    if (t >= mt && t < ntile) acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(am, row[16 * t], acc[t], 0, 0, 0);
-            }
-            for (int ph = 0; ph < 4; ++ph) {         // the four waves add their partial tiles one after the other
-                if (wave == ph) {
-#pragma unroll
-                    for (int t = 0; t < NT; ++t)
-                        if (t >= mt && t < ntile) {
-#pragma unroll
-                            for (int r = 0; r < 4; ++r) Bm[(16 * mt + kq + 4 * r) * LD + 16 * t + cn] += acc[t][r];
-                        }
-                }
-                __syncthreads();
-            }
-        }
-        for (int idx = tid; idx < ns * ns; idx += 256) {
-            const int i = idx / ns, j = idx % ns;
-            if (i <= j) {
-                double b = cc[i] * Bm[i * LD + j] * cc[j];
-                if (i == j) b += a;
-                Bm[j * LD + i] = b;
-            }
-        }
-        __syncthreads();
-        for (int j = 0; j < ns; ++j) {               // right-looking Cholesky on the lower triangle
-            const double piv = Bm[j * LD + j];
-            if (!(piv > 0.0) || !(piv <= 1.79769313486231570815e308)) ok = false;
-            const double d = sqrt(piv);
-            __syncthreads();
-            for (int i = j + 1 + tid; i < ns; i += 256) Bm[i * LD + j] /= d;
-            if (tid == 0) Bm[j * LD + j] = d;
-            __syncthreads();
-            const int m = ns - j - 1;
-            for (int idx = tid; idx < m * m; idx += 256) {
-                const int i = j + 1 + idx / m, k = j + 1 + idx % m;
-                if (k <= i) Bm[i * LD + k] = fma(-Bm[i * LD + j], Bm[k * LD + j], Bm[i * LD + k]);
-            }
-            __syncthreads();
-        }
-    }
     const double nan = __builtin_nan("");
-    if (!ok) {                                       // (uniform: every thread saw the same pivots and the same flag)
+    if (!ok) {                                       // (uniform)
         for (int j = tid; j < n_f; j += 256) {
             p.out_var[prob * n_f + j] = nan;
             if (p.out_prior) p.out_prior[prob * n_f + j] = nan;
@@ -225,17 +107,7 @@ void postvar_kernel(PostVarParams p)
             part[pt * 16 + j] = s;
         }
         __syncthreads();
-        for (int ph = 0; ph < 4; ++ph) {
-            if (wave == ph) {
-#pragma unroll
-                for (int t = 0; t < NT; ++t)
-                    if (t < ntile) {
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) Bm[pv_y<NP>(16 * t + kq + 4 * r, cn)] += acc[t][r];
-                    }
-            }
-            __syncthreads();
-        }
+        add_tiles_in_wave_order<NT>(Bm, acc, 0, ntile, wave, [=](int t, int r) { return pv_y<NP>(16 * t + kq + 4 * r, cn); });
         for (int idx = tid; idx < ns * 16; idx += 256) Bm[pv_y<NP>(idx >> 4, idx & 15)] *= cc[idx >> 4];
         if (tid < 16) {
             double s = 0.0;

@@ -887,6 +887,30 @@ class DeviceContext(object):
                                              float(chi2_factor), *args), 'mxe_eval_batch')
         return out
 
+    def _posterior_problems(self, name, elem_of_problem, alpha_scaled):
+        """the problems of :meth:`posterior_var` / :meth:`posterior_sample` as the library takes them: ``(el, P, al)``"""
+        if self._n_s_dev < self.n_s:
+            raise MaxEntDeviceError('%s on a context that keeps %d of %d singular directions' % (name, self._n_s_dev, self.n_s))
+        el = _c(np.atleast_1d(elem_of_problem), np.int32)
+        P = len(el)
+        al = _c(np.broadcast_to(np.asarray(alpha_scaled, dtype=float), (P,)))
+        if not np.all(al > 0) or not np.all(np.isfinite(al)):
+            raise ValueError('%s: every alpha must be positive and finite' % name)
+        return el, P, al
+
+    def _posterior_rows(self, name, P, H, problem_index, unlaunched_ok=False):
+        """the hidden images of the P problems as the library takes them: ``(H, pi)``, one of them None.
+        ``unlaunched_ok``: before any launch the rows of ``problem_index`` are not checked here."""
+        if H is not None:
+            return _c(H).reshape(P, self.n_omega), None
+        pi = _c(np.arange(P) if problem_index is None else np.atleast_1d(problem_index), np.int32)
+        n_last = self._n_chain * self._n_alpha
+        check_rows = P and (n_last or not unlaunched_ok)
+        if len(pi) != P or (check_rows and (pi.min() < 0 or pi.max() >= n_last)):
+            raise ValueError('%s: problem_index must name %d problems of the last launch (%d x %d)'
+                             % (name, P, self._n_chain, self._n_alpha))
+        return None, pi
+
     def posterior_var(self, elem_of_problem, alpha_scaled, H=None, problem_index=None, F=None, chi2_factor=1.0,
                       want_diag=False, timing=None):
         """``mxe_posterior_var``: Gaussian posterior variances around the minimiser, on the staged elements.
@@ -895,21 +919,8 @@ class DeviceContext(object):
         f^T Gamma f and f^T diag(w) f / alpha~ -- and, with ``want_diag``, ``diag`` (P, n_omega) = Gamma_ii.  A problem whose
         H row is not finite or whose curvature matrix is not positive definite has NaN everywhere.  ``timing``: a dict that
         receives the device time ``ms`` of the kernel."""
-        if self._n_s_dev < self.n_s:
-            raise MaxEntDeviceError('posterior_var on a context that keeps %d of %d singular directions' % (self._n_s_dev, self.n_s))
-        el = _c(np.atleast_1d(elem_of_problem), np.int32)
-        P = len(el)
-        al = _c(np.broadcast_to(np.asarray(alpha_scaled, dtype=float), (P,)))
-        if not np.all(al > 0) or not np.all(np.isfinite(al)):
-            raise ValueError('posterior_var: every alpha must be positive and finite')
-        if H is not None:
-            H = _c(H).reshape(P, self.n_omega)
-            pi = None
-        else:
-            pi = _c(np.arange(P) if problem_index is None else np.atleast_1d(problem_index), np.int32)
-            if len(pi) != P or (P and (pi.min() < 0 or pi.max() >= self._n_chain * self._n_alpha)):
-                raise ValueError('posterior_var: problem_index must name %d problems of the last launch (%d x %d)'
-                                 % (P, self._n_chain, self._n_alpha))
+        el, P, al = self._posterior_problems('posterior_var', elem_of_problem, alpha_scaled)
+        H, pi = self._posterior_rows('posterior_var', P, H, problem_index)
         if F is not None:
             F = _c(np.atleast_2d(F))
             if F.shape[1] != self.n_omega:
@@ -941,13 +952,7 @@ class DeviceContext(object):
         (P, n_samples, n_omega + n_s) standard normals that are used as given.  A problem whose H row is not finite or whose
         curvature matrix is not positive definite has NaN in all its samples.  ``timing``: a dict that receives the device
         time ``ms``."""
-        if self._n_s_dev < self.n_s:
-            raise MaxEntDeviceError('posterior_sample on a context that keeps %d of %d singular directions' % (self._n_s_dev, self.n_s))
-        el = _c(np.atleast_1d(elem_of_problem), np.int32)
-        P = len(el)
-        al = _c(np.broadcast_to(np.asarray(alpha_scaled, dtype=float), (P,)))
-        if not np.all(al > 0) or not np.all(np.isfinite(al)):
-            raise ValueError('posterior_sample: every alpha must be positive and finite')
+        el, P, al = self._posterior_problems('posterior_sample', elem_of_problem, alpha_scaled)
         n_samples = int(n_samples)
         if n_samples < 1:
             raise ValueError('posterior_sample: n_samples must be at least 1')
@@ -955,15 +960,8 @@ class DeviceContext(object):
         if P * n_samples * nz > 2 ** 31 - 1:
             raise ValueError('posterior_sample: P n_samples (n_omega + n_s) = %d exceeds 2^31 - 1; draw in several calls'
                              % (P * n_samples * nz))
-        if H is not None:
-            H = _c(H).reshape(P, self.n_omega)
-            pi = None
-        else:
-            pi = _c(np.arange(P) if problem_index is None else np.atleast_1d(problem_index), np.int32)
-            n_last = self._n_chain * self._n_alpha           # (0: nothing launched, the library answers MXE_ERR_STATE)
-            if len(pi) != P or (n_last and P and (pi.min() < 0 or pi.max() >= n_last)):
-                raise ValueError('posterior_sample: problem_index must name %d problems of the last launch (%d x %d)'
-                                 % (P, self._n_chain, self._n_alpha))
+        # (nothing launched: the library answers MXE_ERR_STATE)
+        H, pi = self._posterior_rows('posterior_sample', P, H, problem_index, unlaunched_ok=True)
         st = None
         if z is not None:
             z = _c(z)

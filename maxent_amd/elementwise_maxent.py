@@ -689,18 +689,14 @@ class ElementwiseMaxEnt(object):
         """default models of the off-diagonal jobs when they are not the worker's own (PoormanMaxEnt), else None"""
         return None
 
-    def posterior_errors(self, result=None, alpha=None, windows=None, functionals=None, pointwise=False, timing=None):
-        """:meth:`TauMaxEnt.posterior_errors` for every matrix element of ``result`` (default: the last result of this
-        object): all elements of a worker -- the diagonal ones, the off-diagonal ones with their plus-minus entropy -- in
-        ONE call of ``mxe_posterior_var`` per device, each with its own error bars or covariance.  Returns a dict of arrays
-        shaped like the result's fields (matrix indices, then the complex index with ``use_complex``, then what
-        :meth:`TauMaxEnt.posterior_errors` returns); elements that were not computed (below the threshold) hold NaN,
-        those that follow from hermiticity are filled from their partners.  ``info``: per computed element its
-        ``nan_rows``."""
+    def _posterior_elements(self, res, run, extra, flip_names, what, with_stream=False, skip=('info',), timing=None):
+        """What :meth:`posterior_errors` and :meth:`posterior_samples` share.  The items (see ``posterior.element_errors``;
+        ``with_stream``: with their ``stream``) of every computed element of ``res``, per worker phase, go to
+        ``run(K, omega, items, default_name=, chi2_factor=, device_ids=, bryan=, timing=)``, which returns one dict per item.
+        These are assembled into a dict (with ``extra``): arrays shaped like the result's fields, NaN (-1 for integers) where nothing was
+        computed, the hermitian partners filled in -- the imaginary part's ``flip_names`` with the other sign; ``info``
+        per element, the names ``skip`` left out."""
         from . import posterior
-        res = self.maxent_result if result is None else result
-        if res is None:
-            raise ValueError('no result: run() first or hand one in')
         zero = set(tuple(z) for z in res.zero_elements)
         phases = [(self.maxent_diagonal, self._diag_jobs(), None)]
         if not isinstance(self, DiagonalMaxEnt):
@@ -731,29 +727,30 @@ class ElementwiseMaxEnt(object):
                 ana = res.analyzer_results
                 for i in key:
                     ana = ana[i]
-                items.append(dict(spec=spec, H=H, alpha=np.asarray(res.alpha, dtype=float), analysis=ana,
-                                  probability=None if np.all(np.isnan(logp)) else logp, B=loop.A_of_H.matrix()))
+                item = dict(spec=spec, H=H, alpha=np.asarray(res.alpha, dtype=float), analysis=ana,
+                            probability=None if np.all(np.isnan(logp)) else logp, B=loop.A_of_H.matrix())
+                if with_stream:
+                    item['stream'] = int(np.ravel_multi_index(tuple(element), tuple(self.shape))) * 2 + cidx
+                items.append(item)
                 keys.append(key)
             if not items:
                 continue
             t = {}
-            outs = posterior.element_errors(worker.K, worker.omega, items, alpha=alpha, windows=windows,
-                                            functionals=functionals, pointwise=pointwise,
-                                            default_name=res.default_analyzer_name,
-                                            chi2_factor=loop.cost_function.chi2_factor, device_ids=ids,
-                                            bryan=posterior.find_bryan(loop.analyzers), timing=t)
+            outs = run(worker.K, worker.omega, items, default_name=res.default_analyzer_name,
+                       chi2_factor=loop.cost_function.chi2_factor, device_ids=ids,
+                       bryan=posterior.find_bryan(loop.analyzers), timing=t)
             ms += t.get('ms', 0.0)
             collected.extend(zip(keys, outs))
         if timing is not None:
             timing['ms'] = ms
         if not collected:
-            raise ValueError('the result holds no element to compute errors for')
+            raise ValueError('the result holds no element to {}'.format(what))
         struct = tuple(self.shape) + ((2,) if self.use_complex else ())
-        out = dict(info={})
+        out = dict(info={}, **extra)
         for key, o in collected:
             out['info'][key] = o['info']
             for name, val in o.items():
-                if name == 'info':
+                if name in skip:
                     continue
                 val = np.asarray(val)
                 if name not in out:
@@ -763,10 +760,29 @@ class ElementwiseMaxEnt(object):
                     raise ValueError('{}: the elements chose different numbers of alphas; use alpha= indices'.format(name))
                 out[name][key] = val
                 if self.use_hermiticity and key[0] != key[1]:
-                    # G_ji = conj(G_ij): the same errors; the imaginary part's values change sign
-                    flip = -1.0 if (len(key) == 3 and key[2] == 1 and name in ('window_weight', 'functional_value', 'A')) else 1.0
+                    # G_ji = conj(G_ij): the same errors and spectra; the imaginary part's values change sign
+                    flip = -1.0 if (len(key) == 3 and key[2] == 1 and name in flip_names) else 1.0
                     out[name][(key[1], key[0]) + key[2:]] = val * flip if val.dtype.kind == 'f' else val
         return out
+
+    def posterior_errors(self, result=None, alpha=None, windows=None, functionals=None, pointwise=False, timing=None):
+        """:meth:`TauMaxEnt.posterior_errors` for every matrix element of ``result`` (default: the last result of this
+        object): all elements of a worker -- the diagonal ones, the off-diagonal ones with their plus-minus entropy -- in
+        ONE call of ``mxe_posterior_var`` per device, each with its own error bars or covariance.  Returns a dict of arrays
+        shaped like the result's fields (matrix indices, then the complex index with ``use_complex``, then what
+        :meth:`TauMaxEnt.posterior_errors` returns); elements that were not computed (below the threshold) hold NaN,
+        those that follow from hermiticity are filled from their partners.  ``info``: per computed element its
+        ``nan_rows``."""
+        from . import posterior
+        res = self.maxent_result if result is None else result
+        if res is None:
+            raise ValueError('no result: run() first or hand one in')
+
+        def run(K, omega, items, **common):
+            return posterior.element_errors(K, omega, items, alpha=alpha, windows=windows, functionals=functionals,
+                                            pointwise=pointwise, **common)
+        return self._posterior_elements(res, run, {}, ('window_weight', 'functional_value', 'A'), 'compute errors for',
+                                        timing=timing)
 
     def posterior_samples(self, result=None, n_samples=100, seed=0, alpha=None, transform='linear', z=None, timing=None):
         """:meth:`TauMaxEnt.posterior_samples` for every matrix element of ``result`` (default: the last result of this
@@ -784,73 +800,12 @@ class ElementwiseMaxEnt(object):
             raise ValueError('n_samples must be at least 1, got {}'.format(n_samples))
         if transform not in posterior.TRANSFORMS:
             raise ValueError('transform={!r}: one of {} is needed'.format(transform, posterior.TRANSFORMS))
-        zero = set(tuple(z0) for z0 in res.zero_elements)
-        phases = [(self.maxent_diagonal, self._diag_jobs(), None)]
-        if not isinstance(self, DiagonalMaxEnt):
-            off = self._offdiag_jobs()
-            phases.append((self.maxent_offdiagonal, off, self._posterior_models(off, res)))
-        ids = self.device_ids if self.device_ids else (self.maxent_diagonal.maxent_loop.device_id,)
-        collected, ms = [], 0.0
-        for worker, jobs, models in phases:
-            loop = worker.maxent_loop
-            items, keys = [], []
-            for n, (element, re) in enumerate(jobs):
-                cidx = 0 if re else 1
-                key = tuple(element) + ((cidx,) if self.use_complex else ())
-                if key in zero:
-                    continue
-                try:
-                    H = np.asarray(res.element_array('H', key), dtype=float)
-                except (KeyError, IndexError, AttributeError, AssertionError):
-                    continue
-                if H.ndim != 2 or H.shape[0] == 0:
-                    continue
-                if models is not None:
-                    worker.set_D(models[n])
-                self._load_element(worker, element, re)
-                spec = loop.make_spec()
-                posterior.check_alpha(spec, res.alpha)
-                logp = np.asarray(res.element_array('probability', key), dtype=float)
-                ana = res.analyzer_results
-                for i in key:
-                    ana = ana[i]
-                flat = int(np.ravel_multi_index(tuple(element), tuple(self.shape)))
-                items.append(dict(spec=spec, H=H, alpha=np.asarray(res.alpha, dtype=float), analysis=ana,
-                                  probability=None if np.all(np.isnan(logp)) else logp, B=loop.A_of_H.matrix(),
-                                  stream=flat * 2 + cidx))
-                keys.append(key)
-            if not items:
-                continue
-            t = {}
-            outs = posterior.element_samples(worker.K, worker.omega, items, n_samples=n_samples, seed=seed, alpha=alpha,
-                                             transform=transform, z=z, default_name=res.default_analyzer_name,
-                                             chi2_factor=loop.cost_function.chi2_factor, device_ids=ids,
-                                             bryan=posterior.find_bryan(loop.analyzers), timing=t)
-            ms += t.get('ms', 0.0)
-            collected.extend(zip(keys, outs))
-        if timing is not None:
-            timing['ms'] = ms
-        if not collected:
-            raise ValueError('the result holds no element to draw samples for')
-        struct = tuple(self.shape) + ((2,) if self.use_complex else ())
-        out = dict(info={}, seed=int(seed))
-        for key, o in collected:
-            out['info'][key] = o['info']
-            for name, val in o.items():
-                if name in ('info', 'seed'):
-                    continue
-                val = np.asarray(val)
-                if name not in out:
-                    out[name] = np.full(struct + val.shape, np.nan) if val.dtype.kind == 'f' else \
-                        np.full(struct + val.shape, -1, dtype=val.dtype)
-                if out[name].shape[len(struct):] != val.shape:
-                    raise ValueError('{}: the elements chose different numbers of alphas; use alpha= indices'.format(name))
-                out[name][key] = val
-                if self.use_hermiticity and key[0] != key[1]:
-                    # G_ji = conj(G_ij): the same spectra; the imaginary part's change sign
-                    flip = -1.0 if (len(key) == 3 and key[2] == 1 and name in ('H', 'H_samples', 'A_samples')) else 1.0
-                    out[name][(key[1], key[0]) + key[2:]] = val * flip if val.dtype.kind == 'f' else val
-        return out
+
+        def run(K, omega, items, **common):
+            return posterior.element_samples(K, omega, items, n_samples=n_samples, seed=seed, alpha=alpha, transform=transform,
+                                             z=z, **common)
+        return self._posterior_elements(res, run, dict(seed=int(seed)), ('H', 'H_samples', 'A_samples'), 'draw samples for',
+                                        with_stream=True, skip=('info', 'seed'), timing=timing)
 
     def resample_errors(self, bins, method='jackknife', block=1, n_resamples=None, seed=None, alpha=None,
                         alpha_mode='per_resample', windows=None, functionals=None, pointwise=True, keep_samples=False,

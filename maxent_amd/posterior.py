@@ -222,21 +222,23 @@ def _stage(K, specs, dev):
     return ctx
 
 
-def device_variances(K, specs, H_rows, alpha_rows, F, want_diag, chi2_factor=1.0, device_ids=None, timing=None):
-    """``mxe_posterior_var`` for the elements ``specs`` of the kernel ``K``: element e with the hidden images
-    ``H_rows[e]`` (n_e, n_omega) at ``alpha_rows[e]`` (n_e).  ONE call per device for everything (element e on device
-    e mod N, as the solve shards them).  Returns per element ``var``, ``prior`` (n_e, n_f) and ``diag`` (n_e, n_omega) or
-    None."""
+def _per_device(K, specs, H_rows, alpha_rows, call, device_ids=None, timing=None):
+    """One ``call(ctx, el, al, Hs, mine, t)`` per device for the elements ``specs`` of the kernel ``K``: element e (with
+    the hidden images ``H_rows[e]`` (n_e, n_omega) at ``alpha_rows[e]`` (n_e)) goes to device e mod N, as the solve shards
+    them; the devices are visited one after the other.  ``ctx``: the solver's staged context when there is one (the call
+    then runs under the solver's lock), else one of its own.  ``el``, ``al``, ``Hs``: the problems of the elements
+    ``mine``, concatenated; ``t``: the call's timing dict.  ``call`` returns a tuple of arrays with one row per problem
+    (or None); per element the tuple of its rows is returned."""
+    from .batch_solver import BatchSolver
     device_ids = tuple(device_ids) if device_ids else (0,)
     n = len(specs)
-    out_var, out_prior, out_diag = [None] * n, [None] * n, [None] * n
+    out = [None] * n
     ms, reused = 0.0, 0
     for r, dev in enumerate(device_ids):
         mine = list(range(r, n, len(device_ids)))
         if not mine:
             continue
         sub = [specs[e] for e in mine]
-        from .batch_solver import BatchSolver
         ctx, solver = BatchSolver.staged_context_for(K, sub, dev) if len(device_ids) == 1 else (None, None)
         own = ctx is None
         reused += 0 if own else 1
@@ -249,9 +251,9 @@ def device_variances(K, specs, H_rows, alpha_rows, F, want_diag, chi2_factor=1.0
             t = {}
             if solver is not None:
                 with solver._lock:
-                    got = ctx.posterior_var(el, al, H=Hs, F=F, chi2_factor=chi2_factor, want_diag=want_diag, timing=t)
+                    got = call(ctx, el, al, Hs, mine, t)
             else:
-                got = ctx.posterior_var(el, al, H=Hs, F=F, chi2_factor=chi2_factor, want_diag=want_diag, timing=t)
+                got = call(ctx, el, al, Hs, mine, t)
             ms += t.get('ms', 0.0)
         finally:
             if own:
@@ -259,13 +261,22 @@ def device_variances(K, specs, H_rows, alpha_rows, F, want_diag, chi2_factor=1.0
         pos = 0
         for e in mine:
             k = len(alpha_rows[e])
-            out_var[e], out_prior[e] = got['var'][pos:pos + k], got['prior'][pos:pos + k]
-            out_diag[e] = got['diag'][pos:pos + k] if want_diag else None
+            out[e] = tuple(None if a is None else a[pos:pos + k] for a in got)
             pos += k
     if timing is not None:
         timing['ms'] = ms
         timing['reused_contexts'] = reused
-    return out_var, out_prior, out_diag
+    return out
+
+
+def device_variances(K, specs, H_rows, alpha_rows, F, want_diag, chi2_factor=1.0, device_ids=None, timing=None):
+    """``mxe_posterior_var`` for the elements ``specs`` of the kernel ``K`` (see :func:`_per_device`): ONE call per device
+    for everything.  Returns per element ``var``, ``prior`` (n_e, n_f) and ``diag`` (n_e, n_omega) or None."""
+    def call(ctx, el, al, Hs, mine, t):
+        got = ctx.posterior_var(el, al, H=Hs, F=F, chi2_factor=chi2_factor, want_diag=want_diag, timing=t)
+        return got['var'], got['prior'], got.get('diag')
+    got = _per_device(K, specs, H_rows, alpha_rows, call, device_ids, timing)
+    return [g[0] for g in got], [g[1] for g in got], [g[2] for g in got]
 
 
 # ---- one job: several elements of one kernel ------------------------------------------------------------------------
@@ -364,49 +375,14 @@ TRANSFORMS = ('linear', 'log')
 
 def device_samples(K, specs, H_rows, alpha_rows, stream_rows, n_samples, seed, z_rows=None, chi2_factor=1.0, device_ids=None,
                    timing=None):
-    """``mxe_posterior_sample`` for the elements ``specs`` of the kernel ``K`` (as :func:`device_variances`; the devices are
-    visited one after the other).  Returns per element ``delta`` (n_e, n_samples, n_omega)."""
-    device_ids = tuple(device_ids) if device_ids else (0,)
-    n = len(specs)
-    out = [None] * n
-    ms, reused = 0.0, 0
-    for r, dev in enumerate(device_ids):
-        mine = list(range(r, n, len(device_ids)))
-        if not mine:
-            continue
-        sub = [specs[e] for e in mine]
-        from .batch_solver import BatchSolver
-        ctx, solver = BatchSolver.staged_context_for(K, sub, dev) if len(device_ids) == 1 else (None, None)
-        own = ctx is None
-        reused += 0 if own else 1
-        if own:
-            ctx = _stage(K, sub, dev)
-        try:
-            el = np.concatenate([np.full(len(alpha_rows[e]), k, dtype=np.int32) for k, e in enumerate(mine)])
-            al = np.concatenate([np.asarray(alpha_rows[e], dtype=float) for e in mine])
-            Hs = np.concatenate([np.asarray(H_rows[e], dtype=float).reshape(len(alpha_rows[e]), -1) for e in mine])
-            st = np.concatenate([np.asarray(stream_rows[e], dtype=np.uint64) for e in mine])
-            zz = None if z_rows is None else np.concatenate([np.asarray(z_rows[e], dtype=float) for e in mine])
-            t = {}
-            kw = dict(H=Hs, chi2_factor=chi2_factor, n_samples=n_samples, seed=seed, stream=st, z=zz, timing=t)
-            if solver is not None:
-                with solver._lock:
-                    got = ctx.posterior_sample(el, al, **kw)
-            else:
-                got = ctx.posterior_sample(el, al, **kw)
-            ms += t.get('ms', 0.0)
-        finally:
-            if own:
-                ctx.close()
-        pos = 0
-        for e in mine:
-            k = len(alpha_rows[e])
-            out[e] = got[pos:pos + k]
-            pos += k
-    if timing is not None:
-        timing['ms'] = ms
-        timing['reused_contexts'] = reused
-    return out
+    """``mxe_posterior_sample`` for the elements ``specs`` of the kernel ``K`` (as :func:`device_variances`).  Returns per
+    element ``delta`` (n_e, n_samples, n_omega)."""
+    def call(ctx, el, al, Hs, mine, t):
+        st = np.concatenate([np.asarray(stream_rows[e], dtype=np.uint64) for e in mine])
+        zz = None if z_rows is None else np.concatenate([np.asarray(z_rows[e], dtype=float) for e in mine])
+        return (ctx.posterior_sample(el, al, H=Hs, chi2_factor=chi2_factor, n_samples=n_samples, seed=seed, stream=st, z=zz,
+                                     timing=t),)
+    return [g[0] for g in _per_device(K, specs, H_rows, alpha_rows, call, device_ids, timing)]
 
 
 def apply_transform(H, delta, transform):
