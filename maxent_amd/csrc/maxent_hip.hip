@@ -3330,6 +3330,30 @@ MXE_CATCH_ALL
 
 
 namespace {
+// the LDS of the decomposition: m_rows values of a column, 16 + 8 of the reductions, SVD_RCAP + SVD_RCAP / 2 of the
+// QR stage -- at most SVD_LDS_LIMIT bytes (device.SVD_MAX_ROWS is the largest m_rows that fits)
+constexpr size_t SVD_LDS_LIMIT = 60 * 1024;
+constexpr size_t svd_lds_bytes(int m_rows)
+{
+    return ((size_t)m_rows + 16 + 8 + mxe::SVD_RCAP + mxe::SVD_RCAP / 2) * sizeof(double);
+}
+
+// what every mxe_kernel_svd* entry asks of its arguments before its own checks
+bool svd_args_ok(int n_grid, int n_omega, int n_b, const double* grid, const double* omega, const double* delta,
+                 const double* preblur_b, double threshold, int ns_max, const double* out_U, const double* out_S,
+                 const double* out_V, const int32_t* out_ns)
+{
+    return n_grid >= 1 && n_omega >= 1 && n_b >= 1 && grid && omega && delta && preblur_b && out_U && out_S && out_V &&
+           out_ns && ns_max >= 1 && ns_max <= mxe::SVD_RCAP && threshold >= 0.0;
+}
+
+// the fill of a kernel whose threads each write one entry (or one column): ``kernel(args...)`` over nel of them
+template <class Kern, class... Args>
+void launch_fill(Kern kernel, hipStream_t st, int nel, Args... args)
+{
+    hipLaunchKernelGGL(kernel, dim3((nel + 255) / 256), dim3(256), 0, st, args...);
+}
+
 // mxe_kernel_svd and its siblings after their argument checks: ``fill(stream, dgrid, domega, dKt)`` writes the
 // unblurred K^T (n_omega columns of m_rows values) from the row grid (n_grid values: tau, iomega, or the rows of a
 // caller's matrix); the preblur
@@ -3343,8 +3367,8 @@ int kernel_svd_common(int device, int n_grid, int m_rows, int n_omega, const dou
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return MXE_ERR_NODEVICE;
     if (device < 0 || device >= ndev) return MXE_ERR_ARG;
-    const size_t lds = ((size_t)m_rows + 16 + 8 + mxe::SVD_RCAP + mxe::SVD_RCAP / 2) * sizeof(double);
-    if (lds > 60 * 1024) return MXE_ERR_LIMIT;
+    const size_t lds = svd_lds_bytes(m_rows);
+    if (lds > SVD_LDS_LIMIT) return MXE_ERR_LIMIT;
     SVDCHK(hipSetDevice(device));
     SvdScratch sc;
     SVDCHK(hipStreamCreateWithFlags(&sc.stream, hipStreamNonBlocking));
@@ -3423,13 +3447,12 @@ extern "C" int mxe_kernel_svd(int device, int n_tau, int n_omega, const double* 
                               double threshold, int ns_max, double* out_K, double* out_U, double* out_S,
                               double* out_V, int32_t* out_ns, int32_t* out_info, float* out_ms)
 try {
-    if (n_tau < 1 || n_omega < 1 || n_b < 1 || !tau || !omega || !delta || !preblur_b || !out_U || !out_S ||
-        !out_V || !out_ns || ns_max < 1 || ns_max > mxe::SVD_RCAP || !(threshold >= 0.0)) return MXE_ERR_ARG;
+    if (!svd_args_ok(n_tau, n_omega, n_b, tau, omega, delta, preblur_b, threshold, ns_max, out_U, out_S, out_V, out_ns))
+        return MXE_ERR_ARG;
     return kernel_svd_common(device, n_tau, n_tau, n_omega, tau, omega, delta, n_b, preblur_b, threshold, ns_max,
                              out_K, out_U, out_S, out_V, out_ns, out_info, out_ms,
                              [=](hipStream_t st, const double* dtau, const double* dom, double* dKt0) {
-        const int nel = n_tau * n_omega;
-        hipLaunchKernelGGL(mxe::tau_kernel_fill, dim3((nel + 255) / 256), dim3(256), 0, st, dtau, dom, beta, n_tau, n_omega, dKt0);
+        launch_fill(mxe::tau_kernel_fill, st, n_tau * n_omega, dtau, dom, beta, n_tau, n_omega, dKt0);
     });
 }
 MXE_CATCH_ALL
@@ -3439,14 +3462,12 @@ extern "C" int mxe_kernel_svd_iw(int device, int n_iw, int n_omega, const double
                                  double* out_K, double* out_U, double* out_S, double* out_V, int32_t* out_ns,
                                  int32_t* out_info, float* out_ms)
 try {
-    if (n_iw < 1 || n_omega < 1 || n_b < 1 || !iomega || !omega || !delta || !preblur_b || !out_U || !out_S ||
-        !out_V || !out_ns || ns_max < 1 || ns_max > mxe::SVD_RCAP || !(threshold >= 0.0) ||
+    if (!svd_args_ok(n_iw, n_omega, n_b, iomega, omega, delta, preblur_b, threshold, ns_max, out_U, out_S, out_V, out_ns) ||
         n_iw > (1 << 29) / n_omega) return MXE_ERR_ARG;
     return kernel_svd_common(device, n_iw, 2 * n_iw, n_omega, iomega, omega, delta, n_b, preblur_b, threshold, ns_max,
                              out_K, out_U, out_S, out_V, out_ns, out_info, out_ms,
                              [=](hipStream_t st, const double* diw, const double* dom, double* dKt0) {
-        const int nel = n_iw * n_omega;
-        hipLaunchKernelGGL(mxe::iomega_kernel_fill, dim3((nel + 255) / 256), dim3(256), 0, st, diw, dom, n_iw, n_omega, dKt0);
+        launch_fill(mxe::iomega_kernel_fill, st, n_iw * n_omega, diw, dom, n_iw, n_omega, dKt0);
     });
 }
 MXE_CATCH_ALL
@@ -3457,17 +3478,15 @@ extern "C" int mxe_kernel_svd_boson(int device, int n_tau, int n_omega, const do
                                     double threshold, int ns_max, double* out_K, double* out_U, double* out_S,
                                     double* out_V, int32_t* out_ns, int32_t* out_info, float* out_ms)
 try {
-    if (n_tau < 1 || n_omega < 1 || n_b < 1 || !tau || !omega || !delta || !preblur_b || !out_U || !out_S ||
-        !out_V || !out_ns || ns_max < 1 || ns_max > mxe::SVD_RCAP || !(threshold >= 0.0) || !(beta > 0.0) ||
-        n_tau > (1 << 30) / n_omega) return MXE_ERR_ARG;
+    if (!svd_args_ok(n_tau, n_omega, n_b, tau, omega, delta, preblur_b, threshold, ns_max, out_U, out_S, out_V, out_ns) ||
+        !(beta > 0.0) || n_tau > (1 << 30) / n_omega) return MXE_ERR_ARG;
     if (symmetric)
         for (int j = 0; j < n_omega; ++j) if (!(omega[j] >= 0.0)) return MXE_ERR_ARG;
     return kernel_svd_common(device, n_tau, n_tau, n_omega, tau, omega, delta, n_b, preblur_b, threshold, ns_max,
                              out_K, out_U, out_S, out_V, out_ns, out_info, out_ms,
                              [=](hipStream_t st, const double* dtau, const double* dom, double* dKt0) {
-        const int nel = n_tau * n_omega;
-        hipLaunchKernelGGL(mxe::boson_tau_kernel_fill, dim3((nel + 255) / 256), dim3(256), 0, st, dtau, dom, beta,
-                           symmetric ? 1 : 0, n_tau, n_omega, dKt0);
+        launch_fill(mxe::boson_tau_kernel_fill, st, n_tau * n_omega, dtau, dom, beta, symmetric ? 1 : 0, n_tau, n_omega,
+                    dKt0);
     });
 }
 MXE_CATCH_ALL
@@ -3479,17 +3498,14 @@ extern "C" int mxe_kernel_svd_boson_iw(int device, int n_inu, int n_omega, const
                                        double threshold, int ns_max, double* out_K, double* out_U, double* out_S,
                                        double* out_V, int32_t* out_ns, int32_t* out_info, float* out_ms)
 try {
-    if (n_inu < 1 || n_omega < 1 || n_b < 1 || !inu || !omega || !delta || !preblur_b || !out_U || !out_S ||
-        !out_V || !out_ns || ns_max < 1 || ns_max > mxe::SVD_RCAP || !(threshold >= 0.0) ||
+    if (!svd_args_ok(n_inu, n_omega, n_b, inu, omega, delta, preblur_b, threshold, ns_max, out_U, out_S, out_V, out_ns) ||
         n_inu > (1 << 29) / n_omega) return MXE_ERR_ARG;
     if (symmetric)
         for (int j = 0; j < n_omega; ++j) if (!(omega[j] >= 0.0)) return MXE_ERR_ARG;
     return kernel_svd_common(device, n_inu, symmetric ? n_inu : 2 * n_inu, n_omega, inu, omega, delta, n_b, preblur_b,
                              threshold, ns_max, out_K, out_U, out_S, out_V, out_ns, out_info, out_ms,
                              [=](hipStream_t st, const double* dnu, const double* dom, double* dKt0) {
-        const int nel = n_inu * n_omega;
-        hipLaunchKernelGGL(mxe::boson_iomega_kernel_fill, dim3((nel + 255) / 256), dim3(256), 0, st, dnu, dom,
-                           symmetric ? 1 : 0, n_inu, n_omega, dKt0);
+        launch_fill(mxe::boson_iomega_kernel_fill, st, n_inu * n_omega, dnu, dom, symmetric ? 1 : 0, n_inu, n_omega, dKt0);
     });
 }
 MXE_CATCH_ALL
@@ -3502,8 +3518,7 @@ extern "C" int mxe_kernel_svd_legendre(int device, int n_l, int n_omega, const d
                                        double threshold, int ns_max, double* out_K, double* out_U, double* out_S,
                                        double* out_V, int32_t* out_ns, int32_t* out_info, float* out_ms)
 try {
-    if (n_l < 1 || n_omega < 1 || n_b < 1 || !l || !omega || !delta || !preblur_b || !out_U || !out_S ||
-        !out_V || !out_ns || ns_max < 1 || ns_max > mxe::SVD_RCAP || !(threshold >= 0.0) ||
+    if (!svd_args_ok(n_l, n_omega, n_b, l, omega, delta, preblur_b, threshold, ns_max, out_U, out_S, out_V, out_ns) ||
         !(beta > 0.0) || !std::isfinite(beta) || n_l > (1 << 29) / n_omega) return MXE_ERR_ARG;
     int l_max = 0;
     for (int i = 0; i < n_l; ++i) {
@@ -3522,8 +3537,7 @@ try {
     return kernel_svd_common(device, 2 * n_l, n_l, n_omega, lgrid.data(), omega, delta, n_b, preblur_b, threshold, ns_max,
                              out_K, out_U, out_S, out_V, out_ns, out_info, out_ms,
                              [=](hipStream_t st, const double* dl, const double* dom, double* dKt0) {
-        hipLaunchKernelGGL(mxe::legendre_kernel_fill, dim3((n_omega + 255) / 256), dim3(256), 0, st, dl, dom, beta,
-                           l_max, n_l, n_omega, dKt0);
+        launch_fill(mxe::legendre_kernel_fill, st, n_omega, dl, dom, beta, l_max, n_l, n_omega, dKt0);
     });
 }
 MXE_CATCH_ALL
@@ -3535,11 +3549,10 @@ extern "C" int mxe_kernel_svd_data(int device, int n_rows, int n_omega, const do
                                    double* out_K, double* out_U, double* out_S, double* out_V, int32_t* out_ns,
                                    int32_t* out_info, float* out_ms)
 try {
-    if (n_rows < 1 || n_omega < 1 || n_b < 1 || !K || !omega || !delta || !preblur_b || !out_U || !out_S ||
-        !out_V || !out_ns || ns_max < 1 || ns_max > mxe::SVD_RCAP || !(threshold >= 0.0) ||
+    if (!svd_args_ok(n_rows, n_omega, n_b, K, omega, delta, preblur_b, threshold, ns_max, out_U, out_S, out_V, out_ns) ||
         n_rows > (1 << 30) / n_omega) return MXE_ERR_ARG;
     // (before the matrix is copied: kernel_svd_common would refuse the same rows after its own check)
-    if (((size_t)n_rows + 16 + 8 + mxe::SVD_RCAP + mxe::SVD_RCAP / 2) * sizeof(double) > 60 * 1024) return MXE_ERR_LIMIT;
+    if (svd_lds_bytes(n_rows) > SVD_LDS_LIMIT) return MXE_ERR_LIMIT;
     // a caller's matrix may hold anything: NaN and Inf are refused before the launch
     for (size_t i = 0, nel = (size_t)n_rows * n_omega; i < nel; ++i) if (!std::isfinite(K[i])) return MXE_ERR_NUMERIC;
     return kernel_svd_common(device, n_rows * n_omega, n_rows, n_omega, K, omega, delta, n_b, preblur_b, threshold,

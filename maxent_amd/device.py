@@ -30,7 +30,8 @@ class MaxEntDeviceError(RuntimeError):
 _MXE_ERR_ARG = -1
 _MXE_ERR_LIMIT = -5
 _MXE_ERR_NUMERIC = -6
-#: most rows of a kernel matrix the device SVD takes (mxe_kernel_svd*: the rows + 216 doubles of the decomposition's LDS <= 60 KB)
+#: most rows of a kernel matrix the device SVD takes: the largest m_rows with svd_lds_bytes(m_rows) <= SVD_LDS_LIMIT
+#: (maxent_hip.hip, the one place the formula is written: m_rows + 216 doubles in 60 KB)
 SVD_MAX_ROWS = 60 * 1024 // 8 - 216
 #: most significant directions (rows of R the pivoted QR keeps, SVD_RCAP of mxe_svd.hip.h) of a matrix the device SVD
 #: decomposes; a matrix of higher numerical rank raises MaxEntDeviceError
@@ -327,36 +328,24 @@ def kernel_svd(tau, omega, delta, beta, preblur_b=(0.0,), threshold=1.e-14,
     ``preblur_b`` > 0) filled and decomposed on the device.  Returns a list of
     dicts ``U, S, V`` (truncated at ``S >= threshold``), ``K`` (if wanted),
     ``qr_rank``, ``sweeps`` and the device time ``ms`` of the whole batch."""
-    lib = load_library()
-    if device_count() < 1:
-        raise MaxEntDeviceError('no HIP device visible; the device SVD has no CPU fallback')
-    tau, omega, delta = _c(tau), _c(omega), _c(delta)
-    return _kernel_svd_call('mxe_kernel_svd', len(tau), (_p(tau),), (float(beta),), omega, delta, preblur_b,
-                            threshold, ns_max, want_K, device)
+    return _kernel_svd('mxe_kernel_svd', tau, (float(beta),), omega, delta, preblur_b, threshold, ns_max, want_K,
+                            device)
 
 
 def kernel_svd_iw(iomega, omega, delta, preblur_b=(0.0,), threshold=1.e-14, ns_max=128, want_K=False, device=0):
     """``mxe_kernel_svd_iw``: IOmegaKernel (stacked real, 2 n_iw rows) and its PreblurKernels filled and
     decomposed on the device; returns what :func:`kernel_svd` returns.  More rows than the decomposition's LDS
     holds (2 n_iw > ``SVD_MAX_ROWS``) raise :class:`MaxEntDeviceError` -- the host SVD (``svd_backend='host'``) takes them."""
-    load_library()
-    if device_count() < 1:
-        raise MaxEntDeviceError('no HIP device visible; the device SVD has no CPU fallback')
-    iomega, omega, delta = _c(iomega), _c(omega), _c(delta)
-    return _kernel_svd_call('mxe_kernel_svd_iw', len(iomega), (_p(iomega),), (), omega, delta, preblur_b,
-                            threshold, ns_max, want_K, device, n_rows=2 * len(iomega))
+    return _kernel_svd('mxe_kernel_svd_iw', iomega, (), omega, delta, preblur_b, threshold, ns_max, want_K, device,
+                            n_rows=2 * len(iomega))
 
 
 def kernel_svd_boson(tau, omega, delta, beta, symmetric=False, preblur_b=(0.0,), threshold=1.e-14, ns_max=128,
                      want_K=False, device=0):
     """``mxe_kernel_svd_boson``: BosonicTauKernel (``symmetric``: its half-axis form) and its PreblurKernels filled
     and decomposed on the device; returns what :func:`kernel_svd` returns."""
-    load_library()
-    if device_count() < 1:
-        raise MaxEntDeviceError('no HIP device visible; the device SVD has no CPU fallback')
-    tau, omega, delta = _c(tau), _c(omega), _c(delta)
-    return _kernel_svd_call('mxe_kernel_svd_boson', len(tau), (_p(tau),), (float(beta), 1 if symmetric else 0), omega,
-                            delta, preblur_b, threshold, ns_max, want_K, device)
+    return _kernel_svd('mxe_kernel_svd_boson', tau, (float(beta), 1 if symmetric else 0), omega, delta, preblur_b,
+                            threshold, ns_max, want_K, device)
 
 
 def kernel_svd_boson_iw(inu, omega, delta, symmetric=False, preblur_b=(0.0,), threshold=1.e-14, ns_max=128,
@@ -364,13 +353,8 @@ def kernel_svd_boson_iw(inu, omega, delta, symmetric=False, preblur_b=(0.0,), th
     """``mxe_kernel_svd_boson_iw``: BosonicIOmegaKernel -- stacked real of 2 n rows, or with ``symmetric`` the real
     half-axis form of n rows -- and its PreblurKernels filled and decomposed on the device; returns what
     :func:`kernel_svd` returns.  Too many rows for the decomposition's LDS: as :func:`kernel_svd_iw`."""
-    load_library()
-    if device_count() < 1:
-        raise MaxEntDeviceError('no HIP device visible; the device SVD has no CPU fallback')
-    inu, omega, delta = _c(inu), _c(omega), _c(delta)
-    return _kernel_svd_call('mxe_kernel_svd_boson_iw', len(inu), (_p(inu),), (1 if symmetric else 0,), omega, delta,
-                            preblur_b, threshold, ns_max, want_K, device,
-                            n_rows=len(inu) if symmetric else 2 * len(inu))
+    return _kernel_svd('mxe_kernel_svd_boson_iw', inu, (1 if symmetric else 0,), omega, delta, preblur_b,
+                            threshold, ns_max, want_K, device, n_rows=len(inu) if symmetric else 2 * len(inu))
 
 
 def kernel_svd_legendre(l, omega, delta, beta, preblur_b=(0.0,), threshold=1.e-14, ns_max=128, want_K=False, device=0):
@@ -378,32 +362,39 @@ def kernel_svd_legendre(l, omega, delta, beta, preblur_b=(0.0,), threshold=1.e-1
     PreblurKernels filled and decomposed on the device; returns what :func:`kernel_svd` returns.  An order that is
     negative, not an integer or too large, or ``beta`` <= 0, is refused by the library before anything is launched
     (:class:`MaxEntDeviceError`)."""
-    load_library()
-    if device_count() < 1:
-        raise MaxEntDeviceError('no HIP device visible; the device SVD has no CPU fallback')
-    l, omega, delta = _c(l), _c(omega), _c(delta)
-    return _kernel_svd_call('mxe_kernel_svd_legendre', len(l), (_p(l),), (float(beta),), omega, delta, preblur_b,
-                            threshold, ns_max, want_K, device)
+    return _kernel_svd('mxe_kernel_svd_legendre', l, (float(beta),), omega, delta, preblur_b, threshold, ns_max,
+                            want_K, device)
 
 
 def kernel_svd_data(K, omega, delta, preblur_b=(0.0,), threshold=1.e-14, ns_max=128, want_K=False, device=0):
     """``mxe_kernel_svd_data``: the decomposition (and the preblur products, one per entry of ``preblur_b`` > 0) of a
     matrix the caller filled, ``K`` of shape (n_rows, n_omega); returns what :func:`kernel_svd` returns.  More rows
     than the decomposition's LDS holds (``SVD_MAX_ROWS``) raise :class:`MaxEntDeviceError` -- the host SVD takes them."""
+    return _kernel_svd('mxe_kernel_svd_data', K, (), omega, delta, preblur_b, threshold, ns_max, want_K, device)
+
+
+def _kernel_svd(name, grid, scalar_args, omega, delta, preblur_b=(0.0,), threshold=1.e-14, ns_max=128, want_K=False,
+                device=0, n_rows=None):
+    """What the ``kernel_svd*`` functions and ``Kernel._device_svd`` share: the C entry ``name`` on the row grid
+    ``grid`` (tau, i omega_n, the orders l, or the rows of a caller's matrix, which is checked here) with
+    ``scalar_args`` between ``delta`` and ``n_b`` in the entry's order; ``n_rows``: the rows of K where they are not
+    ``len(grid)``."""
     load_library()
     if device_count() < 1:
         raise MaxEntDeviceError('no HIP device visible; the device SVD has no CPU fallback')
-    K, omega, delta = _c(K), _c(omega), _c(delta)
-    if K.ndim != 2 or K.shape[1] != len(omega) or len(delta) != len(omega):
-        raise ValueError('kernel_svd_data: K (n_rows, n_omega) = %s on an omega mesh of %d points' % (K.shape, len(omega)))
-    if not np.all(np.isfinite(K)):
-        raise ValueError('kernel_svd_data: K holds %d values that are not finite' % int((~np.isfinite(K)).sum()))
-    return _kernel_svd_call('mxe_kernel_svd_data', K.shape[0], (_p(K),), (), omega, delta, preblur_b, threshold, ns_max,
-                            want_K, device)
+    grid, omega, delta = _c(grid), _c(omega), _c(delta)
+    if name == 'mxe_kernel_svd_data':
+        if grid.ndim != 2 or grid.shape[1] != len(omega) or len(delta) != len(omega):
+            raise ValueError('kernel_svd_data: K (n_rows, n_omega) = %s on an omega mesh of %d points' % (grid.shape, len(omega)))
+        if not np.all(np.isfinite(grid)):
+            raise ValueError('kernel_svd_data: K holds %d values that are not finite' % int((~np.isfinite(grid)).sum()))
+    return _kernel_svd_call(name, len(grid), (_p(grid),), scalar_args, omega, delta, preblur_b, threshold, ns_max, want_K,
+                            device, n_rows)
 
 
 def _kernel_svd_call(name, n_grid, grid_args, scalar_args, omega, delta, preblur_b, threshold, ns_max, want_K, device,
                      n_rows=None):
+    """the C entry itself, on converted arrays, and the mapping of its error codes"""
     lib = load_library()
     bs = _c(np.atleast_1d(np.asarray(preblur_b, dtype=float)))
     n_rows = n_grid if n_rows is None else n_rows      # (rows of K: n_tau, or 2 n_iw)

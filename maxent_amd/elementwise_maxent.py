@@ -834,9 +834,7 @@ class ElementwiseMaxEnt(object):
         omega, beta, no preblur on one side only) the second takes the SVD of the first instead of
         repeating it"""
         a, b = self.maxent_diagonal.K, self.maxent_offdiagonal.K
-        if a is b or type(a) is not type(b) or \
-                not isinstance(a, (kernels.TauKernel, kernels.IOmegaKernel, kernels.BosonicTauKernel,
-                                   kernels.BosonicIOmegaKernel, kernels.LegendreKernel)) or \
+        if a is b or type(a) is not type(b) or getattr(a, 'kind', None) is None or \
                 a.rotation is not None or b.rotation is not None or \
                 getattr(a, 'symmetric', None) != getattr(b, 'symmetric', None):
             return
@@ -982,16 +980,41 @@ class ElementwiseMaxEnt(object):
 
     set_G_iw = set_G_tau
 
+    def _set_array(self, cls, grid, G, put, n_iw=None, direct=True, assign_grid=True, **params):
+        """the common tail of the array setters: both workers get their kernel of class ``cls`` on ``grid`` (``params``:
+        its further constructor arguments), and ``put(worker, grid, x)`` -- the worker's setter -- feeds an element: x is
+        the real part of G[i, j], or its imaginary part for the second scan of an off-diagonal element.  ``n_iw``: the
+        part holds the stacked ``[Re ; Im]`` of that many complex values, and travels to the worker folded.  ``direct``:
+        whether ``_direct_input`` may cut the specs from the array."""
+        def feed(maxent, G_mat, elem, re):
+            x = G_mat[1][elem]
+            x = np.real(x) if re else np.imag(x)
+            put(maxent, G_mat[0], x if n_iw is None else x[:n_iw] + 1j * x[n_iw:])
+        for worker in (self.maxent_diagonal, self.maxent_offdiagonal):
+            worker._use_kernel(cls, grid, assign_grid=assign_grid, **params)
+        self.set_G((grid, G), feed, lambda G_mat: G_mat[1].shape[:2])
+        object.__setattr__(self, '_array_input', direct)
+        object.__setattr__(self, '_n_iw', n_iw)
+
+    @staticmethod
+    def _hermitian_split(G, stacked=True):
+        """complex (M, M, n) data of a hermitian A(omega) as the data of the real-part problems, (G_ij + G_ji) / 2 =
+        K Re A_ij, in the real part and of the imaginary-part problems, (G_ij - G_ji) / (2i) = K Im A_ij, in the imaginary
+        part -- the feed and the arrays of _prepare_batch pick them the way they pick the parts of G(tau); ``stacked``:
+        each as ``[Re ; Im]`` (2 n values), otherwise their real parts (n values)"""
+        Gt = G.transpose(1, 0, 2)
+        re_part = 0.5 * (G + Gt)                    # K Re A_ij
+        im_part = (G - Gt) / 2j                     # K Im A_ij
+        if not stacked:
+            return re_part.real + 1j * im_part.real
+        return np.concatenate([re_part.real, re_part.imag], axis=-1) + \
+            1j * np.concatenate([im_part.real, im_part.imag], axis=-1)
+
     def set_G_tau_data(self, tau, G_tau, *args, **kwargs):
         """``G_tau``: (M, N, T) array (reference elementwise_maxent.py:373-395)."""
-        def feed(maxent, G_mat, elem, re):
-            g = G_mat[1][elem]
-            maxent.set_G_tau_data(G_mat[0], np.real(g) if re else np.imag(g),
-                                  *args, **kwargs)
-        for worker in (self.maxent_diagonal, self.maxent_offdiagonal):
-            worker._use_tau_kernel(tau)
-        self.set_G((tau, G_tau), feed, lambda G_mat: G_mat[1].shape[:2])
-        object.__setattr__(self, '_array_input', not args and not kwargs)
+        # (a worker's kernel that stays gets the grid with its first element, not here)
+        self._set_array(kernels.TauKernel, tau, G_tau, lambda tm, t, x: tm.set_G_tau_data(t, x, *args, **kwargs),
+                        direct=not args and not kwargs, assign_grid=False)
 
     def set_G_iw_data(self, iomega, G_iw, beta=None):
         """``G_iw``: complex (M, N, n_iw) array of G_ij(i omega_n) on the real Matsubara frequencies ``iomega``
@@ -1003,28 +1026,12 @@ class ElementwiseMaxEnt(object):
         G_iw = np.asarray(G_iw)
         if G_iw.ndim != 3 or G_iw.shape[0] != G_iw.shape[1] or G_iw.shape[2] != len(iomega):
             raise AssertionError('G_iw must be (M, M, n_iw) with n_iw = len(iomega)')
-        Gt = G_iw.transpose(1, 0, 2)
-        re_part = 0.5 * (G_iw + Gt)                 # K Re A_ij
-        im_part = (G_iw - Gt) / 2j                  # K Im A_ij
-        # the stacked real data of the real-part problem in the real part, of the imaginary-part problem in the imaginary
-        # part: the feed and the arrays of _prepare_batch pick them the way they pick the parts of G(tau)
-        stacked = np.concatenate([re_part.real, re_part.imag], axis=-1) + \
-            1j * np.concatenate([im_part.real, im_part.imag], axis=-1)
-        self._set_G_iw_stacked(iomega, stacked, beta)
+        self._set_G_iw_stacked(iomega, self._hermitian_split(G_iw), beta)
 
     def _set_G_iw_stacked(self, iomega, stacked, beta):
         """the tail of :meth:`set_G_iw_data`: ``stacked`` (M, M, 2 n_iw) as described there"""
-        n = len(iomega)
-
-        def feed(maxent, G_mat, elem, re):
-            x = G_mat[1][elem]
-            x = np.real(x) if re else np.imag(x)
-            maxent.set_G_iw_data(G_mat[0], x[:n] + 1j * x[n:], beta)
-        for worker in (self.maxent_diagonal, self.maxent_offdiagonal):
-            worker._use_iomega_kernel(iomega, beta)
-        self.set_G((iomega, stacked), feed, lambda G_mat: G_mat[1].shape[:2])
-        object.__setattr__(self, '_array_input', True)
-        object.__setattr__(self, '_n_iw', n)
+        self._set_array(kernels.IOmegaKernel, iomega, stacked, lambda tm, iw, z: tm.set_G_iw_data(iw, z, beta),
+                        n_iw=len(iomega), beta=beta)
 
     def set_chi_tau_data(self, tau, chi, beta=None, symmetric=False):
         """``chi``: (M, N, T) array of bosonic chi_ij(tau) (:meth:`TauMaxEnt.set_chi_tau_data`); the real part of an
@@ -1033,14 +1040,8 @@ class ElementwiseMaxEnt(object):
         chi = np.asarray(chi)
         if chi.ndim != 3 or chi.shape[2] != len(tau):
             raise AssertionError('chi must be (M, N, n_tau) with n_tau = len(tau)')
-
-        def feed(maxent, G_mat, elem, re):
-            g = G_mat[1][elem]
-            maxent.set_chi_tau_data(G_mat[0], np.real(g) if re else np.imag(g), beta, symmetric)
-        for worker in (self.maxent_diagonal, self.maxent_offdiagonal):
-            worker._use_bosonic_kernel(kernels.BosonicTauKernel, tau, beta, symmetric)
-        self.set_G((tau, chi), feed, lambda G_mat: G_mat[1].shape[:2])
-        object.__setattr__(self, '_array_input', True)
+        self._set_array(kernels.BosonicTauKernel, tau, chi, lambda tm, t, x: tm.set_chi_tau_data(t, x, beta, symmetric),
+                        beta=beta, symmetric=bool(symmetric))
 
     def set_chi_iw_data(self, inu, chi_iw, beta=None, symmetric=False):
         """``chi_iw``: complex (M, M, n) array of bosonic chi_ij(i nu_n) (:meth:`TauMaxEnt.set_chi_iw_data`).  The
@@ -1051,25 +1052,9 @@ class ElementwiseMaxEnt(object):
         chi_iw = np.asarray(chi_iw)
         if chi_iw.ndim != 3 or chi_iw.shape[0] != chi_iw.shape[1] or chi_iw.shape[2] != len(inu):
             raise AssertionError('chi_iw must be (M, M, n) with n = len(inu)')
-        Gt = chi_iw.transpose(1, 0, 2)
-        re_part = 0.5 * (chi_iw + Gt)               # K Re A_ij
-        im_part = (chi_iw - Gt) / 2j                # K Im A_ij
-        n = len(inu)
-        if symmetric:
-            data = re_part.real + 1j * im_part.real
-        else:
-            data = np.concatenate([re_part.real, re_part.imag], axis=-1) + \
-                1j * np.concatenate([im_part.real, im_part.imag], axis=-1)
-
-        def feed(maxent, G_mat, elem, re):
-            x = G_mat[1][elem]
-            x = np.real(x) if re else np.imag(x)
-            maxent.set_chi_iw_data(G_mat[0], x if symmetric else x[:n] + 1j * x[n:], beta, symmetric)
-        for worker in (self.maxent_diagonal, self.maxent_offdiagonal):
-            worker._use_bosonic_kernel(kernels.BosonicIOmegaKernel, inu, beta, symmetric)
-        self.set_G((inu, data), feed, lambda G_mat: G_mat[1].shape[:2])
-        object.__setattr__(self, '_array_input', True)
-        object.__setattr__(self, '_n_iw', None if symmetric else n)
+        self._set_array(kernels.BosonicIOmegaKernel, inu, self._hermitian_split(chi_iw, stacked=not symmetric),
+                        lambda tm, nu, z: tm.set_chi_iw_data(nu, z, beta, symmetric),
+                        n_iw=None if symmetric else len(inu), beta=beta, symmetric=bool(symmetric))
 
     def set_G_l_data(self, G_l, beta, l=None):
         """``G_l``: (M, N, n_l) array of Legendre coefficients of G_ij (:meth:`TauMaxEnt.set_G_l_data`; ``l`` defaults to
@@ -1078,15 +1063,8 @@ class ElementwiseMaxEnt(object):
         G_l = np.asarray(G_l)
         if G_l.ndim != 3:
             raise AssertionError('G_l must be (M, N, n_l)')
-        l = TauMaxEnt._legendre_orders(l, G_l.shape[2])
-
-        def feed(maxent, G_mat, elem, re):
-            g = G_mat[1][elem]
-            maxent.set_G_l_data(np.real(g) if re else np.imag(g), beta, G_mat[0])
-        for worker in (self.maxent_diagonal, self.maxent_offdiagonal):
-            worker._use_legendre_kernel(l, beta)
-        self.set_G((l, G_l), feed, lambda G_mat: G_mat[1].shape[:2])
-        object.__setattr__(self, '_array_input', True)
+        self._set_array(kernels.LegendreKernel, TauMaxEnt._legendre_orders(l, G_l.shape[2]), G_l,
+                        lambda tm, orders, x: tm.set_G_l_data(x, beta, orders), beta=beta)
 
     def set_G_tau_filename_pattern(self, filename, dimension, tau_col=0,
                                    G_col_re=1, G_col_im=2, *args, **kwargs):

@@ -174,10 +174,36 @@ class Kernel(KernelSVD):
     #: of what its rotation says (``refill_unrotated`` mends it)
     _projected = False
 
+    # ---- what a kind of kernel says about itself (read by _fill_values, _device_svd, PreblurKernel, TauMaxEnt._use_kernel)
+    #: tag of a kind that fills its matrix itself, in the key of the fill cache: equal tau and i omega grids stay apart.
+    kind = None
+    #: whether beta enters the matrix: a new beta refills it (the Matsubara kernels only remember theirs)
+    beta_in_matrix = True
+    #: constructor arguments whose change makes another kernel, not a refill
+    kind_params = ()
+    #: whether the rows are ``[Re K ; Im K]`` and the data complex (:class:`_StackedRows`)
+    stacked = False
+    #: whether ``_device_entry`` is there: the device fills (or takes) and decomposes the matrix
+    has_device_entry = False
+    #: whether ``PreblurKernel.scan`` takes the kind
+    scannable = False
+
     def __init__(self):
         super(Kernel, self).__init__()
         self.omega = None
         self._T = None
+
+    @property
+    def setter_kind(self):
+        """the ``kind`` whose setters of TauMaxEnt keep this kernel: its own, or -- a kernel that does not fill itself,
+        a DataKernel or a user's class -- that of G(tau) data"""
+        return 'tau' if self.kind is None else self.kind
+
+    @classmethod
+    def _checked_args(cls, grid, **params):
+        """the grid as a setter of TauMaxEnt assigns it (``TauMaxEnt._use_kernel``); a kind that validates its arguments
+        raises here, before anything is changed"""
+        return grid
 
     @property
     def rotation(self):
@@ -196,8 +222,49 @@ class Kernel(KernelSVD):
     def parameter_change(self):
         self._fill_values()
 
-    def _fill_values(self):
+    def _inputs(self, w):
+        """what the matrix depends on besides the omega mesh ``w``, validated: a tuple of arrays and scalars.  It is the
+        kind's part of the key of the fill cache and the arguments of :meth:`_compute`."""
         raise NotImplementedError('Use a subclass of Kernel')
+
+    def _compute(self, w, *inputs):
+        """the unrotated matrix on the mesh ``w`` from :meth:`_inputs`"""
+        raise NotImplementedError('Use a subclass of Kernel')
+
+    def _fill_values(self):
+        """the unrotated matrix from the cache of recent fills or from ``_compute`` -- shared and read-only either way --,
+        then the rotation the kernel carries again"""
+        self._invalidate_svd()
+        w = np.asarray(self.omega, dtype=float)
+        inputs = self._inputs(w)
+        delta = np.asarray(self.omega.delta, dtype=float)
+        key = (self.kind, w.tobytes(), delta.tobytes()) + \
+            tuple([x.tobytes() if type(x) is np.ndarray else x for x in inputs])
+        hit = _recent_fill.get(key, lambda _: True)               # (the key IS the contents)
+        if hit is None:
+            K = self._compute(w, *inputs)
+            hit = (_frozen(K), _frozen(K * delta[np.newaxis, :]))
+            _recent_fill.put(key, None, hit)
+        self._K, self._K_delta = hit
+        self._K_unrotated = hit[0]
+        T = self._T
+        self._T = None
+        self.transform(T)
+
+    def _device_entry(self, preblur_b=0.0):
+        """``(name, grid, scalars, n_rows)``: the C entry that fills and decomposes this kind, its row grid, the scalar
+        arguments between ``delta`` and ``n_b`` in the entry's order, and the number of rows of the matrix"""
+        raise NotImplementedError('svd_backend="device" needs a kernel of this module')
+
+    def _device_svd(self, preblur_b=0.0):
+        """U, S, V of the UNROTATED kernel from the device: everything the QR stage kept
+        (singular values down to eps * sigma_max; the reference's LAPACK values below
+        that are rounding noise), ``reduce_singular_space`` cuts as usual."""
+        from . import device
+        name, grid, scalars, n_rows = self._device_entry(preblur_b)
+        r = device._kernel_svd(name, grid, scalars, np.asarray(self.omega, dtype=float), self.omega.delta,
+                               [preblur_b], threshold=0.0, n_rows=n_rows)[0]
+        return r['U'], r['S'], r['V']
 
     def refill_unrotated(self):
         """the unrotated matrix again, filled afresh: the way out of a rotation with fewer rows than columns, which
@@ -243,6 +310,8 @@ class Kernel(KernelSVD):
 class DataKernel(Kernel):
     """Kernel given as a matrix (reference kernels.py:183-207)."""
 
+    has_device_entry = True
+
     def __init__(self, data_variable, omega, K, svd_backend='host'):
         super(DataKernel, self).__init__()
         self._data_variable = data_variable
@@ -267,22 +336,29 @@ class DataKernel(Kernel):
             self._invalidate_svd()
             self._K = self._K_unrotated
 
-    def _device_svd(self, preblur_b=0.0):
-        """U, S, V of the matrix as it stands (``mxe_kernel_svd_data``); with ``preblur_b`` > 0, of the UNROTATED
-        blurred matrix -- the blur acts from the right, so the rotation is taken off the rows first"""
-        from . import device
+    def _device_entry(self, preblur_b=0.0):
+        """the matrix as it stands (``mxe_kernel_svd_data``); with ``preblur_b`` > 0 the UNROTATED one -- the blur acts
+        from the right, so the rotation is taken off the rows first"""
         K = np.asarray(self._K, dtype=float)
         if preblur_b > 0.0 and self._T is not None:
             K = np.dot(self._T.conjugate().transpose(), K)
-        r = device.kernel_svd_data(K, np.asarray(self.omega, dtype=float), self.omega.delta, [preblur_b],
-                                   threshold=0.0)[0]
-        return r['U'], r['S'], r['V']
+        return 'mxe_kernel_svd_data', K, (), len(K)
+
+
+def _tau_and_beta(kernel):
+    """the tau grid of an imaginary-time kernel and its beta, which defaults to ``tau[-1]``"""
+    tau = np.asarray(kernel.tau, dtype=float)
+    return tau, (tau[-1] if kernel.beta is None else kernel.beta)
 
 
 class TauKernel(Kernel):
     r"""Fermionic imaginary-time kernel
     :math:`K(\tau,\omega) = -e^{-\tau\omega}/(1+e^{-\beta\omega})`
     (reference kernels.py:210-280).  ``beta`` defaults to ``tau[-1]``."""
+
+    kind = 'tau'
+    has_device_entry = True
+    scannable = True
 
     def __init__(self, tau, omega, beta=None, svd_backend='host'):
         super(TauKernel, self).__init__()
@@ -292,34 +368,14 @@ class TauKernel(Kernel):
         self.svd_backend = svd_backend
         self._fill_values()
 
-    def _device_args(self):
-        tau = np.asarray(self.tau, dtype=float)
-        beta = tau[-1] if self.beta is None else self.beta
-        return tau, np.asarray(self.omega, dtype=float), self.omega.delta, beta
+    def _device_entry(self, preblur_b=0.0):
+        tau, beta = _tau_and_beta(self)
+        return 'mxe_kernel_svd', tau, (float(beta),), len(tau)
 
-    def _device_svd(self, preblur_b=0.0):
-        """U, S, V of the UNROTATED kernel from the device: everything the QR stage kept
-        (singular values down to eps * sigma_max; the reference's LAPACK values below
-        that are rounding noise), ``reduce_singular_space`` cuts as usual."""
-        from . import device
-        tau, w, delta, beta = self._device_args()
-        r = device.kernel_svd(tau, w, delta, beta, [preblur_b], threshold=0.0)[0]
-        return r['U'], r['S'], r['V']
+    def _inputs(self, w):
+        return _tau_and_beta(self)
 
-    def _fill_values(self):
-        self._invalidate_svd()
-        tau = np.asarray(self.tau, dtype=float)
-        w = np.asarray(self.omega, dtype=float)
-        beta = tau[-1] if self.beta is None else self.beta
-        delta = np.asarray(self.omega.delta, dtype=float)
-        key = ('tau', tau.tobytes(), w.tobytes(), delta.tobytes(), float(beta))
-        hit = _recent_fill.get(key, lambda _: True)               # (the key IS the contents)
-        if hit is not None:
-            self._K, self._K_delta = hit
-            T = self._T
-            self._T = None
-            self.transform(T)
-            return
+    def _compute(self, w, tau, beta):
         ww = w[np.newaxis, :] * np.ones((len(tau), 1))
         tt = tau[:, np.newaxis] * np.ones((1, len(w)))
         pos = ww >= 0.0
@@ -329,12 +385,7 @@ class TauKernel(Kernel):
         neg = np.logical_not(pos)
         K[neg] = -np.exp(ww[neg] * (beta - tt[neg])) / \
             (1.0 + np.exp(beta * ww[neg]))
-        self._K = _frozen(K)
-        self._K_delta = _frozen(K * self.omega.delta[np.newaxis, :])
-        _recent_fill.put(key, None, (self._K, self._K_delta))
-        T = self._T
-        self._T = None
-        self.transform(T)
+        return K
 
     @property
     def data_variable(self):
@@ -345,7 +396,66 @@ class TauKernel(Kernel):
         self.tau = value
 
 
-class IOmegaKernel(Kernel):
+def stack_complex(z):
+    """complex values (last axis n) as the stacked real ``[Re ; Im]`` (last axis 2 n): the data of a kernel whose rows
+    are ``[Re K ; Im K]``"""
+    z = np.asarray(z)
+    return np.concatenate([z.real, z.imag], axis=-1).astype(float, copy=False)
+
+
+class _StackedRows(object):
+    """What the Matsubara kernels share: the complex ``n x n_omega`` kernel is held as the stacked real matrix
+    ``[Re K ; Im K]`` of ``2 n`` rows (``stacked``), the data the same way; ``beta`` is remembered (default: from the
+    spacing of the grid) and does not enter the matrix.  A kind that is real for some arguments sets ``stacked`` False
+    there: ``n`` rows, ``fold`` and ``unfold`` the identity on real data."""
+
+    stacked = True
+    beta_in_matrix = False
+
+    @property
+    def n_iw(self):
+        return len(self.data_variable)
+
+    def get_beta(self):
+        if self._beta is None:
+            iw = np.asarray(self.data_variable, dtype=float)
+            return 2 * np.pi / (iw[1] - iw[0])
+        return self._beta
+
+    def set_beta(self, beta):
+        self._beta = beta
+
+    beta = property(get_beta, set_beta)
+
+    @property
+    def K_complex(self):
+        """the complex ``K`` (n x n_omega; the reference's ``K`` of an IOmegaKernel), unrotated; real-valued (but
+        complex dtype) where the kernel is not stacked"""
+        n = self.n_iw
+        if not self.stacked:
+            return self._K_unrotated + 0j
+        return self._K_unrotated[:n] + 1j * self._K_unrotated[n:]
+
+    def fold(self, x):
+        """``x[..., :n] + 1j x[..., n:]`` (n = n_iw): stacked real data-space values as the complex data; the identity
+        where the kernel is not stacked"""
+        if not self.stacked:
+            return x
+        x = np.asarray(x)
+        n = self.n_iw
+        if x.shape[-1] != 2 * n:
+            raise ValueError('fold: the last axis has %d values, not 2 x %d' % (x.shape[-1], n))
+        return x[..., :n] + 1j * x[..., n:]
+
+    def unfold(self, z):
+        """complex data (last axis n_iw) as the stacked real vector ``[Re ; Im]`` (:func:`stack_complex`); the real part
+        where the kernel is not stacked, whose data are real"""
+        if not self.stacked:
+            return z if not np.iscomplexobj(z) else np.asarray(z).real.astype(float, copy=False)
+        return stack_complex(z)
+
+
+class IOmegaKernel(_StackedRows, Kernel):
     r"""Fermionic Matsubara kernel :math:`K(i\omega_n, \omega) = 1/(i\omega_n - \omega)` (reference
     kernels.py:283-346), for a REAL spectral function: the complex rows become the stacked real matrix
 
@@ -361,6 +471,9 @@ class IOmegaKernel(Kernel):
     ``K_complex`` here).  ``iomega``: the real frequencies :math:`\omega_n`; ``beta`` defaults to
     :math:`2\pi/(\omega_1 - \omega_0)` and does not enter K."""
 
+    kind = 'iomega'
+    has_device_entry = True
+
     def __init__(self, iomega, omega, beta=None, svd_backend='host'):
         super(IOmegaKernel, self).__init__()
         self.iomega = iomega
@@ -369,65 +482,16 @@ class IOmegaKernel(Kernel):
         self.svd_backend = svd_backend
         self._fill_values()
 
-    @property
-    def n_iw(self):
-        return len(self.iomega)
-
-    def get_beta(self):
-        if self._beta is None:
-            iw = np.asarray(self.iomega, dtype=float)
-            return 2 * np.pi / (iw[1] - iw[0])
-        return self._beta
-
-    def set_beta(self, beta):
-        self._beta = beta
-
-    beta = property(get_beta, set_beta)
-
-    @property
-    def K_complex(self):
-        """the reference's complex ``K`` (n_iw x n_omega), unrotated"""
-        n = self.n_iw
-        return self._K_stacked[:n] + 1j * self._K_stacked[n:]
-
-    def fold(self, x):
-        """``x[..., :n] + 1j x[..., n:]`` (n = n_iw): stacked real data-space values as complex G(i omega_n)"""
-        x = np.asarray(x)
-        n = self.n_iw
-        if x.shape[-1] != 2 * n:
-            raise ValueError('fold: the last axis has %d values, not 2 x %d' % (x.shape[-1], n))
-        return x[..., :n] + 1j * x[..., n:]
-
-    def unfold(self, z):
-        """complex G(i omega_n) (last axis n_iw) as the stacked real vector ``[Re ; Im]``"""
-        z = np.asarray(z)
-        return np.concatenate([z.real, z.imag], axis=-1).astype(float, copy=False)
-
-    def _device_svd(self, preblur_b=0.0):
-        """U, S, V of the UNROTATED stacked kernel from the device (``mxe_kernel_svd_iw``); see TauKernel._device_svd"""
-        from . import device
+    def _device_entry(self, preblur_b=0.0):
         iw = np.asarray(self.iomega, dtype=float)
-        r = device.kernel_svd_iw(iw, np.asarray(self.omega, dtype=float), self.omega.delta, [preblur_b],
-                                 threshold=0.0)[0]
-        return r['U'], r['S'], r['V']
+        return 'mxe_kernel_svd_iw', iw, (), 2 * len(iw)
 
-    def _fill_values(self):
-        self._invalidate_svd()
-        iw = np.asarray(self.iomega, dtype=float)
-        w = np.asarray(self.omega, dtype=float)
-        delta = np.asarray(self.omega.delta, dtype=float)
-        key = ('iomega', iw.tobytes(), w.tobytes(), delta.tobytes())         # (the kind keeps a tau grid of the same values apart)
-        hit = _recent_fill.get(key, lambda _: True)
-        if hit is None:
-            d = iw[:, np.newaxis] ** 2 + w[np.newaxis, :] ** 2           # (one w_n^2 + w^2 for both parts, as the device fill)
-            K = np.concatenate([-w[np.newaxis, :] / d, -iw[:, np.newaxis] / d])
-            hit = (_frozen(K), _frozen(K * delta[np.newaxis, :]))
-            _recent_fill.put(key, None, hit)
-        self._K, self._K_delta = hit
-        self._K_stacked = hit[0]
-        T = self._T
-        self._T = None
-        self.transform(T)
+    def _inputs(self, w):
+        return (np.asarray(self.iomega, dtype=float),)
+
+    def _compute(self, w, iw):
+        d = iw[:, np.newaxis] ** 2 + w[np.newaxis, :] ** 2           # (one w_n^2 + w^2 for both parts, as the device fill)
+        return np.concatenate([-w[np.newaxis, :] / d, -iw[:, np.newaxis] / d])
 
     @property
     def data_variable(self):
@@ -478,6 +542,11 @@ class BosonicTauKernel(Kernel):
     ``expm1`` for the denominator and a short series below ``BOSON_SERIES_CUT``, and compensates the rounding of the
     arguments of ``exp``: every entry is good to a few ulp."""
 
+    kind = 'boson_tau'
+    kind_params = ('symmetric',)
+    has_device_entry = True
+    scannable = True
+
     def __init__(self, tau, omega, beta=None, symmetric=False, svd_backend='host'):
         super(BosonicTauKernel, self).__init__()
         self.tau = tau
@@ -487,17 +556,9 @@ class BosonicTauKernel(Kernel):
         self.svd_backend = svd_backend
         self._fill_values()
 
-    def _device_args(self):
-        tau = np.asarray(self.tau, dtype=float)
-        beta = tau[-1] if self.beta is None else self.beta
-        return tau, np.asarray(self.omega, dtype=float), self.omega.delta, beta
-
-    def _device_svd(self, preblur_b=0.0):
-        """U, S, V of the UNROTATED kernel from the device (``mxe_kernel_svd_boson``); see TauKernel._device_svd"""
-        from . import device
-        tau, w, delta, beta = self._device_args()
-        r = device.kernel_svd_boson(tau, w, delta, beta, self.symmetric, [preblur_b], threshold=0.0)[0]
-        return r['U'], r['S'], r['V']
+    def _device_entry(self, preblur_b=0.0):
+        tau, beta = _tau_and_beta(self)
+        return 'mxe_kernel_svd_boson', tau, (float(beta), 1 if self.symmetric else 0), len(tau)
 
     @staticmethod
     def _values(tau, w, beta, symmetric):
@@ -527,25 +588,15 @@ class BosonicTauKernel(Kernel):
         K[neg] = ww[neg] * _exp_of_product(bt[neg], ww[neg], bt_lo[neg] * ww[neg]) / np.expm1(x[neg])
         return K
 
-    def _fill_values(self):
-        self._invalidate_svd()
-        tau = np.asarray(self.tau, dtype=float)
-        w = np.asarray(self.omega, dtype=float)
+    def _inputs(self, w):
         if self.symmetric:
             _require_half_axis(w, 'BosonicTauKernel')
-        beta = float(tau[-1] if self.beta is None else self.beta)
-        delta = np.asarray(self.omega.delta, dtype=float)
-        key = ('boson_tau', self.symmetric, tau.tobytes(), w.tobytes(), delta.tobytes(), beta)
-        hit = _recent_fill.get(key, lambda _: True)               # (the key IS the contents)
-        if hit is None:
-            with np.errstate(under='ignore'):
-                K = self._values(tau, w, beta, self.symmetric)
-            hit = (_frozen(K), _frozen(K * delta[np.newaxis, :]))
-            _recent_fill.put(key, None, hit)
-        self._K, self._K_delta = hit
-        T = self._T
-        self._T = None
-        self.transform(T)
+        tau, beta = _tau_and_beta(self)
+        return tau, float(beta), self.symmetric
+
+    def _compute(self, w, tau, beta, symmetric):
+        with np.errstate(under='ignore'):
+            return self._values(tau, w, beta, symmetric)
 
     @property
     def data_variable(self):
@@ -556,7 +607,7 @@ class BosonicTauKernel(Kernel):
         self.tau = value
 
 
-class BosonicIOmegaKernel(Kernel):
+class BosonicIOmegaKernel(_StackedRows, Kernel):
     r"""Bosonic Matsubara kernel :math:`K(i\nu_n, \omega) = \omega/(\omega - i\nu_n)
     = (\omega^2 + i\omega\nu_n)/(\omega^2 + \nu_n^2)`, 1 at :math:`\omega = \nu_n = 0`, for
     :math:`A(\omega) = \mathrm{Im}\,\chi(\omega)/(\pi\omega)`; held like :class:`IOmegaKernel` as the stacked real
@@ -565,6 +616,10 @@ class BosonicIOmegaKernel(Kernel):
     :math:`\omega \ge 0`, the real kernel :math:`2\omega^2/(\omega^2 + \nu_n^2)` of ``n`` rows (2 at the origin) for
     the data Re chi(i nu_n); ``fold`` / ``unfold`` are then the identity.  ``inu``: the real frequencies
     :math:`\nu_n = 2\pi n/\beta`; ``beta`` defaults to :math:`2\pi/(\nu_1 - \nu_0)` and does not enter K."""
+
+    kind = 'boson_iomega'
+    kind_params = ('symmetric',)
+    has_device_entry = True
 
     def __init__(self, inu, omega, beta=None, symmetric=False, svd_backend='host'):
         super(BosonicIOmegaKernel, self).__init__()
@@ -576,85 +631,28 @@ class BosonicIOmegaKernel(Kernel):
         self._fill_values()
 
     @property
-    def n_iw(self):
-        return len(self.inu)
-
-    @property
     def stacked(self):
         """whether the rows are ``[Re K ; Im K]`` (2 n of them) and the data complex"""
         return not self.symmetric
 
-    def get_beta(self):
-        if self._beta is None:
-            nu = np.asarray(self.inu, dtype=float)
-            return 2 * np.pi / (nu[1] - nu[0])
-        return self._beta
-
-    def set_beta(self, beta):
-        self._beta = beta
-
-    beta = property(get_beta, set_beta)
-
-    @property
-    def K_complex(self):
-        """the complex ``K`` (n x n_omega), unrotated; real-valued (but complex dtype) for a symmetric kernel"""
-        n = self.n_iw
-        if self.symmetric:
-            return self._K_plain + 0j
-        return self._K_plain[:n] + 1j * self._K_plain[n:]
-
-    def fold(self, x):
-        """``x[..., :n] + 1j x[..., n:]``: stacked real data-space values as complex chi(i nu_n); the identity for
-        a symmetric kernel"""
-        if self.symmetric:
-            return x
-        x = np.asarray(x)
-        n = self.n_iw
-        if x.shape[-1] != 2 * n:
-            raise ValueError('fold: the last axis has %d values, not 2 x %d' % (x.shape[-1], n))
-        return x[..., :n] + 1j * x[..., n:]
-
-    def unfold(self, z):
-        """complex chi(i nu_n) (last axis n) as the stacked real vector ``[Re ; Im]``; the real part for a symmetric
-        kernel, whose data are Re chi(i nu_n)"""
-        if self.symmetric:
-            return z if not np.iscomplexobj(z) else np.asarray(z).real.astype(float, copy=False)
-        z = np.asarray(z)
-        return np.concatenate([z.real, z.imag], axis=-1).astype(float, copy=False)
-
-    def _device_svd(self, preblur_b=0.0):
-        """U, S, V of the UNROTATED kernel from the device (``mxe_kernel_svd_boson_iw``); see TauKernel._device_svd"""
-        from . import device
-        r = device.kernel_svd_boson_iw(np.asarray(self.inu, dtype=float), np.asarray(self.omega, dtype=float),
-                                       self.omega.delta, self.symmetric, [preblur_b], threshold=0.0)[0]
-        return r['U'], r['S'], r['V']
-
-    def _fill_values(self):
-        self._invalidate_svd()
+    def _device_entry(self, preblur_b=0.0):
         nu = np.asarray(self.inu, dtype=float)
-        w = np.asarray(self.omega, dtype=float)
+        return 'mxe_kernel_svd_boson_iw', nu, (1 if self.symmetric else 0,), len(nu) if self.symmetric else 2 * len(nu)
+
+    def _inputs(self, w):
         if self.symmetric:
             _require_half_axis(w, 'BosonicIOmegaKernel')
-        delta = np.asarray(self.omega.delta, dtype=float)
-        key = ('boson_iomega', self.symmetric, nu.tobytes(), w.tobytes(), delta.tobytes())
-        hit = _recent_fill.get(key, lambda _: True)
-        if hit is None:
-            w2 = (w * w)[np.newaxis, :]
-            d = nu[:, np.newaxis] ** 2 + w2                  # (one nu_n^2 + w^2 for both parts, as the device fill)
-            origin = np.logical_not(d > 0.0)                 # (w = nu_n = 0: K = 1)
-            with np.errstate(invalid='ignore', divide='ignore', under='ignore'):
-                if self.symmetric:
-                    K = np.where(origin, 2.0, 2.0 * w2 / d)
-                else:
-                    K = np.concatenate([np.where(origin, 1.0, w2 / d),
-                                        np.where(origin, 0.0, w[np.newaxis, :] * nu[:, np.newaxis] / d)])
-            hit = (_frozen(K), _frozen(K * delta[np.newaxis, :]))
-            _recent_fill.put(key, None, hit)
-        self._K, self._K_delta = hit
-        self._K_plain = hit[0]
-        T = self._T
-        self._T = None
-        self.transform(T)
+        return np.asarray(self.inu, dtype=float), self.symmetric
+
+    def _compute(self, w, nu, symmetric):
+        w2 = (w * w)[np.newaxis, :]
+        d = nu[:, np.newaxis] ** 2 + w2                  # (one nu_n^2 + w^2 for both parts, as the device fill)
+        origin = np.logical_not(d > 0.0)                 # (w = nu_n = 0: K = 1)
+        with np.errstate(invalid='ignore', divide='ignore', under='ignore'):
+            if symmetric:
+                return np.where(origin, 2.0, 2.0 * w2 / d)
+            return np.concatenate([np.where(origin, 1.0, w2 / d),
+                                   np.where(origin, 0.0, w[np.newaxis, :] * nu[:, np.newaxis] / d)])
 
     @property
     def data_variable(self):
@@ -711,6 +709,10 @@ class LegendreKernel(Kernel):
     overflows for any :math:`\beta\omega`, small entries underflow to 0.  The work per column grows like
     :math:`\max(l_{max}, a)`."""
 
+    kind = 'legendre'
+    has_device_entry = True
+    scannable = True
+
     def __init__(self, l, omega, beta=None, svd_backend='host'):
         super(LegendreKernel, self).__init__()
         self._checked_beta(beta)
@@ -746,15 +748,13 @@ class LegendreKernel(Kernel):
             raise ValueError('LegendreKernel: l holds duplicates')
         return a
 
-    def _device_svd(self, preblur_b=0.0):
-        """U, S, V of the UNROTATED kernel from the device (``mxe_kernel_svd_legendre``); see TauKernel._device_svd"""
-        from . import device
-        r = device.kernel_svd_legendre(self.l, np.asarray(self.omega, dtype=float), self.omega.delta, float(self.beta),
-                                       [preblur_b], threshold=0.0)[0]
-        return r['U'], r['S'], r['V']
+    @classmethod
+    def _checked_args(cls, grid, beta=None):
+        cls._checked_beta(beta)
+        return cls._checked_l(grid)
 
-    def _device_args(self):
-        return self.l, np.asarray(self.omega, dtype=float), self.omega.delta, float(self.beta)
+    def _device_entry(self, preblur_b=0.0):
+        return 'mxe_kernel_svd_legendre', self.l, (float(self.beta),), len(self.l)
 
     @staticmethod
     def _scaled_bessel(l_max, a):
@@ -783,25 +783,16 @@ class LegendreKernel(Kernel):
         sign = np.where((l[:, np.newaxis] % 2 == 1) & (w[np.newaxis, :] > 0.0), -1.0, 1.0)
         return sign * (c[:, np.newaxis] * s / (1.0 + np.exp(-2.0 * a))[np.newaxis, :])
 
-    def _fill_values(self):
-        self._invalidate_svd()
+    def _inputs(self, w):
         l = self._checked_l(self.l)
-        w = np.asarray(self.omega, dtype=float)
         beta = float(self.beta)
-        delta = np.asarray(self.omega.delta, dtype=float)
         if not np.all(beta * np.abs(w) / 2.0 <= LEGENDRE_A_MAX):                # (also a NaN)
             raise ValueError('LegendreKernel: beta |omega| / 2 must not exceed %g' % LEGENDRE_A_MAX)
-        key = ('legendre', l.tobytes(), w.tobytes(), delta.tobytes(), beta)
-        hit = _recent_fill.get(key, lambda _: True)               # (the key IS the contents)
-        if hit is None:
-            with np.errstate(under='ignore'):
-                K = self._values(l, w, beta)
-            hit = (_frozen(K), _frozen(K * delta[np.newaxis, :]))
-            _recent_fill.put(key, None, hit)
-        self._K, self._K_delta = hit
-        T = self._T
-        self._T = None
-        self.transform(T)
+        return l, beta
+
+    def _compute(self, w, l, beta):
+        with np.errstate(under='ignore'):
+            return self._values(l, w, beta)
 
     @property
     def data_variable(self):
@@ -810,10 +801,6 @@ class LegendreKernel(Kernel):
     @data_variable.setter
     def data_variable(self, value):
         self.l = self._checked_l(value)
-
-
-#: the kernels a PreblurKernel can hand to the device: each has ``_device_svd(preblur_b)``
-_DEVICE_KERNELS = (TauKernel, IOmegaKernel, BosonicTauKernel, BosonicIOmegaKernel, LegendreKernel, DataKernel)
 
 
 class PreblurKernel(Kernel):
@@ -835,7 +822,7 @@ class PreblurKernel(Kernel):
         return self.kernel.unfold(x)
 
     def _device_svd(self):
-        if not isinstance(self.kernel, _DEVICE_KERNELS):
+        if not getattr(self.kernel, 'has_device_entry', False):
             raise NotImplementedError('device SVD of a PreblurKernel needs a kernel of this module inside')
         U, S, V = self.kernel._device_svd(preblur_b=self._b)
         T = self.kernel._T
@@ -847,15 +834,11 @@ class PreblurKernel(Kernel):
         their truncated SVDs from ONE batched device launch (``mxe_kernel_svd``, ``mxe_kernel_svd_boson``
         for a BosonicTauKernel, ``mxe_kernel_svd_legendre`` for a LegendreKernel)."""
         from . import device
-        if not isinstance(K, (TauKernel, BosonicTauKernel, LegendreKernel)) or K._T is not None:
+        if not getattr(K, 'scannable', False) or K._T is not None:
             raise NotImplementedError('PreblurKernel.scan needs an unrotated TauKernel, BosonicTauKernel or LegendreKernel')
-        tau, w, delta, beta = K._device_args()
-        if isinstance(K, LegendreKernel):
-            res = device.kernel_svd_legendre(tau, w, delta, beta, list(b_values), threshold=threshold)
-        elif isinstance(K, BosonicTauKernel):
-            res = device.kernel_svd_boson(tau, w, delta, beta, K.symmetric, list(b_values), threshold=threshold)
-        else:
-            res = device.kernel_svd(tau, w, delta, beta, list(b_values), threshold=threshold)
+        name, grid, scalars, n_rows = K._device_entry()
+        res = device._kernel_svd(name, grid, scalars, np.asarray(K.omega, dtype=float), K.omega.delta,
+                                 list(b_values), threshold=threshold, n_rows=n_rows)
         out = []
         for b, r in zip(b_values, res):
             Kb = cls(K, b, svd_backend='device')

@@ -309,12 +309,12 @@ def _element_output(got, le, picks, spec, delta, B, method, n_win, n_fun, pointw
 
 def _stacked_single(tm, bins):
     """``bins`` as the real (n_bins, n_data) sets ``set_G_tau_bins`` / ``set_G_iw_bins`` send down"""
-    from . import kernels
     b = np.asarray(bins)
     if b.ndim != 2:
         raise ValueError('resample_errors: bins must be (n_bins, n_points); their shape is {}'.format(b.shape))
-    if isinstance(tm._inner_kernel(), kernels.IOmegaKernel):
-        return np.ascontiguousarray(kernels.IOmegaKernel.unfold(None, b), dtype=float)
+    if getattr(tm._inner_kernel(), 'kind', None) == 'iomega':           # (set_G_iw_bins: the only complex bins there are)
+        from .kernels import stack_complex
+        return np.ascontiguousarray(stack_complex(b), dtype=float)
     if np.iscomplexobj(b):
         raise ValueError('resample_errors: G(tau) bins must be real')
     return np.ascontiguousarray(b, dtype=float)

@@ -94,74 +94,41 @@ class TauMaxEnt(object):
         K = self.K
         return getattr(K, 'kernel', K)
 
-    def _iomega_kernel(self):
-        """the IOmegaKernel of a Matsubara problem (also inside a PreblurKernel), else None"""
-        K = self._inner_kernel()
-        return K if isinstance(K, kernels.IOmegaKernel) else None
-
     def _stacked_kernel(self):
-        """the kernel whose rows are ``[Re K ; Im K]`` -- an IOmegaKernel, or a BosonicIOmegaKernel that is not
-        symmetric -- (also inside a PreblurKernel), else None"""
+        """the kernel whose rows are ``[Re K ; Im K]`` (also inside a PreblurKernel), else None"""
         K = self._inner_kernel()
-        if isinstance(K, kernels.IOmegaKernel) or (isinstance(K, kernels.BosonicIOmegaKernel) and K.stacked):
-            return K
-        return None
+        return K if getattr(K, 'stacked', False) else None
 
-    def _use_tau_kernel(self, tau):
-        """after Matsubara, bosonic or Legendre data: a TauKernel on ``tau`` again (same omega mesh and SVD backend)"""
-        if isinstance(self._inner_kernel(), (kernels.IOmegaKernel, kernels.BosonicTauKernel,
-                                             kernels.BosonicIOmegaKernel, kernels.LegendreKernel)):
-            self.K = kernels.TauKernel(np.asarray(tau, dtype=float), self.omega, svd_backend=self.K.svd_backend)
-
-    def _use_bosonic_kernel(self, cls, grid, beta, symmetric):
-        """a bosonic kernel of class ``cls`` on ``grid`` (same omega mesh and SVD backend); one of the same class and
-        symmetry that is there already -- also inside a PreblurKernel -- is refilled only when grid or beta change"""
+    def _use_kernel(self, cls, grid, assign_grid=True, **params):
+        """A kernel of class ``cls`` on ``grid`` with the constructor arguments ``params`` (same omega mesh and SVD
+        backend).  The kernel that is there -- also inside a PreblurKernel -- stays if its ``setter_kind`` is the wanted
+        ``kind`` and it is equal in ``cls.kind_params``: it is refilled, once, only when the grid changes or a ``beta``
+        that enters its matrix (``beta_in_matrix``; other kernels just remember theirs).  ``assign_grid=False`` leaves the grid of a
+        kernel that stays to the caller.  Arguments are validated before anything is changed."""
+        grid = cls._checked_args(grid, **params)
         K = self._inner_kernel()
-        if type(K) is cls and K.symmetric == bool(symmetric):
-            if cls is kernels.BosonicTauKernel and K.beta != beta:
-                K.beta = beta
-                self.K.parameter_change()
-                self.K = self.K
-            elif cls is kernels.BosonicIOmegaKernel:
-                K.beta = beta
-            self.tau = grid
-        else:
-            self.K = cls(np.array(grid, dtype=float), self.omega, beta=beta, symmetric=symmetric,
-                         svd_backend=self.K.svd_backend)
-
-    def _use_legendre_kernel(self, l, beta):
-        """a LegendreKernel on the orders ``l`` (same omega mesh and SVD backend); one that is there already -- also
-        inside a PreblurKernel -- is refilled only when ``l`` or ``beta`` change"""
-        K = self._inner_kernel()
-        l = kernels.LegendreKernel._checked_l(l)
-        kernels.LegendreKernel._checked_beta(beta)          # (before anything is changed)
-        if isinstance(K, kernels.LegendreKernel):
-            if K.beta != beta:
-                K.beta = beta
-                if np.array_equal(K.l, l):
-                    self.K.parameter_change()
-                    self.K = self.K
-            self.tau = l
-        else:
-            self.K = kernels.LegendreKernel(l, self.omega, beta=beta, svd_backend=self.K.svd_backend)
-
-    def _use_iomega_kernel(self, iomega, beta=None):
-        """an IOmegaKernel on ``iomega`` (same omega mesh and SVD backend); one that is there already -- also inside
-        a PreblurKernel -- is refilled only when the grid changes"""
-        K = self._iomega_kernel()
-        if K is not None:
-            self.tau = iomega
-            K.beta = beta
-        else:
-            self.K = kernels.IOmegaKernel(np.array(iomega, dtype=float), self.omega, beta=beta,
-                                          svd_backend=self.K.svd_backend)
+        keep = getattr(K, 'setter_kind', 'tau') == cls.kind
+        for p in cls.kind_params:
+            keep = keep and getattr(K, p) == params[p]
+        if not keep:
+            self.K = cls(np.array(grid, dtype=float), self.omega, svd_backend=self.K.svd_backend, **params)
+            return
+        refill = False
+        if 'beta' in params and (not cls.beta_in_matrix or K.beta != params['beta']):
+            K.beta = params['beta']
+            refill = cls.beta_in_matrix
+        if assign_grid and self.set_tau(grid):    # (a new grid refills)
+            return
+        if refill:
+            self.K.parameter_change()
+            self.K = self.K
 
     def set_G_tau_data(self, tau, G_tau):
         """G(tau) from arrays (reference tau_maxent.py:181-196)"""
         if len(tau) != len(G_tau):
             raise AssertionError("tau and G_tau don't have the same dimension")
-        self._use_tau_kernel(tau)
-        self.tau, self.G = tau, G_tau
+        self._use_kernel(kernels.TauKernel, tau)
+        self.G = G_tau
         self._adopt_data()
 
     def set_G_iw_data(self, iomega, G_iw, beta=None):
@@ -175,7 +142,7 @@ class TauMaxEnt(object):
         G_iw = np.asarray(G_iw)
         if iomega.ndim != 1 or G_iw.shape != iomega.shape:
             raise AssertionError("iomega and G_iw don't have the same dimension")
-        self._use_iomega_kernel(iomega, beta)
+        self._use_kernel(kernels.IOmegaKernel, iomega, beta=beta)
         self.G = self.K.unfold(G_iw)
         self._adopt_data()
 
@@ -189,7 +156,7 @@ class TauMaxEnt(object):
             raise AssertionError("tau and chi don't have the same dimension")
         if np.iscomplexobj(chi):
             raise AssertionError('chi(tau) must be real')
-        self._use_bosonic_kernel(kernels.BosonicTauKernel, tau, beta, symmetric)
+        self._use_kernel(kernels.BosonicTauKernel, tau, beta=beta, symmetric=bool(symmetric))
         self.G = np.asarray(chi, dtype=float)
         self._adopt_data()
 
@@ -204,7 +171,7 @@ class TauMaxEnt(object):
         chi_iw = np.asarray(chi_iw)
         if inu.ndim != 1 or chi_iw.shape != inu.shape:
             raise AssertionError("inu and chi_iw don't have the same dimension")
-        self._use_bosonic_kernel(kernels.BosonicIOmegaKernel, inu, beta, symmetric)
+        self._use_kernel(kernels.BosonicIOmegaKernel, inu, beta=beta, symmetric=bool(symmetric))
         self.G = np.asarray(self._inner_kernel().unfold(chi_iw), dtype=float)
         self._adopt_data()
 
@@ -226,7 +193,7 @@ class TauMaxEnt(object):
             raise AssertionError('G_l must be one-dimensional')
         if np.iscomplexobj(G_l):
             raise AssertionError('G_l must be real')
-        self._use_legendre_kernel(self._legendre_orders(l, len(G_l)), beta)
+        self._use_kernel(kernels.LegendreKernel, self._legendre_orders(l, len(G_l)), beta=beta)
         self.G = np.asarray(G_l, dtype=float)
         self._adopt_data()
 
@@ -234,8 +201,8 @@ class TauMaxEnt(object):
         """G(tau), optionally with its error bar, from the columns of a text file
         (reference tau_maxent.py:198-225); a file that brings errors ends any rotation"""
         table = np.loadtxt(filename)
-        self._use_tau_kernel(table[:, tau_col])
-        self.tau, self.G = table[:, tau_col], table[:, G_col]
+        self._use_kernel(kernels.TauKernel, table[:, tau_col])
+        self.G = table[:, G_col]
         if err_col is not None:
             self.err = table[:, err_col]
         self._adopt_data(keep_rotation=err_col is None)
@@ -373,8 +340,7 @@ class TauMaxEnt(object):
         if np.iscomplexobj(bins):
             raise AssertionError('G(tau) bins must be real')
         st = self._bins_eig(np.asarray(bins, dtype=float))
-        self._use_tau_kernel(tau)
-        self.tau = tau
+        self._use_kernel(kernels.TauKernel, tau)
         self._adopt_bins(st)
 
     def set_G_iw_bins(self, iomega, bins, beta=None):
@@ -385,8 +351,8 @@ class TauMaxEnt(object):
         bins = self._check_bins(iomega, bins, 'G(i omega_n) bins', per_point=2)
         if bins.ndim != 2:
             raise AssertionError('G(i omega_n) bins must be (n_bins, n_iw); their shape is {}'.format(bins.shape))
-        st = self._bins_eig(kernels.IOmegaKernel.unfold(None, bins))       # (every bin as [Re ; Im]; needs no kernel object)
-        self._use_iomega_kernel(iomega, beta)
+        st = self._bins_eig(kernels.stack_complex(bins))                   # (every bin as [Re ; Im])
+        self._use_kernel(kernels.IOmegaKernel, iomega, beta=beta)
         self._adopt_bins(st)
 
     def set_G_l_bins(self, bins, beta, l=None):
@@ -401,7 +367,7 @@ class TauMaxEnt(object):
         if np.iscomplexobj(bins):
             raise AssertionError('G_l bins must be real')
         st = self._bins_eig(np.asarray(bins, dtype=float))
-        self._use_legendre_kernel(l, beta)
+        self._use_kernel(kernels.LegendreKernel, l, beta=beta)
         self._adopt_bins(st)
 
     # ---- error bars ------------------------------------------------------------
@@ -507,16 +473,17 @@ class TauMaxEnt(object):
         """a new tau grid refills the kernel (and drops its SVD); setting the
         grid it already has is free -- this is what lets the element-wise
         driver reuse one SVD for all matrix elements, where the reference
-        recomputes it per element."""
+        recomputes it per element.  Returns whether the grid was new."""
         old = self.maxent_loop.get_data_variable()
         same = old is not None and np.shape(old) == np.shape(tau) and \
             np.array_equal(np.asarray(old), np.asarray(tau))
         if same:
-            return
+            return False
         self.maxent_loop.set_data_variable(tau, update_K=update_K,
                                            update_chi2=update_chi2,
                                            update_Q=update_Q,
                                            update_H_of_v=update_H_of_v)
+        return True
 
     tau = property(get_tau, set_tau)
 
