@@ -48,6 +48,8 @@
  *                                                          |   integrated quantities, diagonal of the covariance)
  *   (nothing: the reference draws no spectra)              | mxe_posterior_sample (draws of H from the same
  *                                                          |   Gaussian posterior), mxe_normals (its generator)
+ *   (nothing: the reference gives no fit diagnostics)      | mxe_fit_diagnostics (leverages, number of good
+ *                                                          |   data, whitened residuals of a fit)
  *   (nothing: users loop run() over their resamples)       | mxe_bins_resample (the rotated data of every
  *                                                          |   jackknife / bootstrap resample of the bins),
  *                                                          |   mxe_resample_reduce (mean, spread and functional
@@ -412,6 +414,30 @@ int  mxe_posterior_sample(mxe_ctx* ctx, int P, const int32_t* elem_of_problem, c
                           const double* H, const int32_t* problem_index, double chi2_factor,
                           int n_samples, uint64_t seed, const uint64_t* stream, const double* z,
                           double* out_dH, float* out_ms);
+/* Diagnostics of a fit from its hat matrix, the derivative of the fitted whitened data Sigma^-1/2 K H with respect to
+ * the whitened data Sigma^-1/2 G (exact at the minimiser).  Replaces nothing of the reference.  In the notation above
+ * (w, V', c, a = alpha~ / eta, B = c W c + a I = L L^T) and with Sigma^-1/2 K = U^ c V'^T, g^ = U^^T G~, G~ = Sigma^-1/2 G:
+ *   Hat             = U^ (I - a B^-1) U^^T
+ *   out_lev[p][i]   = h_i = |U^_i|^2 - a |L^-1 U^_i^T|^2                  (leverage of data point i, 0 <= h_i <= |U^_i|^2)
+ *   out_ngood[p]    = N_g = sum_i h_i = sum_k lambda_k / (lambda_k + a)   (number of good data; lambda: eigenvalues of c W c)
+ *   out_resid[p][i] = r_i = sum_k U^_ik rho_k - rperp_i = [Sigma^-1/2 (K H - G)]_i,
+ *                     rho = c o V'^T H - g^,  rperp = G~ - U^ g^          (the part of the data outside the singular space)
+ *   out_chi2[p]     = sum_i r_i^2 = |rho|^2 + c_perp                      (the chi2 of the solver)
+ * The rows i are those of the problem's data set (tau points, the 2 n_iw stacked real Matsubara values, the kept
+ * eigen-directions of a covariance).  out_resid and out_lev are [P][ld] with ld at least the largest row count among the
+ * data sets of the problems named (else MXE_ERR_ARG); entries behind a data set's rows are written as 0.
+ * elem_of_problem, alpha_scaled, H, problem_index and chi2_factor as in mxe_posterior_var (also the rows of the last launch
+ * with H == NULL, and MXE_ERR_STATE); only a = alpha~ / chi2_factor enters.  Every output pointer may be NULL.  The
+ * leverage is formed as written, never through B^-1; a difference that rounding makes negative is returned as 0 (a NaN
+ * stays a NaN).  A problem whose H row is not finite or whose B is not positive definite gets NaN in all its outputs,
+ * the others are not touched by it and the call returns MXE_OK.  No atomics, fixed summation order (N_g and chi2 are added
+ * in index order): the bits of a problem do not depend on the other problems of the call.  U^ of the data sets and rperp
+ * of the elements go to the device at the first call and after any change of data sets or elements
+ * (mxe_elements_update_data keeps rperp current).  MXE_ERR_LIMIT as mxe_posterior_var.  out_ms: device time of the kernel
+ * (may be NULL). */
+int  mxe_fit_diagnostics(mxe_ctx* ctx, int P, const int32_t* elem_of_problem, const double* alpha_scaled,
+                         const double* H, const int32_t* problem_index, double chi2_factor, int ld,
+                         double* out_ngood, double* out_chi2, double* out_resid, double* out_lev, float* out_ms);
 /* The standard normals of mxe_posterior_sample, out_z [n_samples][n] (host), by the same device function.  Philox4x32-10
  * (Salmon et al. 2011; multipliers 0xD2511F53, 0xCD9E8D57, Weyl constants 0x9E3779B9, 0xBB67AE85) with the key (seed low,
  * seed high) and the counter (j, s, stream low, stream high): s the sample, j the pair of normals.  From the output

@@ -280,6 +280,14 @@ struct mxe_ctx {
     DevBuf<double> dproj_U, dproj_err, dproj_G;
     DevBuf<long long> dproj_off;                 // [n_ds][3]: offset of Uhat, offset of err, rows
     bool proj_ready = false;
+    // mxe_fit_diagnostics: rperp = G~ - Uhat ghat of every element, [rows of its data set] at elem_roff[e].  The host copy is
+    // written wherever ghat is projected on the host, the device copy by project_kernel; rperp_dirty: the host copy is the
+    // newer one and goes up at the next diagnostics call.  roff_ready: drperp is sized and delem_roff holds elem_roff.
+    std::vector<double> h_rperp;
+    std::vector<long long> elem_roff;
+    DevBuf<double> drperp;
+    DevBuf<long long> delem_roff;
+    bool rperp_dirty = false, roff_ready = false;
     DevBuf<double> dV, dVx, dVt, dc, dcinv, dghat, dcperp, dD, dsumD, dalpha, dv0;
     DevBuf<int> delem_ds, delem_kind, dchain_elem, dsub_prob0, dsub_len, dsub_v0, dwg_chains;
     // H, chi2, S, Q live back to back in ONE allocation (dout_pack) so that a
@@ -413,7 +421,10 @@ int build_dataset(mxe_ctx* ctx, int n_rows, const double* U_rot, const double* e
             const int k = order[kk];
             d.c[kk] = nrm[k];
             for (int i = 0; i < ns; ++i) d.Q[(size_t)i * ns + kk] = Q[(size_t)i * ns + k];
-            if (nrm[k] > 0.0)
+            // (C has rank <= n_rows: with fewer rows than singular directions the columns behind the n_rows largest are
+            //  null, their norms rounding residue of the sweeps -- normalised they would be unit vectors of noise that are
+            //  not orthogonal to the others, and ghat, c_perp and the chi2 reported with them wrong by a constant)
+            if (nrm[k] > 0.0 && kk < n_rows)
                 for (int i = 0; i < n_rows; ++i)
                     d.Uhat[(size_t)i * ns + kk] = C[(size_t)i * ns + k] / nrm[k];
         }
@@ -613,6 +624,7 @@ void mxe_ctx_destroy(mxe_ctx* ctx)
     comm_release(ctx);
     if (ctx->h_sel3_pinned) { (void)hipHostFree(ctx->h_sel3_pinned); ctx->h_sel3_pinned = nullptr; ctx->h_sel3_pinned_n = 0; }
     ctx->dproj_U.release(); ctx->dproj_err.release(); ctx->dproj_G.release(); ctx->dproj_off.release();
+    ctx->drperp.release(); ctx->delem_roff.release();
     ctx->dVx.release(); ctx->dsel3.release(); ctx->dgstate.release(); ctx->dgstate_mc.release(); ctx->dfin_elem.release(); ctx->dfin_prob0.release();
     ctx->dfin_len.release(); ctx->dfin_v0.release(); ctx->dfin_start.release();
     ctx->dfin_budget.release(); ctx->dfin_out.release(); ctx->dfin_alpha.release();
@@ -663,8 +675,9 @@ namespace {
 // (DESIGN.md section 2).  Both along the rows of Uhat (unit stride); the residual is formed term by term (a sum of squares: no
 // cancellation).  A batch of 256 elements is 5.7 M multiply-adds: on one host core 0.5-0.9 ms -- more than the kernel that solves
 // them takes --, so batches are cut over a handful of threads (the arithmetic of an element does not depend on the cut).
+// The residual itself, rperp, is kept for mxe_fit_diagnostics: hrperp + roff[e].
 void project_elements(const mxe_ctx* ctx, int e0, int e1, const int32_t* dataset_of_elem, const double* G, const int64_t* G_offset,
-                      double* hghat, double* hcperp)
+                      double* hghat, double* hcperp, double* hrperp, const long long* roff)
 {
     const int ns = ctx->n_s, NP = ctx->NP;
     std::vector<double> Gt;
@@ -684,6 +697,7 @@ void project_elements(const mxe_ctx* ctx, int e0, int e1, const int32_t* dataset
             const double* ui = DS.Uhat.data() + (size_t)i * ns;
             double r = Gt[i];
             for (int k = 0; k < ns; ++k) r -= ui[k] * gh[k];
+            hrperp[roff[e] + i] = r;
             cp += r * r;
         }
         hcperp[e] = cp;
@@ -691,15 +705,15 @@ void project_elements(const mxe_ctx* ctx, int e0, int e1, const int32_t* dataset
 }
 
 void project_all(const mxe_ctx* ctx, int n_elem, const int32_t* dataset_of_elem, const double* G, const int64_t* G_offset,
-                 double* hghat, double* hcperp)
+                 double* hghat, double* hcperp, double* hrperp, const long long* roff)
 {
     int nt = (int)std::min<unsigned>(8u, std::max(1u, std::thread::hardware_concurrency()));
     nt = std::min(nt, n_elem / 32);
-    if (nt <= 1) { project_elements(ctx, 0, n_elem, dataset_of_elem, G, G_offset, hghat, hcperp); return; }
+    if (nt <= 1) { project_elements(ctx, 0, n_elem, dataset_of_elem, G, G_offset, hghat, hcperp, hrperp, roff); return; }
     std::vector<std::thread> pool;
     for (int t = 0; t < nt; ++t) {
         const int e0 = (int)((long long)n_elem * t / nt), e1 = (int)((long long)n_elem * (t + 1) / nt);
-        pool.emplace_back(project_elements, ctx, e0, e1, dataset_of_elem, G, G_offset, hghat, hcperp);
+        pool.emplace_back(project_elements, ctx, e0, e1, dataset_of_elem, G, G_offset, hghat, hcperp, hrperp, roff);
     }
     for (auto& th : pool) th.join();
 }
@@ -724,7 +738,12 @@ try {
         hsumD[e] = (entropy[e] == MXE_ENTROPY_PLUSMINUS) ? 2.0 * sd : sd;
         ctx->elem_ds[e] = d; ctx->elem_kind[e] = entropy[e];
     }
-    project_all(ctx, n_elem, dataset_of_elem, G, G_offset, hghat.data(), hcperp.data());
+    ctx->elem_roff.assign(n_elem, 0);
+    long long total_rows = 0;
+    for (int e = 0; e < n_elem; ++e) { ctx->elem_roff[e] = total_rows; total_rows += ctx->ds[dataset_of_elem[e]].n_rows; }
+    ctx->h_rperp.assign((size_t)total_rows, 0.0);
+    ctx->rperp_dirty = true; ctx->roff_ready = false;
+    project_all(ctx, n_elem, dataset_of_elem, G, G_offset, hghat.data(), hcperp.data(), ctx->h_rperp.data(), ctx->elem_roff.data());
     ctx->n_elem = n_elem;
     ctx->h_sumD = hsumD;
     ctx->h_D = hD;
@@ -756,7 +775,8 @@ namespace {
 __global__ __launch_bounds__(256)
 void project_kernel(const double* __restrict__ G, const int* __restrict__ elem_ds, const long long* __restrict__ ds_off,
                     const double* __restrict__ U, const double* __restrict__ err, int ns, int NP,
-                    double* __restrict__ ghat, double* __restrict__ cperp, int rows_max, const long long* __restrict__ G_off)
+                    double* __restrict__ ghat, double* __restrict__ cperp, int rows_max, const long long* __restrict__ G_off,
+                    double* __restrict__ rperp, const long long* __restrict__ roff)
 {
     extern __shared__ double psh[];
     double* Gt = psh; double* gh = psh + rows_max; double* r2 = gh + NP;
@@ -776,6 +796,7 @@ void project_kernel(const double* __restrict__ G, const int* __restrict__ elem_d
     for (int i = tid; i < rows; i += 256) {
         double r = Gt[i];
         for (int k = 0; k < ns; ++k) { const double pr = Ud[(size_t)i * ns + k] * gh[k]; r = r - pr; }
+        rperp[roff[e] + i] = r;
         r2[i] = r * r;
     }
     __syncthreads();
@@ -786,6 +807,39 @@ void project_kernel(const double* __restrict__ G, const int* __restrict__ elem_d
     }
 }
 #pragma clang fp contract(fast)
+
+// Uhat | err of every data set on the device (project_kernel, fitdiag_kernel), built again after a change of data sets
+int upload_projection(mxe_ctx* ctx)
+{
+    if (ctx->proj_ready) return MXE_OK;
+    std::vector<double> hU, herr; std::vector<long long> off;
+    for (const DataSet& D : ctx->ds) {
+        off.push_back((long long)hU.size()); off.push_back((long long)herr.size()); off.push_back(D.n_rows);
+        hU.insert(hU.end(), D.Uhat.begin(), D.Uhat.end());
+        herr.insert(herr.end(), D.err.begin(), D.err.end());
+    }
+    HIPCHK(ctx, ctx->dproj_U.ensure(hU.size()));
+    HIPCHK(ctx, ctx->dproj_err.ensure(herr.size()));
+    HIPCHK(ctx, ctx->dproj_off.ensure(off.size()));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->dproj_U.p, hU.data(), hU.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->dproj_err.p, herr.data(), herr.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->dproj_off.p, off.data(), off.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, stream_wait(ctx->stream));
+    ctx->proj_ready = true;
+    return MXE_OK;
+}
+
+// room for rperp of the elements that are set, and where each element's rows begin (after mxe_elements_set)
+int upload_row_offsets(mxe_ctx* ctx)
+{
+    if (ctx->roff_ready) return MXE_OK;
+    HIPCHK(ctx, ctx->drperp.ensure(ctx->h_rperp.size()));
+    HIPCHK(ctx, ctx->delem_roff.ensure(ctx->elem_roff.size()));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->delem_roff.p, ctx->elem_roff.data(), ctx->elem_roff.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, stream_wait(ctx->stream));
+    ctx->roff_ready = true;
+    return MXE_OK;
+}
 }
 
 int mxe_elements_update_data(mxe_ctx* ctx, int n_elem, const double* G, const int64_t* G_offset)
@@ -809,22 +863,10 @@ try {
     for (int e = 0; e < n_elem; ++e) total_rows += ctx->ds[ctx->elem_ds[e]].n_rows;
     const size_t lds = ((size_t)2 * rows_max + NP) * 8;
     if (span && (size_t)(hi - lo) <= 2 * total_rows && lds <= 64 * 1024 && !getenv("MXE_HOST_PROJECTION")) {
-        if (!ctx->proj_ready) {
-            std::vector<double> hU, herr; std::vector<long long> off;
-            for (const DataSet& D : ctx->ds) {
-                off.push_back((long long)hU.size()); off.push_back((long long)herr.size()); off.push_back(D.n_rows);
-                hU.insert(hU.end(), D.Uhat.begin(), D.Uhat.end());
-                herr.insert(herr.end(), D.err.begin(), D.err.end());
-            }
-            HIPCHK(ctx, ctx->dproj_U.ensure(hU.size()));
-            HIPCHK(ctx, ctx->dproj_err.ensure(herr.size()));
-            HIPCHK(ctx, ctx->dproj_off.ensure(off.size()));
-            HIPCHK(ctx, hipMemcpyAsync(ctx->dproj_U.p, hU.data(), hU.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-            HIPCHK(ctx, hipMemcpyAsync(ctx->dproj_err.p, herr.data(), herr.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-            HIPCHK(ctx, hipMemcpyAsync(ctx->dproj_off.p, off.data(), off.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-            HIPCHK(ctx, stream_wait(ctx->stream));
-            ctx->proj_ready = true;
-        }
+        int rc = upload_projection(ctx);
+        if (rc != MXE_OK) return rc;
+        rc = upload_row_offsets(ctx);
+        if (rc != MXE_OK) return rc;
         std::vector<long long> goff(n_elem);
         for (int e = 0; e < n_elem; ++e) goff[e] = G_offset[e] - lo;
         HIPCHK(ctx, ctx->dproj_G.ensure((size_t)(hi - lo) + (size_t)n_elem));
@@ -833,13 +875,17 @@ try {
         HIPCHK(ctx, hipMemcpyAsync(ctx->dproj_G.p, G + lo, (size_t)(hi - lo) * 8, hipMemcpyHostToDevice, ctx->stream));
         HIPCHK(ctx, hipMemcpyAsync(dgoff, goff.data(), (size_t)n_elem * 8, hipMemcpyHostToDevice, ctx->stream));
         hipLaunchKernelGGL(project_kernel, dim3(n_elem), dim3(256), lds, ctx->stream, ctx->dproj_G.p, ctx->delem_ds.p, ctx->dproj_off.p,
-                           ctx->dproj_U.p, ctx->dproj_err.p, ns, NP, ctx->dghat.p, ctx->dcperp.p, rows_max, dgoff);
+                           ctx->dproj_U.p, ctx->dproj_err.p, ns, NP, ctx->dghat.p, ctx->dcperp.p, rows_max, dgoff,
+                           ctx->drperp.p, ctx->delem_roff.p);
         HIPCHK(ctx, hipGetLastError());
+        ctx->rperp_dirty = false;                    // (the device copy of rperp is the one that holds)
         HIPCHK(ctx, stream_wait(ctx->stream));       // (goff is the caller-side vector of this call; G the caller's array)
         return MXE_OK;
     }
     std::vector<double> hghat((size_t)n_elem * NP, 0.0), hcperp(n_elem);
-    project_all(ctx, n_elem, ctx->elem_ds.data(), G, G_offset, hghat.data(), hcperp.data());    // (as mxe_elements_set: the same bits)
+    project_all(ctx, n_elem, ctx->elem_ds.data(), G, G_offset, hghat.data(), hcperp.data(), ctx->h_rperp.data(),
+                ctx->elem_roff.data());                                                     // (as mxe_elements_set: the same bits)
+    ctx->rperp_dirty = true;
     // (behind whatever the stream still runs with the old data)
     HIPCHK(ctx, hipMemcpyAsync(ctx->dghat.p, hghat.data(), hghat.size() * 8, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(ctx->dcperp.p, hcperp.data(), (size_t)n_elem * 8, hipMemcpyHostToDevice, ctx->stream));
@@ -2771,6 +2817,62 @@ try {
     HIPCHK(ctx, launch_factor_kernel(mxe::postsample_kernel<4>, mxe::postsample_kernel<8>, ctx, (size_t)P, st.lds, pp));
     if (out_ms) HIPCHK(ctx, hipEventRecord(sc.e1, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(out_dH, d + oO, n_out * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, stream_wait(ctx->stream));
+    if (out_ms) HIPCHK(ctx, hipEventElapsedTime(out_ms, sc.e0, sc.e1));
+    return MXE_OK;
+}
+MXE_CATCH_ALL
+
+// ---- diagnostics of a fit: leverages, number of good data, whitened residuals (mxe_fitdiag.hip.h) -----------------------
+#include "mxe_fitdiag.hip.h"
+
+extern "C" int mxe_fit_diagnostics(mxe_ctx* ctx, int P, const int32_t* elem_of_problem, const double* alpha_scaled,
+                                   const double* H, const int32_t* problem_index, double chi2_factor, int ld,
+                                   double* out_ngood, double* out_chi2, double* out_resid, double* out_lev, float* out_ms)
+try {
+    if (!ctx || P < 1 || !elem_of_problem || !alpha_scaled || ld < 1) return MXE_ERR_ARG;
+    const int nw = ctx->n_omega;
+    PostStage st;
+    // n_max bounds what the kernel's callers index: residuals / leverages [P][ld] and the H rows [P][nw]
+    int rc = stage_posterior(ctx, P, elem_of_problem, alpha_scaled, H, problem_index, chi2_factor,
+                             std::max((size_t)P * (size_t)ld, (size_t)P * nw), nullptr, 0, st);
+    if (rc != MXE_OK) return rc;
+    for (int p = 0; p < P; ++p)
+        if (ctx->ds[ctx->elem_ds[elem_of_problem[p]]].n_rows > ld) return MXE_ERR_ARG;
+    // Uhat of the data sets and rperp of the elements: at the first call and after any change of either
+    rc = upload_projection(ctx);
+    if (rc != MXE_OK) return rc;
+    rc = upload_row_offsets(ctx);
+    if (rc != MXE_OK) return rc;
+    if (ctx->rperp_dirty) {
+        HIPCHK(ctx, hipMemcpyAsync(ctx->drperp.p, ctx->h_rperp.data(), ctx->h_rperp.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, stream_wait(ctx->stream));
+        ctx->rperp_dirty = false;
+    }
+    // one block of doubles: alpha [P] | H [P][nw] (when handed in) | N_g [P] | chi2 [P] | residuals [P][ld] | leverages [P][ld]
+    const size_t oH = (size_t)P, oN = oH + (H ? (size_t)P * nw : 0), oC = oN + (size_t)P, oR = oC + (size_t)P,
+                 oL = oR + (size_t)P * ld, total = oL + (size_t)P * ld;
+    HIPCHK(ctx, ctx->pv_d.ensure(total));
+    double* d = ctx->pv_d.p;
+    mxe::FitDiagParams pp;
+    rc = upload_posterior(ctx, st, P, H, d, oH, pp);
+    if (rc != MXE_OK) return rc;
+    pp.ghat = ctx->dghat.p; pp.U = ctx->dproj_U.p; pp.ds_off = ctx->dproj_off.p;
+    pp.rperp = ctx->drperp.p; pp.elem_roff = ctx->delem_roff.p;
+    pp.out_ngood = d + oN; pp.out_chi2 = d + oC; pp.out_resid = d + oR; pp.out_lev = d + oL;
+    pp.ld = ld;
+    const size_t lds = mxe::fitdiag_lds_bytes(ctx->NP, ctx->nwp);      // (below postvar_kernel's, which stage_posterior checked)
+    SvdScratch sc;                    // (the two events of the timing, released on every path)
+    if (out_ms) {
+        HIPCHK(ctx, hipEventCreate(&sc.e0)); HIPCHK(ctx, hipEventCreate(&sc.e1));
+        HIPCHK(ctx, hipEventRecord(sc.e0, ctx->stream));
+    }
+    HIPCHK(ctx, launch_factor_kernel(mxe::fitdiag_kernel<4>, mxe::fitdiag_kernel<8>, ctx, (size_t)P, lds, pp));
+    if (out_ms) HIPCHK(ctx, hipEventRecord(sc.e1, ctx->stream));
+    if (out_ngood) HIPCHK(ctx, hipMemcpyAsync(out_ngood, d + oN, (size_t)P * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (out_chi2) HIPCHK(ctx, hipMemcpyAsync(out_chi2, d + oC, (size_t)P * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (out_resid) HIPCHK(ctx, hipMemcpyAsync(out_resid, d + oR, (size_t)P * ld * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (out_lev) HIPCHK(ctx, hipMemcpyAsync(out_lev, d + oL, (size_t)P * ld * 8, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, stream_wait(ctx->stream));
     if (out_ms) HIPCHK(ctx, hipEventElapsedTime(out_ms, sc.e0, sc.e1));
     return MXE_OK;

@@ -117,6 +117,8 @@ SYMBOLS = [
                                          ctypes.POINTER(ctypes.c_float)]),
     ('mxe_posterior_sample', ctypes.c_int, [_vp, ctypes.c_int, _ip, _dp, _dp, _ip, ctypes.c_double, ctypes.c_int, ctypes.c_uint64,
                                             ctypes.POINTER(ctypes.c_uint64), _dp, _dp, ctypes.POINTER(ctypes.c_float)]),
+    ('mxe_fit_diagnostics', ctypes.c_int, [_vp, ctypes.c_int, _ip, _dp, _dp, _ip, ctypes.c_double, ctypes.c_int, _dp, _dp, _dp, _dp,
+                                           ctypes.POINTER(ctypes.c_float)]),
     ('mxe_normals', ctypes.c_int, [ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int, ctypes.c_int, _dp]),
     ('mxe_entropy', ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, _dp, _dp]),
     ('mxe_audit', ctypes.c_int, [_vp, _dp, _dp]),
@@ -657,6 +659,7 @@ class DeviceContext(object):
         self._n_chain = 0
         self._n_alpha = 0
         self._ds_rows = []
+        self._elem_rows = np.zeros(0, dtype=np.int64)      # rows of the data set of every element that is set
 
     # -- plumbing ------------------------------------------------------
     def _check(self, rc, what):
@@ -717,6 +720,7 @@ class DeviceContext(object):
             self._check(self._lib.mxe_elements_set(self._h, n_elem, _p(ds), _p(G), _p(offs), _p(D), _p(ent)),
                         'mxe_elements_set')
             self.n_elem = n_elem
+            self._elem_rows = rows.astype(np.int64)
             return
         offs = np.zeros(n_elem, dtype=np.int64)
         chunks = []
@@ -737,6 +741,7 @@ class DeviceContext(object):
                                                _p(offs), _p(D), _p(ent)),
                     'mxe_elements_set')
         self.n_elem = n_elem
+        self._elem_rows = np.asarray(self._ds_rows, dtype=np.int64)[ds]
 
     def update_data(self, G):
         """``mxe_elements_update_data``: new data vectors (one row per element, all of one length) for the elements that
@@ -974,6 +979,31 @@ class DeviceContext(object):
         if timing is not None:
             timing['ms'] = float(ms.value)
         return out
+
+    def fit_diagnostics(self, elem_of_problem, alpha_scaled, H=None, problem_index=None, chi2_factor=1.0, ld=None,
+                        timing=None):
+        """``mxe_fit_diagnostics``: leverages, number of good data and whitened residuals of the fits, on the staged
+        elements.  ``H``, ``problem_index`` and ``chi2_factor`` as in :meth:`posterior_var`.  Returns a dict: ``n_good``
+        and ``chi2`` (P,), ``residual`` and ``leverage`` (P, ld) -- ``ld``: default the largest row count among the data
+        sets of the problems; entries behind a data set's rows are 0 --, and ``rows`` (P,), the row count of every
+        problem's data set.  A problem whose H row is not finite or whose curvature matrix is not positive definite has
+        NaN everywhere.  ``timing``: a dict that receives the device time ``ms`` of the kernel."""
+        el, P, al = self._posterior_problems('fit_diagnostics', elem_of_problem, alpha_scaled)
+        # (nothing launched: the library answers MXE_ERR_STATE)
+        H, pi = self._posterior_rows('fit_diagnostics', P, H, problem_index, unlaunched_ok=True)
+        if P and (el.min() < 0 or el.max() >= len(self._elem_rows)):
+            raise ValueError('fit_diagnostics: elements 0 .. %d are set' % (len(self._elem_rows) - 1))
+        rows = self._elem_rows[el]
+        ld = int(rows.max()) if ld is None else int(ld)
+        ngood, chi2 = np.empty(P), np.empty(P)
+        resid, lev = np.empty((P, max(ld, 0))), np.empty((P, max(ld, 0)))
+        ms = ctypes.c_float(0)
+        self._check(self._lib.mxe_fit_diagnostics(self._h, P, _p(el), _p(al), _p(H), _p(pi), float(chi2_factor), ld,
+                                                  _p(ngood), _p(chi2), _p(resid), _p(lev), ctypes.byref(ms)),
+                    'mxe_fit_diagnostics')
+        if timing is not None:
+            timing['ms'] = float(ms.value)
+        return dict(n_good=ngood, chi2=chi2, residual=resid, leverage=lev, rows=rows)
 
     def resample_reduce(self, group_offset, scale, H=None, problem_index=None, F=None, want=('mean', 'var', 'fval', 'fmean', 'fcov'),
                         timing=None):

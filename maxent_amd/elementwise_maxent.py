@@ -689,13 +689,16 @@ class ElementwiseMaxEnt(object):
         """default models of the off-diagonal jobs when they are not the worker's own (PoormanMaxEnt), else None"""
         return None
 
-    def _posterior_elements(self, res, run, extra, flip_names, what, with_stream=False, skip=('info',), timing=None):
+    def _posterior_elements(self, res, run, extra, flip_names, what, with_stream=False, skip=('info',), timing=None,
+                            fields=(), ragged=()):
         """What :meth:`posterior_errors` and :meth:`posterior_samples` share.  The items (see ``posterior.element_errors``;
         ``with_stream``: with their ``stream``) of every computed element of ``res``, per worker phase, go to
         ``run(K, omega, items, default_name=, chi2_factor=, device_ids=, bryan=, timing=)``, which returns one dict per item.
         These are assembled into a dict (with ``extra``): arrays shaped like the result's fields, NaN (-1 for integers) where nothing was
         computed, the hermitian partners filled in -- the imaginary part's ``flip_names`` with the other sign; ``info``
-        per element, the names ``skip`` left out."""
+        per element, the names ``skip`` left out.  ``fields``: further fields of the result that an item carries under
+        their names; ``ragged``: names whose last axis (the data rows) may differ between elements and is padded with NaN
+        to the longest."""
         from . import posterior
         zero = set(tuple(z) for z in res.zero_elements)
         phases = [(self.maxent_diagonal, self._diag_jobs(), None)]
@@ -729,6 +732,8 @@ class ElementwiseMaxEnt(object):
                     ana = ana[i]
                 item = dict(spec=spec, H=H, alpha=np.asarray(res.alpha, dtype=float), analysis=ana,
                             probability=None if np.all(np.isnan(logp)) else logp, B=loop.A_of_H.matrix())
+                for name in fields:
+                    item[name] = np.asarray(res.element_array(name, key))
                 if with_stream:
                     item['stream'] = int(np.ravel_multi_index(tuple(element), tuple(self.shape))) * 2 + cidx
                 items.append(item)
@@ -747,6 +752,12 @@ class ElementwiseMaxEnt(object):
             raise ValueError('the result holds no element to {}'.format(what))
         struct = tuple(self.shape) + ((2,) if self.use_complex else ())
         out = dict(info={}, **extra)
+        for name in ragged:
+            longest = max(np.shape(o[name])[-1] for _, o in collected)
+            for _, o in collected:
+                val = np.asarray(o[name], dtype=float)
+                pad = [(0, 0)] * (val.ndim - 1) + [(0, longest - val.shape[-1])]
+                o[name] = np.pad(val, pad, constant_values=np.nan)
         for key, o in collected:
             out['info'][key] = o['info']
             for name, val in o.items():
@@ -806,6 +817,25 @@ class ElementwiseMaxEnt(object):
                                              z=z, **common)
         return self._posterior_elements(res, run, dict(seed=int(seed)), ('H', 'H_samples', 'A_samples'), 'draw samples for',
                                         with_stream=True, skip=('info', 'seed'), timing=timing)
+
+    def fit_diagnostics(self, result=None, alpha='all', timing=None):
+        """:meth:`TauMaxEnt.fit_diagnostics` for every matrix element of ``result`` (default: the last result of this
+        object): all elements of a worker -- the diagonal ones, the off-diagonal ones with their plus-minus entropy -- in
+        ONE call of ``mxe_fit_diagnostics`` per device, each with its own data, error bars or covariance.  Returns a dict of
+        arrays laid out like :meth:`posterior_errors`' (matrix indices, then the complex index with ``use_complex``, then
+        what :meth:`TauMaxEnt.fit_diagnostics` returns; elements that were not computed hold NaN, -1 for indices; those
+        that follow from hermiticity are filled from their partners, the imaginary part's residuals and spectra with the
+        other sign).  The data rows of ``residual``, ``leverage`` and ``studentized`` are padded with NaN to the longest
+        element.  ``info``: per computed element its ``nan_rows``."""
+        from . import diagnostics
+        res = self.maxent_result if result is None else result
+        if res is None:
+            raise ValueError('no result: run() first or hand one in')
+
+        def run(K, omega, items, bryan=None, **common):
+            return diagnostics.element_diagnostics(K, items, alpha=alpha, **common)
+        return self._posterior_elements(res, run, {}, ('residual', 'studentized', 'A_gcv', 'A_classic'), 'compute diagnostics for',
+                                        timing=timing, fields=('S', 'A'), ragged=('residual', 'leverage', 'studentized'))
 
     def resample_errors(self, bins, method='jackknife', block=1, n_resamples=None, seed=None, alpha=None,
                         alpha_mode='per_resample', windows=None, functionals=None, pointwise=True, keep_samples=False,

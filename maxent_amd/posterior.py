@@ -222,13 +222,23 @@ def _stage(K, specs, dev):
     return ctx
 
 
-def _per_device(K, specs, H_rows, alpha_rows, call, device_ids=None, timing=None):
+def _holds_data(solver, ctx, specs):
+    """whether the staged context ``ctx`` of ``solver`` holds the data vectors of ``specs`` (``staged_context_for`` compares
+    everything but them: the posterior does not depend on G)"""
+    old = solver.__dict__.get('_staged', {}).get(id(ctx))
+    G = None if old is None else old.get('G')
+    return G is not None and len(G) == len(specs) and \
+        all(np.shape(s['G']) == G[i].shape and np.array_equal(G[i], s['G']) for i, s in enumerate(specs))
+
+
+def _per_device(K, specs, H_rows, alpha_rows, call, device_ids=None, timing=None, match_data=False):
     """One ``call(ctx, el, al, Hs, mine, t)`` per device for the elements ``specs`` of the kernel ``K``: element e (with
     the hidden images ``H_rows[e]`` (n_e, n_omega) at ``alpha_rows[e]`` (n_e)) goes to device e mod N, as the solve shards
     them; the devices are visited one after the other.  ``ctx``: the solver's staged context when there is one (the call
     then runs under the solver's lock), else one of its own.  ``el``, ``al``, ``Hs``: the problems of the elements
     ``mine``, concatenated; ``t``: the call's timing dict.  ``call`` returns a tuple of arrays with one row per problem
-    (or None); per element the tuple of its rows is returned."""
+    (or None); per element the tuple of its rows is returned.  ``match_data``: a staged context is taken only when it
+    holds the data vectors of ``specs`` too (what ``call`` computes depends on G)."""
     from .batch_solver import BatchSolver
     device_ids = tuple(device_ids) if device_ids else (0,)
     n = len(specs)
@@ -240,6 +250,8 @@ def _per_device(K, specs, H_rows, alpha_rows, call, device_ids=None, timing=None
             continue
         sub = [specs[e] for e in mine]
         ctx, solver = BatchSolver.staged_context_for(K, sub, dev) if len(device_ids) == 1 else (None, None)
+        if ctx is not None and match_data and not _holds_data(solver, ctx, sub):
+            ctx = solver = None
         own = ctx is None
         reused += 0 if own else 1
         if own:

@@ -436,6 +436,33 @@ class TauMaxEnt(object):
                                          chi2_factor=loop.cost_function.chi2_factor, device_ids=ids[:1],
                                          bryan=posterior.find_bryan(loop.analyzers), timing=timing)[0]
 
+    def fit_diagnostics(self, result, alpha='all', timing=None):
+        """Diagnostics of the fits of ``result`` (made by this object: its kernel, data, errors, default model and alpha
+        mesh are used) from the hat matrix of the fit -- the derivative of the fitted whitened data with respect to the
+        whitened data, exact at the minimiser --, computed on the device (``mxe_fit_diagnostics``).  Not in the reference.
+
+        ``alpha``: ``'all'`` (default), an analyzer name, an index or a sequence of indices.  Returns a dict: ``alpha``,
+        ``alpha_index``; ``n_good``, the number of good data N_g = tr Hat; ``chi2``; ``residual`` =
+        Sigma^-1/2 (K H - G) and ``leverage`` = diag Hat per data row (tau points; the 2 n_iw stacked real values of
+        Matsubara data; the kept eigen-directions after ``set_cov`` or ``set_G_*_bins``); ``studentized`` =
+        r / sqrt(1 - h) (NaN where 1 - h < 1e-12); ``autocorr`` = sum r_i r_i+1 / sum r_i^2 (NaN in a covariance
+        eigenbasis, where the data index has no order); ``gcv`` = n chi2 / (n - N_g)^2; ``good_data_ratio`` =
+        -2 a S / N_g with a = alpha~ / chi2_factor; ``info`` (``nan_rows``: alphas whose H is not finite or whose curvature
+        is not positive definite).  With ``'all'`` also ``alpha_index_gcv`` (the smallest GCV score),
+        ``alpha_index_classic`` (the ratio closest to 1 on the logarithmic scale) and the rows ``A_gcv``, ``A_classic`` of
+        ``result.A``.  A single alpha drops the alpha axis in front."""
+        from . import diagnostics, posterior
+        loop = self.maxent_loop
+        spec = loop.make_spec()
+        posterior.check_alpha(spec, result.alpha)
+        item = dict(spec=spec, H=np.asarray(result.element_array('H')), alpha=np.asarray(result.alpha, dtype=float),
+                    S=np.asarray(result.element_array('S'), dtype=float), A=np.asarray(result.element_array('A')),
+                    analysis=result.analyzer_results)
+        ids = loop.device_ids if loop.device_ids else (loop.device_id,)
+        return diagnostics.element_diagnostics(self.K, [item], alpha=alpha, default_name=result.default_analyzer_name,
+                                               chi2_factor=loop.cost_function.chi2_factor, device_ids=ids[:1],
+                                               timing=timing)[0]
+
     def resample_errors(self, bins, method='jackknife', block=1, n_resamples=None, seed=None, alpha=None,
                         alpha_mode='per_resample', windows=None, functionals=None, pointwise=True, keep_samples=False,
                         timing=None):
