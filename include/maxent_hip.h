@@ -54,6 +54,8 @@
  *                                                          |   jackknife / bootstrap resample of the bins),
  *                                                          |   mxe_resample_reduce (mean, spread and functional
  *                                                          |   covariances of the H rows they were continued to)
+ *   (nothing: users rebin by hand until the errors settle) | mxe_bins_check (blocking ladder, skewness and
+ *                                                          |   kurtosis of the block means of the bins)
  *   the arrays of MaxEntResult (numpy allocations)         | mxe_host_alloc / mxe_host_free (optional:
  *     maxent_result.py:835-967                             |   page-locked destinations, one DMA per fetch)
  *
@@ -694,6 +696,35 @@ int  mxe_resample_reduce(mxe_ctx* ctx, int n_groups, const int32_t* group_offset
                          const int32_t* problem_index, const double* scale, int n_f, const double* F,
                          double* out_mean, double* out_var, double* out_fval, double* out_fmean, double* out_fcov,
                          int32_t* out_used, float* out_ms);
+
+/* ---- bin checks: blocking ladder and normality of the block means (no counterpart in the reference) ---- */
+/* May the bins be used as they are?  The covariance of the mean of mxe_bins_eig assumes bins that are uncorrelated and
+ * normally distributed.  Per set, all sets in one launch (one workgroup each), per column c and level k = 0 .. L - 1,
+ * L = floor(log2 n_bins): the bins are cut into n_k = floor(n_bins / 2^k) blocks of 2^k successive bins (a trailing
+ * remainder is dropped at that level only; every n_k >= 2), B_q is the mean of block q, Bbar their mean, and
+ * mu_p = (1 / n_k) sum_q (B_q - Bbar)^p, p = 2, 3, 4 (two passes: Bbar first, then powers of the explicit difference).
+ *   bins        n_sets x n_bins x n_data, as for mxe_bins_eig.  The bin index is Monte Carlo time: here, unlike everywhere
+ *               else, the order of the bins matters.
+ *   T, rank     both NULL: the columns are the data values, y[b][c] = bins[b][c] - mean[c].  Both given (n_sets x n_data x
+ *               n_data and n_sets: out_T and out_rank of mxe_bins_eig): the columns are the eigen-directions chi^2 sums,
+ *               y[b][k] = sum_j T[k][j] (bins[b][j] - mean[j]) for k < rank (v_mfma_f64_16x16x4_f64 tiles, every inner
+ *               product in index order), zeros for k >= rank.
+ *   out_mean    n_sets x n_data: the mean over the bins, formed by the code mxe_bins_eig runs -- the same bits
+ *   out_err2    n_sets x L x n_data: mu_2 / (n_k - 1), the squared error of the mean as estimated at block length 2^k.
+ *               Level 0 is C_cc in the data basis and the eigenvalue out_var[c] of mxe_bins_eig in the eigen basis; the
+ *               ratio to level 0 estimates 2 tau_int and levels off once the blocks are uncorrelated.
+ *   out_skew    n_sets x L x n_data: mu_3 / mu_2^(3/2);   out_kurt: mu_4 / mu_2^2 - 3 (both 0 for normal block means)
+ *               Where mu_2 == 0 -- a constant column, a column k >= rank -- out_err2 is 0 and both are NaN.
+ *   out_levels  one value: L
+ *   out_ms      device time of the kernel (may be NULL)
+ * The block sums of level k + 1 are sums of two block sums of level k (a halving tree over a work array of the set in
+ * device memory); every sum over blocks runs as 16 chunks in chunk order: no atomics, a set's output does not depend on the
+ * other sets and repeats bit for bit.  MXE_ERR_ARG (nothing is launched): what mxe_bins_eig refuses in its sizes and bins,
+ * exactly one of T and rank NULL, a rank outside 0 .. n_data, a NaN or an Inf in bins or T. */
+int  mxe_bins_check(int device, int n_sets, int n_bins, int n_data, const double* bins,
+                    const double* T, const int32_t* rank,
+                    double* out_mean, double* out_err2, double* out_skew, double* out_kurt,
+                    int32_t* out_levels, float* out_ms);
 
 #ifdef __cplusplus
 }

@@ -3931,3 +3931,61 @@ try {
     return MXE_OK;
 }
 MXE_CATCH_ALL
+
+// ---- bin checks: the blocking ladder and the normality of the block means of every set (mxe_bincheck.hip.h) ----
+#include "mxe_bincheck.hip.h"
+
+extern "C" int mxe_bins_check(int device, int n_sets, int n_bins, int n_data, const double* bins,
+                              const double* T, const int32_t* rank,
+                              double* out_mean, double* out_err2, double* out_skew, double* out_kurt,
+                              int32_t* out_levels, float* out_ms)
+try {
+    if (n_sets < 1 || n_bins < 2 || n_data < 1 || n_data > mxe::BINS_NMAX || !bins || !out_mean || !out_err2 || !out_skew ||
+        !out_kurt || !out_levels || (T == nullptr) != (rank == nullptr)) return MXE_ERR_ARG;
+    if ((int64_t)n_bins * n_data > INT32_MAX) return MXE_ERR_ARG;
+    const size_t m = n_bins, n = n_data, ns = n_sets, nel = ns * m * n;
+    if (rank)
+        for (size_t s = 0; s < ns; ++s) if (rank[s] < 0 || rank[s] > n_data) return MXE_ERR_ARG;
+    if (!all_finite(bins, nel) || (T && !all_finite(T, ns * n * n))) return MXE_ERR_ARG;
+    int L = 0;
+    while ((n_bins >> (L + 1)) >= 1) ++L;                             // floor(log2 n_bins): every level has two blocks or more
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return MXE_ERR_NODEVICE;
+    if (device < 0 || device >= ndev) return MXE_ERR_ARG;
+    SVDCHK(hipSetDevice(device));
+    SvdScratch sc;
+    SVDCHK(hipStreamCreateWithFlags(&sc.stream, hipStreamNonBlocking));
+    mxe::BinCheckParams p;
+    p.m = n_bins; p.n = n_data; p.L = L;
+    const size_t nout = ns * (size_t)L * n;
+    double *dbins, *dT = nullptr;
+    int* drank = nullptr;
+    SVDCHK(sc.alloc(&dbins, nel));
+    if (T) { SVDCHK(sc.alloc(&dT, ns * n * n)); SVDCHK(sc.alloc(&drank, ns)); }
+    SVDCHK(sc.alloc(&p.part, ns * mxe::BINS_NWAVE * n * 2)); SVDCHK(sc.alloc(&p.part2, ns * mxe::BINS_NWAVE * n * 3));
+    SVDCHK(sc.alloc(&p.Y0, nel)); SVDCHK(sc.alloc(&p.Y1, std::max<size_t>(ns * (m >> 1) * n, 1)));
+    SVDCHK(sc.alloc(&p.out_mean, ns * n)); SVDCHK(sc.alloc(&p.out_err2, nout));
+    SVDCHK(sc.alloc(&p.out_skew, nout)); SVDCHK(sc.alloc(&p.out_kurt, nout));
+    p.bins = dbins; p.T = dT; p.rank = drank;
+    SVDCHK(hipMemcpyAsync(dbins, bins, nel * 8, hipMemcpyHostToDevice, sc.stream));
+    if (T) {
+        SVDCHK(hipMemcpyAsync(dT, T, ns * n * n * 8, hipMemcpyHostToDevice, sc.stream));
+        SVDCHK(hipMemcpyAsync(drank, rank, ns * 4, hipMemcpyHostToDevice, sc.stream));
+    }
+    if (out_ms) {
+        SVDCHK(hipEventCreate(&sc.e0)); SVDCHK(hipEventCreate(&sc.e1));
+        SVDCHK(hipEventRecord(sc.e0, sc.stream));
+    }
+    hipLaunchKernelGGL(mxe::bins_check_kernel, dim3(n_sets), dim3(mxe::BINS_T), 0, sc.stream, p);
+    SVDCHK(hipGetLastError());
+    if (out_ms) SVDCHK(hipEventRecord(sc.e1, sc.stream));
+    SVDCHK(hipMemcpyAsync(out_mean, p.out_mean, ns * n * 8, hipMemcpyDeviceToHost, sc.stream));
+    SVDCHK(hipMemcpyAsync(out_err2, p.out_err2, nout * 8, hipMemcpyDeviceToHost, sc.stream));
+    SVDCHK(hipMemcpyAsync(out_skew, p.out_skew, nout * 8, hipMemcpyDeviceToHost, sc.stream));
+    SVDCHK(hipMemcpyAsync(out_kurt, p.out_kurt, nout * 8, hipMemcpyDeviceToHost, sc.stream));
+    SVDCHK(hipStreamSynchronize(sc.stream));
+    if (out_ms) SVDCHK(hipEventElapsedTime(out_ms, sc.e0, sc.e1));
+    out_levels[0] = L;
+    return MXE_OK;
+}
+MXE_CATCH_ALL

@@ -171,6 +171,8 @@ SYMBOLS = [
                                          _dp, _dp, _dp, ctypes.POINTER(ctypes.c_float)]),
     ('mxe_resample_reduce', ctypes.c_int, [_vp, ctypes.c_int, _ip, _dp, _ip, _dp, ctypes.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _ip,
                                            ctypes.POINTER(ctypes.c_float)]),
+    ('mxe_bins_check', ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, _dp, _ip,
+                                      _dp, _dp, _dp, _dp, _ip, ctypes.POINTER(ctypes.c_float)]),
 ]
 
 
@@ -581,6 +583,65 @@ def bins_resample(bins, counts, T, rank, device=0, want_dev=True, timing=None):
         out['dev'] = dev
     if single:
         out = dict((k, v[0]) for k, v in out.items())
+    return out
+
+
+def bins_check(bins, T=None, rank=None, device=0, timing=None):
+    """``mxe_bins_check``: the blocking ladder and the normality of the block means of every set, one launch.  ``bins``:
+    (n_sets, n_bins, n_data) or (n_bins, n_data), the bin index being Monte Carlo time; ``T`` (n_sets, n_data, n_data) and
+    ``rank`` (n_sets,): the eigenvector rows as ``mxe_bins_eig`` writes them (zero rows behind the kept ones) -- the columns
+    are then the eigen-directions --, or both None: the columns are the data values.  Returns a dict: ``mean`` (n_sets,
+    n_data) -- the bits of ``bins_eig`` --, ``err2``, ``skew``, ``kurt`` (n_sets, L, n_data) with L = floor(log2 n_bins)
+    levels of block length 2^k, ``levels`` = L.  2-d ``bins``: without the leading axis.  ``timing``: a dict that receives
+    the device time ``ms`` of the kernel.  Sizes and arguments the library would refuse raise ValueError before it is
+    called."""
+    b = np.asarray(bins)
+    single = b.ndim == 2
+    if single:
+        b = b[None]
+    if b.ndim != 3 or np.iscomplexobj(b):
+        raise ValueError('bins_check: bins must be real, (n_sets, n_bins, n_data) or (n_bins, n_data); got %s' % (np.shape(bins),))
+    n_sets, n_bins, n_data = b.shape
+    if n_sets < 1 or n_bins < 2 or n_data < 1 or n_data > BINS_MAX_DATA or n_bins * n_data > 2 ** 31 - 1:
+        raise ValueError('bins_check: %d set(s) of %d bins x %d values; at least one set, two bins and 1 to %d values are '
+                         'needed, and at most 2^31 - 1 values per set' % (n_sets, n_bins, n_data, BINS_MAX_DATA))
+    if (T is None) != (rank is None):
+        raise ValueError('bins_check: T and rank come together (the eigen basis) or not at all (the data basis)')
+    Tm = rk = None
+    if T is not None:
+        Tm = np.asarray(T, dtype=float)
+        rk = np.asarray(rank)
+        if Tm.size != n_sets * n_data * n_data or rk.size != n_sets:
+            raise ValueError('bins_check: T of shape %s and rank of shape %s do not fit %d set(s) of %d values'
+                             % (Tm.shape, rk.shape, n_sets, n_data))
+        Tm = _c(Tm.reshape(n_sets, n_data, n_data))
+        rk = _c(rk.reshape(n_sets), np.int32)
+        if np.any(rk < 0) or np.any(rk > n_data):
+            raise ValueError('bins_check: a rank outside 0..%d' % n_data)
+    b = _c(b)
+    lib = load_library()
+    if device_count() < 1:
+        raise MaxEntDeviceError('no HIP device visible; the checks of the bins have no CPU fallback')
+    L = int(n_bins).bit_length() - 1
+    mean = np.empty((n_sets, n_data))
+    err2, skew, kurt = (np.empty((n_sets, L, n_data)) for _ in range(3))
+    levels = np.zeros(1, dtype=np.int32)
+    ms = ctypes.c_float(0)
+    rc = lib.mxe_bins_check(int(device), n_sets, n_bins, n_data, _p(b), _p(Tm), _p(rk), _p(mean), _p(err2), _p(skew),
+                            _p(kurt), _p(levels), ctypes.byref(ms))
+    if rc == _MXE_ERR_ARG:           # (sizes, T and rank were checked above: what is left is a NaN or an Inf, before any launch)
+        raise ValueError('mxe_bins_check refused its arguments: values of bins or T that are not finite (%d in bins)'
+                         % int((~np.isfinite(b)).sum()))
+    if rc != 0:
+        raise MaxEntDeviceError('mxe_bins_check failed: ' + lib.mxe_strerror(rc).decode())
+    if int(levels[0]) != L:
+        raise MaxEntDeviceError('mxe_bins_check: %d levels came back where %d were expected' % (int(levels[0]), L))
+    if timing is not None:
+        timing['ms'] = float(ms.value)
+    out = dict(mean=mean, err2=err2, skew=skew, kurt=kurt)
+    if single:
+        out = dict((k, v[0]) for k, v in out.items())
+    out['levels'] = L
     return out
 
 

@@ -853,6 +853,14 @@ class ElementwiseMaxEnt(object):
                                                       functionals=functionals, pointwise=pointwise,
                                                       keep_samples=keep_samples, timing=timing)
 
+    def check_bins(self, bins, basis='eigen'):
+        """:meth:`TauMaxEnt.check_bins` for every set of the last ``set_G_*_bins`` call (``bins`` are the ones it
+        received), all sets in one ``mxe_bins_check`` call on the first device.  Returns a dict keyed like
+        ``bin_statistics``, each entry the dict of :func:`maxent_amd.bin_checks.summarize`, and a top-level
+        ``recommended_block``: the largest over the elements, None if any element gives None."""
+        from . import bin_checks
+        return bin_checks.elementwise_check_bins(self, bins, basis=basis)
+
     def _direct_input(self, worker):
         """G(tau) came as one array and the errors are plain (no covariance): specs can be cut from the
         arrays without sending every element through the worker's setters"""

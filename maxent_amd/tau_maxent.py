@@ -491,6 +491,22 @@ class TauMaxEnt(object):
                                               alpha=alpha, alpha_mode=alpha_mode, windows=windows, functionals=functionals,
                                               pointwise=pointwise, keep_samples=keep_samples, timing=timing)
 
+    def check_bins(self, bins, basis='eigen'):
+        """May the Monte Carlo ``bins`` the last ``set_G_*_bins`` call received be used as they are?  The covariance of
+        the mean is right for bins that are uncorrelated, chi^2 is a log-likelihood for bins that are normally
+        distributed; the device (``mxe_bins_check``, :mod:`maxent_amd.bin_checks`) tests both on blocks of 1, 2, 4, ...
+        successive bins -- the bin index must be Monte Carlo time.  The object is not changed.  Not in the reference.
+
+        ``basis='eigen'``: per kept eigen-direction of the covariance (``bin_statistics``), the directions chi^2 sums;
+        ``'data'``: per data value (the stacked ``[Re ; Im]`` values of Matsubara bins), which needs no earlier
+        ``set_G_*_bins`` call.  Returns the dict of :func:`maxent_amd.bin_checks.summarize`: per level ``block``,
+        ``n_blocks``, ``err2``, ``inefficiency`` (the estimate of 2 tau_int), its column mean ``R``, ``skew``, ``kurt``,
+        their z-scores, ``frac_non_normal``; ``plateau_level`` and ``recommended_block`` (None: the bins are correlated
+        beyond what their number resolves).  A ``recommended_block`` other than 1 is reported through the logtaker's
+        error messages: pass ``rebin_bins(bins, block)`` to the setter."""
+        from . import bin_checks
+        return bin_checks.tau_check_bins(self, bins, basis=basis)
+
     # ---- tau ----------------------------------------------------------------
     def get_tau(self):
         return self.maxent_loop.get_data_variable()
