@@ -10,6 +10,7 @@
 #include "mxe_kernel_mc.hip.h"
 #include "mxe_kernel_lv.hip.h"
 #include "mxe_eval.hip.h"
+#include "mxe_plan.h"
 
 #include <algorithm>
 #include <chrono>
@@ -23,7 +24,6 @@
 #include <vector>
 #include <mutex>
 #include <thread>
-#include <array>
 #include <tuple>
 
 using mxe::KParams;
@@ -227,7 +227,7 @@ template <typename T> struct DevBuf {
 } // namespace
 
 struct mxe_ctx {
-    int device = 0;
+    int device = 0, n_cu = 256;         // n_cu: compute units of the device (256 where it does not say)
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_mark = nullptr;
     int n_tau = 0, n_omega = 0, n_s = 0, NP = 64, nwp = 0;
@@ -250,7 +250,7 @@ struct mxe_ctx {
     // (mxe_opts.precision = F32), 2 = first pass of a binary64 launch that does not fill the GPU -- chain_kernel_mc then
     // takes every alpha as a piece of its own from the v it left (the arrays of that second pass: d2_*)
     int lv_mode = 0;
-    int mc_wgpc_hint = 1;               // workgroups per CU the auto rule of mxe_chains_upload expects (piece_taper)
+    int mc_wgpc_hint = 1;               // workgroups per CU the auto rule of the launch plan chose last (mxe_plan.h: pieces_per_scan)
     int n_wg2 = 0, wgpc2 = 1;
     DevBuf<int> d2_elem, d2_prob0, d2_len, d2_v0, d2_queue, dcnt1_niter, dcnt1_nevals;
     DevBuf<int> drounds;                // rounds per workgroup of the last lock-step launch: [n_wg] | [n_wg2] (mxe_launch_depth)
@@ -598,6 +598,7 @@ try {
         hipEventCreate(&ctx->ev_mark) != hipSuccess) {
         delete ctx; return MXE_ERR_HIP;
     }
+    if (hipDeviceGetAttribute(&ctx->n_cu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || ctx->n_cu <= 0) { (void)hipGetLastError(); ctx->n_cu = 256; }
     ctx->n_tau = n_tau; ctx->n_omega = n_omega; ctx->n_s = n_s;
     ctx->NP = (n_s <= 64) ? 64 : 128;
     ctx->nwp = ((n_omega + 127) / 128) * 128;   // the lock-step kernel's fused pass runs whole trips of 128 rows
@@ -1040,702 +1041,128 @@ int placement_rule_holds(mxe_ctx* ctx, int n_cu, bool* holds)
     *holds = g_placement[dev] == 1;
     return MXE_OK;
 }
+
+// the environment overrides of the launch plan (A/B runs and tests): the only environment reads of mxe_chains_upload's decisions
+void read_plan_env(mxe::PlanEnv& env)
+{
+    if (const char* e = getenv("MXE_TAPER")) env.taper = std::max(0.2, atof(e));
+    if (const char* e = getenv("MXE_LADDER_RATIO")) env.ladder_ratio = std::max(1.05, atof(e));
+    env.no_lds_basis = getenv("MXE_NO_LDS_BASIS") != nullptr; env.no_split_by_kind = getenv("MXE_NO_SPLIT_BY_KIND") != nullptr;
+    env.no_ladder = getenv("MXE_NO_LADDER") != nullptr; env.no_na64 = getenv("MXE_NO_NA64") != nullptr; env.no_sorted_static = getenv("MXE_NO_SORTED_STATIC") != nullptr;
+}
 }  // namespace
 
-constexpr double MC_COUPLING_MAX = 1e-3;     // relative coupling of the first direction the 32-row active block leaves out (see below)
-
-namespace {
-// pieces of unequal length for launches that FILL the GPU (see mxe_chains_upload); MXE_TAPER overrides (A/B runs)
-double piece_taper(const mxe_opts& o, int wgpc)
-{
-    if (const char* e = getenv("MXE_TAPER")) return std::max(0.2, atof(e));
-    (void)o; (void)wgpc;
-    return 1.0;
-}
-}
-
+// Stages the chains of a launch.  What is launched -- pieces, kernel, layout, order -- is decided by mxe::plan_launch
+// (mxe_plan.h) from numbers alone; this function checks, asks, and then carries the plan out.
 int mxe_chains_upload(mxe_ctx* ctx, int n_chain, int n_alpha,
                       const int32_t* elem_of_chain, const double* alpha_scaled,
                       const double* v0, const mxe_opts* opts)
 try {
+    // ---- 1. arguments and options (nothing of the context's staged launch is written before the plan stands)
     if (!ctx || n_chain < 1 || n_alpha < 1 || !elem_of_chain || !alpha_scaled || !v0) return MXE_ERR_ARG;
     if (ctx->n_elem < 1) return MXE_ERR_STATE;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     if (ctx->ds_dirty) { int rc = upload_bases(ctx); if (rc != MXE_OK) return rc; }
-    const int ns = ctx->n_s, NP = ctx->NP, nw = ctx->n_omega;
-    if (opts) ctx->opts = *opts; else mxe_opts_default(&ctx->opts);
-    const mxe_opts& o = ctx->opts;
+    const int ns = ctx->n_s, NP = ctx->NP, nw = ctx->n_omega, nwp = ctx->nwp;
+    const size_t P = (size_t)n_chain * n_alpha;
+    mxe_opts o; if (opts) o = *opts; else mxe_opts_default(&o);
     if (o.maxiter < 1 || o.step_max <= 0 || o.mu_first <= 0 || o.mu_grow <= 1.0 || o.decouple_tol < 0) return MXE_ERR_ARG;
-    if (o.waves_per_chain != 0 && o.waves_per_chain != 1 && o.waves_per_chain != 2 &&
-        o.waves_per_chain != 4 && o.waves_per_chain != 8) return MXE_ERR_ARG;
+    if (o.waves_per_chain != 0 && o.waves_per_chain != 1 && o.waves_per_chain != 2 && o.waves_per_chain != 4 && o.waves_per_chain != 8) return MXE_ERR_ARG;
     if (o.chains_per_wg != 0 && o.chains_per_wg != 1 && o.chains_per_wg != 4) return MXE_ERR_ARG;
-    if (o.alpha_split < 0) return MXE_ERR_ARG;
-    if (o.wg_per_cu < 0 || o.wg_per_cu > 2) return MXE_ERR_ARG;
-    if (o.in_flight < 0 || o.in_flight > 64) return MXE_ERR_ARG;
+    if (o.alpha_split < 0 || o.wg_per_cu < 0 || o.wg_per_cu > 2 || o.in_flight < 0 || o.in_flight > 64) return MXE_ERR_ARG;
     if (o.precision != MXE_PRECISION_F64 && o.precision != MXE_PRECISION_F32) return MXE_ERR_ARG;
     if (o.precision == MXE_PRECISION_F32 && NP != 64) return MXE_ERR_LIMIT;
     if (!(o.chi2_factor > 0.0) || !std::isfinite(o.chi2_factor)) return MXE_ERR_ARG;
-    // Q = eta chi2 / 2 - alpha S has the minimiser of chi2 / 2 - (alpha / eta) S: the device iterates on
-    // alpha / eta and the fetch multiplies Q by eta (cost_function.py:60, bryan_cost_function.py:71)
-    ctx->chi2_factor = o.chi2_factor;
-    std::vector<double> alpha_dev(alpha_scaled, alpha_scaled + (size_t)n_chain * n_alpha);
-    if (o.chi2_factor != 1.0) for (double& a : alpha_dev) a /= o.chi2_factor;
-    ctx->chain_elem.assign(elem_of_chain, elem_of_chain + n_chain);
+    for (int c = 0; c < n_chain; ++c) if (elem_of_chain[c] < 0 || elem_of_chain[c] >= ctx->n_elem) return MXE_ERR_ARG;
+    for (size_t i = 0; i < P; ++i) if (!(alpha_scaled[i] > 0.0) || !std::isfinite(alpha_scaled[i])) return MXE_ERR_ARG;
+    // ---- 2. the start vectors in the whitened basis of their data sets: v' = Q^T v
     std::vector<double> hv0((size_t)n_chain * NP, 0.0);
     for (int c = 0; c < n_chain; ++c) {
-        const int e = elem_of_chain[c];
-        if (e < 0 || e >= ctx->n_elem) return MXE_ERR_ARG;
-        const DataSet& DS = ctx->ds[ctx->elem_ds[e]];
+        const DataSet& DS = ctx->ds[ctx->elem_ds[elem_of_chain[c]]];
         for (int k = 0; k < ns; ++k) {
-            double s;
-            if (DS.identity_q) s = v0[(size_t)c * ns + k];
-            else {   // v' = Q^T v
-                s = 0.0;
-                for (int j = 0; j < ns; ++j) s += DS.Q[(size_t)j * ns + k] * v0[(size_t)c * ns + j];
-            }
+            double s = DS.identity_q ? v0[(size_t)c * ns + k] : 0.0;
+            if (!DS.identity_q) for (int j = 0; j < ns; ++j) s += DS.Q[(size_t)j * ns + k] * v0[(size_t)c * ns + j];
             hv0[(size_t)c * NP + k] = s;
         }
     }
-    for (size_t i = 0; i < (size_t)n_chain * n_alpha; ++i)
-        if (!(alpha_scaled[i] > 0.0) || !std::isfinite(alpha_scaled[i])) return MXE_ERR_ARG;
-    const size_t P = (size_t)n_chain * n_alpha;
-    // chain_kernel_lv (V^T resident in LDS as binary32): possible where the basis fits beside the state of four slots
-    const bool lv_fits = NP == 64 && ctx->nwp <= 512 && o.lds_basis != 2 && !getenv("MXE_NO_LDS_BASIS") &&
-                         o.chains_per_wg != 1 && o.tol_d <= 0.0 && o.decouple_tol > 0.0 &&
-                         mxe::lv_lds_bytes(ns, ctx->nwp) + mxe::LV_STATIC_LDS <= (size_t)160 * 1024;
-    // (binary32 launches in that kernel are scheduled like binary64 ones: lock-step pieces, one workgroup per CU)
-    bool f32_lv = o.precision == MXE_PRECISION_F32 && lv_fits;
-    if (f32_lv && ns > 32) {
-        // (chain_kernel_lv has the plain 32-row build only: a job with an alpha that couples more than 32 directions -- the criterion
-        //  of the layout decision below, per scan -- keeps the one-chain binary32 kernel AND its pieces of six alphas)
-        for (int c = 0; c < n_chain && f32_lv; ++c) {
-            const int e = elem_of_chain[c];
-            if (e < 0 || e >= ctx->n_elem) return MXE_ERR_ARG;
-            const DataSet& DS = ctx->ds[ctx->elem_ds[e]];
-            double amin = 1e300;
-            for (int i = 0; i < n_alpha; ++i) amin = std::min(amin, alpha_dev[(size_t)c * n_alpha + i]);
-            if (!(DS.c[32] * DS.c[32] * std::max(1.0, ctx->h_sumD[e]) / amin <= MC_COUPLING_MAX)) f32_lv = false;
-        }
-        if (!f32_lv) {
-            // Binary32 is asked for as the cheaper arithmetic; for such a job the cheaper arithmetic is the binary64 lock-step
-            // build with the 64-row block (and the hand-over of what it leaves): the one-chain binary32 kernel took 0.7-1.5 s
-            // where that takes 4-5 ms, and stops at its rounding floor besides (STRESS_F32=1 tools/stress.py, cases 24 / 25:
-            // profiles/r04_e_stress_f32.txt).  The launch is promoted; mxe_last_launch_info names the kernel that ran.
-            ctx->opts.precision = MXE_PRECISION_F64;
-        }
+    // ---- 3. what the plan reads.  Q = eta chi2 / 2 - alpha S has the minimiser of chi2 / 2 - (alpha / eta) S: the device
+    // iterates on alpha / eta and the fetch multiplies Q by eta (cost_function.py:60, bryan_cost_function.py:71)
+    std::vector<double> alpha_dev(alpha_scaled, alpha_scaled + P);
+    if (o.chi2_factor != 1.0) for (double& a : alpha_dev) a /= o.chi2_factor;
+    std::vector<int> ds_rows(ctx->ds.size()); std::vector<double> ds_c32(ctx->ds.size(), 0.0);
+    for (size_t d = 0; d < ctx->ds.size(); ++d) { ds_rows[d] = ctx->ds[d].n_rows; if (ns > 32) ds_c32[d] = ctx->ds[d].c[32]; }
+    mxe::PlanInput in;
+    in.n_chain = n_chain; in.n_alpha = n_alpha; in.elem_of_chain = elem_of_chain; in.alpha = alpha_dev.data();
+    in.elem_kind = ctx->elem_kind.data(); in.elem_ds = ctx->elem_ds.data(); in.elem_sumD = ctx->h_sumD.data();
+    in.n_ds = (int)ctx->ds.size(); in.ds_rows = ds_rows.data(); in.ds_c32 = ds_c32.data();
+    in.n_s = ns; in.NP = NP; in.n_omega_pad = nwp; in.n_cu = ctx->n_cu; in.opts = o;
+    in.lds_lv = mxe::lv_lds_bytes(ns, nwp) + mxe::LV_STATIC_LDS; in.lds_mc64x1 = mc_lds_bytes(64, nwp, 1);
+    in.lds_mc32x1 = mc_lds_bytes(32, nwp, 1); in.lds_mc32x2 = mc_lds_bytes(32, nwp, 2);
+    in.wgpc_auto = ctx->wgpc_auto; in.mc_wgpc_hint = ctx->mc_wgpc_hint;
+    read_plan_env(in.env);
+    mxe::LaunchPlan plan;       // ---- 4. the plan
+    if (const int rc = mxe::plan_launch(in, plan); rc != MXE_OK) {
+        if (plan.uncovered || plan.covered_twice) fprintf(stderr, "mxe_chains_upload: %zu problems covered by no piece, %zu by two (layout %d, %zu pieces, %zu excluded)\n",
+                                                          plan.uncovered, plan.covered_twice, plan.layout, plan.pieces.size(), plan.excluded.size());
+        return rc;
     }
-    if (o.precision == MXE_PRECISION_F32 && !lv_fits && NP == 64 && o.lds_basis != 2 && !getenv("MXE_NO_LDS_BASIS") &&
-        o.chains_per_wg != 1 && o.tol_d <= 0.0 && o.decouple_tol > 0.0) {
-        // A frequency mesh whose basis does not fit the LDS as binary32 (n_omega > 512, or n_s x (n_omega_pad + 4) floats beyond what
-        // the slots leave): the binary32 request would run one chain per workgroup with V streamed from the L2 by every chain --
-        // 3.6-7.8 ms where the binary64 lock-step kernel takes 0.5-1.7 (8 x 8 and 16 x 16 elements x 100 alpha at n_omega = 640 ...
-        // 1500), and stops at its rounding floor besides (audit 8e-4 against 1e-8).  Binary32 is asked for as the cheaper
-        // arithmetic: the launch is promoted like the two cases above.  lds_basis = 2 or chains_per_wg = 1 keep the one-chain
-        // binary32 kernel (BASELINE config 5's tolerance sweep on such a mesh asks for it that way).
-        ctx->opts.precision = MXE_PRECISION_F64;
+    // ---- 5. solo workgroups only where workgroups b and b + n_wg / 2 do share a CU on this device: probed once, see placement_rule_holds
+    int n_solo = 0, placement_checked = 0;
+    if (plan.solo_rule) {
+        bool holds = false;
+        if (plan.n_solo_wanted > 0) { const int rp = placement_rule_holds(ctx, ctx->n_cu, &holds); if (rp != MXE_OK) return rp; }
+        placement_checked = holds ? 1 : 2; n_solo = (holds && plan.lv_mode != 2) ? plan.n_solo_wanted : 0;
     }
-    ctx->lv_mode = 0;
-    // ---- (sub-)chains: an alpha scan may be cut into pieces that are cold-started
-    //      from the same v0 (the minimiser of each alpha does not depend on the path)
-    int split = o.alpha_split;
-    int split_pm = 0;                 // pieces per plus-minus scan where that differs from the normal-entropy scans' (0: the same)
-    bool cut_by_cost = false;         // launches that do not fill the GPU: pieces of equal COST, one per slot (see below)
-    bool cost_needs_short_pm = false; //   at two workgroups per CU: only when the plus-minus pieces stay within the depth target too
-    long long slots_by_cost = 0;
-    if (split <= 0) {
-        // about two pieces per chain slot of the GPU (CUs x workgroups per CU x 4 slots): the persistent grid
-        // then balances (pieces have unequal costs and are handed out most expensive first), and a batch that
-        // is small for the GPU -- one rank's shard of a job that is spread over several -- is cut into many
-        // short cold-started pieces rather than left on a fraction of the CUs.  None shorter than two alphas
-        // (a cold start costs 4-10 iterations, a warm alpha 2-3).  Measured, kernel time of 256 / 128 / 64 / 32
-        // scans of 100 alphas (profiles/r02_d_shard_sweep.txt): 16 pieces per scan 1.28 / 1.09 / 0.93 / 1.54 ms,
-        // 34: 2.95 / 0.84 / 0.73 / 0.62, 50: 3.27 / 0.87 / 0.67 / 0.57.
-        hipDeviceProp_t prop;
-        HIPCHK(ctx, hipGetDeviceProperties(&prop, ctx->device));
-        // (two workgroups per CU where the lock-step kernel has a build for it: n_omega_pad <= 512)
-        const int n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-        if (f32_lv && o.wg_per_cu == 0 && ctx->nwp <= 512) {
-            // A binary32 launch runs in chain_kernel_lv at ONE workgroup per CU.  A batch that fills the GPU at two per CU (the test
-            // of the loop below) is faster in the binary64 kernel that runs that way: the 25 600-problem batch 0.81 ms against
-            // 1.24 ms -- binary32 is asked for as the cheaper arithmetic, and there it is not.  Such a launch is promoted like the
-            // one that couples more than 32 directions; wg_per_cu = 1 keeps it in chain_kernel_lv.
-            long long weight = 0;
-            for (int c = 0; c < n_chain; ++c) weight += (ctx->elem_kind[elem_of_chain[c]] == MXE_ENTROPY_NORMAL) ? 2 : 1;
-            const int want2 = (int)std::max(1LL, (2LL * 8 * n_cu) / std::max(1LL, weight));
-            if (std::max(1, std::min(want2, n_alpha / 2)) >= want2) { f32_lv = false; ctx->opts.precision = MXE_PRECISION_F64; }
-        }
-        int wgpc_guess = (o.wg_per_cu != 1 && ctx->nwp <= 512 && NP == 64 && o.chains_per_wg != 1 && !f32_lv) ? 2 : 1;
-        for (;;) {
-            const int n_slots = 4 * wgpc_guess * n_cu;
-            // A piece of a normal-entropy scan costs about twice one of a plus-minus scan of the same length (10-18
-            // against 5 evaluations for the cold start, 3 against 2 per alpha): it counts twice, so that a slot gets
-            // two plus-minus pieces or one normal piece, not three (cfg4: 15 pieces per scan instead of 16 -- of
-            // 4096 pieces 14 % of the slots took a third --, 1.228 -> 1.171 ms; 14: 1.34 ms)
-            long long weight = 0;
-            for (int c = 0; c < n_chain; ++c) weight += (ctx->elem_kind[elem_of_chain[c]] == MXE_ENTROPY_NORMAL) ? 2 : 1;
-            // (mxe_opts.in_flight = n: the caller keeps n such batches in flight -- each fills 1 / n of the slots, with 1 / n of
-            //  the cold starts: 25 600 alpha-solves in 4 x 256 pieces of 25 alphas cost 0.65 ms side by side with three other
-            //  batches, in 15 x 256 pieces 0.83 ms alone and 0.74 ms next to one other; profiles/r04_experiments.txt 10.)
-            const long long nfl = std::max(1, o.in_flight);
-            weight *= nfl;
-            // (rounded UP when batches share the GPU: 4 pieces per scan x 4 batches 0.647 ms per batch, 3 x 4: 0.690)
-            const int want = (int)std::max(1LL, (2LL * n_slots + (nfl > 1 ? std::max(1LL, weight) - 1 : 0)) / std::max(1LL, weight));
-            split = std::max(1, std::min(want, n_alpha / 2));
-            // A batch with more scans than that rule has pieces for (two pieces per slot would be fewer than six per scan: 32 x 32
-            // elements and beyond) was left with one to four long pieces per scan, 1.1-2.3 per slot -- and a slot that takes one piece
-            // more than its neighbours then runs half a launch longer: 48 x 48 x 100 alphas 9.6 ms, 23 M alpha-solves/s, where six
-            // pieces per scan take 5.6 ms, 40.8 M (tools/batch_size_sweep.sh, profiles/r05_experiments.txt 11.).  There the count
-            // is chosen by what it costs: the cold start of a piece, 4 evaluations against 2 per alpha of its length, and the
-            // imbalance of a queue of pieces of one size, half a piece per slot.  (Batches in flight fill each other's gaps: fewest
-            // pieces, as above.)
-            if (nfl == 1 && want < 6 && n_alpha >= 16) {
-                double best = 1e300; int bs = split;
-                for (int sp = std::max(1, want); sp <= std::min(16, n_alpha / 4); ++sp) {
-                    const double len = (double)n_alpha / sp, per_slot = (double)sp * (double)weight / n_slots;
-                    const double loss = 4.0 / (4.0 + 2.0 * len) + 0.5 / per_slot;
-                    if (loss < best) { best = loss; bs = sp; }
-                }
-                split = bs;
-            }
-            // (the binary32 streaming variant stops an alpha at its rounding floor, which a cold start reaches
-            //  from further away: it keeps pieces of at least six alphas, at most 16 per scan)
-            if (o.precision == MXE_PRECISION_F32 && !f32_lv) split = std::max(1, std::min(std::min(want, 16), n_alpha / 6));
-            // two workgroups per CU pay when there is work for two rounds of them; a batch that cannot be cut
-            // into that many pieces runs at one per CU, where a round of a workgroup takes 45 k instead of 73 k
-            // cycles (the 3 200-problem shard of cfg4 / 8: 0.48 against 0.59 ms)
-            if (wgpc_guess == 2 && o.wg_per_cu == 0 && split < want) { wgpc_guess = 1; continue; }
-            break;
-        }
-        ctx->wgpc_auto = wgpc_guess;
-        ctx->mc_wgpc_hint = wgpc_guess;
-        // A launch that does not fill the GPU (one workgroup per CU: pieces at the cap of two alphas) is as long as its deepest slot,
-        // and a slot that takes a second piece pays a second cold start.  Where the uniform cut gives more pieces than slots, the
-        // plus-minus scans -- cold start 5 rounds against 12-16, 2 rounds per alpha against 2.75: a piece of twice the alphas costs
-        // what a normal-entropy piece does -- are cut into fewer, longer pieces, so that every slot gets ONE piece (the 3 200-problem
-        // shard of cfg4 / 8: 1 600 pieces on 1 024 slots -> 1 012; profiles/r04_experiments.txt).  MXE_NO_SPLIT_BY_KIND: the old cut
-        // (one workgroup per CU only.  At two per CU -- the two-GPU shard of cfg4, whose plus-minus pieces would stay short enough --
-        //  the cut by cost LOST: 0.565 -> 0.617 ms; two workgroups per CU are the throughput regime, profiles/r04_experiments.txt)
-        if (wgpc_guess == 1 && o.wg_per_cu == 0 && !getenv("MXE_NO_SPLIT_BY_KIND") && n_alpha >= 4) {
-            // (one workgroup per CU is not always a launch that does not fill the GPU -- a binary32 launch runs that way whatever its
-            //  size --: the cut is only taken when the plus-minus pieces it leaves are short, see min_pm below.  Without that test
-            //  the 25 600-problem batch in binary32 got ONE piece per plus-minus scan: 1.24 -> 3.18 ms)
-            cut_by_cost = true; slots_by_cost = 4LL * n_cu; cost_needs_short_pm = true;
-        }
-        // a small batch that cannot fill the lock-step layout (>= 768 pieces) with pieces of six alphas,
-        // but can with shorter ones, takes those: the lock-step kernel serves four pieces with the loads
-        // and the time the one-chain kernel spends on one (cfg3, 16 scans: 1.9 ms with 256 pieces in the
-        // one-chain layout, 0.7 ms with 768 pieces of two alphas in the lock-step layout)
-        if ((long long)n_chain * split < 768 && n_alpha >= 4 && (long long)n_chain * (n_alpha / 2) >= 768 &&
-            NP == 64 && o.chains_per_wg != 1 && o.tol_d <= 0.0 && o.decouple_tol > 0.0 && (o.precision == MXE_PRECISION_F64 || f32_lv))
-            split = (768 + n_chain - 1) / n_chain;
+    // ---- 6. the plan becomes the context's staged launch (a failure from here on leaves nothing staged)
+    ctx->chains_ready = false; ctx->launched = false; ctx->sel3_nc = 0; ctx->has_init = false;
+    ctx->opts = o; ctx->opts.precision = plan.precision; ctx->chi2_factor = o.chi2_factor;
+    ctx->n_chain = n_chain; ctx->n_alpha = n_alpha; ctx->chain_elem.assign(elem_of_chain, elem_of_chain + n_chain);
+    const size_t n_sub = plan.pieces.size();
+    for (auto* v : {&ctx->sub_elem, &ctx->sub_prob0, &ctx->sub_len, &ctx->sub_v0, &ctx->sub_pre, &ctx->sub_walk0}) v->resize(n_sub);
+    ctx->n_sub = (int)n_sub; ctx->has_pre = false;
+    for (size_t sc = 0; sc < n_sub; ++sc) {
+        const mxe::Piece& p = plan.pieces[sc];
+        ctx->sub_elem[sc] = p.elem; ctx->sub_prob0[sc] = p.prob0; ctx->sub_len[sc] = p.len; ctx->sub_v0[sc] = p.v0;
+        ctx->sub_pre[sc] = p.pre; ctx->sub_walk0[sc] = p.walk0; ctx->has_pre |= p.pre > 0;
     }
-    if (split > n_alpha) split = n_alpha;
-    ctx->sub_elem.clear(); ctx->sub_prob0.clear(); ctx->sub_len.clear(); ctx->sub_v0.clear();
-    // Normal entropy: from the default model the smallest alphas of a scan are far away.  Measured on the BASELINE
-    // batch (profiles/r02_f_cold_start_profile.txt), a cold start in the last 6 % of the logarithmic alpha range takes
-    // 20-30 evaluations on average and 50-390 for single scans (above that range: 10-18, at most 21) -- and a launch
-    // ends with its slowest piece.  A piece that starts there is led by the last alpha ABOVE the range: cold start
-    // where it is cheap and safe, then one warm step down to the piece's first alpha (lock-step kernel: chain_pre);
-    // in the other layouts, and where that step would be long, the piece is joined to the one before it.
-    ctx->sub_pre.clear(); ctx->has_pre = false;
-    ctx->sub_walk0.clear(); ctx->walk_alpha.clear(); ctx->has_walk = false;
-    // Launches that do not fill the GPU (cut_by_cost): such a launch is as long as its deepest slot, so the pieces are cut to equal
-    // COST and every slot gets one.  The cost of a normal-entropy piece is its cold start -- 9-10 evaluations in the upper third of
-    // the logarithmic alpha range, rising to 17-19 just above the guarded tail (profiles/r04_b_depth_by_piece.txt; the same numbers
-    // as the cold-start profile of r02) -- plus ~3 per further alpha: with the uniform pieces of two alphas the deepest slot of the
-    // 8-GPU shards was a piece at alpha index 88-92 (19 + 5 evaluations), not the led tail pieces (~22 rounds with their walk).
-    // Pieces of a normal-entropy scan therefore get as many alphas as fit MC_DEPTH_TARGET evaluations (4 at the top of the mesh, 1
-    // next to the tail) and end where the guarded range begins; the plus-minus scans (cold start ~4.5, ~2.2 per alpha) share the
-    // slots the normal-entropy pieces leave.
-    // (the same cut for the normal-entropy scans of the batch that FILLS the GPU -- targets of 34 / 38 / 42 evaluations instead of 15
-    //  uniform pieces -- was 10-13 % slower, 0.814 -> 0.894 / 0.893 / 0.917 ms: there the queue balances, profiles/r04_experiments.txt)
-    constexpr double MC_DEPTH_TARGET = 20.0;
-    auto scan_range = [&](const double* ac, double& lmax, double& lmin) {
-        lmax = -1e300; lmin = 1e300;
-        for (int i = 0; i < n_alpha; ++i) { const double l = std::log(ac[i]); lmax = std::max(lmax, l); lmin = std::min(lmin, l); }
+    ctx->has_walk = !plan.walk_alpha.empty(); ctx->walk_alpha = std::move(plan.walk_alpha); ctx->excluded = std::move(plan.excluded);
+    ctx->queue = std::move(plan.queue); ctx->wg_chains = std::move(plan.wg_chains); ctx->n_queue = (int)ctx->queue.size();
+    ctx->mc_na = plan.mc_na; ctx->mc_wgpc = plan.mc_wgpc; ctx->mc_gst = plan.mc_gst; ctx->lv_mode = plan.lv_mode;
+    ctx->wgpc_auto = plan.wgpc_auto; ctx->mc_wgpc_hint = plan.mc_wgpc_hint; ctx->n_wg = plan.n_wg; ctx->n_wg2 = plan.n_wg2; ctx->wgpc2 = plan.wgpc2;
+    ctx->n_solo = n_solo; ctx->placement_checked = placement_checked;
+    // ---- 7. buffers
+    auto put = [&](auto& buf, const auto& vec) -> hipError_t {
+        if (const hipError_t e = buf.ensure(vec.size()); e != hipSuccess || vec.empty()) return e;
+        return hipMemcpyAsync(buf.p, vec.data(), vec.size() * sizeof(vec[0]), hipMemcpyHostToDevice, ctx->stream);
     };
-    auto cost_cuts = [&](const double* ac, std::vector<int>& cuts) {          // piece starts of one normal-entropy scan (+ n_alpha)
-        double lmax, lmin;
-        scan_range(ac, lmax, lmin);
-        const double lguard = lmax - 0.94 * (lmax - lmin);
-        int lead = -1;                               // the smallest alpha above the guarded range: what leads the tail pieces
-        { double best = 1e300; for (int i = 0; i < n_alpha; ++i) if (std::log(ac[i]) >= lguard && ac[i] < best) { best = ac[i]; lead = i; } }
-        cuts.clear();
-        int a0 = 0;
-        while (a0 < n_alpha) {
-            cuts.push_back(a0);
-            const double la = std::log(ac[a0]);
-            if (lmax > lmin && la < lguard && lead >= 0 && lead < a0) break;     // (the guarded tail: one range, cut into led single alphas below)
-            const double xpos = (lmax > lmin) ? (lmax - la) / (lmax - lmin) : 0.0;
-            const double cold = 9.5 + 13.0 * std::max(0.0, xpos - 0.3);
-            int L = 1 + (int)std::floor(std::max(0.0, (MC_DEPTH_TARGET - cold) / 3.0));
-            L = std::max(1, std::min(L, 6));
-            int a1 = std::min(n_alpha, a0 + L);
-            for (int j = a0 + 1; j < a1; ++j) if (lmax > lmin && std::log(ac[j]) < lguard && lead >= 0 && lead < j) { a1 = j; break; }
-            a0 = a1;
-        }
-        cuts.push_back(n_alpha);
-    };
-    // plus-minus scans: cold start ~4.5 evaluations, then 2 per alpha at the top of the mesh and 3 at its bottom -- with uniform pieces of
-    // seven alphas the deepest slot of the four-GPU shards was a plus-minus piece at the smallest alphas (4.6 + 7 x 3.0 = 26 rounds).
-    // At most `pieces` pieces of equal cost: the smallest cost per piece that needs no more (bisection)
-    auto pm_cuts = [&](const double* ac, int pieces, std::vector<int>& cuts) {
-        double lmax, lmin;
-        scan_range(ac, lmax, lmin);
-        auto w = [&](int a) { return 2.0 + ((lmax > lmin) ? (lmax - std::log(ac[a])) / (lmax - lmin) : 0.0); };
-        auto cut = [&](double T, std::vector<int>* out) {
-            int n = 0, a0 = 0;
-            while (a0 < n_alpha) {
-                if (out) out->push_back(a0);
-                double cost = 4.5 + w(a0);
-                int a1 = a0 + 1;
-                while (a1 < n_alpha && cost + w(a1) <= T) { cost += w(a1); ++a1; }
-                a0 = a1; ++n;
-            }
-            return n;
-        };
-        double lo = 6.0, hi = 4.5 + 3.0 * n_alpha + 1.0;
-        for (int it = 0; it < 40 && hi - lo > 0.05; ++it) {
-            const double mid = 0.5 * (lo + hi);
-            if (cut(mid, nullptr) <= pieces) hi = mid; else lo = mid;
-        }
-        cuts.clear();
-        cut(hi, &cuts);
-        cuts.push_back(n_alpha);
-    };
-    if (cut_by_cost) {
-        long long n_normal = 0, pieces_normal = 0;
-        std::vector<int> cuts;
-        for (int c = 0; c < n_chain; ++c)
-            if (ctx->elem_kind[elem_of_chain[c]] == MXE_ENTROPY_NORMAL) {
-                ++n_normal;
-                cost_cuts(alpha_dev.data() + (size_t)c * n_alpha, cuts);
-                pieces_normal += (long long)cuts.size() - 2 + (n_alpha - cuts[cuts.size() - 2]);      // (the last range: one piece per alpha if it is the guarded tail -- an upper bound otherwise)
-            }
-        const long long n_pm = n_chain - n_normal;
-        // (a plus-minus piece of eight or nine alphas costs ~4.5 + 8 x 2.5 = 24 evaluations: the depth of the led tail pieces.  The
-        //  cut is for launches whose plus-minus pieces stay that short: the four-GPU shard of cfg4 -- 14 pieces per scan -- does,
-        //  cfg4 itself does not)
-        const long long min_pm = cost_needs_short_pm ? (n_alpha + 8) / 9 : 1;       // (at most nine alphas per plus-minus piece)
-        if (pieces_normal + n_pm * min_pm <= slots_by_cost) {
-            if (n_pm > 0) split_pm = (int)std::max(1LL, std::min<long long>(n_alpha / 2, (slots_by_cost - pieces_normal) / n_pm));
-        } else cut_by_cost = false;                  // (more scans than slots can take one piece of each: the uniform cut)
-    }
-    constexpr double MC_LADDER_COARSE = 2.0;      // a step between neighbouring alphas beyond this factor is not taken in one go (measured: up to a factor ~1.5 a warm step is safe, over a factor 2 single scans took 100-300 evaluations; 1.6 here cost stress case 51 -- ratio 1.66, sigma 1e-5 -- two converged flags and 3 x the time)
-    const double MC_LADDER_RATIO = getenv("MXE_LADDER_RATIO") ? std::max(1.05, atof(getenv("MXE_LADDER_RATIO"))) : 1.56;      // ratio of the rungs (just above MXE_X_WALK_RATIO: the walk lands on every rung)
-    constexpr int MC_LADDER_MAX = 28;             // rungs per piece (the slot's alpha table holds 32 entries)
-    const bool ladder_ok = !getenv("MXE_NO_LADDER") && NP == 64 && o.chains_per_wg != 1 && o.tol_d <= 0.0 && o.decouple_tol > 0.0 &&
-                           (o.precision == MXE_PRECISION_F64 || f32_lv);
-    for (int c = 0; c < n_chain; ++c) {
-        const double* ac = alpha_dev.data() + (size_t)c * n_alpha;
-        double pre_alpha = 0.0, lguard = 0.0;
-        int pre_index = -1;
-        const bool normal_c = ctx->elem_kind[elem_of_chain[c]] == MXE_ENTROPY_NORMAL;
-        const double hard_below = 0.25 * ctx->ds[ctx->elem_ds[elem_of_chain[c]]].n_rows;      // alpha~ below N_data / 4
-        if (normal_c && split > 1) {
-            double lmax, lmin;
-            scan_range(ac, lmax, lmin);
-            lguard = lmax - 0.94 * (lmax - lmin);
-            double best = 1e300;                     // the smallest alpha of the scan that is still above the guarded range
-            for (int i = 0; i < n_alpha; ++i) if (std::log(ac[i]) >= lguard && ac[i] < best) { best = ac[i]; pre_index = i; }
-            if (lmax > lmin && best < 1e300) pre_alpha = best;
-        }
-        std::vector<int> cuts;
-        if (cut_by_cost && normal_c && split > 1) cost_cuts(ac, cuts);
-        else if (cut_by_cost && !normal_c && split_pm > 1 && split_pm < n_alpha / 2) pm_cuts(ac, split_pm, cuts);      // (at the cap of two alphas there is nothing to balance)
-        else {
-            const int split_c = (split_pm > 0 && !normal_c) ? std::min(split_pm, n_alpha) : split;
-            // (taper: the pieces of a scan grow from its first alpha to its last -- piece i of n has 1 + (taper - 1) i / (n - 1) parts --
-            //  so that what the queue hands out LAST, the cheap short pieces at the top of the mesh, evens the workgroups out;
-            //  1 = pieces of equal length)
-            const double taper = piece_taper(o, ctx->mc_wgpc_hint);
-            if (taper != 1.0 && split_c > 1) {
-                std::vector<double> wsum(split_c + 1, 0.0);
-                for (int i = 0; i < split_c; ++i) wsum[i + 1] = wsum[i] + 1.0 + (taper - 1.0) * i / (split_c - 1);
-                for (int sidx = 0; sidx <= split_c; ++sidx) {
-                    int a = (int)std::llround(n_alpha * wsum[sidx] / wsum[split_c]);
-                    a = std::max(a, sidx == 0 ? 0 : cuts.back() + 1);          // (no empty piece)
-                    a = std::min(a, n_alpha - (split_c - sidx));
-                    if (sidx == split_c) a = n_alpha;
-                    if (cuts.empty() || a > cuts.back()) cuts.push_back(a);
-                }
-            } else
-            for (int sidx = 0; sidx <= split_c; ++sidx) {
-                const int a = (int)((long long)n_alpha * sidx / split_c);
-                if (cuts.empty() || a > cuts.back()) cuts.push_back(a);
-            }
-        }
-        for (size_t sidx = 0; sidx + 1 < cuts.size(); ++sidx) {
-            const int a0 = cuts[sidx], a1 = cuts[sidx + 1];
-            if (a1 <= a0) continue;
-            const bool guarded = pre_alpha > 0.0 && sidx > 0 && std::log(ac[a0]) < lguard && pre_index < a0;
-            // (the warm step from the leading alpha is safe over a factor of 1.5 in alpha -- measured: at most 11
-            //  evaluations; over a factor of 2 single scans took 100-300 --: deeper into the range, the piece
-            //  before runs on instead)
-            // (lock-step kernel: the piece WALKS from the leading alpha down the mesh to its first alpha with a loose
-            //  tolerance -- every step as safe as the scan itself --, so every piece of the tail stands alone and the tail
-            //  of a scan is as many short chains side by side as it has pieces.  A jump over more than a factor 1.5 in
-            //  alpha -- single scans took 100-300 evaluations over a factor 2 -- was what joined pieces until r02_k)
-            // (a led piece is cut into single alphas: each walks down from the leading alpha on its own, and the tail of
-            //  the scan -- the longest chain of every launch that does not fill the GPU -- is as deep as ONE walk)
-            // (a piece that starts above the range and runs into it stays whole: cutting it where it enters cost the
-            //  batch that fills the GPU 6 % -- cfg4 on one GPU 0.947 -> 1.01 ms)
-            const int g0 = guarded ? a0 : a1;
-            auto emit = [&](int first, int len, int pre, int walk0) {
-                ctx->sub_elem.push_back(elem_of_chain[c]);
-                ctx->sub_prob0.push_back(c * n_alpha + first);
-                ctx->sub_len.push_back(len);
-                ctx->sub_v0.push_back(c);
-                ctx->sub_pre.push_back(pre);
-                ctx->sub_walk0.push_back(walk0);
-                if (pre > 0) ctx->has_pre = true;
-            };
-            // A mesh too coarse to walk on (round 5).  The warm step into an alpha is safe over a factor ~1.5 in alpha; the reference's
-            // own tests and defaults use 3-20 alphas over 4-6 decades (alpha_meshes.py:81, test/python/tau_maxent.py:44), and
-            // where the entropy term no longer holds the solution (alpha~ below about N_data / 4) a step over a factor 2 ... 600 took
-            // 250-2 300 evaluations (profiles/r05_b_coarse_mesh.txt: smoke()'s last alpha 913 of the launch's 308 rounds).  Such an
-            // alpha is a piece of its own that starts cold where that is cheap -- at max(N_data / 4, its own alpha) -- and walks down a
-            // LADDER of alphas of its own (ratio MC_LADDER_RATIO, a few loose rounds per rung, no records) to its alpha: all hard
-            // alphas of a scan side by side, each as deep as one cold start + one walk.
-            auto hard = [&](int i) {
-                if (!ladder_ok || i < 0 || i >= n_alpha) return false;
-                const double a = ac[i];
-                if (!(a < hard_below)) return false;
-                if (i == 0) return false;                  // (the head of a scan starts from the default model as ever)
-                const double r = ac[i - 1] / a;
-                return r > MC_LADDER_COARSE || r < 1.0 / MC_LADDER_COARSE;
-            };
-            auto emit_ladder = [&](int i, int len = 1) {
-                const double a = ac[i];
-                const double top = std::max(hard_below, a * MC_LADDER_RATIO);
-                int rungs = (int)std::ceil(std::log(top / a) / std::log(MC_LADDER_RATIO) - 1e-9);
-                rungs = std::max(1, std::min(rungs, std::min(MC_LADDER_MAX, 30 - len)));      // (rungs + alphas of the piece: the slot's table of 32)
-                const double ratio = std::pow(top / a, 1.0 / rungs);          // (equal rungs; more than MC_LADDER_MAX would not fit the slot's table)
-                const int w0 = (int)ctx->walk_alpha.size();
-                for (int k = 0; k < rungs; ++k) ctx->walk_alpha.push_back(a * std::pow(ratio, rungs - k));
-                emit(i, len, rungs, w0);
-                ctx->has_walk = true;
-            };
-            // A piece whose FIRST alpha is its hardest: the head of a scan that begins deep in the hard region, and every piece of an
-            // ASCENDING scan there (each starts from the default model at its smallest alpha: on 150 alphas rising from alpha~ = 0.5 at
-            // sigma = 4e-5 the head took 2 989 evaluations and did not converge, tools/stress.py case 17).  It is led down a ladder from
-            // N_data / 4 to its first alpha and goes on up its own mesh from there.
-            auto emit_plain = [&](int first, int len) {
-                const bool deep = ladder_ok && len <= 24 && ac[first] * (MC_LADDER_RATIO * MC_LADDER_RATIO) < hard_below &&
-                                  (first == 0 || ac[first - 1] < ac[first]);
-                if (deep) emit_ladder(first, len);
-                else emit(first, len, 0, -1);
-            };
-            {
-                // the part of the piece that is not led: cut at every hard alpha
-                int b = a0;
-                for (int i = a0; i < g0; ++i)
-                    if (hard(i)) {
-                        if (i > b) emit_plain(b, i - b);
-                        emit_ladder(i);
-                        b = i + 1;
-                    }
-                if (g0 > b) emit_plain(b, g0 - b);
-            }
-            for (int b0 = g0; b0 < a1; ++b0) {
-                if (hard(b0)) emit_ladder(b0);
-                else emit(b0, 1, b0 - pre_index, -1);
-            }
-        }
-    }
-    ctx->n_sub = (int)ctx->sub_elem.size();
-    // ---- layout: four chains of one data set per workgroup wherever the lock-step kernel has a build for the
-    //      problem -- also for a handful of pieces: its round (four chains) takes no longer than an iteration of the
-    //      one-chain kernel (one), and a single scan of 100 alphas in 50 pieces runs in 0.45 ms against 0.94 ms
-    //      (profiles/r02_k_small_batches.txt; until r02_j: only from 768 pieces on)
-    int layout = o.chains_per_wg;
-    ctx->mc_na = 0;
-    if (layout == 0) layout = 4;
-    if (layout == 4 && (NP != 64 || o.tol_d > 0.0 || o.decouple_tol <= 0.0 || (o.precision != MXE_PRECISION_F64 && !f32_lv))) layout = 1;
-    if (layout == 4) {
-        // capacity of the active block: the kernel clamps n_act to NA, and the
-        // first neglected direction couples with relative strength
-        // c_NA^2 wmax / alpha (wmax <= sum w ~ max(1, sum D)); accept NA when that
-        // is below MC_COUPLING_MAX for every chain (inexact Newton: the contraction is that number, and the stopping
-        // estimate of the kernel does not know about it -- an alpha stops when (e^{|du|} - 1 + theta) relH < tol_h, so its
-        // last correction relH may be as large as tol_h / theta = 1e-4 and what the neglected direction leaves behind is
-        // coupling x relH.  With 1e-2, the value until r03, converged alphas of launches AT that limit were 1.1e-6 ... 1.6e-6
-        // from their fixed points (profiles/r03_i_small_sigma.txt); 1e-3 keeps a factor ten to the 1e-6 of the audit).
-        double worst32 = 0.0, worst48 = 0.0;
-        for (int sc = 0; sc < ctx->n_sub; ++sc) {
-            const int e = ctx->sub_elem[sc];
-            const DataSet& DS = ctx->ds[ctx->elem_ds[e]];
-            double amin = 1e300;
-            for (int i = 0; i < ctx->sub_len[sc]; ++i) amin = std::min(amin, alpha_dev[ctx->sub_prob0[sc] + i]);
-            const double wbound = std::max(1.0, ctx->h_sumD[e]);
-            if (ns > 32) worst32 = std::max(worst32, DS.c[32] * DS.c[32] * wbound / amin);
-            if (ns > 48) worst48 = std::max(worst48, DS.c[48] * DS.c[48] * wbound / amin);
-        }
-        // (an active block of 48 in the lock-step kernel spilled registers in every tiling that was tried: problems
-        //  that couple more than 32 directions run in the one-chain layout, whose solve lives in LDS)
-        (void)worst48;
-        ctx->excluded.clear();
-        if (worst32 <= MC_COUPLING_MAX) ctx->mc_na = 32;
-        else if (f32_lv) layout = 1;      // (chain_kernel_lv has the plain 32-row build only: the one-chain binary32 kernel, BEFORE any piece is cut or dropped below)
-        else {
-            // Some alphas couple more than 32 directions (very small error bars: sigma = 1e-6 on the BASELINE grids does at
-            // the 27 smallest of 100 alphas).  Until r03 the whole launch then went to the one-chain layout (7 x slower).
-            // (a) Plus-minus scans: the build with a 64-row active block -- ten Gram tiles per slot (80 KB of the LDS: one
-            // workgroup per CU, n_omega_pad <= 512) and the one-row-per-lane elimination (gj1_solve_rows_f32).  240
-            // off-diagonal scans x 100 alphas at sigma = 4e-6 ... 5e-7: 2.2 / 3.5 / 3.8 / 4.4 ms, nothing left over, audit
-            // 5e-10 (one-chain layout: 12.8 ms).  (b) Normal-entropy scans: their systems at those alphas are ill conditioned
-            // beyond what the binary16 Gram products of either lock-step build resolve (the iteration crawls to its limit
-            // where the one-chain kernel, binary64 throughout, takes 3-28 steps): their pieces are cut where the criterion
-            // fails -- coupling grows as alpha falls, so that is the tail of a scan -- and the alphas behind the cut are left
-            // open for mxe_chains_finish: one warm chain per scan from the last alpha before the cut (records of such alphas
-            // are NaN / not converged / 0 iterations until then: clear_excluded_kernel).  Without the 64-row build (a larger
-            // frequency mesh) the plus-minus scans are cut as well.  Measured on the BASELINE batch (16 diagonal + 240
-            // off-diagonal scans) with sigma = 4e-6 / 2e-6 / 1e-6 (maxiter 100): 15.4 / 17.1 / 146 ms in the one-chain
-            // layout, 8-12 / 11-16 / 55-63 ms in every variant of this -- the serial depth of the 16 finishing chains (13-30
-            // alphas x 3-28 iterations x 150-190 us in the one-chain kernel with 64 coupled directions) is the floor.
-            // Leaving the cut alphas to the lock-step kernel's own give-up costs accuracy in the 32-row build (exact Newton
-            // correction up to 9e-7, p99 1e-7, against 4e-8 / 2e-9) and time in the 64-row build (pieces of 10 alphas x 32
-            // iterations: launch 8-9 ms).  Not when more than a third of the alphas would be left to the finishing pass
-            // (sigma = 5e-7 without the 64-row build: 197 against 150 ms).  profiles/r03_c_cut_pieces.txt, r03_e_na64.txt
-            const bool have64 = !getenv("MXE_NO_NA64") && ns > 32 && o.wg_per_cu != 2 && mc_lds_bytes(64, ctx->nwp, 1) <= 160 * 1024 - 6144;
-            bool need64 = false;
-            std::vector<char> bad(P, 0);
-            size_t n_bad = 0;
-            for (int c = 0; c < n_chain; ++c) {
-                const int e = elem_of_chain[c];
-                const DataSet& DS = ctx->ds[ctx->elem_ds[e]];
-                const double lim = MC_COUPLING_MAX / (DS.c[32] * DS.c[32] * std::max(1.0, ctx->h_sumD[e]));    // alpha >= 1 / lim passes
-                const bool to64 = have64 && ctx->elem_kind[e] != MXE_ENTROPY_NORMAL;
-                for (int i = 0; i < n_alpha; ++i)
-                    if (!(alpha_dev[(size_t)c * n_alpha + i] * lim >= 1.0)) {
-                        if (to64) need64 = true;
-                        else { bad[(size_t)c * n_alpha + i] = 1; ++n_bad; }
-                    }
-            }
-            if (3 * n_bad > P) layout = 1;
-            else {
-                ctx->mc_na = need64 ? 64 : 32;
-                std::vector<char> covered(P, 0);
-                size_t w = 0;
-                for (size_t sc = 0; sc < ctx->sub_elem.size(); ++sc) {
-                    const int p0 = ctx->sub_prob0[sc];
-                    int len = 0;
-                    while (len < ctx->sub_len[sc] && !bad[(size_t)p0 + len]) ++len;
-                    // (a led piece starts from an alpha above its own: larger, so it passes when the piece's does)
-                    if (len == 0) continue;
-                    for (int i = 0; i < len; ++i) covered[(size_t)p0 + i] = 1;
-                    ctx->sub_elem[w] = ctx->sub_elem[sc]; ctx->sub_prob0[w] = p0; ctx->sub_len[w] = len;
-                    ctx->sub_v0[w] = ctx->sub_v0[sc]; ctx->sub_pre[w] = ctx->sub_pre[sc]; ctx->sub_walk0[w] = ctx->sub_walk0[sc]; ++w;
-                }
-                if (w == 0) { ctx->mc_na = 0; layout = 1; }
-                else {
-                    ctx->sub_elem.resize(w); ctx->sub_prob0.resize(w); ctx->sub_len.resize(w); ctx->sub_v0.resize(w); ctx->sub_pre.resize(w); ctx->sub_walk0.resize(w);
-                    ctx->n_sub = (int)w;
-                    ctx->has_pre = false;
-                    for (size_t sc = 0; sc < w; ++sc) ctx->has_pre = ctx->has_pre || ctx->sub_pre[sc] > 0;
-                    for (size_t i = 0; i < P; ++i) if (!covered[i]) ctx->excluded.push_back((int)i);
-                }
-            }
-        }
-        if (layout == 4) {
-            ctx->mc_wgpc = (o.wg_per_cu != 1 && (o.wg_per_cu == 2 || ctx->wgpc_auto == 2) && ctx->mc_na == 32 && ctx->nwp <= 512 &&
-                            mc_lds_bytes(32, ctx->nwp, 2) <= 80 * 1024 - 2048) ? 2 : 1;
-            ctx->mc_gst = false;
-            if (mc_lds_bytes(ctx->mc_na, ctx->nwp, ctx->mc_wgpc) > 160 * 1024 - 6144) {
-                // a frequency mesh whose state (u, H, sw of four slots: 80 B per omega) does not fit the LDS beside the
-                // rest: the state goes to device memory (chain_kernel_mc<.., GSTATE>, one workgroup per CU)
-                ctx->mc_wgpc = 1; ctx->mc_gst = true;
-            }
-        }
-    }
-    if (layout == 4 && f32_lv) {
-        // the binary32 launch: only the plain 32-row layout with nothing cut has a build in chain_kernel_lv
-        // (anything else was sent to the one-chain layout above, before the pieces were touched: r04's first form of this fell back
-        //  HERE, after pieces of a 64-row launch had been cut -- the alphas behind the cuts were never solved, their records garbage:
-        //  STRESS_F32=1 tools/stress.py, cases 24 / 25 / 42)
-        if (ctx->mc_na == 32 && ctx->excluded.empty() && !ctx->mc_gst) { ctx->lv_mode = 1; ctx->mc_wgpc = 1; }
-        else return MXE_ERR_STATE;
-    }
-    if (layout != 4 && ctx->has_pre) {
-        size_t w = 0;
-        for (size_t sc = 0; sc < ctx->sub_elem.size(); ++sc) {
-            if (ctx->sub_pre[sc] > 0 && w > 0 && ctx->sub_v0[w - 1] == ctx->sub_v0[sc]) { ctx->sub_len[w - 1] += ctx->sub_len[sc]; continue; }
-            ctx->sub_elem[w] = ctx->sub_elem[sc]; ctx->sub_prob0[w] = ctx->sub_prob0[sc]; ctx->sub_len[w] = ctx->sub_len[sc];
-            ctx->sub_v0[w] = ctx->sub_v0[sc]; ++w;
-        }
-        ctx->sub_elem.resize(w); ctx->sub_prob0.resize(w); ctx->sub_len.resize(w); ctx->sub_v0.resize(w);
-        ctx->sub_pre.assign(w, 0); ctx->has_pre = false;
-        ctx->sub_walk0.assign(w, -1); ctx->has_walk = false;
-        ctx->n_sub = (int)w;
-    }
-    ctx->wg_chains.clear(); ctx->queue.clear(); ctx->n_queue = 0; ctx->n_solo = 0; ctx->placement_checked = 0;
-    if (layout == 4) {
-        bool one_ds = true;
-        for (int sc = 1; sc < ctx->n_sub; ++sc)
-            if (ctx->elem_ds[ctx->sub_elem[sc]] != ctx->elem_ds[ctx->sub_elem[0]]) { one_ds = false; break; }
-        if (one_ds) {
-            // dynamic layout: a persistent grid takes pieces from a queue, most
-            // expensive first (normal entropy and small alpha cost more iterations)
-            std::vector<double> cost(ctx->n_sub);
-            for (int sc = 0; sc < ctx->n_sub; ++sc) {
-                const int e = ctx->sub_elem[sc];
-                double amin = 1e300;
-                for (int i = 0; i < ctx->sub_len[sc]; ++i) amin = std::min(amin, alpha_dev[ctx->sub_prob0[sc] + i]);
-                cost[sc] = ctx->sub_len[sc] * (ctx->elem_kind[e] == MXE_ENTROPY_NORMAL ? 4.0 : 3.0) +
-                           (ctx->elem_kind[e] == MXE_ENTROPY_NORMAL ? 16.0 : 6.0) - 1e-3 * std::log10(amin) +
-                           (ctx->sub_walk0[sc] >= 0 ? 2.0 : 0.7) * ctx->sub_pre[sc];     // (the walk of a led piece: on the scan's mesh a landing every ~third alpha, MXE_X_WALK_RATIO; on a ladder every rung)
-            }
-            ctx->queue.resize(ctx->n_sub);
-            for (int sc = 0; sc < ctx->n_sub; ++sc) ctx->queue[sc] = sc;
-            std::stable_sort(ctx->queue.begin(), ctx->queue.end(), [&](int a, int b) { return cost[a] > cost[b]; });
-            ctx->n_queue = ctx->n_sub;
-            hipDeviceProp_t prop;
-            HIPCHK(ctx, hipGetDeviceProperties(&prop, ctx->device));
-            const int n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-            ctx->n_wg = std::min((ctx->n_sub + 3) / 4, n_cu * ctx->mc_wgpc);
-            // The launch ends with its longest pieces: the last pieces of the normal-entropy scans (the most expensive
-            // cold start, the most evaluations per alpha).  They are at the head of the queue; with two workgroups per
-            // CU, the workgroups that take them get a CU to themselves -- workgroups b and b + n_wg / 2 share one
-            // (tools/wg_placement.hip), the partners leave at once --, where a round takes 47 k instead of 69 k cycles
-            // (cfg4, 16 such pieces in four workgroups: kernel 1.150 -> 1.123 ms; 16 workgroups 1.130, 64: 1.21).
-            // The library's own schedule only.
-            if (o.alpha_split == 0 && ctx->mc_wgpc == 2 && ctx->n_wg == 2 * n_cu) {
-                int n_tail = 0;
-                for (int sc = 0; sc < ctx->n_sub; ++sc)
-                    if (ctx->elem_kind[ctx->sub_elem[sc]] == MXE_ENTROPY_NORMAL &&
-                        ctx->sub_prob0[sc] + ctx->sub_len[sc] == (ctx->sub_v0[sc] + 1) * n_alpha) ++n_tail;
-                ctx->n_solo = std::min((n_tail + 3) / 4, n_cu / 32);
-                // (only where workgroups b and b + n_wg / 2 do share a CU on this device: probed once, see placement_rule_holds)
-                bool holds = false;
-                if (ctx->n_solo > 0) { const int rp = placement_rule_holds(ctx, n_cu, &holds); if (rp != MXE_OK) return rp; }
-                ctx->placement_checked = holds ? 1 : 2;
-                if (!holds) ctx->n_solo = 0;
-            }
-            // A binary64 launch that does not fill the GPU (one workgroup per CU by the rule above) is as long as its
-            // deepest chain of rounds: its first pass runs in chain_kernel_lv -- binary32, V^T in LDS, a round in a
-            // fraction of the time --, every alpha to LV_TOL1, and the binary64 kernel then takes every alpha as a piece
-            // of its own from that v: P pieces of one alpha, start vector = the record of the first pass
-            if (lv_fits && o.precision == MXE_PRECISION_F64 && ctx->mc_na == 32 && !ctx->mc_gst && ctx->excluded.empty() &&
-                o.lds_basis == 1) {
-                ctx->lv_mode = 2;
-                ctx->mc_wgpc = 1; ctx->n_solo = 0;
-                ctx->n_wg = std::min((ctx->n_sub + 3) / 4, n_cu);
-                const int P2 = (int)P;
-                std::vector<int> e2(P2), p2(P2), l2(P2, 1);
-                for (int i = 0; i < P2; ++i) { e2[i] = elem_of_chain[i / n_alpha]; p2[i] = i; }
-                ctx->wgpc2 = (o.wg_per_cu != 1 && (P2 + 3) / 4 >= 2 * n_cu && mc_lds_bytes(32, ctx->nwp, 2) <= 80 * 1024 - 2048) ? 2 : 1;
-                ctx->n_wg2 = std::min((P2 + 3) / 4, n_cu * ctx->wgpc2);
-                HIPCHK(ctx, ctx->d2_elem.ensure(P2)); HIPCHK(ctx, ctx->d2_prob0.ensure(P2));
-                HIPCHK(ctx, ctx->d2_len.ensure(P2)); HIPCHK(ctx, ctx->d2_v0.ensure(P2)); HIPCHK(ctx, ctx->d2_queue.ensure(P2));
-                HIPCHK(ctx, ctx->dcnt1_niter.ensure(P2)); HIPCHK(ctx, ctx->dcnt1_nevals.ensure(P2));
-                HIPCHK(ctx, hipMemcpyAsync(ctx->d2_elem.p, e2.data(), (size_t)P2 * 4, hipMemcpyHostToDevice, ctx->stream));
-                HIPCHK(ctx, hipMemcpyAsync(ctx->d2_prob0.p, p2.data(), (size_t)P2 * 4, hipMemcpyHostToDevice, ctx->stream));
-                HIPCHK(ctx, hipMemcpyAsync(ctx->d2_v0.p, p2.data(), (size_t)P2 * 4, hipMemcpyHostToDevice, ctx->stream));
-                HIPCHK(ctx, hipMemcpyAsync(ctx->d2_queue.p, p2.data(), (size_t)P2 * 4, hipMemcpyHostToDevice, ctx->stream));
-                HIPCHK(ctx, hipMemcpyAsync(ctx->d2_len.p, l2.data(), (size_t)P2 * 4, hipMemcpyHostToDevice, ctx->stream));
-                HIPCHK(ctx, stream_wait(ctx->stream));          // (the host vectors go out of scope)
-            }
-        } else {
-            // static layout (several data sets: a workgroup streams ONE basis, its four pieces come from one data set and it takes no
-            // others): group by data set, four per workgroup, -1 pads.  The four pieces of a workgroup run in lock-step until the
-            // longest is through, so pieces of like cost go together (the estimate the queue of the one-data-set launch is ordered
-            // by), and the workgroups with the longest pieces are dispatched first: with a data set per element the BASELINE batch
-            // 2.13 -> 1.29 ms, with two data sets 1.42 -> 0.95 (tools/many_datasets.py, profiles/r05_experiments.txt 12.)
-            std::vector<double> cost(ctx->n_sub);
-            for (int sc = 0; sc < ctx->n_sub; ++sc) {
-                const int e = ctx->sub_elem[sc];
-                double amin = 1e300;
-                for (int i = 0; i < ctx->sub_len[sc]; ++i) amin = std::min(amin, alpha_dev[ctx->sub_prob0[sc] + i]);
-                cost[sc] = ctx->sub_len[sc] * (ctx->elem_kind[e] == MXE_ENTROPY_NORMAL ? 4.0 : 3.0) +
-                           (ctx->elem_kind[e] == MXE_ENTROPY_NORMAL ? 16.0 : 6.0) - 1e-3 * std::log10(amin) +
-                           (ctx->sub_walk0[sc] >= 0 ? 2.0 : 0.7) * ctx->sub_pre[sc];
-            }
-            std::vector<std::vector<int>> by_ds(ctx->ds.size());
-            for (int sc = 0; sc < ctx->n_sub; ++sc) by_ds[ctx->elem_ds[ctx->sub_elem[sc]]].push_back(sc);
-            std::vector<std::pair<double, std::array<int, 4>>> wgs;
-            const bool sorted = !getenv("MXE_NO_SORTED_STATIC");
-            for (auto& g : by_ds) {
-                if (sorted) std::stable_sort(g.begin(), g.end(), [&](int a, int b) { return cost[a] > cost[b]; });
-                for (size_t i0 = 0; i0 < g.size(); i0 += 4) {
-                    std::array<int, 4> w4;
-                    for (int q = 0; q < 4; ++q) w4[q] = i0 + q < g.size() ? g[i0 + q] : -1;
-                    wgs.emplace_back(cost[g[i0]], w4);
-                }
-            }
-            if (sorted) std::stable_sort(wgs.begin(), wgs.end(), [](const auto& a, const auto& b) { return a.first > b.first; });
-            for (auto& w : wgs) for (int q = 0; q < 4; ++q) ctx->wg_chains.push_back(w.second[q]);
-            ctx->n_wg = (int)ctx->wg_chains.size() / 4;
-        }
-    } else {
-        ctx->n_wg = ctx->n_sub;
-    }
-    HIPCHK(ctx, ctx->dqueue.ensure(std::max<size_t>(ctx->queue.size(), 1)));
-    HIPCHK(ctx, ctx->dcounter.ensure(2));
-    if (!ctx->queue.empty())
-        HIPCHK(ctx, hipMemcpyAsync(ctx->dqueue.p, ctx->queue.data(), ctx->queue.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, ctx->dchain_elem.ensure(ctx->n_sub));
-    HIPCHK(ctx, ctx->dsub_prob0.ensure(ctx->n_sub));
-    HIPCHK(ctx, ctx->dsub_len.ensure(ctx->n_sub));
-    HIPCHK(ctx, ctx->dsub_v0.ensure(ctx->n_sub));
-    HIPCHK(ctx, ctx->dsub_pre.ensure(std::max(ctx->n_sub, 1)));
-    HIPCHK(ctx, ctx->dwg_chains.ensure(std::max<size_t>(ctx->wg_chains.size(), 1)));
-    HIPCHK(ctx, ctx->dalpha.ensure(P));
-    HIPCHK(ctx, ctx->dv0.ensure(hv0.size()));
-    HIPCHK(ctx, ctx->dout_v.ensure(P * NP));
+    HIPCHK(ctx, ctx->dcounter.ensure(2)); HIPCHK(ctx, put(ctx->dqueue, ctx->queue)); HIPCHK(ctx, put(ctx->dwg_chains, ctx->wg_chains));
+    HIPCHK(ctx, put(ctx->dchain_elem, ctx->sub_elem)); HIPCHK(ctx, put(ctx->dsub_prob0, ctx->sub_prob0));
+    HIPCHK(ctx, put(ctx->dsub_len, ctx->sub_len)); HIPCHK(ctx, put(ctx->dsub_v0, ctx->sub_v0));
+    HIPCHK(ctx, ctx->dsub_pre.ensure(n_sub));
+    if (ctx->has_pre || ctx->mc_gst) HIPCHK(ctx, put(ctx->dsub_pre, ctx->sub_pre));     // (the device-memory-state build is the LEAD build: it reads the array)
+    if (ctx->has_walk && ctx->has_pre) { HIPCHK(ctx, put(ctx->dsub_walk0, ctx->sub_walk0)); HIPCHK(ctx, put(ctx->dwalk_alpha, ctx->walk_alpha)); }
+    if (!ctx->excluded.empty()) HIPCHK(ctx, put(ctx->dexcluded, ctx->excluded));
+    HIPCHK(ctx, put(ctx->dalpha, alpha_dev)); HIPCHK(ctx, put(ctx->dv0, hv0)); HIPCHK(ctx, ctx->dout_v.ensure(P * NP));
     // one allocation: H [P][nw] | chi2 S Q [3P] | H of the analyzer's alpha [n_chain][nw] | its index [n_chain]
     // (everything behind H is the COMPACT result pack that a gather between GPUs moves)
     HIPCHK(ctx, ctx->dout_pack.ensure(P * nw + 3 * P + (size_t)n_chain * (nw + 1)));
     ctx->result_buffer = 0;
-    ctx->dout_H.p = ctx->dout_pack.p;
-    ctx->dout_chi2.p = ctx->dout_pack.p + P * nw;
-    ctx->dout_S.p = ctx->dout_chi2.p + P;
-    ctx->dout_Q.p = ctx->dout_S.p + P;
-    HIPCHK(ctx, ctx->dout_niter.ensure(3 * P));
-    ctx->dout_conv.p = ctx->dout_niter.p + P;
-    ctx->dout_nevals.p = ctx->dout_conv.p + P;
-    HIPCHK(ctx, ctx->dout_nact.ensure(P));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->dchain_elem.p, ctx->sub_elem.data(), (size_t)ctx->n_sub * 4, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->dsub_prob0.p, ctx->sub_prob0.data(), (size_t)ctx->n_sub * 4, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->dsub_len.p, ctx->sub_len.data(), (size_t)ctx->n_sub * 4, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->dsub_v0.p, ctx->sub_v0.data(), (size_t)ctx->n_sub * 4, hipMemcpyHostToDevice, ctx->stream));
-    if (ctx->has_pre || ctx->mc_gst)     // (the device-memory-state build is the LEAD build: it reads the array)
-        HIPCHK(ctx, hipMemcpyAsync(ctx->dsub_pre.p, ctx->sub_pre.data(), (size_t)ctx->n_sub * 4, hipMemcpyHostToDevice, ctx->stream));
-    if (ctx->has_walk && ctx->has_pre) {
-        HIPCHK(ctx, ctx->dsub_walk0.ensure(std::max(ctx->n_sub, 1)));
-        HIPCHK(ctx, ctx->dwalk_alpha.ensure(std::max<size_t>(ctx->walk_alpha.size(), 1)));
-        HIPCHK(ctx, hipMemcpyAsync(ctx->dsub_walk0.p, ctx->sub_walk0.data(), (size_t)ctx->n_sub * 4, hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(ctx->dwalk_alpha.p, ctx->walk_alpha.data(), ctx->walk_alpha.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+    ctx->dout_H.p = ctx->dout_pack.p; ctx->dout_chi2.p = ctx->dout_pack.p + P * nw;
+    ctx->dout_S.p = ctx->dout_chi2.p + P; ctx->dout_Q.p = ctx->dout_S.p + P;
+    HIPCHK(ctx, ctx->dout_niter.ensure(3 * P)); HIPCHK(ctx, ctx->dout_nact.ensure(P));
+    ctx->dout_conv.p = ctx->dout_niter.p + P; ctx->dout_nevals.p = ctx->dout_conv.p + P;
+    std::vector<int> e2, p2, l2;       // the second pass of lv_mode 2: every alpha a piece of its own, in the order of the problems
+    if (ctx->lv_mode == 2) {
+        e2.resize(P); p2.resize(P); l2.assign(P, 1);
+        for (size_t i = 0; i < P; ++i) { e2[i] = elem_of_chain[i / n_alpha]; p2[i] = (int)i; }
+        HIPCHK(ctx, put(ctx->d2_elem, e2)); HIPCHK(ctx, put(ctx->d2_len, l2));
+        HIPCHK(ctx, put(ctx->d2_prob0, p2)); HIPCHK(ctx, put(ctx->d2_v0, p2)); HIPCHK(ctx, put(ctx->d2_queue, p2));
+        HIPCHK(ctx, ctx->dcnt1_niter.ensure(P)); HIPCHK(ctx, ctx->dcnt1_nevals.ensure(P));
     }
-    if (!ctx->wg_chains.empty())
-        HIPCHK(ctx, hipMemcpyAsync(ctx->dwg_chains.p, ctx->wg_chains.data(), ctx->wg_chains.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-    if (layout != 4) ctx->excluded.clear();
-    {
-        // every problem belongs to exactly one piece, or to the list the finishing pass takes (checked: a problem that nothing
-        // covers would keep whatever the result buffers held before)
-        std::vector<char> cov(P, 0);
-        size_t twice = 0;
-        for (int sc = 0; sc < ctx->n_sub; ++sc)
-            for (int i = 0; i < ctx->sub_len[sc]; ++i) { char& c = cov[(size_t)ctx->sub_prob0[sc] + i]; if (c) ++twice; c = 1; }
-        for (int x : ctx->excluded) { char& c = cov[(size_t)x]; if (c) ++twice; c = 1; }
-        size_t missing = 0;
-        for (size_t i = 0; i < P; ++i) if (!cov[i]) ++missing;
-        if (missing || twice) {
-            fprintf(stderr, "mxe_chains_upload: %zu problems covered by no piece, %zu by two (layout %d, %d pieces, %zu excluded)\n",
-                    missing, twice, layout, ctx->n_sub, ctx->excluded.size());
-            return MXE_ERR_STATE;
-        }
-    }
-    if (!ctx->excluded.empty()) {
-        HIPCHK(ctx, ctx->dexcluded.ensure(ctx->excluded.size()));
-        HIPCHK(ctx, hipMemcpyAsync(ctx->dexcluded.p, ctx->excluded.data(), ctx->excluded.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-    }
-    HIPCHK(ctx, hipMemcpyAsync(ctx->dalpha.p, alpha_dev.data(), P * 8, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->dv0.p, hv0.data(), hv0.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, stream_wait(ctx->stream));
-    ctx->n_chain = n_chain; ctx->n_alpha = n_alpha;
-    ctx->has_init = false;
+    HIPCHK(ctx, stream_wait(ctx->stream));          // (the host vectors go out of scope)
+    // ---- 8. the start states of the pieces
     { const int rc_init = build_init_table(ctx, n_chain, elem_of_chain, hv0); if (rc_init != MXE_OK) return rc_init; }
-    ctx->chains_ready = true; ctx->launched = false; ctx->sel3_nc = 0;
+    ctx->chains_ready = true;
     return MXE_OK;
 }
 MXE_CATCH_ALL
@@ -2107,7 +1534,7 @@ try {
             if (rungs_ok && i == 0 && f_src.back() > (size_t)-1 - (size_t)ctx->n_chain - 1) {
                 // a run that begins at the head of a scan from the default model, deep in the hard region (an ascending mesh, or a
                 // mesh that lies there altogether): rungs from N_data / 4 down to its first alpha, like the led pieces of the
-                // lock-step kernel (mxe_chains_upload: emit_ladder) -- the cold start at alpha~ = 0.5 of tools/stress.py case 17 ran
+                // lock-step kernel (mxe_plan.h: emit_scan) -- the cold start at alpha~ = 0.5 of tools/stress.py case 17 ran
                 // into maxiter
                 const double a_to = halpha[p_head];
                 const double a_from = 0.25 * ctx->ds[ctx->elem_ds[ctx->chain_elem[c]]].n_rows;

@@ -81,6 +81,29 @@ def test_chain_matches_kernel_model_and_truth(n_tau, n_omega, n_alpha, entropy, 
     ctx.close()
 
 
+def test_a_refused_upload_leaves_the_staged_launch_as_it_was():
+    """mxe_chains_upload with options it refuses (maxiter = 0: MXE_ERR_ARG) writes nothing: the chains staged before it launch
+    again with THEIR options and give the bytes they gave before"""
+    n_tau, n_omega, n_alpha = 100, 200, 20
+    tau, omega, K, G, err, D, p = _setup(n_tau, n_omega)
+    alphas = np.array(synthetic.alpha_mesh(n_alpha)) * n_tau
+    v0 = R.initial_v(p, omega.delta)[np.newaxis, :]
+    ctx = device.DeviceContext(p.U, p.S, p.V)
+    ctx.set_elements([ctx.add_dataset(err)], [G], D[np.newaxis, :], [device.ENTROPY_NORMAL])
+    ctx.upload_chains([0], alphas, v0)
+    ctx.launch()
+    first = ctx.fetch()
+    assert first['converged'].all()
+    with pytest.raises(device.MaxEntDeviceError, match='mxe_chains_upload') as refused:
+        ctx.upload_chains([0], alphas, v0, device.default_opts(maxiter=0))
+    assert ctx._lib.mxe_strerror(-1).decode() in str(refused.value)         # MXE_ERR_ARG
+    ctx.launch()
+    again = ctx.fetch()
+    for k in ('v', 'H', 'chi2', 'S', 'Q', 'n_iter', 'converged', 'n_evals'):
+        assert first[k].tobytes() == again[k].tobytes(), k
+    ctx.close()
+
+
 def test_four_chain_kernel_equals_single_chain_kernel():
     """a 3x3 matrix problem (mixed normal / plusminus chains in one workgroup)
     through both layouts; per-alpha results agree to the convergence level."""

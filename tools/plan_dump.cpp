@@ -1,0 +1,102 @@
+// Runs the launch planner of mxe_chains_upload (maxent_amd/csrc/mxe_plan.h) stand-alone, on the host: reads one PlanInput from
+// stdin, prints the LaunchPlan.  tests/test_launch_plan_host.py builds and drives it;
+//   c++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all tools/plan_dump.cpp -o plan_dump
+//
+// Input: words separated by white space, `key value...`, in any order except that the counts come before their lists:
+//   n_chain N  n_alpha M  n_s K  NP K  n_omega_pad K  n_cu K  wgpc_auto K  mc_wgpc_hint K
+//   lds LV MC32x1 MC32x2 MC64x1                     (bytes)
+//   opt NAME VALUE                                  (alpha_split wg_per_cu in_flight chains_per_wg precision lds_basis tol_d decouple_tol)
+//   env NAME VALUE                                  (taper ladder_ratio no_lds_basis no_split_by_kind no_ladder no_na64 no_sorted_static)
+//   elems E  then E x (kind data_set sumD)          ds D  then D x (n_rows c32)
+//   elem_of_chain  then n_chain integers            alpha  then n_chain x n_alpha numbers (already divided by chi2_factor)
+// Output: `rc`, the scalars of the plan, then pieces (with the a-priori cost of each), walk_alpha, excluded, queue, wg_chains.
+#include "../maxent_amd/csrc/mxe_plan.h"
+#include <cstdio>
+#include <iostream>
+#include <string>
+
+int main()
+{
+    mxe::PlanInput in;
+    in.opts = mxe_opts();
+    in.opts.decouple_tol = 1e-5;
+    std::vector<int32_t> elem_of_chain;
+    std::vector<double> alpha, sumD, c32;
+    std::vector<int> kind, eds, rows;
+    std::string key, name;
+    auto fail = [&](const std::string& what) { std::fprintf(stderr, "plan_dump: %s\n", what.c_str()); return 2; };
+    while (std::cin >> key) {
+        if (key == "n_chain") std::cin >> in.n_chain;
+        else if (key == "n_alpha") std::cin >> in.n_alpha;
+        else if (key == "n_s") std::cin >> in.n_s;
+        else if (key == "NP") std::cin >> in.NP;
+        else if (key == "n_omega_pad") std::cin >> in.n_omega_pad;
+        else if (key == "n_cu") std::cin >> in.n_cu;
+        else if (key == "wgpc_auto") std::cin >> in.wgpc_auto;
+        else if (key == "mc_wgpc_hint") std::cin >> in.mc_wgpc_hint;
+        else if (key == "lds") std::cin >> in.lds_lv >> in.lds_mc32x1 >> in.lds_mc32x2 >> in.lds_mc64x1;
+        else if (key == "opt") {
+            double v; std::cin >> name >> v;
+            mxe_opts& o = in.opts;
+            if (name == "alpha_split") o.alpha_split = (int)v; else if (name == "wg_per_cu") o.wg_per_cu = (int)v;
+            else if (name == "in_flight") o.in_flight = (int)v; else if (name == "chains_per_wg") o.chains_per_wg = (int)v;
+            else if (name == "precision") o.precision = (int)v; else if (name == "lds_basis") o.lds_basis = (int)v;
+            else if (name == "tol_d") o.tol_d = v; else if (name == "decouple_tol") o.decouple_tol = v;
+            else return fail("unknown option " + name);
+        } else if (key == "env") {
+            double v; std::cin >> name >> v;
+            mxe::PlanEnv& e = in.env;
+            if (name == "taper") e.taper = v; else if (name == "ladder_ratio") e.ladder_ratio = v;
+            else if (name == "no_lds_basis") e.no_lds_basis = v != 0; else if (name == "no_split_by_kind") e.no_split_by_kind = v != 0;
+            else if (name == "no_ladder") e.no_ladder = v != 0; else if (name == "no_na64") e.no_na64 = v != 0;
+            else if (name == "no_sorted_static") e.no_sorted_static = v != 0;
+            else return fail("unknown override " + name);
+        } else if (key == "elems") {
+            size_t n; std::cin >> n;
+            if (!std::cin || n > (1u << 24)) return fail("bad element count");
+            kind.resize(n); eds.resize(n); sumD.resize(n);
+            for (size_t i = 0; i < n; ++i) std::cin >> kind[i] >> eds[i] >> sumD[i];
+        } else if (key == "ds") {
+            size_t n; std::cin >> n;
+            if (!std::cin || n > (1u << 24)) return fail("bad data set count");
+            rows.resize(n); c32.resize(n);
+            for (size_t i = 0; i < n; ++i) std::cin >> rows[i] >> c32[i];
+        } else if (key == "elem_of_chain") {
+            if (in.n_chain < 1 || in.n_chain > (1 << 24)) return fail("n_chain comes before elem_of_chain");
+            elem_of_chain.resize(in.n_chain);
+            for (auto& e : elem_of_chain) std::cin >> e;
+        } else if (key == "alpha") {
+            if (in.n_chain < 1 || in.n_alpha < 1 || (long long)in.n_chain * in.n_alpha > (1 << 26)) return fail("n_chain and n_alpha come before alpha");
+            alpha.resize((size_t)in.n_chain * in.n_alpha);
+            for (auto& a : alpha) std::cin >> a;
+        } else return fail("unknown key " + key);
+        if (!std::cin) return fail("bad value for " + key);
+    }
+    // what mxe_chains_upload checks before it plans
+    if (elem_of_chain.size() != (size_t)in.n_chain || in.n_chain < 1 || alpha.size() != (size_t)in.n_chain * in.n_alpha) return fail("elem_of_chain or alpha missing");
+    for (int e : elem_of_chain) if (e < 0 || (size_t)e >= kind.size()) return fail("element out of range");
+    for (int d : eds) if (d < 0 || (size_t)d >= rows.size()) return fail("data set out of range");
+    for (double a : alpha) if (!(a > 0.0) || !std::isfinite(a)) return fail("alpha not positive");
+    if (in.n_cu < 1 || in.opts.alpha_split < 0 || in.opts.in_flight < 0) return fail("bad n_cu or option");
+    in.elem_of_chain = elem_of_chain.data(); in.alpha = alpha.data();
+    in.elem_kind = kind.data(); in.elem_ds = eds.data(); in.elem_sumD = sumD.data();
+    in.n_ds = (int)rows.size(); in.ds_rows = rows.data(); in.ds_c32 = c32.data();
+
+    mxe::LaunchPlan lp;
+    const int rc = mxe::plan_launch(in, lp);
+    std::printf("rc %d\nprecision %d\nlayout %d\nmc_na %d\nmc_wgpc %d\nmc_gst %d\nlv_mode %d\nwgpc_auto %d\nmc_wgpc_hint %d\n", rc, lp.precision,
+                lp.layout, lp.mc_na, lp.mc_wgpc, (int)lp.mc_gst, lp.lv_mode, lp.wgpc_auto, lp.mc_wgpc_hint);
+    std::printf("n_wg %d\nn_wg2 %d\nwgpc2 %d\nsolo_rule %d\nn_solo_wanted %d\nuncovered %zu\ncovered_twice %zu\n", lp.n_wg, lp.n_wg2, lp.wgpc2,
+                (int)lp.solo_rule, lp.n_solo_wanted, lp.uncovered, lp.covered_twice);
+    std::printf("pieces %zu\n", lp.pieces.size());
+    for (const mxe::Piece& p : lp.pieces)
+        std::printf("%d %d %d %d %d %d %.17g\n", p.elem, p.prob0, p.len, p.v0, p.pre, p.walk0, mxe::plan::piece_cost(in, p));
+    std::printf("walk_alpha %zu\n", lp.walk_alpha.size());
+    for (double a : lp.walk_alpha) std::printf("%.17g\n", a);
+    auto ints = [](const char* what, const std::vector<int>& v) {
+        std::printf("%s %zu\n", what, v.size());
+        for (int x : v) std::printf("%d\n", x);
+    };
+    ints("excluded", lp.excluded); ints("queue", lp.queue); ints("wg_chains", lp.wg_chains);
+    return 0;
+}
