@@ -50,6 +50,8 @@
  *                                                          |   Gaussian posterior), mxe_normals (its generator)
  *   (nothing: the reference gives no fit diagnostics)      | mxe_fit_diagnostics (leverages, number of good
  *                                                          |   data, whitened residuals of a fit)
+ *   (nothing: the reference gives chi2(alpha) only)        | mxe_response (resolution operator of a fit, its
+ *                                                          |   response to the data and to the default model)
  *   (nothing: users loop run() over their resamples)       | mxe_bins_resample (the rotated data of every
  *                                                          |   jackknife / bootstrap resample of the bins),
  *                                                          |   mxe_resample_reduce (mean, spread and functional
@@ -440,6 +442,30 @@ int  mxe_posterior_sample(mxe_ctx* ctx, int P, const int32_t* elem_of_problem, c
 int  mxe_fit_diagnostics(mxe_ctx* ctx, int P, const int32_t* elem_of_problem, const double* alpha_scaled,
                          const double* H, const int32_t* problem_index, double chi2_factor, int ld,
                          double* out_ngood, double* out_chi2, double* out_resid, double* out_lev, float* out_ms);
+/* The linear response of the minimiser: what the continuation does to a feature that is really there.  Replaces nothing
+ * of the reference.  Differentiating the stationarity condition of Q = eta chi2 / 2 - alpha~ S gives, in the notation
+ * above (w, V', c, a = alpha~ / eta, B = c W c + a I = L L^T, Sigma^-1/2 K = U^ c V'^T), exactly at the minimiser
+ *   space 1 (data):   dH = diag(w) V' c B^-1 U^^T dG~            dG~ = Sigma^-1/2 dG in the rows of the problem's data set
+ *   space 0 (model):  dH = R f,  R = diag(w) S,  S = V' c B^-1 c V'^T = S^T     (f: a perturbation of the true H, dG = K f)
+ *                     R = I - alpha~ Gamma diag(1/w),  tr R = sum_k lambda_k / (lambda_k + a) = N_g of mxe_fit_diagnostics
+ *   default model:    dH = (I - R)(H o dlnD)  for both entropies (the caller subtracts)
+ * out_X[p][j] = [diag(w)] V' c B^-1 y_j with y_j = c o V'^T F[p][j] (space 0) or U^^T F[p][j] (space 1); diag(w) only when
+ * weighted != 0 (weighted == 0 in space 0 gives the rows of the symmetric S: column j of it is row j, so
+ * w_j S_j. is the averaging kernel of the value returned at omega_j).  Only a enters: eta scales nothing.
+ * F [P][n_rhs][ld], host, finite: ld >= n_omega in space 0 (the first n_omega entries of a row are used), in space 1 at
+ * least the largest row count among the data sets of the problems named; entries behind a data set's rows do not enter
+ * the result, but like every entry of F they must be finite (the check covers all P n_rhs ld values).
+ * out_X [P][n_rhs][n_omega], host.  elem_of_problem, alpha_scaled, H, problem_index and chi2_factor as in
+ * mxe_posterior_var (also the rows of the last launch with H == NULL, and MXE_ERR_STATE).  x = L^-T L^-1 y by a forward
+ * and a backward substitution; B^-1 is never formed.  A problem whose H row is not finite or whose B is not positive
+ * definite gets NaN in all its outputs, the others are not touched by it and the call returns MXE_OK.  No atomics, fixed
+ * summation order: the bits of a column depend on neither the other problems of the call, nor on n_rhs, nor on the
+ * column's place among the right-hand sides.  MXE_ERR_ARG: n_rhs < 1, space other than 0 or 1, ld too small, an F that is
+ * not finite, P n_rhs max(ld, n_omega) > 2^31 - 1.  MXE_ERR_LIMIT as mxe_posterior_var.  out_ms: device time of the kernel
+ * (may be NULL). */
+int  mxe_response(mxe_ctx* ctx, int P, const int32_t* elem_of_problem, const double* alpha_scaled,
+                  const double* H, const int32_t* problem_index, double chi2_factor,
+                  int space, int weighted, int n_rhs, int ld, const double* F, double* out_X, float* out_ms);
 /* The standard normals of mxe_posterior_sample, out_z [n_samples][n] (host), by the same device function.  Philox4x32-10
  * (Salmon et al. 2011; multipliers 0xD2511F53, 0xCD9E8D57, Weyl constants 0x9E3779B9, 0xBB67AE85) with the key (seed low,
  * seed high) and the counter (j, s, stream low, stream high): s the sample, j the pair of normals.  From the output

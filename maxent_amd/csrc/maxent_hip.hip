@@ -2306,6 +2306,55 @@ try {
 }
 MXE_CATCH_ALL
 
+// ---- linear response of the minimiser: resolution operator, response to the data (mxe_response.hip.h) -------------------
+#include "mxe_response.hip.h"
+
+extern "C" int mxe_response(mxe_ctx* ctx, int P, const int32_t* elem_of_problem, const double* alpha_scaled,
+                            const double* H, const int32_t* problem_index, double chi2_factor,
+                            int space, int weighted, int n_rhs, int ld, const double* F, double* out_X, float* out_ms)
+try {
+    if (!ctx || P < 1 || !elem_of_problem || !alpha_scaled || !F || !out_X || n_rhs < 1 || ld < 1) return MXE_ERR_ARG;
+    if (space != 0 && space != 1) return MXE_ERR_ARG;
+    const int nw = ctx->n_omega;
+    if (space == 0 && ld < nw) return MXE_ERR_ARG;
+    // n_max bounds the arrays of the call: F [P][n_rhs][ld] and X [P][n_rhs][nw]
+    if ((size_t)P * (size_t)n_rhs > 0x7fffffffull) return MXE_ERR_ARG;       // (the products below stay within 64 bits)
+    const size_t n_F = (size_t)P * (size_t)n_rhs * (size_t)ld, n_X = (size_t)P * (size_t)n_rhs * (size_t)nw;
+    PostStage st;
+    int rc = stage_posterior(ctx, P, elem_of_problem, alpha_scaled, H, problem_index, chi2_factor, std::max(n_F, n_X), F, n_F, st);
+    if (rc != MXE_OK) return rc;
+    if (space == 1) {
+        for (int p = 0; p < P; ++p)
+            if (ctx->ds[ctx->elem_ds[elem_of_problem[p]]].n_rows > ld) return MXE_ERR_ARG;
+        rc = upload_projection(ctx);          // Uhat of the data sets: at the first call and after any change of them
+        if (rc != MXE_OK) return rc;
+    }
+    // one block of doubles: alpha [P] | H [P][nw] (when handed in) | F [P][n_rhs][ld] | X [P][n_rhs][nw]
+    const size_t oH = (size_t)P, oF = oH + (H ? (size_t)P * nw : 0), oX = oF + n_F, total = oX + n_X;
+    HIPCHK(ctx, ctx->pv_d.ensure(total));
+    double* d = ctx->pv_d.p;
+    mxe::ResponseParams pp;
+    rc = upload_posterior(ctx, st, P, H, d, oH, pp);
+    if (rc != MXE_OK) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(d + oF, F, n_F * 8, hipMemcpyHostToDevice, ctx->stream));
+    pp.F = d + oF; pp.out = d + oX;
+    pp.U = space ? ctx->dproj_U.p : nullptr; pp.ds_off = space ? ctx->dproj_off.p : nullptr;
+    pp.n_rhs = n_rhs; pp.ld = ld; pp.space = space; pp.weighted = weighted ? 1 : 0;
+    const size_t lds = mxe::response_lds_bytes(ctx->NP, ctx->nwp);     // (below postvar_kernel's, which stage_posterior checked)
+    SvdScratch sc;                    // (the two events of the timing, released on every path)
+    if (out_ms) {
+        HIPCHK(ctx, hipEventCreate(&sc.e0)); HIPCHK(ctx, hipEventCreate(&sc.e1));
+        HIPCHK(ctx, hipEventRecord(sc.e0, ctx->stream));
+    }
+    HIPCHK(ctx, launch_factor_kernel(mxe::response_kernel<4>, mxe::response_kernel<8>, ctx, (size_t)P, lds, pp));
+    if (out_ms) HIPCHK(ctx, hipEventRecord(sc.e1, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(out_X, d + oX, n_X * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, stream_wait(ctx->stream));
+    if (out_ms) HIPCHK(ctx, hipEventElapsedTime(out_ms, sc.e0, sc.e1));
+    return MXE_OK;
+}
+MXE_CATCH_ALL
+
 extern "C" int mxe_normals(int device, uint64_t seed, uint64_t stream, int n_samples, int n, double* out_z)
 try {
     if (n_samples < 1 || n < 1 || !out_z || (size_t)n_samples * (size_t)n > 0x7fffffffull) return MXE_ERR_ARG;

@@ -1,9 +1,10 @@
-// mxe_factor.hip.h -- the Cholesky factor of B = c W c + a I in LDS, and what its four consumers share
+// mxe_factor.hip.h -- the Cholesky factor of B = c W c + a I in LDS, and what its five consumers share
 //
 //   factor_B            -> logdet_kernel      (mxe_logdet, below)
 //                          postvar_kernel     (mxe_posterior_var, mxe_postvar.hip.h)
 //                          postsample_kernel  (mxe_posterior_sample, mxe_postsample.hip.h)
 //                          fitdiag_kernel     (mxe_fit_diagnostics, mxe_fitdiag.hip.h)
+//                          response_kernel    (mxe_response, mxe_response.hip.h)
 //
 // In the whitened singular basis (K^T Sigma^-1 K = V' c^2 V'^T) the curvature of Q = eta chi2 / 2 - alpha~ S collapses
 // onto the n_s x n_s matrix

@@ -119,6 +119,8 @@ SYMBOLS = [
                                             ctypes.POINTER(ctypes.c_uint64), _dp, _dp, ctypes.POINTER(ctypes.c_float)]),
     ('mxe_fit_diagnostics', ctypes.c_int, [_vp, ctypes.c_int, _ip, _dp, _dp, _ip, ctypes.c_double, ctypes.c_int, _dp, _dp, _dp, _dp,
                                            ctypes.POINTER(ctypes.c_float)]),
+    ('mxe_response', ctypes.c_int, [_vp, ctypes.c_int, _ip, _dp, _dp, _ip, ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                    ctypes.c_int, _dp, _dp, ctypes.POINTER(ctypes.c_float)]),
     ('mxe_normals', ctypes.c_int, [ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int, ctypes.c_int, _dp]),
     ('mxe_entropy', ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, _dp, _dp]),
     ('mxe_audit', ctypes.c_int, [_vp, _dp, _dp]),
@@ -1065,6 +1067,63 @@ class DeviceContext(object):
         if timing is not None:
             timing['ms'] = float(ms.value)
         return dict(n_good=ngood, chi2=chi2, residual=resid, leverage=lev, rows=rows)
+
+    def response(self, elem_of_problem, alpha_scaled, F, H=None, problem_index=None, chi2_factor=1.0, space='model',
+                 weighted=True, max_values=None, timing=None):
+        """``mxe_response``: the linear response of the minimiser, on the staged elements.  ``F``: right-hand sides,
+        (n_rhs, ld) for every problem alike or (P, n_rhs, ld) -- ``space='model'``: perturbations of the true H
+        (ld = n_omega), ``X = [diag(w)] V' c B^-1 c V'^T F``: with ``weighted`` the rows ``R f`` of the resolution operator,
+        without it those of the symmetric ``S``; ``space='data'``: whitened perturbations of the data in the rows of each
+        problem's data set (ld at least the largest row count; entries behind a set's rows are ignored),
+        ``X = [diag(w)] V' c B^-1 U^^T F``.  ``H``, ``problem_index`` and ``chi2_factor`` as in :meth:`posterior_var`.
+        Returns X (P, n_rhs, n_omega).  A problem whose H row is not finite or whose curvature matrix is not positive
+        definite has NaN everywhere.  The problems go in calls of at most ``max_values`` values of the largest array
+        (default 2^31 - 1, the library's limit); the bits of a problem do not depend on the call it is in.  ``timing``: a
+        dict that receives the device time ``ms`` of the kernels and the number of ``launches``."""
+        el, P, al = self._posterior_problems('response', elem_of_problem, alpha_scaled)
+        if space not in ('model', 'data'):
+            raise ValueError("response: space must be 'model' or 'data', got %r" % (space,))
+        # (nothing launched: the library answers MXE_ERR_STATE)
+        H, pi = self._posterior_rows('response', P, H, problem_index, unlaunched_ok=True)
+        F = np.asarray(F, dtype=float)
+        if F.ndim == 2:
+            F = np.broadcast_to(F, (P,) + F.shape)
+        if F.ndim != 3 or F.shape[0] != P or F.shape[1] < 1:
+            raise ValueError('response: F must have the shape (n_rhs, ld) or (P, n_rhs, ld), got %r' % (F.shape,))
+        n_rhs, ld = F.shape[1], F.shape[2]
+        if space == 'model':
+            if ld != self.n_omega:
+                raise ValueError('response: F has %d columns, the omega mesh %d points' % (ld, self.n_omega))
+        else:
+            if P and (el.min() < 0 or el.max() >= len(self._elem_rows)):
+                raise ValueError('response: elements 0 .. %d are set' % (len(self._elem_rows) - 1))
+            if ld < 1 or ld < int(self._elem_rows[el].max()):
+                raise ValueError('response: F has %d columns, the largest data set %d rows' % (ld, int(self._elem_rows[el].max())))
+        if not np.all(np.isfinite(F)):
+            raise ValueError('response: F holds values that are not finite')
+        per = n_rhs * max(ld, self.n_omega)
+        limit = 2 ** 31 - 1 if max_values is None else min(int(max_values), 2 ** 31 - 1)
+        cap = limit // per
+        if cap < 1:
+            raise ValueError('response: n_rhs max(ld, n_omega) = %d exceeds %d values; hand the right-hand sides in in '
+                             'several calls' % (per, limit))
+        out = np.empty((P, n_rhs, self.n_omega))
+        ms_total, launches = 0.0, 0
+        for p0 in range(0, P, cap):
+            p1 = min(p0 + cap, P)
+            ms = ctypes.c_float(0)
+            Fp = _c(F[p0:p1])
+            Xp = out[p0:p1]                   # (a C-contiguous slice of problems: the library writes it in place)
+            self._check(self._lib.mxe_response(
+                self._h, p1 - p0, _p(el[p0:p1]), _p(al[p0:p1]), None if H is None else _p(H[p0:p1]),
+                None if pi is None else _p(pi[p0:p1]), float(chi2_factor), 0 if space == 'model' else 1,
+                int(bool(weighted)), n_rhs, ld, _p(Fp), Xp.ctypes.data_as(_dp), ctypes.byref(ms)), 'mxe_response')
+            ms_total += float(ms.value)
+            launches += 1
+        if timing is not None:
+            timing['ms'] = ms_total
+            timing['launches'] = launches
+        return out
 
     def resample_reduce(self, group_offset, scale, H=None, problem_index=None, F=None, want=('mean', 'var', 'fval', 'fmean', 'fcov'),
                         timing=None):

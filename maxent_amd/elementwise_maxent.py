@@ -706,7 +706,7 @@ class ElementwiseMaxEnt(object):
             off = self._offdiag_jobs()
             phases.append((self.maxent_offdiagonal, off, self._posterior_models(off, res)))
         ids = self.device_ids if self.device_ids else (self.maxent_diagonal.maxent_loop.device_id,)
-        collected, ms = [], 0.0
+        collected, ms, counts = [], 0.0, {}
         for worker, jobs, models in phases:
             loop = worker.maxent_loop
             items, keys = [], []
@@ -745,9 +745,13 @@ class ElementwiseMaxEnt(object):
                        chi2_factor=loop.cost_function.chi2_factor, device_ids=ids,
                        bryan=posterior.find_bryan(loop.analyzers), timing=t)
             ms += t.get('ms', 0.0)
+            for name in ('reused_contexts', 'launches'):             # (what the drivers of a phase report beside the time)
+                if name in t:
+                    counts[name] = counts.get(name, 0) + t[name]
             collected.extend(zip(keys, outs))
         if timing is not None:
             timing['ms'] = ms
+            timing.update(counts)
         if not collected:
             raise ValueError('the result holds no element to {}'.format(what))
         struct = tuple(self.shape) + ((2,) if self.use_complex else ())
@@ -836,6 +840,55 @@ class ElementwiseMaxEnt(object):
             return diagnostics.element_diagnostics(K, items, alpha=alpha, **common)
         return self._posterior_elements(res, run, {}, ('residual', 'studentized', 'A_gcv', 'A_classic'), 'compute diagnostics for',
                                         timing=timing, fields=('S', 'A'), ragged=('residual', 'leverage', 'studentized'))
+
+    def resolution(self, result=None, omega0=None, alpha=None, test=None, timing=None):
+        """:meth:`TauMaxEnt.resolution` for every matrix element of ``result`` (default: the last result of this object):
+        all elements of a worker -- the diagonal ones, the off-diagonal ones with their plus-minus entropy -- in the same
+        ``mxe_response`` calls.  Returns a dict of arrays laid out like :meth:`posterior_errors`' (matrix indices, then the
+        complex index with ``use_complex``, then what :meth:`TauMaxEnt.resolution` returns); ``index`` and ``omega0`` are
+        shared by all elements.  Elements that were not computed (below the threshold) hold NaN; those that follow from
+        hermiticity are filled from their partners UNCHANGED, the imaginary part too: a point-spread function, an averaging
+        kernel and an ``image`` per unit of the element's own true spectrum are ratios of two quantities that change sign
+        together.  ``test`` is applied to every element alike.  ``timing``: ``ms``, ``launches``, ``reused_contexts``."""
+        from . import response
+        res = self.maxent_result if result is None else result
+        if res is None:
+            raise ValueError('no result: run() first or hand one in')
+        shared, noted = {}, []
+
+        def note(msg, *args):
+            if not noted:
+                noted.append(msg)
+                self.maxent_diagonal.logtaker.error_message(msg, *args)
+
+        def run(K, omega, items, bryan=None, **common):
+            outs = response.element_resolution(K, omega, items, omega0=omega0, alpha=alpha, test=test, note=note, **common)
+            for o in outs:
+                shared['index'], shared['omega0'] = o.pop('index'), o.pop('omega0')
+                if o['averaging_kernel'] is None:
+                    del o['averaging_kernel']
+            return outs
+        out = self._posterior_elements(res, run, {}, (), 'compute the resolution of', timing=timing)
+        out.update(shared)
+        out.setdefault('averaging_kernel', None)
+        return out
+
+    def default_model_response(self, result=None, dlogD=None, alpha=None, timing=None):
+        """:meth:`TauMaxEnt.default_model_response` for every matrix element of ``result`` (default: the last result of
+        this object), every element with its own default model (``PoormanMaxEnt``: the off-diagonal models built from the
+        diagonal results) and the same relative changes ``dlogD`` (n_dir, n_omega).  Returns a dict of arrays laid out like
+        :meth:`posterior_errors`'.  Elements that follow from hermiticity are filled from their partners; ``dA`` and ``dH``
+        of a mirrored imaginary part take the other sign (the spectrum itself changes sign, ln D does not)."""
+        from . import response
+        res = self.maxent_result if result is None else result
+        if res is None:
+            raise ValueError('no result: run() first or hand one in')
+        if dlogD is None:
+            raise ValueError('dlogD: shape (n_dir, n_omega) is needed')
+
+        def run(K, omega, items, bryan=None, **common):
+            return response.element_default_model_response(K, omega, items, dlogD, alpha=alpha, **common)
+        return self._posterior_elements(res, run, {}, ('dA', 'dH'), 'compute the default-model response of', timing=timing)
 
     def resample_errors(self, bins, method='jackknife', block=1, n_resamples=None, seed=None, alpha=None,
                         alpha_mode='per_resample', windows=None, functionals=None, pointwise=True, keep_samples=False,

@@ -463,6 +463,49 @@ class TauMaxEnt(object):
                                                chi2_factor=loop.cost_function.chi2_factor, device_ids=ids[:1],
                                                timing=timing)[0]
 
+    def _response_item(self, result):
+        from . import posterior
+        loop = self.maxent_loop
+        spec = loop.make_spec()
+        posterior.check_alpha(spec, result.alpha)
+        item = dict(spec=spec, H=np.asarray(result.element_array('H')), alpha=np.asarray(result.alpha, dtype=float),
+                    analysis=result.analyzer_results, B=loop.A_of_H.matrix())
+        ids = loop.device_ids if loop.device_ids else (loop.device_id,)
+        return item, dict(default_name=result.default_analyzer_name, chi2_factor=loop.cost_function.chi2_factor,
+                          device_ids=ids[:1])
+
+    def resolution(self, result, omega0=None, alpha=None, test=None, timing=None):
+        """What this continuation does to a feature that is really there: the linear response of the minimiser of
+        ``result`` (made by this object) to a change of the true spectrum, exact at the minimiser, computed on the device
+        (``mxe_response``, :mod:`maxent_amd.response`).  Not in the reference.
+
+        ``omega0``: a point or a sequence of points, snapped to the mesh (None: every mesh point, in chunks).  ``alpha``: an
+        analyzer name (default: the result's default analyzer), an index, a sequence of indices or ``'all'``;
+        ``'bryan'`` raises ``ValueError`` (the mixture weights depend on the data).  Returns a dict: ``index``, ``omega0``
+        (the mesh points taken); ``psf`` (n_pts, n_omega), the change of the returned A for a unit of weight at omega0 --
+        column j of the resolution operator R over delta_omega --; ``averaging_kernel`` (n_pts, n_omega), r_j with
+        ``dA_returned(omega0_j) = sum_i r_j(omega_i) dA_true(omega_i) delta_omega_i``; of each psf ``weight`` (what comes back
+        of the unit), ``centroid``, ``shift`` (centroid - omega0), ``spread`` (Backus-Gilbert's), ``peak``, ``height``,
+        ``fwhm`` (NaN when a side does not fall to half the maximum on the mesh) and ``data_share`` = R_jj in [0, 1], the
+        share of point j that the data decide (the default model decides the rest); ``alpha``, ``alpha_index``, ``info``
+        (``nan_rows``).  ``test``: (n_test, n_omega) changes of the true A -> ``image``, the linearised change of the
+        returned A.  A sequence of alphas or ``'all'`` keeps an alpha axis in front.  With a ``PreblurKernel`` everything
+        refers to A = B H and goes through the data (dG = K_delta dA_true); ``averaging_kernel`` is None."""
+        from . import response
+        item, common = self._response_item(result)
+        return response.element_resolution(self.K, self.omega, [item], omega0=omega0, alpha=alpha, test=test, timing=timing,
+                                           note=self.logtaker.error_message, **common)[0]
+
+    def default_model_response(self, result, dlogD, alpha=None, timing=None):
+        """How much of ``result`` is the default model: the linear response ``dA`` (n_dir, n_omega) of the returned A to
+        the changes ``dlogD`` (n_dir, n_omega) of ln D, ``dH = (I - R)(H o dlnD)`` with the resolution operator R of
+        :meth:`resolution`, exact at the minimiser, for both entropies (``mxe_response``).  Not in the reference.
+        ``alpha`` as in :meth:`resolution`.  Returns a dict: ``dA``, ``dH``, ``alpha``, ``alpha_index``, ``info``."""
+        from . import response
+        item, common = self._response_item(result)
+        return response.element_default_model_response(self.K, self.omega, [item], dlogD, alpha=alpha, timing=timing,
+                                                       **common)[0]
+
     def resample_errors(self, bins, method='jackknife', block=1, n_resamples=None, seed=None, alpha=None,
                         alpha_mode='per_resample', windows=None, functionals=None, pointwise=True, keep_samples=False,
                         timing=None):
