@@ -58,6 +58,8 @@
  *                                                          |   covariances of the H rows they were continued to)
  *   (nothing: users rebin by hand until the errors settle) | mxe_bins_check (blocking ladder, skewness and
  *                                                          |   kurtosis of the block means of the bins)
+ *   (nothing: users loop run() over their default models)  | mxe_evidence_reduce (evidence of every default
+ *                                                          |   model, model-averaged image, spread between models)
  *   the arrays of MaxEntResult (numpy allocations)         | mxe_host_alloc / mxe_host_free (optional:
  *     maxent_result.py:835-967                             |   page-locked destinations, one DMA per fetch)
  *
@@ -722,6 +724,50 @@ int  mxe_resample_reduce(mxe_ctx* ctx, int n_groups, const int32_t* group_offset
                          const int32_t* problem_index, const double* scale, int n_f, const double* F,
                          double* out_mean, double* out_var, double* out_fval, double* out_fmean, double* out_fcov,
                          int32_t* out_used, float* out_ms);
+
+/* ---- default-model scans: evidence and model averages (no counterpart in the reference) ---- */
+/* The same data continued under a family of default models: the alpha-integrated evidence of every scan, the row it stands
+ * for, and per group of scans (the models of one matrix element) the evidence weights of the models, the model-averaged
+ * hidden image and the spread between the models.  Two launches on the stream of ctx: one workgroup per scan, then one
+ * per group.  Group g owns the scans group_offset[g] .. group_offset[g + 1] - 1 (group_offset[0] = 0, not decreasing; a
+ * group may be empty), n_scan = group_offset[n_groups].
+ *   H           n_scan x n_alpha x n_omega on the host, or NULL: scan s is chain chain_index[s] (NULL: s) of the last
+ *               launch on ctx, its rows read where they lie on the device -- no H row crosses to the host
+ *   logp        n_scan x n_alpha: log p(alpha, D | G) (NormalLogProbability.from_logdet).  NaN and +-inf are data: an
+ *               alpha is GOOD when its logp is finite and, in row_mode 0, its H row is finite (a failed alpha leaves NaN)
+ *   log_quad    n_alpha: log |get_delta(alpha~)|, the measure of the evidence integral
+ *   log_mix     n_alpha: the measure of the mixture over alpha: zeros (BryanAnalyzer) or log_quad (average_by_integration)
+ *   log_prior   n_scan: log P(model), NULL: equal.  -inf switches a model off
+ *   row_mode    0: the Bryan mixture over alpha, 1: the row at the largest logp (classic), 2: the row pick[s]
+ *   F           n_f x n_omega weights on H (n_f may be 0)
+ * Per scan:
+ *   out_logZ    m + log sum_good exp(logp[k] + log_quad[k] - m), m the largest exponent, the terms added in k order
+ *   out_kmax    the first index of the largest logp among the good alphas, -1 when there is none;  out_ngood  their number
+ *   out_walpha  n_scan x n_alpha: exp(logp[k] + log_mix[k] - m') / their sum in k order over the good alphas, 0 elsewhere
+ *   out_row     n_scan x n_omega: sum_k walpha[k] H[k] in k order (mode 0), H[kmax] (mode 1), H[pick[s]] (mode 2)
+ *   out_fval    n_scan x n_f: F row (lanes over omega, butterfly sum)
+ *               A scan with no good alpha, a chosen row that is not finite or pick[s] < 0 is left out of its group: its
+ *               out_logZ is -inf, its out_row and out_fval NaN, its out_wmodel 0.
+ * Per group:
+ *   out_wmodel  n_scan: u_s = exp(logZ_s + log_prior_s - max) / their sum in s order over the usable scans of the group
+ *               (NaN when every usable scan of the group is switched off)
+ *   out_mean    n_groups x n_omega: sum_s u_s row_s in s order
+ *   out_between n_groups x n_omega: sum_s u_s (row_s - mean)^2, a second pass on the explicit difference
+ *   out_fmean   n_groups x n_f, out_fcov n_groups x n_f x n_f: the same sums of the functional values
+ *   out_used    n_groups: the usable scans.  A group with none has NaN means.
+ *   out_ms      device time of the two kernels (may be NULL)
+ * Every output pointer may be NULL.  Fixed summation order, no atomics: a scan's bits depend on nothing but its own rows,
+ * a group's on nothing but its own scans, and both repeat.  MXE_ERR_STATE: H == NULL and nothing was launched.
+ * MXE_ERR_ARG (nothing is launched, no output is touched): n_groups < 1, n_alpha < 1, offsets that decrease or do not
+ * start at 0, with H == NULL a chain_index outside the last launch or an n_alpha that is not the launch's, a row_mode
+ * outside 0 .. 2, row_mode 2 without pick, a pick >= n_alpha, a log_quad, log_mix or F that is not finite, a log_prior that
+ * is NaN or +inf, sizes whose products exceed 2^31 - 1. */
+int  mxe_evidence_reduce(mxe_ctx* ctx, int n_groups, const int32_t* group_offset, int n_alpha, const double* H,
+                         const int32_t* chain_index, const double* logp, const double* log_quad, const double* log_mix,
+                         const double* log_prior, int row_mode, const int32_t* pick, int n_f, const double* F,
+                         double* out_logZ, int32_t* out_kmax, int32_t* out_ngood, double* out_walpha,
+                         double* out_row, double* out_fval, double* out_wmodel, double* out_mean, double* out_between,
+                         double* out_fmean, double* out_fcov, int32_t* out_used, float* out_ms);
 
 /* ---- bin checks: blocking ladder and normality of the block means (no counterpart in the reference) ---- */
 /* May the bins be used as they are?  The covariance of the mean of mxe_bins_eig assumes bins that are uncorrelated and

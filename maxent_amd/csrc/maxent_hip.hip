@@ -323,6 +323,11 @@ struct mxe_ctx {
     // mxe_resample_reduce scratch: scale | H rows | F | fval | mean | var | fmean | fcov;  offsets | flags | used | rows
     DevBuf<double> rr_d;
     DevBuf<int> rr_i;
+    // mxe_evidence_reduce scratch: H rows | logp | log_quad | log_mix | log_prior | F | logZ | walpha | row | fval | wmodel | mean |
+    // between | fmean | fcov;  offsets | pick | good | usable | kmax | ngood | used;  first row of every scan
+    DevBuf<double> er_d;
+    DevBuf<int> er_i;
+    DevBuf<long long> er_l;
     DevBuf<double> rows_out;        // mxe_fetch_rows: the selected rows, gathered on the device
     DevBuf<int> rows_idx;
     double chi2_factor = 1.0;     // of the staged chains (mxe_opts.chi2_factor)
@@ -640,6 +645,7 @@ void mxe_ctx_destroy(mxe_ctx* ctx)
     ctx->ev_mat.release(); ctx->ev_elem.release();
     ctx->pv_d.release(); ctx->pv_i.release();
     ctx->rr_d.release(); ctx->rr_i.release();
+    ctx->er_d.release(); ctx->er_i.release(); ctx->er_l.release();
     if (ctx->ev0) hipEventDestroy(ctx->ev0);
     if (ctx->ev1) hipEventDestroy(ctx->ev1);
     if (ctx->ev_mark) hipEventDestroy(ctx->ev_mark);
@@ -3403,6 +3409,113 @@ try {
     if (out_used) HIPCHK(ctx, hipMemcpyAsync(hused.data(), di + iU, ng * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, stream_wait(ctx->stream));
     if (out_used) for (size_t g = 0; g < ng; ++g) out_used[g] = hused[g];
+    if (out_ms) HIPCHK(ctx, hipEventElapsedTime(out_ms, sc.e0, sc.e1));
+    return MXE_OK;
+}
+MXE_CATCH_ALL
+
+// ---- default-model scans: the evidence of every scan, the model averages of every group of scans (mxe_evidence.hip.h) ----
+#include "mxe_evidence.hip.h"
+
+extern "C" int mxe_evidence_reduce(mxe_ctx* ctx, int n_groups, const int32_t* group_offset, int n_alpha, const double* H,
+                                   const int32_t* chain_index, const double* logp, const double* log_quad,
+                                   const double* log_mix, const double* log_prior, int row_mode, const int32_t* pick,
+                                   int n_f, const double* F,
+                                   double* out_logZ, int32_t* out_kmax, int32_t* out_ngood, double* out_walpha,
+                                   double* out_row, double* out_fval, double* out_wmodel, double* out_mean,
+                                   double* out_between, double* out_fmean, double* out_fcov, int32_t* out_used, float* out_ms)
+try {
+    if (!ctx || n_groups < 1 || !group_offset || n_alpha < 1 || !logp || !log_quad || !log_mix || n_f < 0 || (n_f > 0 && !F) ||
+        row_mode < 0 || row_mode > 2 || (row_mode == 2 && !pick)) return MXE_ERR_ARG;
+    if (group_offset[0] != 0) return MXE_ERR_ARG;
+    for (int g = 0; g < n_groups; ++g)
+        if (group_offset[g + 1] < group_offset[g]) return MXE_ERR_ARG;
+    const size_t ns = (size_t)group_offset[n_groups], na = n_alpha, nw = ctx->n_omega, nf = n_f, ng = n_groups;
+    const size_t lim = 0x7fffffffull;
+    if (ns * na > lim || (H && ns * na * nw > lim) || ns * nw > lim || ns * std::max<size_t>(nf, 1) > lim || nf * nw > lim ||
+        ng * nw > lim || ng * nf * nf > lim) return MXE_ERR_ARG;
+    if (!H && !ctx->launched) return MXE_ERR_STATE;
+    std::vector<long long> hrow0(std::max<size_t>(ns, 1));
+    if (!H) {
+        if (n_alpha != ctx->n_alpha) return MXE_ERR_ARG;
+        for (size_t s = 0; s < ns; ++s) {
+            const int c = chain_index ? chain_index[s] : (int)s;
+            if (c < 0 || c >= ctx->n_chain) return MXE_ERR_ARG;
+            hrow0[s] = (long long)c * n_alpha;
+        }
+    } else {
+        for (size_t s = 0; s < ns; ++s) hrow0[s] = (long long)(s * na);
+    }
+    if (row_mode == 2)
+        for (size_t s = 0; s < ns; ++s) if (pick[s] >= n_alpha) return MXE_ERR_ARG;
+    if (!all_finite(log_quad, na) || !all_finite(log_mix, na) || (nf && !all_finite(F, nf * nw))) return MXE_ERR_ARG;
+    if (log_prior)
+        for (size_t s = 0; s < ns; ++s)
+            if (std::isnan(log_prior[s]) || log_prior[s] == INFINITY) return MXE_ERR_ARG;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    // doubles: H [ns][na][nw] (when handed in; first: its rows start on 16 bytes where nw is even) | logp [ns][na] | log_quad,
+    // log_mix [na] | log_prior [ns] | F [nf][nw] | logZ [ns] | walpha [ns][na] | row [ns][nw] | fval [ns][nf] | wmodel [ns] |
+    // mean, between [ng][nw] | fmean [ng][nf] | fcov [ng][nf][nf]
+    const size_t oP = H ? ns * na * nw : 0, oQ = oP + ns * na, oX = oQ + na, oPr = oX + na, oF = oPr + ns, oZ = oF + nf * nw,
+                 oW = oZ + ns, oR = oW + ns * na, oV = oR + ns * nw, oU = oV + ns * nf, oM = oU + ns, oB = oM + ng * nw,
+                 oFm = oB + ng * nw, oFc = oFm + ng * nf, total = oFc + ng * nf * nf;
+    // integers: offsets [ng + 1] | pick [ns] | good [ns][na] | usable, kmax, ngood [ns] | used [ng]
+    const size_t iP = ng + 1, iG = iP + ns, iUs = iG + ns * na, iK = iUs + ns, iN = iK + ns, iU = iN + ns, itotal = iU + ng;
+    HIPCHK(ctx, ctx->er_d.ensure(total));
+    HIPCHK(ctx, ctx->er_i.ensure(itotal));
+    HIPCHK(ctx, ctx->er_l.ensure(hrow0.size()));
+    double* d = ctx->er_d.p;
+    int* di = ctx->er_i.p;
+    std::vector<int> hi(group_offset, group_offset + ng + 1);
+    hi.resize(iG, 0);
+    if (row_mode == 2) for (size_t s = 0; s < ns; ++s) hi[iP + s] = pick[s];
+    std::vector<double> hprior(std::max<size_t>(ns, 1), 0.0);
+    if (log_prior) for (size_t s = 0; s < ns; ++s) hprior[s] = log_prior[s];
+    if (H && ns) HIPCHK(ctx, hipMemcpyAsync(d, H, ns * na * nw * 8, hipMemcpyHostToDevice, ctx->stream));
+    if (ns) HIPCHK(ctx, hipMemcpyAsync(d + oP, logp, ns * na * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(d + oQ, log_quad, na * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(d + oX, log_mix, na * 8, hipMemcpyHostToDevice, ctx->stream));
+    if (ns) HIPCHK(ctx, hipMemcpyAsync(d + oPr, hprior.data(), ns * 8, hipMemcpyHostToDevice, ctx->stream));
+    if (nf) HIPCHK(ctx, hipMemcpyAsync(d + oF, F, nf * nw * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(di, hi.data(), iG * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->er_l.p, hrow0.data(), hrow0.size() * sizeof(long long), hipMemcpyHostToDevice, ctx->stream));
+    mxe::EvidenceParams ep;
+    ep.H = H ? d : ctx->dout_H.p; ep.row0 = ctx->er_l.p;
+    ep.logp = d + oP; ep.log_quad = d + oQ; ep.log_mix = d + oX; ep.log_prior = d + oPr; ep.pick = di + iP; ep.off = di;
+    ep.F = d + oF; ep.n_alpha = n_alpha; ep.nw = (int)nw; ep.n_f = n_f; ep.row_mode = row_mode;
+    ep.good = di + iG; ep.usable = di + iUs; ep.logZ = d + oZ; ep.kmax = di + iK; ep.ngood = di + iN; ep.walpha = d + oW;
+    ep.row = d + oR; ep.fval = d + oV; ep.wmodel = d + oU; ep.mean = d + oM; ep.between = d + oB; ep.fmean = d + oFm;
+    ep.fcov = d + oFc; ep.used = di + iU;
+    SvdScratch sc;                    // (the two events of the timing, released on every path)
+    if (out_ms) {
+        HIPCHK(ctx, hipEventCreate(&sc.e0)); HIPCHK(ctx, hipEventCreate(&sc.e1));
+        HIPCHK(ctx, hipEventRecord(sc.e0, ctx->stream));
+    }
+    if (ns) {
+        hipLaunchKernelGGL(mxe::evidence_scan_kernel, dim3((unsigned)ns), dim3(mxe::EV_T), 0, ctx->stream, ep);
+        HIPCHK(ctx, hipGetLastError());
+    }
+    hipLaunchKernelGGL(mxe::evidence_group_kernel, dim3((unsigned)ng), dim3(mxe::EV_T), 0, ctx->stream, ep);
+    HIPCHK(ctx, hipGetLastError());
+    if (out_ms) HIPCHK(ctx, hipEventRecord(sc.e1, ctx->stream));
+    if (out_logZ && ns) HIPCHK(ctx, hipMemcpyAsync(out_logZ, d + oZ, ns * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (out_walpha && ns) HIPCHK(ctx, hipMemcpyAsync(out_walpha, d + oW, ns * na * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (out_row && ns) HIPCHK(ctx, hipMemcpyAsync(out_row, d + oR, ns * nw * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (out_fval && ns * nf) HIPCHK(ctx, hipMemcpyAsync(out_fval, d + oV, ns * nf * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (out_wmodel && ns) HIPCHK(ctx, hipMemcpyAsync(out_wmodel, d + oU, ns * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (out_mean) HIPCHK(ctx, hipMemcpyAsync(out_mean, d + oM, ng * nw * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (out_between) HIPCHK(ctx, hipMemcpyAsync(out_between, d + oB, ng * nw * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (out_fmean && nf) HIPCHK(ctx, hipMemcpyAsync(out_fmean, d + oFm, ng * nf * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (out_fcov && nf) HIPCHK(ctx, hipMemcpyAsync(out_fcov, d + oFc, ng * nf * nf * 8, hipMemcpyDeviceToHost, ctx->stream));
+    std::vector<int> hout(2 * ns + ng);                   // kmax | ngood (back to back on the device) | used
+    if (ns) HIPCHK(ctx, hipMemcpyAsync(hout.data(), di + iK, 2 * ns * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(hout.data() + 2 * ns, di + iU, ng * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, stream_wait(ctx->stream));
+    for (size_t s = 0; s < ns; ++s) {
+        if (out_kmax) out_kmax[s] = hout[s];
+        if (out_ngood) out_ngood[s] = hout[ns + s];
+    }
+    if (out_used) for (size_t g = 0; g < ng; ++g) out_used[g] = hout[2 * ns + g];
     if (out_ms) HIPCHK(ctx, hipEventElapsedTime(out_ms, sc.e0, sc.e1));
     return MXE_OK;
 }

@@ -41,6 +41,49 @@ class FlatDefaultModel(BaseDefaultModel):
         return np.full(len(omega), 1.0 / np.sum(omega.delta))
 
 
+class GaussianDefaultModel(BaseDefaultModel):
+    """Gaussian density around ``center`` with the standard deviation ``width``, normalised on the mesh like
+    :class:`FlatDefaultModel` (sum of ``D`` = 1).  Not in the reference; the family ``default_model_scan`` is usually
+    run over.  After changing ``center`` or ``width`` call ``parameter_change()``."""
+
+    def __init__(self, omega, center=0.0, width=1.0):
+        if not (np.isfinite(center) and np.isfinite(width) and width > 0):
+            raise ValueError('GaussianDefaultModel: a finite center and a positive width are needed')
+        self.center, self.width = float(center), float(width)
+        super(GaussianDefaultModel, self).__init__(omega)
+
+    def shape(self, omega):
+        x = (np.asarray(omega, dtype=float) - self.center) / self.width
+        return np.exp(-0.5 * x * x)
+
+    def density(self, omega):
+        g = self.shape(omega)
+        norm = np.sum(g * omega.delta)
+        if not norm > 0:
+            raise ValueError('{}: the density vanishes on every point of the omega mesh'.format(type(self).__name__))
+        return g / norm
+
+    def _fill_values(self):
+        D = np.asarray(self.density(self.omega), dtype=float) * self.omega.delta
+        D = D / np.sum(D)
+        self._D = D / np.sum(D)              # (once more: sum D = 1 to the rounding of the sum itself)
+
+
+class LorentzianDefaultModel(GaussianDefaultModel):
+    """Lorentzian density around ``center`` with the half width ``gamma``, normalised on the mesh (sum of ``D`` = 1).
+    Not in the reference."""
+
+    def __init__(self, omega, center=0.0, gamma=1.0):
+        if not (np.isfinite(center) and np.isfinite(gamma) and gamma > 0):
+            raise ValueError('LorentzianDefaultModel: a finite center and a positive gamma are needed')
+        self.center, self.gamma = float(center), float(gamma)
+        BaseDefaultModel.__init__(self, omega)
+
+    def shape(self, omega):
+        x = (np.asarray(omega, dtype=float) - self.center) / self.gamma
+        return 1.0 / (1.0 + x * x)
+
+
 class DataDefaultModel(BaseDefaultModel):
     """tabulated density ``default`` on ``omega_in``; linear interpolation onto another mesh
     (default_models.py:66-93)"""

@@ -173,6 +173,9 @@ SYMBOLS = [
                                          _dp, _dp, _dp, ctypes.POINTER(ctypes.c_float)]),
     ('mxe_resample_reduce', ctypes.c_int, [_vp, ctypes.c_int, _ip, _dp, _ip, _dp, ctypes.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _ip,
                                            ctypes.POINTER(ctypes.c_float)]),
+    ('mxe_evidence_reduce', ctypes.c_int, [_vp, ctypes.c_int, _ip, ctypes.c_int, _dp, _ip, _dp, _dp, _dp, _dp, ctypes.c_int, _ip,
+                                           ctypes.c_int, _dp, _dp, _ip, _ip, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _ip,
+                                           ctypes.POINTER(ctypes.c_float)]),
     ('mxe_bins_check', ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, _dp, _ip,
                                       _dp, _dp, _dp, _dp, _ip, ctypes.POINTER(ctypes.c_float)]),
 ]
@@ -1174,6 +1177,79 @@ class DeviceContext(object):
         if timing is not None:
             timing['ms'] = float(ms.value)
         out['used'] = used
+        return out
+
+    def evidence_reduce(self, group_offset, logp, log_quad, log_mix=None, H=None, chain_index=None, log_prior=None,
+                        row_mode=0, pick=None, F=None,
+                        want=('walpha', 'row', 'fval', 'mean', 'between', 'fmean', 'fcov'), timing=None):
+        """``mxe_evidence_reduce``: the evidence of every scan and the model averages of every group of scans.  Group g
+        owns the scans ``group_offset[g] .. group_offset[g + 1] - 1``; ``logp``: (n_scan, n_alpha) log probabilities (NaN
+        and infinities are data); ``log_quad``: (n_alpha,) the log measure of the evidence integral; ``log_mix``: the one of
+        the mixture over alpha (default zeros); ``H``: (n_scan, n_alpha, n_omega) on the host, or None for the chains
+        ``chain_index`` (default 0 .. n_scan - 1) of the last launch, read on the device; ``log_prior``: (n_scan,) or
+        None; ``row_mode``: 0 Bryan mixture, 1 the row at the largest logp, 2 the row ``pick[s]``; ``F``: (n_f, n_omega)
+        weights on H.  Returns a dict with ``logZ``, ``kmax``, ``ngood``, ``wmodel`` (n_scan), ``used`` (n_groups) and what
+        ``want`` names: ``walpha`` (n_scan, n_alpha), ``row`` (n_scan, n_omega), ``fval`` (n_scan, n_f), ``mean``,
+        ``between`` (n_groups, n_omega), ``fmean`` (n_groups, n_f), ``fcov`` (n_groups, n_f, n_f).  ``timing``: a dict that
+        receives the device time ``ms`` of the two kernels."""
+        off = _c(np.atleast_1d(group_offset), np.int32)
+        ng = len(off) - 1
+        if ng < 1 or off[0] != 0 or np.any(np.diff(off) < 0):
+            raise ValueError('evidence_reduce: group_offset must start at 0, not decrease and name at least one group')
+        ns = int(off[-1])
+        lq = _c(np.atleast_1d(log_quad))
+        na = len(lq)
+        lp = _c(logp).reshape(ns, na) if ns else np.zeros((0, na))
+        lm = np.zeros(na) if log_mix is None else _c(np.atleast_1d(log_mix))
+        if lq.ndim != 1 or na < 1 or lm.shape != lq.shape:
+            raise ValueError('evidence_reduce: log_quad and log_mix must hold one value per alpha')
+        ci = None
+        if H is not None:
+            H = _c(H).reshape(ns, na, self.n_omega)
+        elif chain_index is not None:
+            ci = _c(np.atleast_1d(chain_index), np.int32)
+            if len(ci) != ns:
+                raise ValueError('evidence_reduce: chain_index must name %d chains' % ns)
+        pr = None
+        if log_prior is not None:
+            pr = _c(np.atleast_1d(log_prior))
+            if pr.shape != (ns,):
+                raise ValueError('evidence_reduce: log_prior must hold one value per scan')
+        pk = None
+        if pick is not None:
+            pk = _c(np.atleast_1d(pick), np.int32)
+            if pk.shape != (ns,):
+                raise ValueError('evidence_reduce: pick must hold one index per scan')
+        n_f = 0
+        if F is not None and len(F):
+            F = _c(np.atleast_2d(F))
+            if F.shape[1] != self.n_omega:
+                raise ValueError('evidence_reduce: F has %d columns, the omega mesh %d points' % (F.shape[1], self.n_omega))
+            n_f = F.shape[0]
+        nw = self.n_omega
+        shapes = dict(walpha=(ns, na), row=(ns, nw), fval=(ns, n_f), mean=(ng, nw), between=(ng, nw), fmean=(ng, n_f),
+                      fcov=(ng, n_f, n_f))
+        out = {}
+        for k in want:
+            if k not in shapes:
+                raise TypeError('unknown output {!r}'.format(k))
+            out[k] = np.empty(shapes[k])
+        out.update(logZ=np.empty(ns), wmodel=np.empty(ns), kmax=np.zeros(ns, dtype=np.int32),
+                   ngood=np.zeros(ns, dtype=np.int32), used=np.zeros(ng, dtype=np.int32))
+        ms = ctypes.c_float(0)
+        rc = self._lib.mxe_evidence_reduce(
+            self._h, ng, _p(off), na, _p(H), _p(ci), _p(lp), _p(lq), _p(lm), _p(pr), int(row_mode), _p(pk), n_f,
+            _p(F) if n_f else None, _p(out['logZ']), _p(out['kmax']), _p(out['ngood']), _p(out.get('walpha')),
+            _p(out.get('row')), _p(out.get('fval')), _p(out['wmodel']), _p(out.get('mean')), _p(out.get('between')),
+            _p(out.get('fmean')), _p(out.get('fcov')), _p(out['used']), ctypes.byref(ms))
+        if rc == _MXE_ERR_ARG:
+            raise ValueError('mxe_evidence_reduce refused its arguments: a row_mode outside 0 .. 2, row_mode 2 without pick, a '
+                             'pick >= n_alpha, a chain_index outside the last launch (%d chains of %d alphas), a log_quad, log_mix '
+                             'or F that is not finite, a log_prior that is NaN or +inf, or sizes whose products exceed 2^31 - 1'
+                             % (self._n_chain, self._n_alpha))
+        self._check(rc, 'mxe_evidence_reduce')
+        if timing is not None:
+            timing['ms'] = float(ms.value)
         return out
 
     def audit(self):

@@ -906,6 +906,20 @@ class ElementwiseMaxEnt(object):
                                                       functionals=functionals, pointwise=pointwise,
                                                       keep_samples=keep_samples, timing=timing)
 
+    def default_model_scan(self, models, prior=None, alpha='bryan', windows=None, functionals=None, pointwise=True,
+                           keep_models=True, timing=None):
+        """:meth:`TauMaxEnt.default_model_scan` for every matrix element: the same ``models`` go to every computed element
+        (the off-diagonal ones with their plus-minus entropy), all models of all elements of a phase in one launch per
+        device, reduced there by ``mxe_evidence_reduce``.  Returns a dict of arrays laid out like
+        :meth:`resample_errors`' (matrix indices, then the complex index with ``use_complex``; elements that were not
+        computed hold NaN, -1 for indices; those that follow from hermiticity are filled from their partners, the
+        imaginary part's spectra and weights with the other sign).  The object's default models and its last result are
+        not changed."""
+        from . import model_scan
+        return model_scan.elementwise_default_model_scan(self, models, prior=prior, alpha=alpha, windows=windows,
+                                                         functionals=functionals, pointwise=pointwise,
+                                                         keep_models=keep_models, timing=timing)
+
     def check_bins(self, bins, basis='eigen'):
         """:meth:`TauMaxEnt.check_bins` for every set of the last ``set_G_*_bins`` call (``bins`` are the ones it
         received), all sets in one ``mxe_bins_check`` call on the first device.  Returns a dict keyed like
@@ -1379,6 +1393,11 @@ class PoormanMaxEnt(ElementwiseMaxEnt):
                                   'the diagonal results, so every resample would need the diagonal results of that resample '
                                   'first -- two dependent launches per resample, which this driver does not do; use '
                                   'ElementwiseMaxEnt or DiagonalMaxEnt')
+
+    def default_model_scan(self, *args, **kwargs):
+        raise NotImplementedError('PoormanMaxEnt.default_model_scan: the default model of an off-diagonal element is built '
+                                  'from the diagonal results, so it is not the caller\'s to choose; use ElementwiseMaxEnt or '
+                                  'DiagonalMaxEnt')
 
     def run_offdiagonal(self):
         self.prepare_maxent_result(overwrite=False)

@@ -254,6 +254,16 @@ class MaxEntLoop(object):
             else np.asarray(err, dtype=float) * np.ones(len(G_use))
         return spec
 
+    def spec_with_model(self, template, D):
+        """the spec of the problem ``template`` was made for under ANOTHER default model ``D`` (density x delta on the
+        omega mesh): everything but D and the start vector -- ``H_of_v.inv`` under that model of what ``make_spec`` starts
+        from, the reference's doubled delta included -- is shared with it; the loop itself is untouched"""
+        from .hostprep import initial_v
+        spec = dict(template)
+        spec['D'] = np.array(D, dtype=float)
+        spec['v0'] = initial_v(self.K.V, spec['D'], np.asarray(self.omega.delta, dtype=float), template['kind'], self.A_init)
+        return spec
+
     def make_record(self, spec, sol):
         """MaxEntResult arrays of one finished scan (maxent_result.py:835-967)."""
         A = sol.get('A')

@@ -534,6 +534,38 @@ class TauMaxEnt(object):
                                               alpha=alpha, alpha_mode=alpha_mode, windows=windows, functionals=functionals,
                                               pointwise=pointwise, keep_samples=keep_samples, timing=timing)
 
+    def default_model_scan(self, models, prior=None, alpha='bryan', windows=None, functionals=None, pointwise=True,
+                           keep_models=True, timing=None):
+        """Continue the data of this object under a family of default models in one launch and let the data say which
+        they prefer (:mod:`maxent_amd.model_scan`, ``mxe_evidence_reduce``).  The object is not changed.  Not in the
+        reference.
+
+        ``models``: a list, or a dict name -> model, of ``BaseDefaultModel`` objects on this object's omega mesh or
+        arrays of length n_omega holding ``D`` (density times delta_omega).  ``prior``: P(model), one value per model
+        (default: equal; 0 switches a model off).  ``alpha``: ``'bryan'`` (default; the mixture over alpha with the weights
+        of ``BryanAnalyzer``, ``average_by_integration`` as the one among this object's analyzers has it), ``'classic'``
+        (the alpha of the largest probability), ``'LineFitAnalyzer'``, ``'Chi2CurvatureAnalyzer'``, ``'EntropyAnalyzer'``
+        or one index.  ``windows``, ``functionals``, ``pointwise`` as in :meth:`posterior_errors` (with a
+        ``PreblurKernel`` they refer to A = B H).  The probability is the object's, or ``NormalLogProbability()`` when it
+        has none.
+
+        Returns a dict: ``log_evidence`` (n_models), log of the integral of p(alpha, D | G) over the alpha mesh --
+        comparable between models on the same data, errors, omega mesh and alpha mesh only --; ``log_bayes_factor``
+        (``log_evidence`` minus the largest); ``weight`` (prior times evidence, normalised), ``best``, ``n_eff`` =
+        1 / sum weight^2; ``alpha_index`` per model (the alpha of the largest probability, or the pick);
+        ``alpha_at_edge`` per model: True where the probability peaks at the first or last alpha -- the mesh then
+        truncates that model's evidence integral and its ``log_evidence`` is a lower bound: widen the alpha mesh --;
+        ``n_good`` (alphas that have a probability and a finite H); ``A`` (the evidence-weighted average) and
+        ``A_model_err`` (the spread between the models, the square root of the weighted centred second moment) with
+        ``pointwise``; ``A_models`` (n_models, n_omega) with ``keep_models``; ``window_weight``, ``window_err``,
+        ``window_models``; ``functional_value``, ``functional_err``, ``functional_cov``, ``functional_models``;
+        ``names``; ``info`` (``kernel_ms``, ``reduce_ms``, ``launches``, ``devices``; ``audit_max`` with
+        ``MAXENT_AMD_AUDIT=1``)."""
+        from . import model_scan
+        return model_scan.tau_default_model_scan(self, models, prior=prior, alpha=alpha, windows=windows,
+                                                 functionals=functionals, pointwise=pointwise, keep_models=keep_models,
+                                                 timing=timing)
+
     def check_bins(self, bins, basis='eigen'):
         """May the Monte Carlo ``bins`` the last ``set_G_*_bins`` call received be used as they are?  The covariance of
         the mean is right for bins that are uncorrelated, chi^2 is a log-likelihood for bins that are normally
