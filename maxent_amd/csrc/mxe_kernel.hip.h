@@ -386,10 +386,12 @@ __device__ __forceinline__ float wave_bcast_f(float x, int src) {
 // preconditions the step) -- eight dependent instructions --, and the order of the code is: update the NEXT pivot columns first,
 // start the next step's chain (swap, broadcasts, determinant, reciprocal, multipliers, right-hand side), then the rest of this
 // step's trailing update with the multipliers kept from before.
-template <int N>
+template <int N, bool PK = true>
 __device__ __forceinline__ bool gj2_solve64_f32(float (&A)[N / 2], float b, int i, float& z, bool& small_pivot)
 {
     constexpr int NHALF = N / 2;
+    static_assert(N % 4 == 0, "the trailing update pairs the registers (2 m, 2 m + 1)");
+    typedef float f2v __attribute__((ext_vector_type(2)));
 #ifndef MXE_X_PIV_TAU
 #define MXE_X_PIV_TAU 1e-3f
 #endif
@@ -431,13 +433,42 @@ __device__ __forceinline__ bool gj2_solve64_f32(float (&A)[N / 2], float b, int 
             }
             // ... so that its chain runs beside the rest of this step's update
             head(std::integral_constant<int, kj + 1>{}, g0, g1);
+            if constexpr (PK) {
+                // the rest two columns at a time: registers (2 m, 2 m + 1) as one two-float vector, two v_pk_fma_f32 with the
+                // multiplier in both halves -- each half is the multiply-add it was, so the solve keeps its bits.  The pairs are
+                // the same registers at every step (NHALF is even: the last one is complete); an odd first column goes alone
+                // (240 -> 120 multiply-add instructions per 32-row solve; cfg4 0.8332 -> 0.8248 ms per step, profiles/r06_experiments.txt)
+                constexpr int kp = (kj + 2) | 1;             // first odd register index at or behind kj + 2
+                if constexpr (kp == kj + 2 && kp < NHALF) {
+                    const float r0 = half_bcast_f<j>(A[kp]), r1 = half_bcast_f<j + 1>(A[kp]);
+                    A[kp] = __builtin_fmaf(-f1, r1, __builtin_fmaf(-f0, r0, A[kp]));
+                }
+                constexpr int kfirst = (kj + 3) & ~1;        // first even register index at or behind kj + 2
+                const f2v nf0 = {-f0, -f0}, nf1 = {-f1, -f1};
 #pragma unroll
-            for (int k0 = kj + 2; k0 < NHALF; k0 += 8) {
-                float r0[8], r1[8];
+                for (int k0 = kfirst; k0 < NHALF; k0 += 8) {
+                    f2v r0[4], r1[4];
 #pragma unroll
-                for (int r = 0; r < 8; ++r) if (k0 + r < NHALF) { r0[r] = half_bcast_f<j>(A[k0 + r]); r1[r] = half_bcast_f<j + 1>(A[k0 + r]); }
+                    for (int r = 0; r < 4; ++r) if (k0 + 2 * r < NHALF) {
+                        r0[r] = f2v{half_bcast_f<j>(A[k0 + 2 * r]), half_bcast_f<j>(A[k0 + 2 * r + 1])};
+                        r1[r] = f2v{half_bcast_f<j + 1>(A[k0 + 2 * r]), half_bcast_f<j + 1>(A[k0 + 2 * r + 1])};
+                    }
 #pragma unroll
-                for (int r = 0; r < 8; ++r) if (k0 + r < NHALF) A[k0 + r] = __builtin_fmaf(-f1, r1[r], __builtin_fmaf(-f0, r0[r], A[k0 + r]));
+                    for (int r = 0; r < 4; ++r) if (k0 + 2 * r < NHALF) {
+                        const f2v a = {A[k0 + 2 * r], A[k0 + 2 * r + 1]};
+                        const f2v u = __builtin_elementwise_fma(nf1, r1[r], __builtin_elementwise_fma(nf0, r0[r], a));
+                        A[k0 + 2 * r] = u.x; A[k0 + 2 * r + 1] = u.y;
+                    }
+                }
+            } else {
+#pragma unroll
+                for (int k0 = kj + 2; k0 < NHALF; k0 += 8) {
+                    float r0[8], r1[8];
+#pragma unroll
+                    for (int r = 0; r < 8; ++r) if (k0 + r < NHALF) { r0[r] = half_bcast_f<j>(A[k0 + r]); r1[r] = half_bcast_f<j + 1>(A[k0 + r]); }
+#pragma unroll
+                    for (int r = 0; r < 8; ++r) if (k0 + r < NHALF) A[k0 + r] = __builtin_fmaf(-f1, r1[r], __builtin_fmaf(-f0, r0[r], A[k0 + r]));
+                }
             }
             f0 = g0; f1 = g1;
         }

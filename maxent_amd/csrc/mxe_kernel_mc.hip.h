@@ -294,6 +294,11 @@ void chain_kernel_mc(const KParams p, const MCExtra x)
         wave_sync();
     };
     auto start_piece = [&](Slot& t, int c) {     // home wave: take chain (piece) c into this slot
+        // (the lane number as a value of this call: the addresses array + lane and LDS row + lane below are formed here, once per
+        //  piece, where the compiler kept every one of them in registers across all rounds -- register pairs for the global ones,
+        //  which the 256-register builds then spilled: 28 B of scratch in <32, 2> before, none now; profiles/r06_experiments.txt)
+        int ln = lane;
+        asm volatile("" : "+v"(ln));
         t.elem = p.chain_elem[c];
         t.cperp = p.cperp[t.elem];
         t.steplim = p.step_max * p.sumD[t.elem];
@@ -309,7 +314,7 @@ void chain_kernel_mc(const KParams p, const MCExtra x)
         //  walk on, from a ladder the library laid for this piece: KParams::walk_alpha from chain_walk0[c] on; both loads with indices
         //  inside their arrays)
         const int walk0 = (p.chain_walk0 && lead > 0) ? p.chain_walk0[c] : -1;
-        for (int i = lane; i < min(t.clen + lead, ACAP); i += 64) {
+        for (int i = ln; i < min(t.clen + lead, ACAP); i += 64) {
             const double a_mesh = p.alpha[(size_t)max(t.prob0 - lead + i, 0)];
             const double a_walk = p.walk_alpha ? p.walk_alpha[max(walk0, 0) + min(i, max(lead - 1, 0))] : a_mesh;
             s_alpha[wave][i] = (walk0 >= 0 && i < lead) ? a_walk : a_mesh;
@@ -318,10 +323,10 @@ void chain_kernel_mc(const KParams p, const MCExtra x)
         t.mu = 0.0; t.muh = 0.0; t.Qprev = __builtin_nan("");
         t.chi2 = 0.0; t.S = 0.0; t.Hn2 = 1.0; t.wmax = 1.0; t.Q = 0.0; t.sc2 = 1.0; t.pred = 0.0;
         t.active = 1; t.scratch = 1;
-        gh[wave * NP + lane] = p.ghat[(size_t)t.elem * NP + lane];
-        vv[wave * NP + lane] = p.v0[(size_t)p.chain_v0[c] * NP + lane];
-        ecor[wave * NP + lane] = 0.0; eacc[wave * NP + lane] = 0.0;
-        if (lane == 0) { s_elem[wave] = t.elem; s_kind[wave] = p.elem_kind[t.elem]; }
+        gh[wave * NP + ln] = p.ghat[(size_t)t.elem * NP + ln];
+        vv[wave * NP + ln] = p.v0[(size_t)p.chain_v0[c] * NP + ln];
+        ecor[wave * NP + ln] = 0.0; eacc[wave * NP + ln] = 0.0;
+        if (ln == 0) { s_elem[wave] = t.elem; s_kind[wave] = p.elem_kind[t.elem]; }
         // Every piece of a class starts from the same vector: what its evaluation gives -- H, S, h, the Gram
         // tiles -- is tabulated, only rho = c h - ghat is the piece's own.  The slot is in the state "evaluated at v0"
         // right away (scratch = 2): its first round is a Newton step, not the evaluation of the start vector.
@@ -330,9 +335,9 @@ void chain_kernel_mc(const KParams p, const MCExtra x)
             if (ic >= 0) {
                 const double* T = p.init_tab + (size_t)ic * MC_INIT_STRIDE;
                 double* Wq = Wt + (size_t)wave * NPAIR * 256;
-                for (int i = lane; i < NPAIR * 256; i += 64) Wq[i] = T[i];
-                const double r = (lane < ns) ? p.c[p.elem_ds[t.elem] * NP + lane] * T[NPAIR * 256 + lane] - gh[wave * NP + lane] : 0.0;
-                rho[wave * NP + lane] = r;
+                for (int i = ln; i < NPAIR * 256; i += 64) Wq[i] = T[i];
+                const double r = (ln < ns) ? p.c[p.elem_ds[t.elem] * NP + ln] * T[NPAIR * 256 + ln] - gh[wave * NP + ln] : 0.0;
+                rho[wave * NP + ln] = r;
                 const double r2 = wave_sum(r * r);
                 const double* sc = T + NPAIR * 256 + NP;
                 t.S = sc[0]; t.Hn2 = sc[1]; t.wmax = sc[2]; t.sc2 = sc[3];
@@ -776,7 +781,11 @@ void chain_kernel_mc(const KParams p, const MCExtra x)
                         if (estimated && t.pred > 0.0 && sdH > t.pred) relH2_min = fmin(sdH, relH2_min * (sdH / t.pred));     // (rare: one division)
     #endif
                         // (a leading alpha is only a starting point for the piece's first alpha: 1e-3 is enough)
-                        const double tol_here = (LEAD && t.ia < 0) ? fmax(p.tol_h, (t.ia == -t.lead) ? MXE_X_LEAD_TOL : MXE_X_WALK_TOL) : p.tol_h;
+                        // (tol_h as a value of this round: its square is one multiplication here, not a register pair kept -- and in
+                        //  the 256-register builds spilled -- across all rounds)
+                        double tol_h = p.tol_h;
+                        asm volatile("" : "+s"(tol_h));
+                        const double tol_here = (LEAD && t.ia < 0) ? fmax(tol_h, (t.ia == -t.lead) ? MXE_X_LEAD_TOL : MXE_X_WALK_TOL) : tol_h;
                         const double tol2Hn = tol_here * tol_here * t.Hn2;
                         vv[q * NP + k] -= dlc[q * NP + k];
                         if (t.niter == 0) t.capp = (t.okprev == 5) ? 2 : (t.okprev == 1 && t.mu == 0.0) ? 1 : 0;
