@@ -56,6 +56,9 @@
  *                                                          |   jackknife / bootstrap resample of the bins),
  *                                                          |   mxe_resample_reduce (mean, spread and functional
  *                                                          |   covariances of the H rows they were continued to)
+ *   (nothing: users loop run() over mock data by hand)     | mxe_mock_data (mock data drawn from continued spectra
+ *                                                          |   with the noise of the job), mxe_resample_quantiles
+ *                                                          |   (percentile bands of the H rows of resamples or mocks)
  *   (nothing: users rebin by hand until the errors settle) | mxe_bins_check (blocking ladder, skewness and
  *                                                          |   kurtosis of the block means of the bins)
  *   (nothing: users loop run() over their default models)  | mxe_evidence_reduce (evidence of every default
@@ -724,6 +727,52 @@ int  mxe_resample_reduce(mxe_ctx* ctx, int n_groups, const int32_t* group_offset
                          const int32_t* problem_index, const double* scale, int n_f, const double* F,
                          double* out_mean, double* out_var, double* out_fval, double* out_fmean, double* out_fcov,
                          int32_t* out_used, float* out_ms);
+
+/* Quantiles over the rows of groups of hidden images, per omega point: the percentile bands of a bootstrap.  The groups,
+ * H and problem_index are those of mxe_resample_reduce (also the rows of the last launch with H == NULL, read where they
+ * lie, and MXE_ERR_STATE).  Two launches on the stream of ctx: one wavefront per row (is it finite), then one workgroup
+ * per (group, tile of 16 omega points), which sorts its tile in LDS by a bitonic network.
+ *   q           n_q probabilities in [0, 1]
+ *   out_used    n_groups: the rows of the group that are finite -- the rule and the numbers of mxe_resample_reduce; the
+ *               others are left out
+ *   out_q       n_groups x n_q x n_omega: per omega point the type-7 quantile (numpy's default, method='linear') of the
+ *               n = out_used[g] values x_0 <= ... <= x_(n-1): h = (n - 1) q, lo = floor(h), t = h - lo, d = x_(lo+1) - x_lo,
+ *               x_lo + t d for t < 1/2 and x_(lo+1) - (1 - t) d from there on, every operation rounded on its own: the
+ *               order statistic itself where h is an integer (q = 0: the smallest, q = 1: the largest value).  NaN for a
+ *               group without a used row.
+ *   out_ms      device time of the two kernels (may be NULL)
+ * out_q and out_used may be NULL.  A fixed sequence of compare-exchanges, no atomics: a group's bits do not depend on the
+ * other groups and repeat.  MXE_ERR_ARG: n_groups < 1, n_q < 1, offsets that decrease or do not start at 0, a problem_index
+ * outside the last launch, a q outside [0, 1] or NaN, sizes whose products exceed 2^31 - 1.  MXE_ERR_LIMIT: a group of more
+ * than MXE_QUANTILE_MAX_ROWS rows (16 columns of them fill 128 KB of the 160 KB of LDS; the network needs a power of two).
+ * Nothing is written in either case. */
+#define MXE_QUANTILE_MAX_ROWS 1024
+int  mxe_resample_quantiles(mxe_ctx* ctx, int n_groups, const int32_t* group_offset, const double* H,
+                            const int32_t* problem_index, int n_q, const double* q,
+                            double* out_q, int32_t* out_used, float* out_ms);
+
+/* ---- parametric bootstrap: mock data (no counterpart in the reference) ---- */
+/* Mock data drawn from continued spectra with the noise of the job, all sets in one launch (one workgroup per tile of 16
+ * sets and chunk of mocks).  What is sampled is N(K H0, diag(err^2)) in the data space of the job, not a posterior.
+ *   K           n_data x n_omega: the job's kernel (rotated / stacked / pre-blurred as the job has it), shared by the sets
+ *   H0          n_sets x n_omega: the hidden image the mocks of a set are drawn from
+ *   err         n_sets x n_data: the error bar of every data row (> 0, finite; also behind rank, where it is not used)
+ *   T, rank     both NULL, or n_sets x n_data x n_data and n_sets: a rotation per set applied to K H0 (out_T and out_rank
+ *               of mxe_bins_eig: rows >= rank are zero)
+ *   seed, stream   stream[s] (n_sets) names the stream of set s of the generator of mxe_normals
+ *   out_model   n_sets x n_data: m_s = K H0_s, or T_s K H0_s
+ *   out_G       n_sets x n_mock x n_data: out_G[s][k][i] = m_s[i] + err[s][i] z, one fused multiply-add, z the standard
+ *               normal number i of sample k of the stream (seed, stream[s]): what mxe_normals(seed, stream[s], n_mock,
+ *               n_data) returns.  With T, rows i >= rank[s] of out_model and out_G are zeros.
+ *   out_ms      device time of the kernel (may be NULL)
+ * K H0 runs as v_mfma_f64_16x16x4_f64 tiles, every sum over all omega in index order inside one wavefront; T m one
+ * wavefront per row.  No atomics: a set's output depends on nothing but its own H0, err, T, rank and stream and on K, it
+ * is the same bits alone or in a batch, for any n_mock, and from call to call.  MXE_ERR_ARG (nothing is launched, nothing is
+ * written): a size below 1, n_mock < 1, exactly one of T and rank NULL, a rank outside 0 .. n_data, a NaN or an Inf in K,
+ * H0, err or T, an err <= 0, sizes whose products exceed 2^31 - 1.  MXE_ERR_NODEVICE: no device. */
+int  mxe_mock_data(int device, int n_sets, int n_mock, int n_data, int n_omega,
+                   const double* K, const double* H0, const double* err, const double* T, const int32_t* rank,
+                   uint64_t seed, const uint64_t* stream, double* out_model, double* out_G, float* out_ms);
 
 /* ---- default-model scans: evidence and model averages (no counterpart in the reference) ---- */
 /* The same data continued under a family of default models: the alpha-integrated evidence of every scan, the row it stands

@@ -3414,6 +3414,141 @@ try {
 }
 MXE_CATCH_ALL
 
+extern "C" int mxe_resample_quantiles(mxe_ctx* ctx, int n_groups, const int32_t* group_offset, const double* H,
+                                      const int32_t* problem_index, int n_q, const double* q,
+                                      double* out_q, int32_t* out_used, float* out_ms)
+try {
+    static_assert(mxe::RQ_MAX_ROWS == MXE_QUANTILE_MAX_ROWS, "the cap the header names is the one the kernel is built for");
+    if (!ctx || n_groups < 1 || !group_offset || n_q < 1 || !q) return MXE_ERR_ARG;
+    if (group_offset[0] != 0) return MXE_ERR_ARG;
+    int longest = 0;
+    for (int g = 0; g < n_groups; ++g) {
+        if (group_offset[g + 1] < group_offset[g]) return MXE_ERR_ARG;
+        longest = std::max(longest, group_offset[g + 1] - group_offset[g]);
+    }
+    for (int k = 0; k < n_q; ++k) if (!(q[k] >= 0.0 && q[k] <= 1.0)) return MXE_ERR_ARG;
+    if (!H && !ctx->launched) return MXE_ERR_STATE;
+    const size_t rows = (size_t)group_offset[n_groups], nw = ctx->n_omega, nq = n_q, ng = n_groups;
+    if (rows * nw > 0x7fffffffull || ng * nq * nw > 0x7fffffffull || (nw + mxe::RQ_COLS - 1) / mxe::RQ_COLS > 65535) return MXE_ERR_ARG;
+    const size_t n_last = (size_t)ctx->n_chain * ctx->n_alpha;
+    // integers: offsets [ng + 1] | flags [rows] | used [ng] | rows of the launch [rows] (H == NULL)
+    std::vector<int> hi(group_offset, group_offset + ng + 1);
+    const size_t iO = 0, iK = iO + ng + 1, iU = iK + rows, iR = iU + ng, itotal = iR + (H ? 0 : rows);
+    hi.resize(itotal, 0);
+    if (!H)
+        for (size_t r = 0; r < rows; ++r) {
+            const int row = problem_index ? problem_index[r] : (int)r;
+            if (row < 0 || (size_t)row >= n_last) return MXE_ERR_ARG;
+            hi[iR + r] = row;
+        }
+    if (longest > mxe::RQ_MAX_ROWS) return MXE_ERR_LIMIT;
+    int padded = 2;
+    while (padded < longest) padded <<= 1;
+    const size_t lds = (size_t)padded * mxe::RQ_COLS * sizeof(double);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    // doubles: q [nq] | H [rows][nw] (when handed in) | quantiles [ng][nq][nw]
+    const size_t oH = nq, oQ = oH + (H ? rows * nw : 0), total = oQ + ng * nq * nw;
+    HIPCHK(ctx, ctx->rr_d.ensure(total));
+    HIPCHK(ctx, ctx->rr_i.ensure(itotal));
+    double* d = ctx->rr_d.p;
+    int* di = ctx->rr_i.p;
+    HIPCHK(ctx, hipMemcpyAsync(d, q, nq * 8, hipMemcpyHostToDevice, ctx->stream));
+    if (H && rows) HIPCHK(ctx, hipMemcpyAsync(d + oH, H, rows * nw * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(di, hi.data(), itotal * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    mxe::QuantileParams qp;
+    qp.H = H ? d + oH : ctx->dout_H.p; qp.row = H ? nullptr : di + iR;
+    qp.off = di + iO; qp.q = d; qp.nw = (int)nw; qp.n_q = n_q; qp.rows = (int)rows; qp.padded = padded;
+    qp.ok = di + iK; qp.out = d + oQ; qp.used = di + iU;
+    HIPCHK(ctx, hipFuncSetAttribute((const void*)mxe::resample_quantile_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    SvdScratch sc;                    // (the two events of the timing, released on every path)
+    if (out_ms) {
+        HIPCHK(ctx, hipEventCreate(&sc.e0)); HIPCHK(ctx, hipEventCreate(&sc.e1));
+        HIPCHK(ctx, hipEventRecord(sc.e0, ctx->stream));
+    }
+    if (rows) {
+        hipLaunchKernelGGL(mxe::rows_finite_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, ctx->stream, qp);
+        HIPCHK(ctx, hipGetLastError());
+    }
+    hipLaunchKernelGGL(mxe::resample_quantile_kernel, dim3((unsigned)n_groups, (unsigned)((nw + mxe::RQ_COLS - 1) / mxe::RQ_COLS)),
+                       dim3(256), lds, ctx->stream, qp);
+    HIPCHK(ctx, hipGetLastError());
+    if (out_ms) HIPCHK(ctx, hipEventRecord(sc.e1, ctx->stream));
+    std::vector<double> hq(out_q ? ng * nq * nw : 0);    // (nothing is written to the caller's arrays before the stream is through)
+    std::vector<int> hused(ng);
+    if (out_q) HIPCHK(ctx, hipMemcpyAsync(hq.data(), d + oQ, ng * nq * nw * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (out_used) HIPCHK(ctx, hipMemcpyAsync(hused.data(), di + iU, ng * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, stream_wait(ctx->stream));
+    if (out_q) std::copy(hq.begin(), hq.end(), out_q);
+    if (out_used) for (size_t g = 0; g < ng; ++g) out_used[g] = hused[g];
+    if (out_ms) HIPCHK(ctx, hipEventElapsedTime(out_ms, sc.e0, sc.e1));
+    return MXE_OK;
+}
+MXE_CATCH_ALL
+
+// ---- parametric bootstrap: mock data drawn from a continued spectrum with the noise of the job (mxe_mock.hip.h) ----
+#include "mxe_mock.hip.h"
+
+extern "C" int mxe_mock_data(int device, int n_sets, int n_mock, int n_data, int n_omega,
+                             const double* K, const double* H0, const double* err, const double* T, const int32_t* rank,
+                             uint64_t seed, const uint64_t* stream, double* out_model, double* out_G, float* out_ms)
+try {
+    if (n_sets < 1 || n_mock < 1 || n_data < 1 || n_omega < 1 || !K || !H0 || !err || !stream || !out_model || !out_G)
+        return MXE_ERR_ARG;
+    if ((T == nullptr) != (rank == nullptr)) return MXE_ERR_ARG;
+    const size_t ns = n_sets, nm = n_mock, n = n_data, nw = n_omega;
+    if (n * nw > 0x7fffffffull || ns * nw > 0x7fffffffull || ns * nm * n > 0x7fffffffull || 16 * n > 0x7fffffffull ||
+        (T && ns * n * n > 0x7fffffffull)) return MXE_ERR_ARG;
+    if (!all_finite(K, n * nw) || !all_finite(H0, ns * nw) || !all_finite(err, ns * n)) return MXE_ERR_ARG;
+    for (size_t i = 0; i < ns * n; ++i) if (!(err[i] > 0.0)) return MXE_ERR_ARG;
+    if (T) {
+        for (size_t s = 0; s < ns; ++s) if (rank[s] < 0 || rank[s] > n_data) return MXE_ERR_ARG;
+        if (!all_finite(T, ns * n * n)) return MXE_ERR_ARG;
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return MXE_ERR_NODEVICE;
+    if (device < 0 || device >= ndev) return MXE_ERR_ARG;
+    // chunks of mocks: MOCK_CHUNK each, more where gridDim.y would pass 1024
+    size_t chunk = mxe::MOCK_CHUNK;
+    while ((nm + chunk - 1) / chunk > 1024) chunk *= 2;
+    const size_t gy = (nm + chunk - 1) / chunk, gx = (ns + 15) / 16;
+    if (16 * chunk * ((n + 1) / 2) > 0x7fffffffull || gy * ns * n > 0x7fffffffull) return MXE_ERR_ARG;
+    SVDCHK(hipSetDevice(device));
+    SvdScratch sc;
+    SVDCHK(hipStreamCreateWithFlags(&sc.stream, hipStreamNonBlocking));
+    mxe::MockParams p;
+    p.n_sets = n_sets; p.n_mock = n_mock; p.n_data = n_data; p.nw = n_omega; p.chunk = (int)chunk; p.seed = seed;
+    double *dK, *dH0, *derr, *dT = nullptr;
+    int* drank = nullptr;
+    uint64_t* dstream;
+    SVDCHK(sc.alloc(&dK, n * nw)); SVDCHK(sc.alloc(&dH0, ns * nw)); SVDCHK(sc.alloc(&derr, ns * n));
+    SVDCHK(sc.alloc(&dstream, ns));
+    if (T) { SVDCHK(sc.alloc(&dT, ns * n * n)); SVDCHK(sc.alloc(&drank, ns)); }
+    SVDCHK(sc.alloc(&p.kh, T ? gy * ns * n : 1)); SVDCHK(sc.alloc(&p.mdl, gy * ns * n));
+    SVDCHK(sc.alloc(&p.out_model, ns * n)); SVDCHK(sc.alloc(&p.out_G, ns * nm * n));
+    p.K = dK; p.H0 = dH0; p.err = derr; p.T = dT; p.rank = drank; p.stream = dstream;
+    SVDCHK(hipMemcpyAsync(dK, K, n * nw * 8, hipMemcpyHostToDevice, sc.stream));
+    SVDCHK(hipMemcpyAsync(dH0, H0, ns * nw * 8, hipMemcpyHostToDevice, sc.stream));
+    SVDCHK(hipMemcpyAsync(derr, err, ns * n * 8, hipMemcpyHostToDevice, sc.stream));
+    SVDCHK(hipMemcpyAsync(dstream, stream, ns * 8, hipMemcpyHostToDevice, sc.stream));
+    if (T) {
+        SVDCHK(hipMemcpyAsync(dT, T, ns * n * n * 8, hipMemcpyHostToDevice, sc.stream));
+        SVDCHK(hipMemcpyAsync(drank, rank, ns * 4, hipMemcpyHostToDevice, sc.stream));
+    }
+    if (out_ms) {
+        SVDCHK(hipEventCreate(&sc.e0)); SVDCHK(hipEventCreate(&sc.e1));
+        SVDCHK(hipEventRecord(sc.e0, sc.stream));
+    }
+    hipLaunchKernelGGL(mxe::mock_data_kernel, dim3((unsigned)gx, (unsigned)gy), dim3(mxe::MOCK_T), 0, sc.stream, p);
+    SVDCHK(hipGetLastError());
+    if (out_ms) SVDCHK(hipEventRecord(sc.e1, sc.stream));
+    SVDCHK(hipMemcpyAsync(out_model, p.out_model, ns * n * 8, hipMemcpyDeviceToHost, sc.stream));
+    SVDCHK(hipMemcpyAsync(out_G, p.out_G, ns * nm * n * 8, hipMemcpyDeviceToHost, sc.stream));
+    SVDCHK(hipStreamSynchronize(sc.stream));
+    if (out_ms) SVDCHK(hipEventElapsedTime(out_ms, sc.e0, sc.e1));
+    return MXE_OK;
+}
+MXE_CATCH_ALL
+
 // ---- default-model scans: the evidence of every scan, the model averages of every group of scans (mxe_evidence.hip.h) ----
 #include "mxe_evidence.hip.h"
 

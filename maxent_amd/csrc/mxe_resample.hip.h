@@ -2,6 +2,7 @@
 //
 //   bins, a table of multiplicities counts[r][b]   ->  the rotated data of every resample   bins_resample_kernel
 //   the H rows the resamples were continued to     ->  mean, spread, functional covariances  resample_reduce_kernel
+//   the same rows (resamples, or the mocks of a parametric bootstrap)  ->  percentile bands   rows_finite_kernel, resample_quantile_kernel
 //
 // bins_resample_kernel: one workgroup of 16 wavefronts per set, all sets in one launch.
 //   1. mean over the bins: bins_mean of mxe_bins.hip.h, the code bins_eig_kernel runs -- the same bits.
@@ -228,6 +229,108 @@ void resample_reduce_kernel(const ReduceParams p)
         p.fcov[((size_t)g * n_f + f1) * n_f + f2] = (nu >= 2) ? sc * q : nan;
     }
     if (tid == 0) p.used[g] = nu;
+}
+
+// ---- quantiles over the rows of a group (mxe_resample_quantiles) --------------------------------------------------------
+// rows_finite_kernel: one wavefront per row, the rule of resample_reduce_kernel (a row takes part iff every entry is finite).
+// resample_quantile_kernel: one workgroup (4 wavefronts) per (group, tile of RQ_COLS omega columns).  A row's segment of the
+// tile is one 128-byte line.  The tile goes to LDS row-major ([row][column]: the load and every stage of the sort touch 64
+// successive doubles per wavefront), a row that is left out and the padding up to the power of two `padded` as +inf; the 16
+// columns are sorted side by side by one bitonic network (a fixed sequence of compare-exchanges: no atomics, nothing depends
+// on the other groups); the first `used` entries of a column are then its order statistics.  Quantile q is the type-7 one:
+// h = (n - 1) q, lo = floor(h), t = h - lo, d = x[lo + 1] - x[lo]; x[lo] + t d for t < 1/2 and x[lo + 1] - (1 - t) d from
+// there on (the nearer end, as numpy forms it: the order statistic itself where t = 0, and no step at q -> 1), every
+// operation rounded on its own.
+constexpr int RQ_COLS = 16;              // omega columns of a tile
+constexpr int RQ_MAX_ROWS = 1024;        // rows of a group: RQ_COLS x 1024 doubles = 128 KB of the 160 KB of LDS, the next power of two does not fit
+
+struct QuantileParams {
+    const double* H;         // rows of nw values
+    const int* row;          // [rows] the row of H a member is, or NULL: its own index
+    const int* off;          // [n_groups + 1]
+    const double* q;         // [n_q]
+    int nw, n_q, rows;
+    int padded;              // power of two >= the longest group (and >= 2)
+    int* ok;                 // [rows]  1: the row is finite
+    double* out;             // [n_groups][n_q][nw]
+    int* used;               // [n_groups]
+};
+
+__global__ __launch_bounds__(256)
+void rows_finite_kernel(const QuantileParams p)
+{
+    const int lane = threadIdx.x & 63;
+    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= p.rows) return;                             // (wave-uniform)
+    const double* h = p.H + (size_t)(p.row ? p.row[r] : r) * p.nw;
+    int bad = 0;
+    for (int i = lane; i < p.nw; i += 64) if (!(fabs(h[i]) <= 1.79769313486231570815e308)) bad = 1;
+    bad = __ballot(bad) != 0;
+    if (lane == 0) p.ok[r] = bad ? 0 : 1;
+}
+
+__global__ __launch_bounds__(256)
+void resample_quantile_kernel(const QuantileParams p)
+{
+    extern __shared__ double rq_x[];                     // [padded][RQ_COLS]
+    __shared__ int rq_cnt[4];
+    const int g = blockIdx.x, w0 = RQ_COLS * blockIdx.y;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int nw = p.nw, P = p.padded;
+    const int r0 = p.off[g], n = p.off[g + 1] - r0;      // (n <= P: the host checked)
+    const double inf = __builtin_inf();
+
+    // ---- the tile, and the number of rows that take part ----
+    int cnt = 0;
+    for (int base = 0; base < P; base += 256 / RQ_COLS) {
+        const int r = base + (tid >> 4), c = tid & (RQ_COLS - 1);
+        if (r < P) {
+            double x = inf;
+            if (r < n && p.ok[r0 + r]) {
+                if (c == 0) ++cnt;
+                if (w0 + c < nw) x = p.H[(size_t)(p.row ? p.row[r0 + r] : r0 + r) * nw + w0 + c];
+            }
+            rq_x[r * RQ_COLS + c] = x;
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);
+    if (lane == 0) rq_cnt[wave] = cnt;
+    __syncthreads();
+    const int nu = rq_cnt[0] + rq_cnt[1] + rq_cnt[2] + rq_cnt[3];
+
+    // ---- bitonic network over the rows, the columns side by side ----
+    const int c = tid & (RQ_COLS - 1);
+    for (int k = 2; k <= P; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int pr = tid >> 4; pr < (P >> 1); pr += 256 / RQ_COLS) {
+                const int i = ((pr & ~(j - 1)) << 1) | (pr & (j - 1)), l = i | j;
+                const double a = rq_x[i * RQ_COLS + c], b = rq_x[l * RQ_COLS + c];
+                const bool up = (i & k) == 0;
+                if ((a > b) == up) { rq_x[i * RQ_COLS + c] = b; rq_x[l * RQ_COLS + c] = a; }
+            }
+            __syncthreads();
+        }
+
+    // ---- type-7 quantiles of the first nu entries of every column ----
+    for (int idx = tid; idx < p.n_q * RQ_COLS; idx += 256) {
+        const int iq = idx >> 4;
+        if (w0 + c >= nw) continue;
+        double v = __builtin_nan("");
+        if (nu > 0) {
+#pragma clang fp contract(off)                           // (every operation rounded on its own: no product may fuse with the sum behind it)
+            const double h = (double)(nu - 1) * p.q[iq];
+            int lo = (int)floor(h);
+            lo = lo < 0 ? 0 : (lo > nu - 1 ? nu - 1 : lo);
+            const int hi = lo + 1 < nu ? lo + 1 : nu - 1;
+            const double t = h - (double)lo;
+            const double a = rq_x[lo * RQ_COLS + c], b = rq_x[hi * RQ_COLS + c];
+            const double d = b - a;
+            const double u = 1.0 - t;
+            v = (t < 0.5) ? a + d * t : b - d * u;
+        }
+        p.out[((size_t)g * p.n_q + iq) * nw + w0 + c] = v;
+    }
+    if (tid == 0 && blockIdx.y == 0) p.used[g] = nu;
 }
 
 } // namespace mxe

@@ -36,6 +36,9 @@ SVD_MAX_ROWS = 60 * 1024 // 8 - 216
 #: most significant directions (rows of R the pivoted QR keeps, SVD_RCAP of mxe_svd.hip.h) of a matrix the device SVD
 #: decomposes; a matrix of higher numerical rank raises MaxEntDeviceError
 SVD_MAX_RANK = 128
+#: most rows of a group ``mxe_resample_quantiles`` sorts (MXE_QUANTILE_MAX_ROWS of include/maxent_hip.h: 16 columns of them
+#: fill 128 KB of the 160 KB of LDS)
+QUANTILE_MAX_ROWS = 1024
 
 
 class MxeOpts(ctypes.Structure):
@@ -173,6 +176,10 @@ SYMBOLS = [
                                          _dp, _dp, _dp, ctypes.POINTER(ctypes.c_float)]),
     ('mxe_resample_reduce', ctypes.c_int, [_vp, ctypes.c_int, _ip, _dp, _ip, _dp, ctypes.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _ip,
                                            ctypes.POINTER(ctypes.c_float)]),
+    ('mxe_resample_quantiles', ctypes.c_int, [_vp, ctypes.c_int, _ip, _dp, _ip, ctypes.c_int, _dp, _dp, _ip,
+                                              ctypes.POINTER(ctypes.c_float)]),
+    ('mxe_mock_data', ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, _dp, _ip,
+                                     ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), _dp, _dp, ctypes.POINTER(ctypes.c_float)]),
     ('mxe_evidence_reduce', ctypes.c_int, [_vp, ctypes.c_int, _ip, ctypes.c_int, _dp, _ip, _dp, _dp, _dp, _dp, ctypes.c_int, _ip,
                                            ctypes.c_int, _dp, _dp, _ip, _ip, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _ip,
                                            ctypes.POINTER(ctypes.c_float)]),
@@ -682,6 +689,77 @@ def normals(seed, stream, n_samples, n, device=0):
     return z
 
 
+def mock_data(K, H0, err, seed, streams, n_mock, T=None, rank=None, device=0, timing=None):
+    """``mxe_mock_data``: mock data drawn from hidden images with the noise of a job, all sets in one launch.  ``K``:
+    (n_data, n_omega), the job's kernel as the job has it; ``H0``: (n_sets, n_omega) or (n_omega,); ``err``: (n_sets,
+    n_data) error bars (> 0); ``streams``: (n_sets,) stream ids of the generator of :func:`normals`; ``T`` (n_sets, n_data,
+    n_data) and ``rank`` (n_sets,): a rotation per set applied to K H0 (zero rows behind the kept ones), or both None.
+    Returns a dict: ``model`` (n_sets, n_data) = (T) K H0, ``G`` (n_sets, n_mock, n_data) = model + err z with z the
+    normals ``(seed, streams[s])`` -- :func:`maxent_amd.mock.mock_rows` is the host mirror --; rows >= rank are zeros.
+    1-d ``H0``: without the leading axis.  ``timing``: a dict that receives the device time ``ms`` of the kernel.
+    Arguments the library would refuse raise ValueError before anything is launched."""
+    Km = np.asarray(K)
+    H = np.asarray(H0)
+    single = H.ndim == 1
+    if single:
+        H = H[None]
+    if Km.ndim != 2 or H.ndim != 2 or np.iscomplexobj(Km) or np.iscomplexobj(H) or H.shape[1] != Km.shape[1]:
+        raise ValueError('mock_data: K must be real (n_data, n_omega) and H0 real (n_sets, n_omega); got %s and %s'
+                         % (np.shape(K), np.shape(H0)))
+    Km, H = _c(Km), _c(H)
+    n_data, n_omega = Km.shape
+    n_sets = H.shape[0]
+    n_mock = int(n_mock)
+    e = np.asarray(err, dtype=float)
+    if e.size != n_sets * n_data:
+        raise ValueError('mock_data: err of shape %s does not fit %d set(s) of %d values' % (e.shape, n_sets, n_data))
+    e = _c(e.reshape(n_sets, n_data))
+    st = np.ascontiguousarray([int(s) & (2 ** 64 - 1) for s in np.atleast_1d(streams)], dtype=np.uint64)
+    if st.shape != (n_sets,):
+        raise ValueError('mock_data: %d stream(s) for %d set(s)' % (st.size, n_sets))
+    if n_sets < 1 or n_data < 1 or n_omega < 1 or n_mock < 1:
+        raise ValueError('mock_data: %d set(s), %d mock(s), %d data values, %d omega points; at least one of each is needed'
+                         % (n_sets, n_mock, n_data, n_omega))
+    if (T is None) != (rank is None):
+        raise ValueError('mock_data: T and rank come together or not at all')
+    Tm = rk = None
+    if T is not None:
+        Tm = np.asarray(T, dtype=float)
+        rk = np.asarray(rank)
+        if Tm.size != n_sets * n_data * n_data or rk.size != n_sets:
+            raise ValueError('mock_data: T of shape %s and rank of shape %s do not fit %d set(s) of %d values'
+                             % (Tm.shape, rk.shape, n_sets, n_data))
+        Tm = _c(Tm.reshape(n_sets, n_data, n_data))
+        rk = _c(rk.reshape(n_sets), np.int32)
+        if np.any(rk < 0) or np.any(rk > n_data):
+            raise ValueError('mock_data: a rank outside 0..%d' % n_data)
+    bad = [name for name, a in (('K', Km), ('H0', H), ('err', e), ('T', Tm)) if a is not None and not np.all(np.isfinite(a))]
+    if bad:
+        raise ValueError('mock_data: values that are not finite in ' + ', '.join(bad))
+    if not np.all(e > 0.0):
+        raise ValueError('mock_data: every error bar must be positive')
+    lib = load_library()
+    if device_count() < 1:
+        raise MaxEntDeviceError('no HIP device visible; mxe_mock_data has no CPU fallback (mock.mock_rows is the host mirror)')
+    model = np.empty((n_sets, n_data))
+    G = np.empty((n_sets, n_mock, n_data))
+    ms = ctypes.c_float(0)
+    rc = lib.mxe_mock_data(int(device), n_sets, n_mock, n_data, n_omega, _p(Km), _p(H), _p(e), _p(Tm), _p(rk),
+                           int(seed) & (2 ** 64 - 1), st.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), _p(model), _p(G),
+                           ctypes.byref(ms))
+    if rc == _MXE_ERR_ARG:
+        raise ValueError('mxe_mock_data refused its arguments: sizes whose products exceed 2^31 - 1 (%d sets x %d mocks x %d '
+                         'values, %d omega points)' % (n_sets, n_mock, n_data, n_omega))
+    if rc != 0:
+        raise MaxEntDeviceError('mxe_mock_data failed: ' + lib.mxe_strerror(rc).decode())
+    if timing is not None:
+        timing['ms'] = float(ms.value)
+    out = dict(model=model, G=G)
+    if single:
+        out = dict((k, v[0]) for k, v in out.items())
+    return out
+
+
 class DeviceContext(object):
     """One solver context on one GPU: holds the truncated SVD of the kernel.
 
@@ -1178,6 +1256,43 @@ class DeviceContext(object):
             timing['ms'] = float(ms.value)
         out['used'] = used
         return out
+
+    def resample_quantiles(self, group_offset, q, H=None, problem_index=None, timing=None):
+        """``mxe_resample_quantiles``: per omega point the type-7 quantiles (numpy's ``method='linear'``) ``q`` over the
+        finite rows of every group of hidden images.  The groups, ``H`` and ``problem_index`` are those of
+        :meth:`resample_reduce`.  Returns a dict: ``q`` (n_groups, n_q, n_omega; NaN for a group without a finite row) and
+        ``used`` (n_groups, as :meth:`resample_reduce` counts them).  A group of more than ``QUANTILE_MAX_ROWS`` rows
+        raises :class:`MaxEntDeviceError` (MXE_ERR_LIMIT).  ``timing``: a dict that receives the device time ``ms`` of the
+        two kernels."""
+        off = _c(np.atleast_1d(group_offset), np.int32)
+        ng = len(off) - 1
+        if ng < 1 or off[0] != 0 or np.any(np.diff(off) < 0):
+            raise ValueError('resample_quantiles: group_offset must start at 0, not decrease and name at least one group')
+        rows = int(off[-1])
+        qq = _c(np.atleast_1d(q))
+        if qq.ndim != 1 or len(qq) < 1 or not np.all((qq >= 0.0) & (qq <= 1.0)):
+            raise ValueError('resample_quantiles: at least one probability, every one in [0, 1], is needed')
+        pi = None
+        if H is not None:
+            H = _c(H).reshape(rows, self.n_omega)
+        else:
+            pi = _c(np.arange(rows) if problem_index is None else np.atleast_1d(problem_index), np.int32)
+            n_last = self._n_chain * self._n_alpha           # (0: nothing was staged -- the library answers MXE_ERR_STATE)
+            if len(pi) != rows or (rows and n_last and (pi.min() < 0 or pi.max() >= n_last)):
+                raise ValueError('resample_quantiles: problem_index must name %d problems of the last launch (%d x %d)'
+                                 % (rows, self._n_chain, self._n_alpha))
+        out = np.empty((ng, len(qq), self.n_omega))
+        used = np.zeros(ng, dtype=np.int32)
+        ms = ctypes.c_float(0)
+        rc = self._lib.mxe_resample_quantiles(self._h, ng, _p(off), _p(H), _p(pi), len(qq), _p(qq), _p(out), _p(used),
+                                              ctypes.byref(ms))
+        if rc == _MXE_ERR_LIMIT:
+            raise MaxEntDeviceError('mxe_resample_quantiles failed: a group of %d rows exceeds the limit of %d rows the kernel '
+                                    'sorts in LDS' % (int(np.diff(off).max()), QUANTILE_MAX_ROWS))
+        self._check(rc, 'mxe_resample_quantiles')
+        if timing is not None:
+            timing['ms'] = float(ms.value)
+        return dict(q=out, used=used)
 
     def evidence_reduce(self, group_offset, logp, log_quad, log_mix=None, H=None, chain_index=None, log_prior=None,
                         row_mode=0, pick=None, F=None,

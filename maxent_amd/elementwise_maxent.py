@@ -892,19 +892,39 @@ class ElementwiseMaxEnt(object):
 
     def resample_errors(self, bins, method='jackknife', block=1, n_resamples=None, seed=None, alpha=None,
                         alpha_mode='per_resample', windows=None, functionals=None, pointwise=True, keep_samples=False,
-                        timing=None):
+                        timing=None, quantiles=None):
         """:meth:`TauMaxEnt.resample_errors` for every matrix element: ``bins`` are those the last ``set_G_tau_bins`` /
         ``set_G_iw_bins`` call received; all elements see the same resamples (bins are joint measurements).  The rotated
         data of all sets come from one ``mxe_bins_resample`` call on the first device, every phase is one launch per
         device for all elements and resamples, each element with ONE data set.  Returns a dict of arrays laid out like
         :meth:`posterior_errors`' (matrix indices, then the complex index with ``use_complex``; elements that were not
         computed hold NaN, those that follow from hermiticity are filled from their partners); ``info['n_datasets']``
-        and ``info['n_elements']`` per phase."""
+        and ``info['n_elements']`` per phase.  ``quantiles`` (bootstrap only): the ``*_quantiles`` of
+        :meth:`TauMaxEnt.resample_errors` per element; a mirrored imaginary part holds minus its partner's quantile at
+        1 - q."""
         from . import resampling
         return resampling.elementwise_resample_errors(self, bins, method=method, block=block, n_resamples=n_resamples,
                                                       seed=seed, alpha=alpha, alpha_mode=alpha_mode, windows=windows,
                                                       functionals=functionals, pointwise=pointwise,
-                                                      keep_samples=keep_samples, timing=timing)
+                                                      keep_samples=keep_samples, timing=timing, quantiles=quantiles)
+
+    def parametric_bootstrap(self, result=None, n_mock=200, seed=None, alpha=None, alpha_mode='per_mock',
+                             quantiles=(0.16, 0.5, 0.84), windows=None, functionals=None, pointwise=True, keep_samples=False,
+                             keep_data=False, timing=None):
+        """:meth:`TauMaxEnt.parametric_bootstrap` for every matrix element of ``result`` (default: ``run()``): the mocks of
+        all sets of the job come from one ``mxe_mock_data`` call on the first device -- every element with its own error
+        bars or covariance --, every phase is one launch per device for all elements and mocks.  The stream of an element
+        is ``posterior.stream_id(flat matrix index, complex index, 1, 0)``: it draws the same mocks alone and inside a
+        matrix, and different elements draw independently.  Returns a dict of arrays laid out like
+        :meth:`resample_errors`' (elements that were not computed hold NaN, -1 for indices; those that follow from
+        hermiticity are filled from their partners, the imaginary part's values with the other sign and its quantiles
+        minus the partner's at 1 - q, which is what the sign does to the order); ``G_mock`` is padded with NaN to the
+        longest element."""
+        from . import mock
+        return mock.elementwise_parametric_bootstrap(self, result=result, n_mock=n_mock, seed=seed, alpha=alpha,
+                                                     alpha_mode=alpha_mode, quantiles=quantiles, windows=windows,
+                                                     functionals=functionals, pointwise=pointwise,
+                                                     keep_samples=keep_samples, keep_data=keep_data, timing=timing)
 
     def default_model_scan(self, models, prior=None, alpha='bryan', windows=None, functionals=None, pointwise=True,
                            keep_models=True, timing=None):
@@ -1392,6 +1412,12 @@ class PoormanMaxEnt(ElementwiseMaxEnt):
         raise NotImplementedError('PoormanMaxEnt.resample_errors: the default model of an off-diagonal element is built from '
                                   'the diagonal results, so every resample would need the diagonal results of that resample '
                                   'first -- two dependent launches per resample, which this driver does not do; use '
+                                  'ElementwiseMaxEnt or DiagonalMaxEnt')
+
+    def parametric_bootstrap(self, *args, **kwargs):
+        raise NotImplementedError('PoormanMaxEnt.parametric_bootstrap: the default model of an off-diagonal element is built '
+                                  'from the diagonal results, so every mock would need the diagonal results of that mock '
+                                  'first -- two dependent launches per mock, which this driver does not do; use '
                                   'ElementwiseMaxEnt or DiagonalMaxEnt')
 
     def default_model_scan(self, *args, **kwargs):

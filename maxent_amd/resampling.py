@@ -71,8 +71,8 @@ def resample_counts(method, n_bins, block=1, n_resamples=None, seed=None):
 
 
 def spread_scale(method, n_used):
-    """the factor on the centred sum of squares of ``n_used`` resamples: (n - 1) / n jackknife, 1 / (n - 1) bootstrap
-    (1 where fewer than two are left: the variances are NaN then)"""
+    """the factor on the centred sum of squares of ``n_used`` resamples: (n - 1) / n jackknife, 1 / (n - 1) bootstrap and
+    parametric bootstrap (1 where fewer than two are left: the variances are NaN then)"""
     n = float(n_used)
     if n < 2:
         return 1.0
@@ -116,11 +116,21 @@ def padded_T(st, n_data):
 # ---- the device part: the scans of all resamples of several elements of one kernel -------------------------------------
 
 def element_resamples(K, omega, loop, templates, G_rows, method, alpha=None, alpha_mode='per_resample', windows=None,
-                      functionals=None, pointwise=True, keep_samples=False, device_ids=None):
+                      functionals=None, pointwise=True, keep_samples=False, device_ids=None, quantiles=None):
     """The resampling errors of the elements ``templates`` (their specs, as ``MaxEntLoop.make_spec`` makes them) of one
     kernel.  ``G_rows[e]``: (1 + n_res, rank_e) rotated data of element e, row 0 the full sample.  Element e is solved on
     device e mod N -- all its chains on that device, one launch per device -- and reduced there.  Returns (list of dicts,
-    one per element, info)."""
+    one per element, info).
+
+    ``method``: ``'jackknife'``, ``'bootstrap'`` or ``'parametric'`` (rows 1 .. are mock data, :mod:`maxent_amd.mock`: the
+    spread scale of the bootstrap, no jackknife bias, and the chi2 of every scan at its pick as ``chi2_scans``).
+    ``quantiles``: probabilities in [0, 1] -> ``quantiles``, ``A_quantiles`` (n_q, n_omega; with ``pointwise``),
+    ``window_quantiles``, ``functional_quantiles`` (n_q, n): type-7 quantiles (numpy's default) over the resamples that
+    were used.  The bands of the hidden image come from ``mxe_resample_quantiles`` on the same groups, read where the rows
+    lie.  With a ``PreblurKernel`` the bands must refer to A = B H, which is no row of the launch: they go the ``BLUR_CHUNK``
+    way of the means -- the values of a chunk of rows of B on every resample from ``mxe_resample_reduce``, the quantile of
+    those few numbers taken on the host; the device kernel serves the plain case.  The quantiles of windows and
+    functionals are taken on the host from the values that are returned anyway."""
     from .batch_solver import BatchSolver, directions_to_keep
     from .maxent_loop import solve_elements, select_params
     if alpha_mode not in ('per_resample', 'full_sample'):
@@ -130,6 +140,7 @@ def element_resamples(K, omega, loop, templates, G_rows, method, alpha=None, alp
     n_omega = len(delta)
     n_elem, n_tot = len(templates), int(G_rows[0].shape[0])
     n_res = n_tot - 1
+    quantiles = check_quantiles(quantiles, method, n_res)
     n_alpha = len(templates[0]['alpha'])
     n_win = 0 if windows is None else len(windows)
     Wrows = window_rows(omega, windows) if n_win else np.zeros((0, n_omega))
@@ -184,10 +195,16 @@ def element_resamples(K, omega, loop, templates, G_rows, method, alpha=None, alp
             if alpha_mode == 'full_sample':
                 picks = np.repeat(picks[:, :1], n_tot, axis=1)
             got = _reduce_device(solver.ctxs[0], picks, n_alpha, method, rows, B if pointwise else None, pointwise,
-                                 keep_samples, info)
+                                 keep_samples, info, quantiles)
             for le, e in enumerate(mine):
                 outs[e] = _element_output(got, le, picks[le], templates[e], delta, B, method, n_win, n_fun, pointwise,
                                           keep_samples)
+                if method == 'parametric':
+                    chi2 = np.full(n_tot, np.nan)
+                    for k in range(n_tot):
+                        if picks[le, k] >= 0:
+                            chi2[k] = sols[le * n_tot + k]['chi2'][picks[le, k]]
+                    outs[e]['chi2_scans'] = chi2
                 if got['left_out'][le]:
                     info['left_out'][e] = got['left_out'][le]
     finally:
@@ -201,7 +218,31 @@ def element_resamples(K, omega, loop, templates, G_rows, method, alpha=None, alp
     return outs, info
 
 
-def _reduce_device(ctx, picks, n_alpha, method, rows, B, pointwise, keep_samples, info):
+def check_quantiles(quantiles, method, n_res):
+    """``quantiles=`` of the resampling drivers -> a float array or None; refused before anything is launched"""
+    if quantiles is None:
+        return None
+    if method == 'jackknife':
+        raise ValueError("quantiles need method='bootstrap': jackknife pseudo-values are not a sample of the distribution")
+    q = np.array(quantiles, dtype=float, ndmin=1)
+    if q.ndim != 1 or len(q) < 1 or not np.all((q >= 0.0) & (q <= 1.0)):
+        raise ValueError('quantiles={!r}: probabilities in [0, 1] are needed'.format(quantiles))
+    if n_res is not None and n_res > device.QUANTILE_MAX_ROWS:
+        raise ValueError('quantiles: {} resamples; mxe_resample_quantiles sorts at most {} rows of a group'.format(
+            n_res, device.QUANTILE_MAX_ROWS))
+    return q
+
+
+def _host_quantiles(values, q):
+    """type-7 quantiles over the finite rows of ``values`` (rows, n) -> (n_q, n); NaN without a finite row"""
+    v = np.asarray(values, dtype=float)
+    v = v[np.all(np.isfinite(v), axis=1)]
+    if len(v) == 0:
+        return np.full((len(q), values.shape[1]), np.nan)
+    return np.quantile(v, q, axis=0)
+
+
+def _reduce_device(ctx, picks, n_alpha, method, rows, B, pointwise, keep_samples, info, quantiles=None):
     """``mxe_resample_reduce`` over the elements of one device: per element a group of its resamples (chains 1 ..) at their
     alphas and a group of the full-sample chain alone, whose 'mean' is its H row"""
     n_e, n_tot = picks.shape
@@ -255,6 +296,28 @@ def _reduce_device(ctx, picks, n_alpha, method, rows, B, pointwise, keep_samples
             A_full[:, c0:c1] = part['fmean'][1::2]
             A_var[:, c0:c1] = np.diagonal(part['fcov'][0::2], axis1=1, axis2=2) * fix[:, None]
         out.update(A_mean=A_mean, A_var=A_var, A_full=A_full)
+    if quantiles is not None:
+        if pointwise and B is None:
+            qs = ctx.resample_quantiles(off, quantiles, problem_index=prob, timing=t)
+            info['reduce_ms'] += t.get('ms', 0.0)
+            info['reduce_launches'] += 1
+            if not np.array_equal(qs['used'][0::2], used):
+                raise RuntimeError('resample_errors: mxe_resample_quantiles and mxe_resample_reduce used different rows')
+            out['H_q'] = qs['q'][0::2]
+        elif pointwise:
+            # A = B H: the values of a chunk of rows of B on every resample, their quantiles on the host
+            A_q = np.empty((n_e, len(quantiles), nw))
+            for c0 in range(0, nw, BLUR_CHUNK):
+                c1 = min(c0 + BLUR_CHUNK, nw)
+                part = ctx.resample_reduce(off, scale, problem_index=prob, F=Bm[c0:c1], want=('fval',), timing=t)
+                info['reduce_ms'] += t.get('ms', 0.0)
+                info['reduce_launches'] += 1
+                for le in range(n_e):
+                    A_q[le, :, c0:c1] = _host_quantiles(part['fval'][off[2 * le]:off[2 * le + 1]], quantiles)
+            out['A_q'] = A_q
+        if n_f:
+            out['f_q'] = np.stack([_host_quantiles(red['fval'][off[2 * le]:off[2 * le + 1]], quantiles) for le in range(n_e)])
+        out['quantiles'] = quantiles
     if keep_samples:
         # (asked for: the chosen rows of the resamples come to the host)
         safe = np.where(picks[:, 1:] >= 0, picks[:, 1:], 0)
@@ -286,6 +349,10 @@ def _element_output(got, le, picks, spec, delta, B, method, n_win, n_fun, pointw
             out['A_mean'], out['A_err'] = got['A_mean'][le], np.sqrt(got['A_var'][le])
         if method == 'jackknife':
             out['A_bias'] = (n_u - 1) * (out['A_mean'] - out['A'])
+        if 'quantiles' in got:
+            out['A_quantiles'] = got['H_q'][le] / delta if B is None else got['A_q'][le]
+    if 'quantiles' in got:
+        out['quantiles'] = np.array(got['quantiles'])
     nf = n_win + n_fun
     if nf:
         fmean, fcov, ffull = got['fmean'][le], got['fcov'][le], got['f_full'][le]
@@ -295,6 +362,11 @@ def _element_output(got, le, picks, spec, delta, B, method, n_win, n_fun, pointw
         if n_fun:
             out['functional_value'], out['functional_err'] = fmean[n_win:], ferr[n_win:]
             out['functional_cov'], out['functional_full'] = fcov[n_win:, n_win:], ffull[n_win:]
+        if 'f_q' in got:
+            if n_win:
+                out['window_quantiles'] = got['f_q'][le][:, :n_win]
+            if n_fun:
+                out['functional_quantiles'] = got['f_q'][le][:, n_win:]
     if keep_samples:
         fun = np.full((n_res, nf), np.nan)
         mem = got['members'][le]
@@ -322,7 +394,8 @@ def _stacked_single(tm, bins):
 
 def tau_resample_errors(tm, bins, method='jackknife', block=1, n_resamples=None, seed=None, alpha=None,
                         alpha_mode='per_resample', windows=None, functionals=None, pointwise=True, keep_samples=False,
-                        timing=None):
+                        timing=None, quantiles=None):
+    quantiles = check_quantiles(quantiles, method, None)
     st = tm.__dict__.get('bin_statistics')
     if st is None:
         raise ValueError('resample_errors: no bins were set; call set_G_tau_bins or set_G_iw_bins first')
@@ -345,7 +418,7 @@ def tau_resample_errors(tm, bins, method='jackknife', block=1, n_resamples=None,
     ids = loop.device_ids if loop.device_ids else (loop.device_id,)
     outs, info = element_resamples(tm.K, tm.omega, loop, [template], [got['G'][:, :st['rank']]], method, alpha=alpha,
                                    alpha_mode=alpha_mode, windows=windows, functionals=functionals, pointwise=pointwise,
-                                   keep_samples=keep_samples, device_ids=ids[:1])
+                                   keep_samples=keep_samples, device_ids=ids[:1], quantiles=quantiles)
     info['resample_ms'] = t.get('ms', 0.0)
     info['left_out'] = info['left_out'].get(0, [])
     out = outs[0]
@@ -384,8 +457,13 @@ def _sets_of(ew, bins):
 
 def elementwise_resample_errors(ew, bins, method='jackknife', block=1, n_resamples=None, seed=None, alpha=None,
                                 alpha_mode='per_resample', windows=None, functionals=None, pointwise=True,
-                                keep_samples=False, timing=None):
+                                keep_samples=False, timing=None, quantiles=None):
     from .elementwise_maxent import DiagonalMaxEnt
+    quantiles = check_quantiles(quantiles, method, None)
+    # a mirrored imaginary part is minus its partner: its quantile q is minus the partner's quantile 1 - q
+    mirror = quantiles is not None and ew.use_complex and ew.use_hermiticity and not isinstance(ew, DiagonalMaxEnt)
+    n_q = 0 if quantiles is None else len(quantiles)
+    q_dev = np.concatenate([quantiles, 1.0 - quantiles]) if mirror else quantiles
     if not ew.__dict__.get('_errors_from_bins') or ew.__dict__.get('bin_statistics') is None:
         raise ValueError('resample_errors: no bins were set; call set_G_tau_bins or set_G_iw_bins first')
     for worker in (ew.maxent_diagonal, ew.maxent_offdiagonal):
@@ -448,7 +526,7 @@ def elementwise_resample_errors(ew, bins, method='jackknife', block=1, n_resampl
             continue
         outs, pinfo = element_resamples(worker.K, worker.omega, loop, templates, G_rows, method, alpha=alpha,
                                         alpha_mode=alpha_mode, windows=windows, functionals=functionals,
-                                        pointwise=pointwise, keep_samples=keep_samples, device_ids=ids)
+                                        pointwise=pointwise, keep_samples=keep_samples, device_ids=ids, quantiles=q_dev)
         info['kernel_ms'] += pinfo['kernel_ms']
         info['reduce_ms'] += pinfo['reduce_ms']
         info['launches'] += pinfo['launches']
@@ -466,16 +544,38 @@ def elementwise_resample_errors(ew, bins, method='jackknife', block=1, n_resampl
     if timing is not None:
         timing.update(ms=info['kernel_ms'] + info['reduce_ms'] + info['resample_ms'], kernel_ms=info['kernel_ms'],
                       reduce_ms=info['reduce_ms'], resample_ms=info['resample_ms'])
-    # the layout of ElementwiseMaxEnt.posterior_errors: matrix indices, then the complex index with use_complex
-    struct = tuple(ew.shape) + ((2,) if ew.use_complex else ())
     out = dict(info=info, method=method, n_resamples=len(counts) - 1)
-    signed = ('window_weight', 'window_full', 'functional_value', 'functional_full', 'A', 'A_mean', 'A_bias')
+    if quantiles is not None:
+        out['quantiles'] = np.array(quantiles)
+    return assemble_elements(ew, collected, out, n_q, mirror)
+
+
+#: what changes sign in the imaginary part of a hermitian partner, and what is a quantile band (it changes sign AND goes to 1 - q)
+SIGNED = ('window_weight', 'window_full', 'functional_value', 'functional_full', 'A', 'A_mean', 'A_bias')
+BANDS = ('A_quantiles', 'window_quantiles', 'functional_quantiles')
+
+
+def assemble_elements(ew, collected, out, n_q=0, mirror=False, shared=('method', 'n_resamples', 'quantiles'), signed=SIGNED):
+    """The per-element dicts ``collected`` ((key, dict) pairs) into ``out`` in the layout of
+    ``ElementwiseMaxEnt.posterior_errors``: matrix indices, then the complex index with ``use_complex``; NaN (-1 for
+    integers) where nothing was computed, the hermitian partners filled in.  The names ``shared`` are the caller's.  A band
+    holds ``n_q`` quantiles and, with ``mirror``, behind them the quantiles at 1 - q, which -- with the other sign -- are
+    the quantiles of a mirrored imaginary part."""
+    struct = tuple(ew.shape) + ((2,) if ew.use_complex else ())
     for key, o in collected:
         partner = (key[1], key[0]) + key[2:] if (ew.use_hermiticity and key[0] != key[1]) else None
         # G_ji = conj(G_ij): the same errors; the imaginary part's values change sign
         flip = -1.0 if (len(key) == 3 and key[2] == 1) else 1.0
         for name, val in o.items():
-            if name in ('method', 'n_resamples'):
+            if name in shared:
+                continue
+            if name in BANDS:
+                val = np.asarray(val)
+                if name not in out:
+                    out[name] = np.full(struct + (n_q,) + val.shape[1:], np.nan)
+                out[name][key] = val[:n_q]
+                if partner is not None:
+                    out[name][partner] = -val[n_q:] if (mirror and flip < 0) else val[:n_q]
                 continue
             if name == 'samples':
                 held = out.setdefault('samples', {})

@@ -508,7 +508,7 @@ class TauMaxEnt(object):
 
     def resample_errors(self, bins, method='jackknife', block=1, n_resamples=None, seed=None, alpha=None,
                         alpha_mode='per_resample', windows=None, functionals=None, pointwise=True, keep_samples=False,
-                        timing=None):
+                        timing=None, quantiles=None):
         """Jackknife or bootstrap error bars from the Monte Carlo ``bins`` the last ``set_G_tau_bins`` / ``set_G_iw_bins``
         call of this object received: every resample of the bins is continued with the covariance of the full sample (one
         launch for all of them, :mod:`maxent_amd.resampling`) and the spread of the results is taken on the device.  The
@@ -528,11 +528,46 @@ class TauMaxEnt(object):
         ``functional_cov``, ``functional_full``; ``alpha_index_samples`` (n_res); ``n_used`` (a resample whose chosen
         alpha failed is left out), ``n_resamples``, ``method``; ``info`` (kernel times, launches, ``n_datasets``,
         ``left_out``); with ``keep_samples`` ``samples['H']`` (n_res, n_omega) and ``samples['functional']``
-        (n_res, windows then functionals) for anything nonlinear downstream."""
+        (n_res, windows then functionals) for anything nonlinear downstream.  ``quantiles`` (bootstrap only; with the
+        jackknife a ``ValueError``: pseudo-values are not a sample of the distribution): probabilities in [0, 1] ->
+        ``quantiles``, ``A_quantiles`` (n_q, n_omega), ``window_quantiles``, ``functional_quantiles``, the percentile
+        intervals over the resamples (type 7, numpy's default; ``mxe_resample_quantiles``)."""
         from . import resampling
         return resampling.tau_resample_errors(self, bins, method=method, block=block, n_resamples=n_resamples, seed=seed,
                                               alpha=alpha, alpha_mode=alpha_mode, windows=windows, functionals=functionals,
-                                              pointwise=pointwise, keep_samples=keep_samples, timing=timing)
+                                              pointwise=pointwise, keep_samples=keep_samples, timing=timing,
+                                              quantiles=quantiles)
+
+    def parametric_bootstrap(self, result=None, n_mock=200, seed=None, alpha=None, alpha_mode='per_mock',
+                             quantiles=(0.16, 0.5, 0.84), windows=None, functionals=None, pointwise=True, keep_samples=False,
+                             keep_data=False, timing=None):
+        """Parametric bootstrap (closure test) of this continuation, for data without bins: ``n_mock`` mock data sets are
+        drawn from the continued spectrum with the noise of the job -- N(K H0, diag(err^2)) in the data space of the job:
+        the eigenbasis after ``set_cov``, the stacked real form of Matsubara data --, every one is continued exactly like
+        the data (one launch for all of them, :mod:`maxent_amd.mock`), and the distribution of what comes back is reduced
+        on the device.  This is the distribution of the procedure's answers to data from ONE spectrum, not a posterior.
+        The object is not changed.  Not in the reference.
+
+        ``result``: a result of this object's present job (None: ``run()``); another job's is refused before anything is
+        launched.  ``alpha`` as in :meth:`resample_errors`; H0 is the row of ``result.H`` at that pick.  ``seed`` is
+        required; the mocks are rows of the counter-based generator of :meth:`posterior_samples`
+        (:func:`maxent_amd.mock.mock_rows` mirrors them), so more mocks extend a draw.  ``alpha_mode='per_mock'``: every
+        mock at the alpha the analyzer picks for its own scan; ``'fixed'``: all at the pick of the data.  ``quantiles``:
+        probabilities in [0, 1] or None.  ``windows``, ``functionals``, ``pointwise`` as in :meth:`resample_errors`
+        (with a ``PreblurKernel`` they refer to A = B H; at most 1024 mocks with ``quantiles``).
+
+        Returns the keys of :meth:`resample_errors` (``A``, ``A_mean``, ``A_err``, ``alpha_index``,
+        ``alpha_index_samples``, ``n_used``, ``window_*``, ``functional_*``, ``info``, ``samples`` with
+        ``keep_samples``) and: ``A_bias`` = A_mean - A -- the mocks were drawn from A, so this is what the procedure does
+        to A on average (it says nothing about the distance of A from the truth) --; ``A_quantiles`` (n_q, n_omega),
+        ``quantiles``, ``window_quantiles``, ``functional_quantiles``; ``chi2`` (the data's at its pick),
+        ``chi2_samples`` (every mock's at its own pick), ``chi2_p_value`` (:func:`maxent_amd.mock.chi2_p_value`);
+        ``G_mock`` (n_mock, n_data) with ``keep_data``; ``method='parametric'``, ``n_mock``, ``seed``."""
+        from . import mock
+        return mock.tau_parametric_bootstrap(self, result=result, n_mock=n_mock, seed=seed, alpha=alpha, alpha_mode=alpha_mode,
+                                             quantiles=quantiles, windows=windows, functionals=functionals,
+                                             pointwise=pointwise, keep_samples=keep_samples, keep_data=keep_data,
+                                             timing=timing)
 
     def default_model_scan(self, models, prior=None, alpha='bryan', windows=None, functionals=None, pointwise=True,
                            keep_models=True, timing=None):
