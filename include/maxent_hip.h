@@ -63,6 +63,8 @@
  *                                                          |   kurtosis of the block means of the bins)
  *   (nothing: users loop run() over their default models)  | mxe_evidence_reduce (evidence of every default
  *                                                          |   model, model-averaged image, spread between models)
+ *   (nothing: positivity of the matrix is not checked)     | mxe_hermitian_eig (eigenvalues of A(w) as a matrix,
+ *                                                          |   its nearest positive semi-definite matrix)
  *   the arrays of MaxEntResult (numpy allocations)         | mxe_host_alloc / mxe_host_free (optional:
  *     maxent_result.py:835-967                             |   page-locked destinations, one DMA per fetch)
  *
@@ -846,6 +848,40 @@ int  mxe_bins_check(int device, int n_sets, int n_bins, int n_data, const double
                     const double* T, const int32_t* rank,
                     double* out_mean, double* out_err2, double* out_skew, double* out_kurt,
                     int32_t* out_levels, float* out_ms);
+
+/* ---- positivity of a matrix-valued A: batched Hermitian eigenproblems (no counterpart in the reference) ---- */
+/* A physical spectral function matrix is Hermitian and positive semi-definite at every frequency; one continued element by
+ * element usually is not (the reference's guide says so and offers no check).  Per matrix, all matrices in one launch: the
+ * eigen-decomposition of Herm(A) = (A + A^H) / 2, formed on the device, by a parallel two-sided cyclic Jacobi iteration
+ * (round-robin ordering, A and V in the LDS; one wavefront per matrix and four matrices per workgroup for m <= 16, one
+ * workgroup per matrix above), its projection onto the cone of matrices with eigenvalues >= floor, and what that costs.
+ *   A           n_mat x m x m row-major; is_complex = 1: interleaved (re, im).  It need not be Hermitian.
+ *   floor       eigenvalues below it are raised to it in out_proj (0: the positive semi-definite cone)
+ *   out_lambda  n_mat x m: the eigenvalues, ascending (by index on ties)
+ *   out_vec     n_mat x m x m (complex: x 2): column k is the eigenvector of out_lambda[k], of unit norm, its component of
+ *               largest magnitude (lowest index on ties) real and positive
+ *   out_proj    n_mat x m x m (x 2): V max(Lambda, floor) V^H, the nearest such matrix in the Frobenius norm; the upper
+ *               triangle is computed, the lower is its conjugate and the diagonal is real: exactly Hermitian
+ *   out_neg     n_mat: sum over lambda < floor of (floor - lambda)
+ *   out_dist    n_mat: || out_proj - Herm(A) ||_F = sqrt(sum over the same of (floor - lambda)^2)
+ *   out_pair    n_mat: max over i < j of |h_ij| - sqrt(max(h_ii, 0) max(h_jj, 0)), h = Herm(A): positive where the
+ *               reference's necessary condition |A_ij| <= sqrt(A_ii A_jj) fails; 0 for m = 1
+ *   out_asym    n_mat: || A - A^H ||_F of the input
+ *   out_info    n_mat: the sweeps that rotated (>= 0; 0: the matrix was diagonal), -1: the matrix holds a NaN or an Inf,
+ *               -2: MXE_HERMEIG_MAX_SWEEPS sweeps did not end the iteration
+ *   out_ms      device time of the kernel (may be NULL)
+ * Every output pointer may be NULL.  A pair (p, q) is rotated when |a_pq| > 2^-53 || Herm(A) ||_F / m -- a threshold that does
+ * not look at the diagonal, which may vanish --, and a sweep without a rotation ends the solve.  A matrix with a NaN or an
+ * Inf gets info -1 and NaN in all its outputs; the other matrices of the call are not touched by it.  No atomics: a
+ * matrix's bits depend on nothing but the matrix, they are the same alone or in a batch, and from call to call.
+ * MXE_ERR_ARG (nothing is launched, nothing is written): n_mat < 1, m < 1, A == NULL, is_complex outside {0, 1}, a floor
+ * that is not finite, sizes whose products exceed 2^31 - 1.  MXE_ERR_LIMIT (likewise): m > MXE_HERMEIG_MAX_M -- two padded
+ * 64 x 64 complex matrices fill 133 KB of the 160 KB of LDS.  MXE_ERR_NODEVICE: no device. */
+#define MXE_HERMEIG_MAX_M      64
+#define MXE_HERMEIG_MAX_SWEEPS 30
+int  mxe_hermitian_eig(int device, int n_mat, int m, int is_complex, const double* A, double floor,
+                       double* out_lambda, double* out_vec, double* out_proj, double* out_neg, double* out_dist,
+                       double* out_pair, double* out_asym, int32_t* out_info, float* out_ms);
 
 #ifdef __cplusplus
 }

@@ -3713,3 +3713,69 @@ try {
     return MXE_OK;
 }
 MXE_CATCH_ALL
+
+// ---- positivity of a matrix-valued spectral function: batched Hermitian eigenproblems (mxe_hermeig.hip.h) ----
+#include "mxe_hermeig.hip.h"
+
+extern "C" int mxe_hermitian_eig(int device, int n_mat, int m, int is_complex, const double* A, double floor,
+                                 double* out_lambda, double* out_vec, double* out_proj, double* out_neg, double* out_dist,
+                                 double* out_pair, double* out_asym, int32_t* out_info, float* out_ms)
+try {
+    static_assert(MXE_HERMEIG_MAX_M == mxe::HERMEIG_MAX_M, "the header and the kernel disagree on the largest matrix");
+    if (n_mat < 1 || m < 1 || (is_complex != 0 && is_complex != 1) || !A || !std::isfinite(floor)) return MXE_ERR_ARG;
+    if (m > mxe::HERMEIG_MAX_M) return MXE_ERR_LIMIT;
+    const size_t nm = n_mat, mm = (size_t)m * m, w = is_complex ? 2 : 1;
+    if (nm * mm * w > 0x7fffffffull) return MXE_ERR_ARG;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return MXE_ERR_NODEVICE;
+    if (device < 0 || device >= ndev) return MXE_ERR_ARG;
+    SVDCHK(hipSetDevice(device));
+    SvdScratch sc;
+    SVDCHK(hipStreamCreateWithFlags(&sc.stream, hipStreamNonBlocking));
+    mxe::HermEigParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.n_mat = n_mat; p.m = m; p.floor = floor;
+    double* dA;
+    SVDCHK(sc.alloc(&dA, nm * mm * w));
+    p.A = dA;
+    if (out_lambda) SVDCHK(sc.alloc(&p.lambda, nm * m));
+    if (out_vec) SVDCHK(sc.alloc(&p.vec, nm * mm * w));
+    if (out_proj) SVDCHK(sc.alloc(&p.proj, nm * mm * w));
+    if (out_neg) SVDCHK(sc.alloc(&p.neg, nm));
+    if (out_dist) SVDCHK(sc.alloc(&p.dist, nm));
+    if (out_pair) SVDCHK(sc.alloc(&p.pair, nm));
+    if (out_asym) SVDCHK(sc.alloc(&p.asym, nm));
+    if (out_info) SVDCHK(sc.alloc(&p.info, nm));
+    SVDCHK(hipMemcpyAsync(dA, A, nm * mm * w * 8, hipMemcpyHostToDevice, sc.stream));
+    if (out_ms) {
+        SVDCHK(hipEventCreate(&sc.e0)); SVDCHK(hipEventCreate(&sc.e1));
+        SVDCHK(hipEventRecord(sc.e0, sc.stream));
+    }
+    const bool wave = m <= mxe::HERMEIG_WAVE_M;
+    const size_t slots = wave ? mxe::HERMEIG_T / 64 : 1;
+    const size_t lds = slots * mxe::hermeig_slot_doubles(m, is_complex != 0) * sizeof(double);
+    if (lds > 160 * 1024) return MXE_ERR_LIMIT;
+    const unsigned grid = (unsigned)((nm + slots - 1) / slots);
+    hipError_t e;
+#define MXE_LAUNCH_HERMEIG(C_, T_) do { \
+        e = hipFuncSetAttribute((const void*)mxe::hermeig_kernel<C_, T_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+        if (e == hipSuccess) { hipLaunchKernelGGL((mxe::hermeig_kernel<C_, T_>), dim3(grid), dim3(mxe::HERMEIG_T), lds, sc.stream, p); \
+                               e = hipGetLastError(); } } while (0)
+    if (is_complex) { if (wave) MXE_LAUNCH_HERMEIG(true, 64); else MXE_LAUNCH_HERMEIG(true, 256); }
+    else            { if (wave) MXE_LAUNCH_HERMEIG(false, 64); else MXE_LAUNCH_HERMEIG(false, 256); }
+#undef MXE_LAUNCH_HERMEIG
+    SVDCHK(e);
+    if (out_ms) SVDCHK(hipEventRecord(sc.e1, sc.stream));
+    if (out_lambda) SVDCHK(hipMemcpyAsync(out_lambda, p.lambda, nm * m * 8, hipMemcpyDeviceToHost, sc.stream));
+    if (out_vec) SVDCHK(hipMemcpyAsync(out_vec, p.vec, nm * mm * w * 8, hipMemcpyDeviceToHost, sc.stream));
+    if (out_proj) SVDCHK(hipMemcpyAsync(out_proj, p.proj, nm * mm * w * 8, hipMemcpyDeviceToHost, sc.stream));
+    if (out_neg) SVDCHK(hipMemcpyAsync(out_neg, p.neg, nm * 8, hipMemcpyDeviceToHost, sc.stream));
+    if (out_dist) SVDCHK(hipMemcpyAsync(out_dist, p.dist, nm * 8, hipMemcpyDeviceToHost, sc.stream));
+    if (out_pair) SVDCHK(hipMemcpyAsync(out_pair, p.pair, nm * 8, hipMemcpyDeviceToHost, sc.stream));
+    if (out_asym) SVDCHK(hipMemcpyAsync(out_asym, p.asym, nm * 8, hipMemcpyDeviceToHost, sc.stream));
+    if (out_info) SVDCHK(hipMemcpyAsync(out_info, p.info, nm * 4, hipMemcpyDeviceToHost, sc.stream));
+    SVDCHK(hipStreamSynchronize(sc.stream));
+    if (out_ms) SVDCHK(hipEventElapsedTime(out_ms, sc.e0, sc.e1));
+    return MXE_OK;
+}
+MXE_CATCH_ALL

@@ -185,6 +185,8 @@ SYMBOLS = [
                                            ctypes.POINTER(ctypes.c_float)]),
     ('mxe_bins_check', ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, _dp, _ip,
                                       _dp, _dp, _dp, _dp, _ip, ctypes.POINTER(ctypes.c_float)]),
+    ('mxe_hermitian_eig', ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, ctypes.c_double,
+                                         _dp, _dp, _dp, _dp, _dp, _dp, _dp, _ip, ctypes.POINTER(ctypes.c_float)]),
 ]
 
 
@@ -755,6 +757,72 @@ def mock_data(K, H0, err, seed, streams, n_mock, T=None, rank=None, device=0, ti
     if timing is not None:
         timing['ms'] = float(ms.value)
     out = dict(model=model, G=G)
+    if single:
+        out = dict((k, v[0]) for k, v in out.items())
+    return out
+
+
+#: largest matrix ``mxe_hermitian_eig`` takes (MXE_HERMEIG_MAX_M of include/maxent_hip.h)
+HERMEIG_MAX_M = 64
+#: sweeps after which ``mxe_hermitian_eig`` gives a matrix up (info -2)
+HERMEIG_MAX_SWEEPS = 30
+HERMEIG_WANT = ('lambda', 'vec', 'proj', 'neg', 'dist', 'pair', 'asym')
+
+
+def hermitian_eig(A, floor=0.0, want=HERMEIG_WANT, device=0, timing=None):
+    """``mxe_hermitian_eig``: the eigen-decomposition of the Hermitian part of every matrix of a batch, one launch.  ``A``:
+    (n_mat, m, m) or (m, m), real or complex, m <= ``HERMEIG_MAX_M``; it need not be Hermitian, the device works on
+    (A + A^H) / 2.  Returns a dict with the entries named in ``want`` -- ``lambda`` (n_mat, m) ascending, ``vec`` (n_mat, m,
+    m), column k the eigenvector of ``lambda[k]`` (unit norm, the component of largest magnitude real and positive),
+    ``proj`` (n_mat, m, m) = V max(Lambda, floor) V^H, exactly Hermitian, ``neg`` = sum over lambda < floor of (floor -
+    lambda), ``dist`` = || proj - Herm(A) ||_F, ``pair`` = max_{i<j} |a_ij| - sqrt(max(a_ii, 0) max(a_jj, 0)), ``asym`` =
+    || A - A^H ||_F -- and always ``info`` (n_mat,) int32: the sweeps that rotated, -1 for a matrix that is not finite (all
+    its outputs are NaN), -2 when ``HERMEIG_MAX_SWEEPS`` sweeps did not end the iteration.  ``vec`` and ``proj`` are
+    complex when ``A`` is.  2-d ``A``: without the leading axis.  ``timing``: a dict that receives the device time ``ms``
+    of the kernel.  Arguments the library would refuse raise ValueError before it is called."""
+    a = np.asarray(A)
+    single = a.ndim == 2
+    if single:
+        a = a[None]
+    if a.ndim != 3 or a.shape[1] != a.shape[2] or a.dtype.kind not in 'biufc':
+        raise ValueError('hermitian_eig: A must be numeric, (n_mat, m, m) or (m, m); got %s' % (np.shape(A),))
+    n_mat, m = a.shape[0], a.shape[1]
+    if n_mat < 1 or m < 1:
+        raise ValueError('hermitian_eig: %d matrices of %d x %d; at least one matrix of one element is needed' % (n_mat, m, m))
+    if m > HERMEIG_MAX_M:
+        raise ValueError('hermitian_eig: matrices of %d x %d; at most %d x %d fit the LDS' % (m, m, HERMEIG_MAX_M, HERMEIG_MAX_M))
+    cplx = np.iscomplexobj(a)
+    if n_mat * m * m * (2 if cplx else 1) > 2 ** 31 - 1:
+        raise ValueError('hermitian_eig: %d matrices of %d x %d hold more than 2^31 - 1 numbers' % (n_mat, m, m))
+    try:
+        floor = float(floor)
+    except (TypeError, ValueError):
+        raise ValueError('hermitian_eig: floor must be a real number; got %r' % (floor,))
+    if not np.isfinite(floor):
+        raise ValueError('hermitian_eig: floor must be finite; got %r' % (floor,))
+    want = (want,) if isinstance(want, str) else tuple(want)
+    unknown = [w for w in want if w not in HERMEIG_WANT]
+    if unknown:
+        raise ValueError('hermitian_eig: want names %r; known are %s' % (unknown, ', '.join(HERMEIG_WANT)))
+    a = _c(a, np.complex128 if cplx else np.float64)
+    lib = load_library()
+    if device_count() < 1:
+        raise MaxEntDeviceError('no HIP device visible; mxe_hermitian_eig has no CPU fallback')
+    mat_dtype = np.complex128 if cplx else np.float64
+    shapes = dict((('lambda', ((n_mat, m), np.float64)), ('vec', ((n_mat, m, m), mat_dtype)), ('proj', ((n_mat, m, m), mat_dtype)),
+                   ('neg', ((n_mat,), np.float64)), ('dist', ((n_mat,), np.float64)), ('pair', ((n_mat,), np.float64)),
+                   ('asym', ((n_mat,), np.float64))))
+    out = dict((w, np.empty(*shapes[w])) for w in want)
+    info = np.empty(n_mat, dtype=np.int32)
+    ptr = lambda x: None if x is None else x.ctypes.data_as(_dp)
+    ms = ctypes.c_float(0)
+    rc = lib.mxe_hermitian_eig(int(device), n_mat, m, 1 if cplx else 0, ptr(a), floor,
+                               *([ptr(out.get(w)) for w in HERMEIG_WANT] + [_p(info), ctypes.byref(ms)]))
+    if rc != 0:
+        raise MaxEntDeviceError('mxe_hermitian_eig failed: ' + lib.mxe_strerror(rc).decode())
+    if timing is not None:
+        timing['ms'] = float(ms.value)
+    out['info'] = info
     if single:
         out = dict((k, v[0]) for k, v in out.items())
     return out

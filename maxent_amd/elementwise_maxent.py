@@ -948,6 +948,29 @@ class ElementwiseMaxEnt(object):
         from . import bin_checks
         return bin_checks.elementwise_check_bins(self, bins, basis=basis)
 
+    def positivity(self, result=None, alpha=None, floor=0.0, keep_vectors=False, back_continue=True):
+        """Is the continued A(omega), taken as a matrix, positive semi-definite -- and what is the nearest spectrum that
+        is?  Element-wise continuation usually does not give a positive matrix (:class:`PoormanMaxEnt` usually improves
+        it).  The matrix is assembled from ``result`` (default: ``run()``): ``A_out`` / ``A`` of the elements with their
+        hermitian mirror, ``zero_elements`` as zeros; an element that was never continued (NaN) raises ValueError, and
+        the message names it.  ``alpha``: None -- ``A_out`` of the default analyzer --, an analyzer name, an integer
+        index into the alpha mesh, or ``'all'``: every alpha of the mesh, the outputs then carry a leading ``n_alpha``
+        axis (at which alpha does positivity break?).  All eigenproblems -- one per frequency and alpha -- are one
+        ``mxe_hermitian_eig`` launch; with several GPUs it runs on the first device (the matrices are assembled from host
+        arrays).  Returns the dict of :func:`maxent_amd.positivity.matrix_positivity` (weights: the ``delta`` of the omega
+        mesh) and ``alpha``, what was taken.  Clipping adds weight: the sum rule of ``A_psd`` is off by exactly
+        ``negative_weight``.
+
+        With ``back_continue`` and a single alpha, per element (laid out like the matrix, then the complex index with
+        ``use_complex``; NaN for elements that were not computed, mirrored ones filled from their partners):
+        ``G_rec_psd`` = K_delta A_psd, the data the repaired spectrum stands for (a host product with the un-blurred
+        ``K_delta``), and ``chi2`` / ``chi2_psd``: the misfit of A and of A_psd in that element's own data space (its
+        ``err``, its rotation after ``set_cov``) -- what the repair costs.  The result must have been made from the data
+        the object holds now."""
+        from . import positivity
+        return positivity.elementwise_positivity(self, result=result, alpha=alpha, floor=floor, keep_vectors=keep_vectors,
+                                                 back_continue=back_continue)
+
     def _direct_input(self, worker):
         """G(tau) came as one array and the errors are plain (no covariance): specs can be cut from the
         arrays without sending every element through the worker's setters"""
@@ -1387,6 +1410,11 @@ class DiagonalMaxEnt(ElementwiseMaxEnt):
 
     def run_offdiagonal(self):
         raise TypeError('DiagonalMaxEnt cannot run for off-diagonals.')
+
+    def positivity(self, *args, **kwargs):
+        raise NotImplementedError('DiagonalMaxEnt.positivity: a job without off-diagonal elements has no matrix to test -- a '
+                                  'diagonal A(omega) is positive where its elements are; use ElementwiseMaxEnt or PoormanMaxEnt, '
+                                  'or maxent_amd.matrix_positivity on a matrix of your own')
 
 
 class PoormanMaxEnt(ElementwiseMaxEnt):
