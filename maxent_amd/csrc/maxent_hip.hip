@@ -315,19 +315,15 @@ struct mxe_ctx {
     // mxe_eval_batch / mxe_audit scratch
     DevBuf<double> ev_x, ev_alpha, ev_scal, ev_vecw, ev_vecs, ev_mat;
     DevBuf<int> ev_elem;
-    // mxe_posterior_var scratch: alpha | H rows | F | var | prior | diag;  elem | row
-    DevBuf<double> pv_d;
-    DevBuf<int> pv_i;
-    // mxe_posterior_sample scratch: alpha | stream ids | H rows | normals | samples  (elem | row in pv_i)
-    DevBuf<double> ps_d;
-    // mxe_resample_reduce scratch: scale | H rows | F | fval | mean | var | fmean | fcov;  offsets | flags | used | rows
-    DevBuf<double> rr_d;
-    DevBuf<int> rr_i;
-    // mxe_evidence_reduce scratch: H rows | logp | log_quad | log_mix | log_prior | F | logZ | walpha | row | fval | wmodel | mean |
-    // between | fmean | fcov;  offsets | pick | good | usable | kmax | ngood | used;  first row of every scan
-    DevBuf<double> er_d;
-    DevBuf<int> er_i;
-    DevBuf<long long> er_l;
+    // scratch blocks of the single-launch entries (each lays its block out where it fills it)
+    DevBuf<double> pv_d;            // mxe_posterior_var, mxe_fit_diagnostics, mxe_response
+    DevBuf<int> pv_i;               //   and mxe_posterior_sample: element | row of every problem
+    DevBuf<double> ps_d;            // mxe_posterior_sample
+    DevBuf<double> rr_d;            // mxe_resample_reduce, mxe_resample_quantiles
+    DevBuf<int> rr_i;               //   their integers
+    DevBuf<double> er_d;            // mxe_evidence_reduce
+    DevBuf<int> er_i;               //   its integers
+    DevBuf<long long> er_l;         //   the first row of every scan
     DevBuf<double> rows_out;        // mxe_fetch_rows: the selected rows, gathered on the device
     DevBuf<int> rows_idx;
     double chi2_factor = 1.0;     // of the staged chains (mxe_opts.chi2_factor)
@@ -342,6 +338,9 @@ struct mxe_ctx {
 
 #define HIPCHK(ctx, call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { \
     (ctx)->hip_err = std::string(#call) + ": " + hipGetErrorString(e__); return MXE_ERR_HIP; } } while (0)
+
+// Stage, Block and the shared checks of the single-launch entry points
+#include "mxe_stage.h"
 
 namespace {
 
@@ -1920,11 +1919,7 @@ template <typename... KArgs, typename... Args>
 static hipError_t launch_factor_kernel(void (*k4)(KArgs...), void (*k8)(KArgs...), const mxe_ctx* ctx, size_t P, size_t lds,
                                        Args... args)
 {
-    void (*k)(KArgs...) = ctx->NP == 64 ? k4 : k8;
-    hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k, dim3((unsigned)P), dim3(256), lds, ctx->stream, args...);
-    return hipGetLastError();
+    return launch_lds(ctx->NP == 64 ? k4 : k8, dim3((unsigned)P), dim3(256), lds, ctx->stream, args...);
 }
 
 extern "C" int mxe_logdet(mxe_ctx* ctx, double* out_logdet)
@@ -1948,28 +1943,6 @@ try {
 }
 MXE_CATCH_ALL
 
-// stream + device buffers of a context-free entry point, released on every path
-namespace {
-struct SvdScratch {
-    hipStream_t stream = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    std::vector<void*> bufs;
-    template <typename T> hipError_t alloc(T** p, size_t count) {
-        hipError_t e = hipMalloc((void**)p, std::max<size_t>(count, 1) * sizeof(T));
-        if (e == hipSuccess) bufs.push_back((void*)*p);
-        return e;
-    }
-    ~SvdScratch() {
-        for (void* b : bufs) hipFree(b);
-        if (e0) hipEventDestroy(e0);
-        if (e1) hipEventDestroy(e1);
-        if (stream) hipStreamDestroy(stream);
-    }
-};
-#define SVDCHK(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { \
-    fprintf(stderr, "[mxe] %s: %s\n", #call, hipGetErrorString(e__)); return MXE_ERR_HIP; } } while (0)
-} // namespace
-
 // ---- cost function and derivatives at caller-supplied points; audit of a launch ----------
 namespace {
 size_t eval_lds_bytes(int NP, int nwp) { return ((size_t)NP * (NP + 1) + 2 * (size_t)nwp + 7 * (size_t)NP + 16) * sizeof(double); }
@@ -1978,14 +1951,8 @@ int launch_eval(mxe_ctx* ctx, const mxe::EvalParams& ep, size_t P)
 {
     const size_t lds = eval_lds_bytes(ctx->NP, ctx->nwp);
     if (lds > 160 * 1024) return MXE_ERR_LIMIT;
-    hipError_t e;
-#define MXE_LAUNCH_EVAL(NT_) do { \
-        e = hipFuncSetAttribute((const void*)mxe::eval_kernel<NT_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        if (e == hipSuccess) { hipLaunchKernelGGL((mxe::eval_kernel<NT_>), dim3((unsigned)P), dim3(256), lds, ctx->stream, ep); \
-                               e = hipGetLastError(); } } while (0)
-    if (ctx->NP == 64) MXE_LAUNCH_EVAL(4); else MXE_LAUNCH_EVAL(8);
-#undef MXE_LAUNCH_EVAL
-    HIPCHK(ctx, e);
+    HIPCHK(ctx, launch_lds(ctx->NP == 64 ? mxe::eval_kernel<4> : mxe::eval_kernel<8>, dim3((unsigned)P), dim3(256), lds,
+                           ctx->stream, ep));
     return MXE_OK;
 }
 
@@ -2115,10 +2082,10 @@ struct PostStage {
     std::vector<int> hi;        // [P] element | [P] row of H
 };
 
-// Checks the state and the problems (elem, alpha, chi2_factor, row) of mxe_posterior_var / mxe_posterior_sample and fills
-// st; uploads the bases when they are stale.  n_max: the largest element count among the call's arrays; z: n_z host values
-// (or NULL) that must be finite before the device is touched.
-int stage_posterior(mxe_ctx* ctx, int P, const int32_t* elem_of_problem, const double* alpha_scaled, const double* H,
+// Checks the state and the problems (elem, alpha, chi2_factor, row) of the posterior calls, opens sg on the context
+// and fills st; uploads the bases when they are stale.  n_max: the largest element count among the call's arrays;
+// z: n_z host values (or NULL) that must be finite before the device is touched.
+int stage_posterior(Stage& sg, mxe_ctx* ctx, int P, const int32_t* elem_of_problem, const double* alpha_scaled, const double* H,
                     const int32_t* problem_index, double chi2_factor, size_t n_max, const double* z, size_t n_z, PostStage& st)
 {
     if (ctx->n_elem < 1) return MXE_ERR_STATE;
@@ -2127,10 +2094,9 @@ int stage_posterior(mxe_ctx* ctx, int P, const int32_t* elem_of_problem, const d
     if (n_max > 0x7fffffffull) return MXE_ERR_ARG;
     st.lds = mxe::postvar_lds_bytes(ctx->NP, ctx->nwp);
     if (st.lds > 160 * 1024) return MXE_ERR_LIMIT;
-    if (z) for (size_t i = 0; i < n_z; ++i) if (!std::isfinite(z[i])) return MXE_ERR_ARG;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    if (ctx->ds_dirty) { int rc = upload_bases(ctx); if (rc != MXE_OK) return rc; }
-    const size_t n_last = (size_t)ctx->n_chain * ctx->n_alpha;
+    if (z && !all_finite(z, n_z)) return MXE_ERR_ARG;
+    if (int rc = sg.open(ctx); rc != MXE_OK) return rc;
+    if (ctx->ds_dirty) if (int rc = upload_bases(ctx); rc != MXE_OK) return rc;
     st.ha.resize(P);
     st.hi.resize((size_t)2 * P);
     for (int p = 0; p < P; ++p) {
@@ -2139,27 +2105,24 @@ int stage_posterior(mxe_ctx* ctx, int P, const int32_t* elem_of_problem, const d
         if (!(alpha_scaled[p] > 0.0) || !std::isfinite(alpha_scaled[p])) return MXE_ERR_ARG;
         st.ha[p] = alpha_scaled[p] / chi2_factor;
         st.hi[p] = e;
-        int row = p;
-        if (!H) {
-            row = problem_index ? problem_index[p] : p;
-            if (row < 0 || (size_t)row >= n_last) return MXE_ERR_ARG;
-        }
-        st.hi[(size_t)P + p] = row;
+        st.hi[(size_t)P + p] = p;
     }
+    if (!H && !launch_rows(problem_index, P, (size_t)ctx->n_chain * ctx->n_alpha, st.hi.data() + P)) return MXE_ERR_ARG;
     return MXE_OK;
 }
 
-// st and the H rows (when handed in) into the block d (alpha first, H at oH) and pv_i; fp: what the kernels share
-int upload_posterior(mxe_ctx* ctx, const PostStage& st, int P, const double* H, double* d, size_t oH, mxe::FactorParams& fp)
+// st and the H rows (when handed in) into the block of the call (alpha at dalpha, the rows at dH) and pv_i; fp: what
+// the kernels share
+int upload_posterior(Stage& sg, const PostStage& st, int P, const double* H, double* dalpha, double* dH, mxe::FactorParams& fp)
 {
+    mxe_ctx* ctx = sg.ctx;
     const int nw = ctx->n_omega;
-    HIPCHK(ctx, ctx->pv_i.ensure((size_t)2 * P));
-    HIPCHK(ctx, hipMemcpyAsync(d, st.ha.data(), (size_t)P * 8, hipMemcpyHostToDevice, ctx->stream));
-    if (H) HIPCHK(ctx, hipMemcpyAsync(d + oH, H, (size_t)P * nw * 8, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->pv_i.p, st.hi.data(), st.hi.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    STGCHK(sg, ctx->pv_i.ensure((size_t)2 * P));
+    STGCHK(sg, sg.upload(dalpha, st.ha.data(), (size_t)P)); STGCHK(sg, sg.upload(dH, H, (size_t)P * nw));
+    STGCHK(sg, sg.upload(ctx->pv_i.p, st.hi.data(), st.hi.size()));
     fp.V = ctx->dV.p; fp.c = ctx->dc.p; fp.elem_ds = ctx->delem_ds.p; fp.elem_kind = ctx->delem_kind.p; fp.D = ctx->dD.p;
-    fp.elem = ctx->pv_i.p; fp.alpha = d;
-    fp.H = H ? d + oH : ctx->dout_H.p; fp.row = H ? nullptr : ctx->pv_i.p + P;
+    fp.elem = ctx->pv_i.p; fp.alpha = dalpha;
+    fp.H = H ? dH : ctx->dout_H.p; fp.row = H ? nullptr : ctx->pv_i.p + P;
     fp.nw = nw; fp.nwp = ctx->nwp; fp.ns = ctx->n_s;
     return MXE_OK;
 }
@@ -2173,40 +2136,38 @@ try {
     if (!ctx || P < 1 || !elem_of_problem || !alpha_scaled || n_f < 0 || (n_f > 0 && (!F || !out_var))) return MXE_ERR_ARG;
     if (n_f == 0 && !out_diag) return MXE_ERR_ARG;
     if (out_prior && n_f == 0) return MXE_ERR_ARG;
-    const int nw = ctx->n_omega;
+    const size_t nw = ctx->n_omega, np = P, nf = n_f;
+    Stage sg;
     PostStage st;
     // n_max bounds what the kernel indexes with 32 bits: var / prior [P][n_f], diag [P][nw] and F [n_f][nw]
-    const size_t n_max = std::max({(size_t)P * (size_t)std::max(n_f, 1), (size_t)P * nw, (size_t)n_f * nw});
-    int rc = stage_posterior(ctx, P, elem_of_problem, alpha_scaled, H, problem_index, chi2_factor, n_max, nullptr, 0, st);
-    if (rc != MXE_OK) return rc;
-    for (size_t i = 0; i < (size_t)n_f * nw; ++i) if (!std::isfinite(F[i])) return MXE_ERR_ARG;
-    // one block of doubles: alpha [P] | H [P][nw] (when handed in) | F [n_f][nw] | var [P][n_f] | prior [P][n_f] | diag [P][nw]
-    const size_t oH = (size_t)P, oF = oH + (H ? (size_t)P * nw : 0), oV = oF + (size_t)n_f * nw, oP = oV + (size_t)P * n_f,
-                 oD = oP + (out_prior ? (size_t)P * n_f : 0), total = oD + (out_diag ? (size_t)P * nw : 0);
-    HIPCHK(ctx, ctx->pv_d.ensure(total));
+    const size_t n_max = std::max({np * std::max<size_t>(nf, 1), np * nw, nf * nw});
+    if (int rc = stage_posterior(sg, ctx, P, elem_of_problem, alpha_scaled, H, problem_index, chi2_factor, n_max, nullptr, 0, st);
+        rc != MXE_OK) return rc;
+    if (!all_finite(F, nf * nw)) return MXE_ERR_ARG;
+    Block b;                                                  // pv_d
+    const size_t oA = b.add(np);                              // alpha [P]
+    const size_t oH = b.add(H ? np * nw : 0);                 // H [P][nw], when handed in
+    const size_t oF = b.add(nf * nw);                         // F [n_f][nw]
+    const size_t oV = b.add(np * nf);                         // var [P][n_f]
+    const size_t oP = b.add(out_prior ? np * nf : 0);         // prior [P][n_f]
+    const size_t oD = b.add(out_diag ? np * nw : 0);          // diag [P][nw]
+    STGCHK(sg, ctx->pv_d.ensure(b.total));
     double* d = ctx->pv_d.p;
     mxe::PostVarParams pp;
-    rc = upload_posterior(ctx, st, P, H, d, oH, pp);
-    if (rc != MXE_OK) return rc;
-    if (n_f) HIPCHK(ctx, hipMemcpyAsync(d + oF, F, (size_t)n_f * nw * 8, hipMemcpyHostToDevice, ctx->stream));
+    if (int rc = upload_posterior(sg, st, P, H, d + oA, d + oH, pp); rc != MXE_OK) return rc;
+    STGCHK(sg, sg.upload(d + oF, F, nf * nw));
     pp.F = n_f ? d + oF : nullptr;
     pp.out_var = d + oV; pp.out_prior = out_prior ? d + oP : nullptr; pp.out_diag = out_diag ? d + oD : nullptr;
     pp.n_f = n_f;
-    SvdScratch sc;                    // (the two events of the timing, released on every path)
-    if (out_ms) {
-        HIPCHK(ctx, hipEventCreate(&sc.e0)); HIPCHK(ctx, hipEventCreate(&sc.e1));
-        HIPCHK(ctx, hipEventRecord(sc.e0, ctx->stream));
-    }
-    HIPCHK(ctx, launch_factor_kernel(mxe::postvar_kernel<4>, mxe::postvar_kernel<8>, ctx, (size_t)P, st.lds, pp));
-    if (out_ms) HIPCHK(ctx, hipEventRecord(sc.e1, ctx->stream));
-    if (n_f) HIPCHK(ctx, hipMemcpyAsync(out_var, d + oV, (size_t)P * n_f * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (out_prior) HIPCHK(ctx, hipMemcpyAsync(out_prior, d + oP, (size_t)P * n_f * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (out_diag) HIPCHK(ctx, hipMemcpyAsync(out_diag, d + oD, (size_t)P * nw * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, stream_wait(ctx->stream));
-    if (out_ms) HIPCHK(ctx, hipEventElapsedTime(out_ms, sc.e0, sc.e1));
+    STGCHK(sg, sg.time_begin(out_ms != nullptr));
+    STGCHK(sg, launch_factor_kernel(mxe::postvar_kernel<4>, mxe::postvar_kernel<8>, ctx, np, st.lds, pp));
+    STGCHK(sg, sg.time_end());
+    STGCHK(sg, sg.fetch(out_var, d + oV, np * nf)); STGCHK(sg, sg.fetch(out_prior, d + oP, np * nf));
+    STGCHK(sg, sg.fetch(out_diag, d + oD, np * nw));
+    STGCHK(sg, sg.finish(out_ms));
     if (chi2_factor != 1.0) {         // Gamma(eta, alpha~) = Gamma(1, alpha~ / eta) / eta
-        for (size_t i = 0; i < (size_t)P * n_f; ++i) { out_var[i] /= chi2_factor; if (out_prior) out_prior[i] /= chi2_factor; }
-        if (out_diag) for (size_t i = 0; i < (size_t)P * nw; ++i) out_diag[i] /= chi2_factor;
+        for (size_t i = 0; i < np * nf; ++i) { out_var[i] /= chi2_factor; if (out_prior) out_prior[i] /= chi2_factor; }
+        if (out_diag) for (size_t i = 0; i < np * nw; ++i) out_diag[i] /= chi2_factor;
     }
     return MXE_OK;
 }
@@ -2219,39 +2180,38 @@ extern "C" int mxe_posterior_sample(mxe_ctx* ctx, int P, const int32_t* elem_of_
 try {
     if (!ctx || P < 1 || !elem_of_problem || !alpha_scaled || !out_dH || n_samples < 1 || (!z && !stream)) return MXE_ERR_ARG;
     const int nw = ctx->n_omega, nz = nw + ctx->n_s;
-    const size_t n_z = (size_t)P * n_samples * nz, n_out = (size_t)P * n_samples * nw;
+    const size_t np = P, n_z = np * n_samples * nz, n_out = np * n_samples * nw;
+    Stage sg;
     PostStage st;
     // n_max = n_z bounds the kernel's 32-bit indices: z [P][n_samples][nz] is the largest array of the call
-    int rc = stage_posterior(ctx, P, elem_of_problem, alpha_scaled, H, problem_index, chi2_factor, n_z, z, n_z, st);
-    if (rc != MXE_OK) return rc;
-    // one block of doubles: alpha [P] | stream ids [P] (64-bit words) | H [P][nw] (when handed in) | z | samples
-    const size_t oS = (size_t)P, oH = oS + (size_t)P, oZ = oH + (H ? (size_t)P * nw : 0), oO = oZ + n_z, total = oO + n_out;
-    HIPCHK(ctx, ctx->ps_d.ensure(total));
+    if (int rc = stage_posterior(sg, ctx, P, elem_of_problem, alpha_scaled, H, problem_index, chi2_factor, n_z, z, n_z, st);
+        rc != MXE_OK) return rc;
+    Block b;                                                  // ps_d
+    const size_t oA = b.add(np);                              // alpha [P]
+    const size_t oS = b.add(np);                              // stream ids [P] (64-bit words)
+    const size_t oH = b.add(H ? np * nw : 0);                 // H [P][nw], when handed in
+    const size_t oZ = b.add(n_z);                             // z [P][n_samples][nz]
+    const size_t oO = b.add(n_out);                           // samples [P][n_samples][nw]
+    STGCHK(sg, ctx->ps_d.ensure(b.total));
     double* d = ctx->ps_d.p;
     mxe::PostSampleParams pp;
-    rc = upload_posterior(ctx, st, P, H, d, oH, pp);
-    if (rc != MXE_OK) return rc;
-    if (z) HIPCHK(ctx, hipMemcpyAsync(d + oZ, z, n_z * 8, hipMemcpyHostToDevice, ctx->stream));
-    else HIPCHK(ctx, hipMemcpyAsync(d + oS, stream, (size_t)P * 8, hipMemcpyHostToDevice, ctx->stream));
+    if (int rc = upload_posterior(sg, st, P, H, d + oA, d + oH, pp); rc != MXE_OK) return rc;
+    if (z) STGCHK(sg, sg.upload(d + oZ, z, n_z));
+    else STGCHK(sg, sg.upload((uint64_t*)(d + oS), stream, np));
     pp.z = d + oZ; pp.out = d + oO; pp.scale = 1.0 / std::sqrt(chi2_factor);
     pp.n_samples = n_samples;
-    SvdScratch sc;                    // (the two events of the timing, released on every path)
-    if (out_ms) {
-        HIPCHK(ctx, hipEventCreate(&sc.e0)); HIPCHK(ctx, hipEventCreate(&sc.e1));
-        HIPCHK(ctx, hipEventRecord(sc.e0, ctx->stream));
-    }
+    STGCHK(sg, sg.time_begin(out_ms != nullptr));
     if (!z) {
         const size_t per = (size_t)n_samples * ((nz + 1) / 2);
         const unsigned gx = (unsigned)std::min<size_t>((per + 255) / 256, 1024), gy = (unsigned)std::min(P, 65535);
         hipLaunchKernelGGL(mxe::normals_kernel, dim3(gx, gy), dim3(256), 0, ctx->stream, seed, (const uint64_t*)(d + oS),
                            (uint64_t)0, P, n_samples, nz, d + oZ);
-        HIPCHK(ctx, hipGetLastError());
+        STGCHK(sg, hipGetLastError());
     }
-    HIPCHK(ctx, launch_factor_kernel(mxe::postsample_kernel<4>, mxe::postsample_kernel<8>, ctx, (size_t)P, st.lds, pp));
-    if (out_ms) HIPCHK(ctx, hipEventRecord(sc.e1, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(out_dH, d + oO, n_out * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, stream_wait(ctx->stream));
-    if (out_ms) HIPCHK(ctx, hipEventElapsedTime(out_ms, sc.e0, sc.e1));
+    STGCHK(sg, launch_factor_kernel(mxe::postsample_kernel<4>, mxe::postsample_kernel<8>, ctx, np, st.lds, pp));
+    STGCHK(sg, sg.time_end());
+    STGCHK(sg, sg.fetch(out_dH, d + oO, n_out));
+    STGCHK(sg, sg.finish(out_ms));
     return MXE_OK;
 }
 MXE_CATCH_ALL
@@ -2264,50 +2224,44 @@ extern "C" int mxe_fit_diagnostics(mxe_ctx* ctx, int P, const int32_t* elem_of_p
                                    double* out_ngood, double* out_chi2, double* out_resid, double* out_lev, float* out_ms)
 try {
     if (!ctx || P < 1 || !elem_of_problem || !alpha_scaled || ld < 1) return MXE_ERR_ARG;
-    const int nw = ctx->n_omega;
+    const size_t nw = ctx->n_omega, np = P, nl = ld;
+    Stage sg;
     PostStage st;
     // n_max bounds what the kernel's callers index: residuals / leverages [P][ld] and the H rows [P][nw]
-    int rc = stage_posterior(ctx, P, elem_of_problem, alpha_scaled, H, problem_index, chi2_factor,
-                             std::max((size_t)P * (size_t)ld, (size_t)P * nw), nullptr, 0, st);
-    if (rc != MXE_OK) return rc;
+    if (int rc = stage_posterior(sg, ctx, P, elem_of_problem, alpha_scaled, H, problem_index, chi2_factor,
+                             std::max(np * nl, np * nw), nullptr, 0, st); rc != MXE_OK) return rc;
     for (int p = 0; p < P; ++p)
         if (ctx->ds[ctx->elem_ds[elem_of_problem[p]]].n_rows > ld) return MXE_ERR_ARG;
     // Uhat of the data sets and rperp of the elements: at the first call and after any change of either
-    rc = upload_projection(ctx);
-    if (rc != MXE_OK) return rc;
-    rc = upload_row_offsets(ctx);
-    if (rc != MXE_OK) return rc;
+    if (int rc = upload_projection(ctx); rc != MXE_OK) return rc;
+    if (int rc = upload_row_offsets(ctx); rc != MXE_OK) return rc;
     if (ctx->rperp_dirty) {
-        HIPCHK(ctx, hipMemcpyAsync(ctx->drperp.p, ctx->h_rperp.data(), ctx->h_rperp.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(ctx, stream_wait(ctx->stream));
+        STGCHK(sg, sg.upload(ctx->drperp.p, ctx->h_rperp.data(), ctx->h_rperp.size()));
+        STGCHK(sg, stream_wait(ctx->stream));
         ctx->rperp_dirty = false;
     }
-    // one block of doubles: alpha [P] | H [P][nw] (when handed in) | N_g [P] | chi2 [P] | residuals [P][ld] | leverages [P][ld]
-    const size_t oH = (size_t)P, oN = oH + (H ? (size_t)P * nw : 0), oC = oN + (size_t)P, oR = oC + (size_t)P,
-                 oL = oR + (size_t)P * ld, total = oL + (size_t)P * ld;
-    HIPCHK(ctx, ctx->pv_d.ensure(total));
+    Block b;                                                  // pv_d
+    const size_t oA = b.add(np);                              // alpha [P]
+    const size_t oH = b.add(H ? np * nw : 0);                 // H [P][nw], when handed in
+    const size_t oN = b.add(np);                              // N_g [P]
+    const size_t oC = b.add(np);                              // chi2 [P]
+    const size_t oR = b.add(np * nl);                         // residuals [P][ld]
+    const size_t oL = b.add(np * nl);                         // leverages [P][ld]
+    STGCHK(sg, ctx->pv_d.ensure(b.total));
     double* d = ctx->pv_d.p;
     mxe::FitDiagParams pp;
-    rc = upload_posterior(ctx, st, P, H, d, oH, pp);
-    if (rc != MXE_OK) return rc;
+    if (int rc = upload_posterior(sg, st, P, H, d + oA, d + oH, pp); rc != MXE_OK) return rc;
     pp.ghat = ctx->dghat.p; pp.U = ctx->dproj_U.p; pp.ds_off = ctx->dproj_off.p;
     pp.rperp = ctx->drperp.p; pp.elem_roff = ctx->delem_roff.p;
     pp.out_ngood = d + oN; pp.out_chi2 = d + oC; pp.out_resid = d + oR; pp.out_lev = d + oL;
     pp.ld = ld;
     const size_t lds = mxe::fitdiag_lds_bytes(ctx->NP, ctx->nwp);      // (below postvar_kernel's, which stage_posterior checked)
-    SvdScratch sc;                    // (the two events of the timing, released on every path)
-    if (out_ms) {
-        HIPCHK(ctx, hipEventCreate(&sc.e0)); HIPCHK(ctx, hipEventCreate(&sc.e1));
-        HIPCHK(ctx, hipEventRecord(sc.e0, ctx->stream));
-    }
-    HIPCHK(ctx, launch_factor_kernel(mxe::fitdiag_kernel<4>, mxe::fitdiag_kernel<8>, ctx, (size_t)P, lds, pp));
-    if (out_ms) HIPCHK(ctx, hipEventRecord(sc.e1, ctx->stream));
-    if (out_ngood) HIPCHK(ctx, hipMemcpyAsync(out_ngood, d + oN, (size_t)P * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (out_chi2) HIPCHK(ctx, hipMemcpyAsync(out_chi2, d + oC, (size_t)P * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (out_resid) HIPCHK(ctx, hipMemcpyAsync(out_resid, d + oR, (size_t)P * ld * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (out_lev) HIPCHK(ctx, hipMemcpyAsync(out_lev, d + oL, (size_t)P * ld * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, stream_wait(ctx->stream));
-    if (out_ms) HIPCHK(ctx, hipEventElapsedTime(out_ms, sc.e0, sc.e1));
+    STGCHK(sg, sg.time_begin(out_ms != nullptr));
+    STGCHK(sg, launch_factor_kernel(mxe::fitdiag_kernel<4>, mxe::fitdiag_kernel<8>, ctx, np, lds, pp));
+    STGCHK(sg, sg.time_end());
+    STGCHK(sg, sg.fetch(out_ngood, d + oN, np)); STGCHK(sg, sg.fetch(out_chi2, d + oC, np));
+    STGCHK(sg, sg.fetch(out_resid, d + oR, np * nl)); STGCHK(sg, sg.fetch(out_lev, d + oL, np * nl));
+    STGCHK(sg, sg.finish(out_ms));
     return MXE_OK;
 }
 MXE_CATCH_ALL
@@ -2321,42 +2275,40 @@ extern "C" int mxe_response(mxe_ctx* ctx, int P, const int32_t* elem_of_problem,
 try {
     if (!ctx || P < 1 || !elem_of_problem || !alpha_scaled || !F || !out_X || n_rhs < 1 || ld < 1) return MXE_ERR_ARG;
     if (space != 0 && space != 1) return MXE_ERR_ARG;
-    const int nw = ctx->n_omega;
-    if (space == 0 && ld < nw) return MXE_ERR_ARG;
+    const size_t nw = ctx->n_omega, np = P;
+    if (space == 0 && (size_t)ld < nw) return MXE_ERR_ARG;
     // n_max bounds the arrays of the call: F [P][n_rhs][ld] and X [P][n_rhs][nw]
-    if ((size_t)P * (size_t)n_rhs > 0x7fffffffull) return MXE_ERR_ARG;       // (the products below stay within 64 bits)
-    const size_t n_F = (size_t)P * (size_t)n_rhs * (size_t)ld, n_X = (size_t)P * (size_t)n_rhs * (size_t)nw;
+    if (np * (size_t)n_rhs > 0x7fffffffull) return MXE_ERR_ARG;       // (the products below stay within 64 bits)
+    const size_t n_F = np * (size_t)n_rhs * (size_t)ld, n_X = np * (size_t)n_rhs * nw;
+    Stage sg;
     PostStage st;
-    int rc = stage_posterior(ctx, P, elem_of_problem, alpha_scaled, H, problem_index, chi2_factor, std::max(n_F, n_X), F, n_F, st);
-    if (rc != MXE_OK) return rc;
+    if (int rc = stage_posterior(sg, ctx, P, elem_of_problem, alpha_scaled, H, problem_index, chi2_factor, std::max(n_F, n_X), F,
+                                 n_F, st); rc != MXE_OK) return rc;
     if (space == 1) {
         for (int p = 0; p < P; ++p)
             if (ctx->ds[ctx->elem_ds[elem_of_problem[p]]].n_rows > ld) return MXE_ERR_ARG;
-        rc = upload_projection(ctx);          // Uhat of the data sets: at the first call and after any change of them
-        if (rc != MXE_OK) return rc;
+        // Uhat of the data sets: at the first call and after any change of them
+        if (int rc = upload_projection(ctx); rc != MXE_OK) return rc;
     }
-    // one block of doubles: alpha [P] | H [P][nw] (when handed in) | F [P][n_rhs][ld] | X [P][n_rhs][nw]
-    const size_t oH = (size_t)P, oF = oH + (H ? (size_t)P * nw : 0), oX = oF + n_F, total = oX + n_X;
-    HIPCHK(ctx, ctx->pv_d.ensure(total));
+    Block b;                                                  // pv_d
+    const size_t oA = b.add(np);                              // alpha [P]
+    const size_t oH = b.add(H ? np * nw : 0);                 // H [P][nw], when handed in
+    const size_t oF = b.add(n_F);                             // F [P][n_rhs][ld]
+    const size_t oX = b.add(n_X);                             // X [P][n_rhs][nw]
+    STGCHK(sg, ctx->pv_d.ensure(b.total));
     double* d = ctx->pv_d.p;
     mxe::ResponseParams pp;
-    rc = upload_posterior(ctx, st, P, H, d, oH, pp);
-    if (rc != MXE_OK) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(d + oF, F, n_F * 8, hipMemcpyHostToDevice, ctx->stream));
+    if (int rc = upload_posterior(sg, st, P, H, d + oA, d + oH, pp); rc != MXE_OK) return rc;
+    STGCHK(sg, sg.upload(d + oF, F, n_F));
     pp.F = d + oF; pp.out = d + oX;
     pp.U = space ? ctx->dproj_U.p : nullptr; pp.ds_off = space ? ctx->dproj_off.p : nullptr;
     pp.n_rhs = n_rhs; pp.ld = ld; pp.space = space; pp.weighted = weighted ? 1 : 0;
     const size_t lds = mxe::response_lds_bytes(ctx->NP, ctx->nwp);     // (below postvar_kernel's, which stage_posterior checked)
-    SvdScratch sc;                    // (the two events of the timing, released on every path)
-    if (out_ms) {
-        HIPCHK(ctx, hipEventCreate(&sc.e0)); HIPCHK(ctx, hipEventCreate(&sc.e1));
-        HIPCHK(ctx, hipEventRecord(sc.e0, ctx->stream));
-    }
-    HIPCHK(ctx, launch_factor_kernel(mxe::response_kernel<4>, mxe::response_kernel<8>, ctx, (size_t)P, lds, pp));
-    if (out_ms) HIPCHK(ctx, hipEventRecord(sc.e1, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(out_X, d + oX, n_X * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, stream_wait(ctx->stream));
-    if (out_ms) HIPCHK(ctx, hipEventElapsedTime(out_ms, sc.e0, sc.e1));
+    STGCHK(sg, sg.time_begin(out_ms != nullptr));
+    STGCHK(sg, launch_factor_kernel(mxe::response_kernel<4>, mxe::response_kernel<8>, ctx, np, lds, pp));
+    STGCHK(sg, sg.time_end());
+    STGCHK(sg, sg.fetch(out_X, d + oX, n_X));
+    STGCHK(sg, sg.finish(out_ms));
     return MXE_OK;
 }
 MXE_CATCH_ALL
@@ -2364,20 +2316,16 @@ MXE_CATCH_ALL
 extern "C" int mxe_normals(int device, uint64_t seed, uint64_t stream, int n_samples, int n, double* out_z)
 try {
     if (n_samples < 1 || n < 1 || !out_z || (size_t)n_samples * (size_t)n > 0x7fffffffull) return MXE_ERR_ARG;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return MXE_ERR_NODEVICE;
-    if (device < 0 || device >= ndev) return MXE_ERR_ARG;
-    SvdScratch sc;                    // stream + buffer released on every path
-    SVDCHK(hipSetDevice(device));
-    SVDCHK(hipStreamCreateWithFlags(&sc.stream, hipStreamNonBlocking));
+    Stage sg;
+    if (int rc = sg.open(device); rc != MXE_OK) return rc;
     double* dz;
-    SVDCHK(sc.alloc(&dz, (size_t)n_samples * n));
+    STGCHK(sg, sg.alloc(&dz, (size_t)n_samples * n));
     const size_t per = (size_t)n_samples * ((n + 1) / 2);
-    hipLaunchKernelGGL(mxe::normals_kernel, dim3((unsigned)std::min<size_t>((per + 255) / 256, 1024), 1), dim3(256), 0, sc.stream,
+    hipLaunchKernelGGL(mxe::normals_kernel, dim3((unsigned)std::min<size_t>((per + 255) / 256, 1024), 1), dim3(256), 0, sg.stream,
                        seed, (const uint64_t*)nullptr, stream, 1, n_samples, n, dz);
-    SVDCHK(hipGetLastError());
-    SVDCHK(hipMemcpyAsync(out_z, dz, (size_t)n_samples * n * 8, hipMemcpyDeviceToHost, sc.stream));
-    SVDCHK(hipStreamSynchronize(sc.stream));
+    STGCHK(sg, hipGetLastError());
+    STGCHK(sg, sg.fetch(out_z, dz, (size_t)n_samples * n));
+    STGCHK(sg, sg.finish(nullptr));
     return MXE_OK;
 }
 MXE_CATCH_ALL
@@ -2386,24 +2334,18 @@ extern "C" int mxe_entropy(int device, int kind, int n_omega, int P, const doubl
                            double* out_S, double* out_dS, double* out_ddS)
 try {
     if (n_omega < 1 || P < 1 || !H || !D || (kind != MXE_ENTROPY_NORMAL && kind != MXE_ENTROPY_PLUSMINUS)) return MXE_ERR_ARG;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return MXE_ERR_NODEVICE;
-    if (device < 0 || device >= ndev) return MXE_ERR_ARG;
-    SvdScratch sc;                    // stream + buffers released on every path
-    SVDCHK(hipSetDevice(device));
-    SVDCHK(hipStreamCreateWithFlags(&sc.stream, hipStreamNonBlocking));
-    const size_t n = n_omega;
+    Stage sg;
+    if (int rc = sg.open(device); rc != MXE_OK) return rc;
+    const size_t n = n_omega, np = P;
     double *dH, *dD, *dS, *dd, *ddd;
-    SVDCHK(sc.alloc(&dH, (size_t)P * n)); SVDCHK(sc.alloc(&dD, n)); SVDCHK(sc.alloc(&dS, (size_t)P));
-    SVDCHK(sc.alloc(&dd, (size_t)P * n)); SVDCHK(sc.alloc(&ddd, (size_t)P * n));
-    SVDCHK(hipMemcpyAsync(dH, H, (size_t)P * n * 8, hipMemcpyHostToDevice, sc.stream));
-    SVDCHK(hipMemcpyAsync(dD, D, n * 8, hipMemcpyHostToDevice, sc.stream));
-    hipLaunchKernelGGL(mxe::entropy_kernel, dim3((unsigned)P), dim3(256), 0, sc.stream, kind, n_omega, dH, dD, dS, dd, ddd);
-    SVDCHK(hipGetLastError());
-    if (out_S) SVDCHK(hipMemcpyAsync(out_S, dS, (size_t)P * 8, hipMemcpyDeviceToHost, sc.stream));
-    if (out_dS) SVDCHK(hipMemcpyAsync(out_dS, dd, (size_t)P * n * 8, hipMemcpyDeviceToHost, sc.stream));
-    if (out_ddS) SVDCHK(hipMemcpyAsync(out_ddS, ddd, (size_t)P * n * 8, hipMemcpyDeviceToHost, sc.stream));
-    SVDCHK(hipStreamSynchronize(sc.stream));
+    STGCHK(sg, sg.alloc(&dH, np * n)); STGCHK(sg, sg.alloc(&dD, n)); STGCHK(sg, sg.alloc(&dS, np));
+    STGCHK(sg, sg.alloc(&dd, np * n)); STGCHK(sg, sg.alloc(&ddd, np * n));
+    STGCHK(sg, sg.upload(dH, H, np * n)); STGCHK(sg, sg.upload(dD, D, n));
+    hipLaunchKernelGGL(mxe::entropy_kernel, dim3((unsigned)P), dim3(256), 0, sg.stream, kind, n_omega, dH, dD, dS, dd, ddd);
+    STGCHK(sg, hipGetLastError());
+    STGCHK(sg, sg.fetch(out_S, dS, np)); STGCHK(sg, sg.fetch(out_dS, dd, np * n));
+    STGCHK(sg, sg.fetch(out_ddS, ddd, np * n));
+    STGCHK(sg, sg.finish(nullptr));
     return MXE_OK;
 }
 MXE_CATCH_ALL
@@ -2948,63 +2890,48 @@ int kernel_svd_common(int device, int n_grid, int m_rows, int n_omega, const dou
                       double* out_K, double* out_U, double* out_S, double* out_V, int32_t* out_ns,
                       int32_t* out_info, float* out_ms, Fill fill)
 {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return MXE_ERR_NODEVICE;
-    if (device < 0 || device >= ndev) return MXE_ERR_ARG;
+    Stage sg;
+    if (int rc = sg.open(device); rc != MXE_OK) return rc;
     const size_t lds = svd_lds_bytes(m_rows);
     if (lds > SVD_LDS_LIMIT) return MXE_ERR_LIMIT;
-    SVDCHK(hipSetDevice(device));
-    SvdScratch sc;
-    SVDCHK(hipStreamCreateWithFlags(&sc.stream, hipStreamNonBlocking));
-    SVDCHK(hipEventCreate(&sc.e0));
-    SVDCHK(hipEventCreate(&sc.e1));
-    const size_t m = m_rows, n = n_omega, R = mxe::SVD_RCAP;
+    const size_t m = m_rows, n = n_omega, R = mxe::SVD_RCAP, nb = n_b;
     double *dgrid, *dom, *ddel, *dKt0, *dr1, *ddc, *dB;
     mxe::SvdParams sp;
     sp.m = m_rows; sp.n = n_omega; sp.ns_max = ns_max; sp.threshold = threshold;
-    SVDCHK(sc.alloc(&dgrid, n_grid)); SVDCHK(sc.alloc(&dom, n)); SVDCHK(sc.alloc(&ddel, n));
-    SVDCHK(sc.alloc(&dKt0, n * m)); SVDCHK(sc.alloc(&dr1, n)); SVDCHK(sc.alloc(&ddc, n)); SVDCHK(sc.alloc(&dB, n * n));
-    SVDCHK(sc.alloc(&sp.A, (size_t)n_b * n * m)); SVDCHK(sc.alloc(&sp.Vh, (size_t)n_b * R * m));
-    SVDCHK(sc.alloc(&sp.Rm, (size_t)n_b * R * n)); SVDCHK(sc.alloc(&sp.Jt, (size_t)n_b * R * R));
-    SVDCHK(sc.alloc(&sp.Qc, (size_t)n_b * R * m)); SVDCHK(sc.alloc(&sp.cn2, (size_t)n_b * n));
-    SVDCHK(sc.alloc(&sp.perm, (size_t)n_b * n));
-    SVDCHK(sc.alloc(&sp.out_U, (size_t)n_b * m * ns_max)); SVDCHK(sc.alloc(&sp.out_S, (size_t)n_b * ns_max));
-    SVDCHK(sc.alloc(&sp.out_V, (size_t)n_b * n * ns_max)); SVDCHK(sc.alloc(&sp.out_info, (size_t)n_b * 4));
-    SVDCHK(hipMemcpyAsync(dgrid, grid, (size_t)n_grid * 8, hipMemcpyHostToDevice, sc.stream));
-    SVDCHK(hipMemcpyAsync(dom, omega, n * 8, hipMemcpyHostToDevice, sc.stream));
-    SVDCHK(hipMemcpyAsync(ddel, delta, n * 8, hipMemcpyHostToDevice, sc.stream));
-    SVDCHK(hipEventRecord(sc.e0, sc.stream));
-    fill(sc.stream, dgrid, dom, dKt0);
-    SVDCHK(hipGetLastError());
+    STGCHK(sg, sg.alloc(&dgrid, (size_t)n_grid)); STGCHK(sg, sg.alloc(&dom, n)); STGCHK(sg, sg.alloc(&ddel, n));
+    STGCHK(sg, sg.alloc(&dKt0, n * m)); STGCHK(sg, sg.alloc(&dr1, n)); STGCHK(sg, sg.alloc(&ddc, n)); STGCHK(sg, sg.alloc(&dB, n * n));
+    STGCHK(sg, sg.alloc(&sp.A, nb * n * m)); STGCHK(sg, sg.alloc(&sp.Vh, nb * R * m));
+    STGCHK(sg, sg.alloc(&sp.Rm, nb * R * n)); STGCHK(sg, sg.alloc(&sp.Jt, nb * R * R));
+    STGCHK(sg, sg.alloc(&sp.Qc, nb * R * m)); STGCHK(sg, sg.alloc(&sp.cn2, nb * n));
+    STGCHK(sg, sg.alloc(&sp.perm, nb * n));
+    STGCHK(sg, sg.alloc(&sp.out_U, nb * m * ns_max)); STGCHK(sg, sg.alloc(&sp.out_S, nb * ns_max));
+    STGCHK(sg, sg.alloc(&sp.out_V, nb * n * ns_max)); STGCHK(sg, sg.alloc(&sp.out_info, nb * 4));
+    STGCHK(sg, sg.upload(dgrid, grid, (size_t)n_grid)); STGCHK(sg, sg.upload(dom, omega, n)); STGCHK(sg, sg.upload(ddel, delta, n));
+    STGCHK(sg, sg.time_begin(out_ms != nullptr));
+    fill(sg.stream, dgrid, dom, dKt0);
+    STGCHK(sg, hipGetLastError());
     for (int ib = 0; ib < n_b; ++ib) {
         double* Ai = sp.A + (size_t)ib * n * m;
         const double b = preblur_b[ib];
         if (b > 0.0) {
-            hipLaunchKernelGGL(mxe::preblur_rows, dim3(n_omega), dim3(256), 0, sc.stream, dom, ddel, b, n_omega, dr1);
-            hipLaunchKernelGGL(mxe::preblur_cols, dim3(n_omega), dim3(256), 0, sc.stream, dom, ddel, b, n_omega, dr1, ddc);
-            hipLaunchKernelGGL(mxe::preblur_matrix, dim3((n_omega * n_omega + 255) / 256), dim3(256), 0, sc.stream, dom, b, n_omega, dr1, ddc, dB);
-            hipLaunchKernelGGL(mxe::preblur_product, dim3(n_omega), dim3(256), n * 8, sc.stream, dKt0, ddel, dB, m_rows, n_omega, Ai);
-            SVDCHK(hipGetLastError());
+            hipLaunchKernelGGL(mxe::preblur_rows, dim3(n_omega), dim3(256), 0, sg.stream, dom, ddel, b, n_omega, dr1);
+            hipLaunchKernelGGL(mxe::preblur_cols, dim3(n_omega), dim3(256), 0, sg.stream, dom, ddel, b, n_omega, dr1, ddc);
+            hipLaunchKernelGGL(mxe::preblur_matrix, dim3((n_omega * n_omega + 255) / 256), dim3(256), 0, sg.stream, dom, b, n_omega, dr1, ddc, dB);
+            hipLaunchKernelGGL(mxe::preblur_product, dim3(n_omega), dim3(256), n * 8, sg.stream, dKt0, ddel, dB, m_rows, n_omega, Ai);
+            STGCHK(sg, hipGetLastError());
         } else {
-            SVDCHK(hipMemcpyAsync(Ai, dKt0, n * m * 8, hipMemcpyDeviceToDevice, sc.stream));
+            STGCHK(sg, hipMemcpyAsync(Ai, dKt0, n * m * 8, hipMemcpyDeviceToDevice, sg.stream));
         }
     }
-    std::vector<double> hKt;
-    if (out_K) {
-        hKt.resize((size_t)n_b * n * m);
-        SVDCHK(hipMemcpyAsync(hKt.data(), sp.A, hKt.size() * 8, hipMemcpyDeviceToHost, sc.stream));
-    }
-    SVDCHK(hipFuncSetAttribute((const void*)mxe::svd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(mxe::svd_kernel, dim3(n_b), dim3(mxe::SVD_T), lds, sc.stream, sp);
-    SVDCHK(hipGetLastError());
-    SVDCHK(hipEventRecord(sc.e1, sc.stream));
-    std::vector<int> hinfo((size_t)n_b * 4);
-    SVDCHK(hipMemcpyAsync(out_U, sp.out_U, (size_t)n_b * m * ns_max * 8, hipMemcpyDeviceToHost, sc.stream));
-    SVDCHK(hipMemcpyAsync(out_S, sp.out_S, (size_t)n_b * ns_max * 8, hipMemcpyDeviceToHost, sc.stream));
-    SVDCHK(hipMemcpyAsync(out_V, sp.out_V, (size_t)n_b * n * ns_max * 8, hipMemcpyDeviceToHost, sc.stream));
-    SVDCHK(hipMemcpyAsync(hinfo.data(), sp.out_info, hinfo.size() * 4, hipMemcpyDeviceToHost, sc.stream));
-    SVDCHK(hipStreamSynchronize(sc.stream));
-    if (out_ms) SVDCHK(hipEventElapsedTime(out_ms, sc.e0, sc.e1));
+    // K^T and the info words go through host vectors: K is transposed, the info words are unpacked below
+    std::vector<double> hKt(out_K ? nb * n * m : 0);
+    STGCHK(sg, sg.fetch(hKt.data(), sp.A, hKt.size()));
+    STGCHK(sg, launch_lds(mxe::svd_kernel, dim3(n_b), dim3(mxe::SVD_T), lds, sg.stream, sp));
+    STGCHK(sg, sg.time_end());
+    std::vector<int> hinfo(nb * 4);
+    STGCHK(sg, sg.fetch(out_U, sp.out_U, nb * m * ns_max)); STGCHK(sg, sg.fetch(out_S, sp.out_S, nb * ns_max));
+    STGCHK(sg, sg.fetch(out_V, sp.out_V, nb * n * ns_max)); STGCHK(sg, sg.fetch(hinfo.data(), sp.out_info, hinfo.size()));
+    STGCHK(sg, sg.finish(out_ms));
     int rc = MXE_OK;
     for (int ib = 0; ib < n_b; ++ib) {
         out_ns[ib] = hinfo[(size_t)ib * 4];
@@ -3018,10 +2945,10 @@ int kernel_svd_common(int device, int n_grid, int m_rows, int n_omega, const dou
             if (std::isnan(out_S[(size_t)ib * ns_max + k])) rc = MXE_ERR_NUMERIC;
     }
     if (out_K)
-        for (int ib = 0; ib < n_b; ++ib)
+        for (size_t ib = 0; ib < nb; ++ib)
             for (size_t j = 0; j < n; ++j)
                 for (size_t i = 0; i < m; ++i)
-                    out_K[((size_t)ib * m + i) * n + j] = hKt[((size_t)ib * n + j) * m + i];
+                    out_K[(ib * m + i) * n + j] = hKt[(ib * n + j) * m + i];
     return rc;
 }
 } // namespace
@@ -3138,7 +3065,7 @@ try {
     // (before the matrix is copied: kernel_svd_common would refuse the same rows after its own check)
     if (svd_lds_bytes(n_rows) > SVD_LDS_LIMIT) return MXE_ERR_LIMIT;
     // a caller's matrix may hold anything: NaN and Inf are refused before the launch
-    for (size_t i = 0, nel = (size_t)n_rows * n_omega; i < nel; ++i) if (!std::isfinite(K[i])) return MXE_ERR_NUMERIC;
+    if (!all_finite(K, (size_t)n_rows * n_omega)) return MXE_ERR_NUMERIC;
     return kernel_svd_common(device, n_rows * n_omega, n_rows, n_omega, K, omega, delta, n_b, preblur_b, threshold,
                              ns_max, out_K, out_U, out_S, out_V, out_ns, out_info, out_ms,
                              [=](hipStream_t st, const double* dK, const double*, double* dKt0) {
@@ -3167,10 +3094,8 @@ extern "C" int mxe_kramers_kronig(int device, int n_w, const double* w, const do
 try {
     if (n_w < 1 || n_out < 1 || n_spec < 1 || !w || !weight || !eta || !w_out || !A || !out_G) return MXE_ERR_ARG;
     if ((int64_t)n_spec * n_out > INT32_MAX || (int64_t)n_spec * n_w > INT32_MAX) return MXE_ERR_ARG;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return MXE_ERR_NODEVICE;
-    if (device < 0 || device >= ndev) return MXE_ERR_ARG;
-    SVDCHK(hipSetDevice(device));
+    Stage sg;
+    if (int rc = sg.open(device); rc != MXE_OK) return rc;
     const int TS = n_spec <= 2 ? 2 : n_spec <= 8 ? 8 : 16;        // spectra per workgroup tile
     const int n_slice = (n_w + mxe::KK_SLICE - 1) / mxe::KK_SLICE;
     const int n_o_tiles = (n_out + mxe::KK_T - 1) / mxe::KK_T;
@@ -3180,36 +3105,29 @@ try {
     const int64_t wgs = (int64_t)((n_spec + TS - 1) / TS) * n_o_tiles;
     const bool split = n_slice > 1 && n_slice <= 65535 && wgs < 1024 && (int64_t)n_slice * n_res * 16 <= ((int64_t)1 << 30);
     if (n_o_tiles > 65535) return MXE_ERR_LIMIT;                   // (the grid's y extent)
-    SvdScratch sc;
-    SVDCHK(hipStreamCreateWithFlags(&sc.stream, hipStreamNonBlocking));
-    SVDCHK(hipEventCreate(&sc.e0));
-    SVDCHK(hipEventCreate(&sc.e1));
     double *dw, *dwt, *deta, *dwo, *dA, *dG, *dP = nullptr;
-    SVDCHK(sc.alloc(&dw, n_w)); SVDCHK(sc.alloc(&dwt, n_w)); SVDCHK(sc.alloc(&deta, n_w));
-    SVDCHK(sc.alloc(&dwo, n_out)); SVDCHK(sc.alloc(&dA, (size_t)n_spec * n_w)); SVDCHK(sc.alloc(&dG, 2 * n_res));
-    if (split) SVDCHK(sc.alloc(&dP, 2 * n_res * n_slice));
-    SVDCHK(hipMemcpyAsync(dw, w, (size_t)n_w * 8, hipMemcpyHostToDevice, sc.stream));
-    SVDCHK(hipMemcpyAsync(dwt, weight, (size_t)n_w * 8, hipMemcpyHostToDevice, sc.stream));
-    SVDCHK(hipMemcpyAsync(deta, eta, (size_t)n_w * 8, hipMemcpyHostToDevice, sc.stream));
-    SVDCHK(hipMemcpyAsync(dwo, w_out, (size_t)n_out * 8, hipMemcpyHostToDevice, sc.stream));
-    SVDCHK(hipMemcpyAsync(dA, A, (size_t)n_spec * n_w * 8, hipMemcpyHostToDevice, sc.stream));
-    SVDCHK(hipEventRecord(sc.e0, sc.stream));
+    const size_t nwz = n_w, n_A = (size_t)n_spec * n_w;
+    STGCHK(sg, sg.alloc(&dw, nwz)); STGCHK(sg, sg.alloc(&dwt, nwz)); STGCHK(sg, sg.alloc(&deta, nwz));
+    STGCHK(sg, sg.alloc(&dwo, (size_t)n_out)); STGCHK(sg, sg.alloc(&dA, n_A)); STGCHK(sg, sg.alloc(&dG, 2 * n_res));
+    if (split) STGCHK(sg, sg.alloc(&dP, 2 * n_res * n_slice));
+    STGCHK(sg, sg.upload(dw, w, nwz)); STGCHK(sg, sg.upload(dwt, weight, nwz)); STGCHK(sg, sg.upload(deta, eta, nwz));
+    STGCHK(sg, sg.upload(dwo, w_out, (size_t)n_out)); STGCHK(sg, sg.upload(dA, A, n_A));
+    STGCHK(sg, sg.time_begin(out_ms != nullptr));
     mxe::KKParams p;
     p.w = dw; p.weight = dwt; p.eta = deta; p.w_out = dwo; p.A = dA; p.out = split ? dP : dG;
     p.n_w = n_w; p.n_out = n_out; p.n_spec = n_spec; p.n_slice = n_slice;
-    if (TS == 2) kk_launch<2>(sc.stream, p, n_o_tiles, split);
-    else if (TS == 8) kk_launch<8>(sc.stream, p, n_o_tiles, split);
-    else kk_launch<16>(sc.stream, p, n_o_tiles, split);
-    SVDCHK(hipGetLastError());
+    if (TS == 2) kk_launch<2>(sg.stream, p, n_o_tiles, split);
+    else if (TS == 8) kk_launch<8>(sg.stream, p, n_o_tiles, split);
+    else kk_launch<16>(sg.stream, p, n_o_tiles, split);
+    STGCHK(sg, hipGetLastError());
     if (split) {
-        hipLaunchKernelGGL(mxe::kk_combine, dim3((unsigned)((n_res + 255) / 256)), dim3(256), 0, sc.stream,
+        hipLaunchKernelGGL(mxe::kk_combine, dim3((unsigned)((n_res + 255) / 256)), dim3(256), 0, sg.stream,
                            (const double2*)dP, n_slice, n_res, (double2*)dG);
-        SVDCHK(hipGetLastError());
+        STGCHK(sg, hipGetLastError());
     }
-    SVDCHK(hipEventRecord(sc.e1, sc.stream));
-    SVDCHK(hipMemcpyAsync(out_G, dG, 2 * n_res * 8, hipMemcpyDeviceToHost, sc.stream));
-    SVDCHK(hipStreamSynchronize(sc.stream));
-    if (out_ms) SVDCHK(hipEventElapsedTime(out_ms, sc.e0, sc.e1));
+    STGCHK(sg, sg.time_end());
+    STGCHK(sg, sg.fetch(out_G, dG, 2 * n_res));
+    STGCHK(sg, sg.finish(out_ms));
     return MXE_OK;
 }
 MXE_CATCH_ALL
@@ -3224,20 +3142,9 @@ try {
         !out_rank || !out_sweeps || !(threshold >= 0.0) || !std::isfinite(threshold)) return MXE_ERR_ARG;
     if ((int64_t)n_bins * n_data > INT32_MAX) return MXE_ERR_ARG;
     const size_t m = n_bins, n = n_data, ns = n_sets, nel = ns * m * n;
-    {   // a NaN or an Inf anywhere: x - x is then NaN (eight independent chains)
-        double acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        size_t i = 0;
-        for (; i + 8 <= nel; i += 8)
-            for (int q = 0; q < 8; ++q) acc[q] += bins[i + q] - bins[i + q];
-        for (; i < nel; ++i) acc[0] += bins[i] - bins[i];
-        for (int q = 0; q < 8; ++q) if (acc[q] != 0.0) return MXE_ERR_ARG;
-    }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return MXE_ERR_NODEVICE;
-    if (device < 0 || device >= ndev) return MXE_ERR_ARG;
-    SVDCHK(hipSetDevice(device));
-    SvdScratch sc;
-    SVDCHK(hipStreamCreateWithFlags(&sc.stream, hipStreamNonBlocking));
+    if (!all_finite(bins, nel)) return MXE_ERR_ARG;
+    Stage sg;
+    if (int rc = sg.open(device); rc != MXE_OK) return rc;
     mxe::BinsParams p;
     p.m = n_bins; p.n = n_data;
     p.rcap = (std::min(n_bins, n_data) + 1) & ~1;
@@ -3246,23 +3153,21 @@ try {
     const double floor1 = (double)std::max(n_bins, n_data) * 2.220446049250313e-16;
     p.floor2 = floor1 * floor1;
     double* dbins;
-    SVDCHK(sc.alloc(&dbins, nel));
+    STGCHK(sg, sg.alloc(&dbins, nel));
     p.bins = dbins;
-    SVDCHK(sc.alloc(&p.A, (n_bins > n_data) ? nel : 1));
-    SVDCHK(sc.alloc(&p.Rm, ns * p.rcap * n)); SVDCHK(sc.alloc(&p.vk, ns * m));
-    SVDCHK(sc.alloc(&p.part, ns * mxe::BINS_NWAVE * n * 2)); SVDCHK(sc.alloc(&p.cn2, ns * n));
-    SVDCHK(sc.alloc(&p.perm, ns * n));
-    SVDCHK(sc.alloc(&p.out_mean, ns * n)); SVDCHK(sc.alloc(&p.out_var, ns * n));
-    SVDCHK(sc.alloc(&p.out_T, ns * n * n)); SVDCHK(sc.alloc(&p.out_info, ns * 4));
-    SVDCHK(hipMemcpyAsync(dbins, bins, nel * 8, hipMemcpyHostToDevice, sc.stream));
-    hipLaunchKernelGGL(mxe::bins_eig_kernel, dim3(n_sets), dim3(mxe::BINS_T), 0, sc.stream, p);
-    SVDCHK(hipGetLastError());
-    std::vector<int> hinfo(ns * 4);
-    SVDCHK(hipMemcpyAsync(out_mean, p.out_mean, ns * n * 8, hipMemcpyDeviceToHost, sc.stream));
-    SVDCHK(hipMemcpyAsync(out_var, p.out_var, ns * n * 8, hipMemcpyDeviceToHost, sc.stream));
-    SVDCHK(hipMemcpyAsync(out_T, p.out_T, ns * n * n * 8, hipMemcpyDeviceToHost, sc.stream));
-    SVDCHK(hipMemcpyAsync(hinfo.data(), p.out_info, hinfo.size() * 4, hipMemcpyDeviceToHost, sc.stream));
-    SVDCHK(hipStreamSynchronize(sc.stream));
+    STGCHK(sg, sg.alloc(&p.A, (n_bins > n_data) ? nel : 1));
+    STGCHK(sg, sg.alloc(&p.Rm, ns * p.rcap * n)); STGCHK(sg, sg.alloc(&p.vk, ns * m));
+    STGCHK(sg, sg.alloc(&p.part, ns * mxe::BINS_NWAVE * n * 2)); STGCHK(sg, sg.alloc(&p.cn2, ns * n));
+    STGCHK(sg, sg.alloc(&p.perm, ns * n));
+    STGCHK(sg, sg.alloc(&p.out_mean, ns * n)); STGCHK(sg, sg.alloc(&p.out_var, ns * n));
+    STGCHK(sg, sg.alloc(&p.out_T, ns * n * n)); STGCHK(sg, sg.alloc(&p.out_info, ns * 4));
+    STGCHK(sg, sg.upload(dbins, bins, nel));
+    hipLaunchKernelGGL(mxe::bins_eig_kernel, dim3(n_sets), dim3(mxe::BINS_T), 0, sg.stream, p);
+    STGCHK(sg, hipGetLastError());
+    std::vector<int> hinfo(ns * 4);                           // (through a host vector: rank and sweeps are picked out of it below)
+    STGCHK(sg, sg.fetch(out_mean, p.out_mean, ns * n)); STGCHK(sg, sg.fetch(out_var, p.out_var, ns * n));
+    STGCHK(sg, sg.fetch(out_T, p.out_T, ns * n * n)); STGCHK(sg, sg.fetch(hinfo.data(), p.out_info, hinfo.size()));
+    STGCHK(sg, sg.finish(nullptr));
     int rc = MXE_OK;
     for (size_t s = 0; s < ns; ++s) {
         out_rank[s] = hinfo[s * 4];
@@ -3276,20 +3181,6 @@ MXE_CATCH_ALL
 // ---- resampling of the bins: the rotated data of every jackknife / bootstrap resample, and the reduction of the
 // ---- H rows they were continued to (mxe_resample.hip.h) ----
 #include "mxe_resample.hip.h"
-
-namespace {
-// a NaN or an Inf anywhere: x - x is then NaN (eight independent chains)
-bool all_finite(const double* x, size_t nel)
-{
-    double acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    size_t i = 0;
-    for (; i + 8 <= nel; i += 8)
-        for (int q = 0; q < 8; ++q) acc[q] += x[i + q] - x[i + q];
-    for (; i < nel; ++i) acc[0] += x[i] - x[i];
-    for (int q = 0; q < 8; ++q) if (acc[q] != 0.0) return false;
-    return true;
-}
-} // namespace
 
 extern "C" int mxe_bins_resample(int device, int n_sets, int n_bins, int n_data, const double* bins,
                                  int n_res, const int32_t* counts, const double* T, const int32_t* rank,
@@ -3313,38 +3204,26 @@ try {
     }
     for (size_t s = 0; s < ns; ++s) if (rank[s] < 0 || rank[s] > n_data) return MXE_ERR_ARG;
     if (!all_finite(bins, nel) || !all_finite(T, ns * n * n)) return MXE_ERR_ARG;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return MXE_ERR_NODEVICE;
-    if (device < 0 || device >= ndev) return MXE_ERR_ARG;
-    SVDCHK(hipSetDevice(device));
-    SvdScratch sc;
-    SVDCHK(hipStreamCreateWithFlags(&sc.stream, hipStreamNonBlocking));
+    Stage sg;
+    if (int rc = sg.open(device); rc != MXE_OK) return rc;
     mxe::ResampleParams p;
     p.m = n_bins; p.n = n_data; p.n_res = n_res;
     double *dbins, *dNr, *dT;
     int *dcounts, *drank;
-    SVDCHK(sc.alloc(&dbins, nel)); SVDCHK(sc.alloc(&dcounts, nr * m)); SVDCHK(sc.alloc(&dNr, nr));
-    SVDCHK(sc.alloc(&dT, ns * n * n)); SVDCHK(sc.alloc(&drank, ns));
-    SVDCHK(sc.alloc(&p.part, ns * mxe::BINS_NWAVE * n * 2)); SVDCHK(sc.alloc(&p.D, ns * nr * n));
-    SVDCHK(sc.alloc(&p.out_mean, ns * n)); SVDCHK(sc.alloc(&p.out_G, ns * nr * n)); SVDCHK(sc.alloc(&p.out_dev, ns * nr * n));
+    STGCHK(sg, sg.alloc(&dbins, nel)); STGCHK(sg, sg.alloc(&dcounts, nr * m)); STGCHK(sg, sg.alloc(&dNr, nr));
+    STGCHK(sg, sg.alloc(&dT, ns * n * n)); STGCHK(sg, sg.alloc(&drank, ns));
+    STGCHK(sg, sg.alloc(&p.part, ns * mxe::BINS_NWAVE * n * 2)); STGCHK(sg, sg.alloc(&p.D, ns * nr * n));
+    STGCHK(sg, sg.alloc(&p.out_mean, ns * n)); STGCHK(sg, sg.alloc(&p.out_G, ns * nr * n)); STGCHK(sg, sg.alloc(&p.out_dev, ns * nr * n));
     p.bins = dbins; p.counts = dcounts; p.Nr = dNr; p.T = dT; p.rank = drank;
-    SVDCHK(hipMemcpyAsync(dbins, bins, nel * 8, hipMemcpyHostToDevice, sc.stream));
-    SVDCHK(hipMemcpyAsync(dcounts, counts, nr * m * 4, hipMemcpyHostToDevice, sc.stream));
-    SVDCHK(hipMemcpyAsync(dNr, hNr.data(), nr * 8, hipMemcpyHostToDevice, sc.stream));
-    SVDCHK(hipMemcpyAsync(dT, T, ns * n * n * 8, hipMemcpyHostToDevice, sc.stream));
-    SVDCHK(hipMemcpyAsync(drank, rank, ns * 4, hipMemcpyHostToDevice, sc.stream));
-    if (out_ms) {
-        SVDCHK(hipEventCreate(&sc.e0)); SVDCHK(hipEventCreate(&sc.e1));
-        SVDCHK(hipEventRecord(sc.e0, sc.stream));
-    }
-    hipLaunchKernelGGL(mxe::bins_resample_kernel, dim3(n_sets), dim3(mxe::BINS_T), 0, sc.stream, p);
-    SVDCHK(hipGetLastError());
-    if (out_ms) SVDCHK(hipEventRecord(sc.e1, sc.stream));
-    SVDCHK(hipMemcpyAsync(out_mean, p.out_mean, ns * n * 8, hipMemcpyDeviceToHost, sc.stream));
-    SVDCHK(hipMemcpyAsync(out_G, p.out_G, ns * nr * n * 8, hipMemcpyDeviceToHost, sc.stream));
-    if (out_dev) SVDCHK(hipMemcpyAsync(out_dev, p.out_dev, ns * nr * n * 8, hipMemcpyDeviceToHost, sc.stream));
-    SVDCHK(hipStreamSynchronize(sc.stream));
-    if (out_ms) SVDCHK(hipEventElapsedTime(out_ms, sc.e0, sc.e1));
+    STGCHK(sg, sg.upload(dbins, bins, nel)); STGCHK(sg, sg.upload(dcounts, counts, nr * m));
+    STGCHK(sg, sg.upload(dNr, hNr.data(), nr)); STGCHK(sg, sg.upload(dT, T, ns * n * n)); STGCHK(sg, sg.upload(drank, rank, ns));
+    STGCHK(sg, sg.time_begin(out_ms != nullptr));
+    hipLaunchKernelGGL(mxe::bins_resample_kernel, dim3(n_sets), dim3(mxe::BINS_T), 0, sg.stream, p);
+    STGCHK(sg, hipGetLastError());
+    STGCHK(sg, sg.time_end());
+    STGCHK(sg, sg.fetch(out_mean, p.out_mean, ns * n)); STGCHK(sg, sg.fetch(out_G, p.out_G, ns * nr * n));
+    STGCHK(sg, sg.fetch(out_dev, p.out_dev, ns * nr * n));
+    STGCHK(sg, sg.finish(out_ms));
     return MXE_OK;
 }
 MXE_CATCH_ALL
@@ -3355,61 +3234,52 @@ extern "C" int mxe_resample_reduce(mxe_ctx* ctx, int n_groups, const int32_t* gr
                                    int32_t* out_used, float* out_ms)
 try {
     if (!ctx || n_groups < 1 || !group_offset || !scale || n_f < 0 || (n_f > 0 && !F)) return MXE_ERR_ARG;
-    if (group_offset[0] != 0) return MXE_ERR_ARG;
-    for (int g = 0; g < n_groups; ++g) {
-        if (group_offset[g + 1] < group_offset[g]) return MXE_ERR_ARG;
-        if (!std::isfinite(scale[g])) return MXE_ERR_ARG;
-    }
+    if (!group_offsets_ok(group_offset, n_groups) || !all_finite(scale, n_groups)) return MXE_ERR_ARG;
     if (!H && !ctx->launched) return MXE_ERR_STATE;
     const size_t rows = (size_t)group_offset[n_groups], nw = ctx->n_omega, nf = n_f, ng = n_groups;
     if (rows * nw > 0x7fffffffull || rows * std::max<size_t>(nf, 1) > 0x7fffffffull || nf * nw > 0x7fffffffull ||
         ng * nw > 0x7fffffffull || ng * nf * nf > 0x7fffffffull) return MXE_ERR_ARG;
-    const size_t n_last = (size_t)ctx->n_chain * ctx->n_alpha;
-    // integers: offsets [ng + 1] | scratch flags [rows] | used [ng] | rows of the launch [rows] (H == NULL)
+    Block bi;                                                 // rr_i
+    const size_t iO = bi.add(ng + 1);                         // offsets [ng + 1]
+    const size_t iK = bi.add(rows);                           // scratch flags [rows]
+    const size_t iU = bi.add(ng);                             // used [ng]
+    const size_t iR = bi.add(H ? 0 : rows);                   // rows of the launch [rows] (H == NULL)
     std::vector<int> hi(group_offset, group_offset + ng + 1);
-    const size_t iO = 0, iK = iO + ng + 1, iU = iK + rows, iR = iU + ng, itotal = iR + (H ? 0 : rows);
-    hi.resize(itotal, 0);
-    if (!H)
-        for (size_t r = 0; r < rows; ++r) {
-            const int row = problem_index ? problem_index[r] : (int)r;
-            if (row < 0 || (size_t)row >= n_last) return MXE_ERR_ARG;
-            hi[iR + r] = row;
-        }
-    if (nf && !all_finite(F, nf * nw)) return MXE_ERR_ARG;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    // doubles: scale [ng] | H [rows][nw] (when handed in) | F [nf][nw] | fval [rows][nf] | mean, var [ng][nw] | fmean [ng][nf] | fcov [ng][nf][nf]
-    const size_t oH = ng, oF = oH + (H ? rows * nw : 0), oV = oF + nf * nw, oM = oV + rows * nf, oS = oM + ng * nw,
-                 oFm = oS + ng * nw, oFc = oFm + ng * nf, total = oFc + ng * nf * nf;
-    HIPCHK(ctx, ctx->rr_d.ensure(total));
-    HIPCHK(ctx, ctx->rr_i.ensure(itotal));
+    hi.resize(bi.total, 0);
+    if (!H && !launch_rows(problem_index, rows, (size_t)ctx->n_chain * ctx->n_alpha, hi.data() + iR)) return MXE_ERR_ARG;
+    if (!all_finite(F, nf * nw)) return MXE_ERR_ARG;
+    Stage sg;
+    if (int rc = sg.open(ctx); rc != MXE_OK) return rc;
+    Block b;                                                  // rr_d
+    const size_t oS = b.add(ng);                              // scale [ng]
+    const size_t oH = b.add(H ? rows * nw : 0);               // H [rows][nw], when handed in
+    const size_t oF = b.add(nf * nw);                         // F [nf][nw]
+    const size_t oV = b.add(rows * nf);                       // fval [rows][nf]
+    const size_t oM = b.add(ng * nw);                         // mean [ng][nw]
+    const size_t oVar = b.add(ng * nw);                       // var [ng][nw]
+    const size_t oFm = b.add(ng * nf);                        // fmean [ng][nf]
+    const size_t oFc = b.add(ng * nf * nf);                   // fcov [ng][nf][nf]
+    STGCHK(sg, ctx->rr_d.ensure(b.total));
+    STGCHK(sg, ctx->rr_i.ensure(bi.total));
     double* d = ctx->rr_d.p;
     int* di = ctx->rr_i.p;
-    HIPCHK(ctx, hipMemcpyAsync(d, scale, ng * 8, hipMemcpyHostToDevice, ctx->stream));
-    if (H && rows) HIPCHK(ctx, hipMemcpyAsync(d + oH, H, rows * nw * 8, hipMemcpyHostToDevice, ctx->stream));
-    if (nf) HIPCHK(ctx, hipMemcpyAsync(d + oF, F, nf * nw * 8, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(di, hi.data(), itotal * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    STGCHK(sg, sg.upload(d + oS, scale, ng)); STGCHK(sg, sg.upload(d + oH, H, rows * nw));
+    STGCHK(sg, sg.upload(d + oF, F, nf * nw)); STGCHK(sg, sg.upload(di, hi.data(), bi.total));
     mxe::ReduceParams rp;
     rp.H = H ? d + oH : ctx->dout_H.p; rp.row = H ? nullptr : di + iR;
-    rp.off = di + iO; rp.scale = d; rp.F = d + oF; rp.nw = (int)nw; rp.n_f = n_f;
-    rp.ok = di + iK; rp.fval = d + oV; rp.mean = d + oM; rp.var = d + oS; rp.fmean = d + oFm; rp.fcov = d + oFc; rp.used = di + iU;
-    SvdScratch sc;                    // (the two events of the timing, released on every path)
-    if (out_ms) {
-        HIPCHK(ctx, hipEventCreate(&sc.e0)); HIPCHK(ctx, hipEventCreate(&sc.e1));
-        HIPCHK(ctx, hipEventRecord(sc.e0, ctx->stream));
-    }
+    rp.off = di + iO; rp.scale = d + oS; rp.F = d + oF; rp.nw = (int)nw; rp.n_f = n_f;
+    rp.ok = di + iK; rp.fval = d + oV; rp.mean = d + oM; rp.var = d + oVar; rp.fmean = d + oFm; rp.fcov = d + oFc; rp.used = di + iU;
+    STGCHK(sg, sg.time_begin(out_ms != nullptr));
     hipLaunchKernelGGL(mxe::resample_reduce_kernel, dim3((unsigned)n_groups), dim3(256), 0, ctx->stream, rp);
-    HIPCHK(ctx, hipGetLastError());
-    if (out_ms) HIPCHK(ctx, hipEventRecord(sc.e1, ctx->stream));
-    if (out_mean) HIPCHK(ctx, hipMemcpyAsync(out_mean, d + oM, ng * nw * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (out_var) HIPCHK(ctx, hipMemcpyAsync(out_var, d + oS, ng * nw * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (out_fval && rows * nf) HIPCHK(ctx, hipMemcpyAsync(out_fval, d + oV, rows * nf * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (out_fmean && nf) HIPCHK(ctx, hipMemcpyAsync(out_fmean, d + oFm, ng * nf * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (out_fcov && nf) HIPCHK(ctx, hipMemcpyAsync(out_fcov, d + oFc, ng * nf * nf * 8, hipMemcpyDeviceToHost, ctx->stream));
-    std::vector<int> hused(ng);
-    if (out_used) HIPCHK(ctx, hipMemcpyAsync(hused.data(), di + iU, ng * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, stream_wait(ctx->stream));
-    if (out_used) for (size_t g = 0; g < ng; ++g) out_used[g] = hused[g];
-    if (out_ms) HIPCHK(ctx, hipEventElapsedTime(out_ms, sc.e0, sc.e1));
+    STGCHK(sg, hipGetLastError());
+    STGCHK(sg, sg.time_end());
+    STGCHK(sg, sg.fetch(out_mean, d + oM, ng * nw)); STGCHK(sg, sg.fetch(out_var, d + oVar, ng * nw));
+    STGCHK(sg, sg.fetch(out_fval, d + oV, rows * nf)); STGCHK(sg, sg.fetch(out_fmean, d + oFm, ng * nf));
+    STGCHK(sg, sg.fetch(out_fcov, d + oFc, ng * nf * nf));
+    std::vector<int> hused(out_used ? ng : 0);                // (int32_t for the caller: through a host vector)
+    STGCHK(sg, sg.fetch(hused.data(), di + iU, hused.size()));
+    STGCHK(sg, sg.finish(out_ms));
+    std::copy(hused.begin(), hused.end(), out_used);
     return MXE_OK;
 }
 MXE_CATCH_ALL
@@ -3420,67 +3290,56 @@ extern "C" int mxe_resample_quantiles(mxe_ctx* ctx, int n_groups, const int32_t*
 try {
     static_assert(mxe::RQ_MAX_ROWS == MXE_QUANTILE_MAX_ROWS, "the cap the header names is the one the kernel is built for");
     if (!ctx || n_groups < 1 || !group_offset || n_q < 1 || !q) return MXE_ERR_ARG;
-    if (group_offset[0] != 0) return MXE_ERR_ARG;
     int longest = 0;
-    for (int g = 0; g < n_groups; ++g) {
-        if (group_offset[g + 1] < group_offset[g]) return MXE_ERR_ARG;
-        longest = std::max(longest, group_offset[g + 1] - group_offset[g]);
-    }
+    if (!group_offsets_ok(group_offset, n_groups, &longest)) return MXE_ERR_ARG;
     for (int k = 0; k < n_q; ++k) if (!(q[k] >= 0.0 && q[k] <= 1.0)) return MXE_ERR_ARG;
     if (!H && !ctx->launched) return MXE_ERR_STATE;
     const size_t rows = (size_t)group_offset[n_groups], nw = ctx->n_omega, nq = n_q, ng = n_groups;
     if (rows * nw > 0x7fffffffull || ng * nq * nw > 0x7fffffffull || (nw + mxe::RQ_COLS - 1) / mxe::RQ_COLS > 65535) return MXE_ERR_ARG;
-    const size_t n_last = (size_t)ctx->n_chain * ctx->n_alpha;
-    // integers: offsets [ng + 1] | flags [rows] | used [ng] | rows of the launch [rows] (H == NULL)
+    Block bi;                                                 // rr_i
+    const size_t iO = bi.add(ng + 1);                         // offsets [ng + 1]
+    const size_t iK = bi.add(rows);                           // flags [rows]
+    const size_t iU = bi.add(ng);                             // used [ng]
+    const size_t iR = bi.add(H ? 0 : rows);                   // rows of the launch [rows] (H == NULL)
     std::vector<int> hi(group_offset, group_offset + ng + 1);
-    const size_t iO = 0, iK = iO + ng + 1, iU = iK + rows, iR = iU + ng, itotal = iR + (H ? 0 : rows);
-    hi.resize(itotal, 0);
-    if (!H)
-        for (size_t r = 0; r < rows; ++r) {
-            const int row = problem_index ? problem_index[r] : (int)r;
-            if (row < 0 || (size_t)row >= n_last) return MXE_ERR_ARG;
-            hi[iR + r] = row;
-        }
+    hi.resize(bi.total, 0);
+    if (!H && !launch_rows(problem_index, rows, (size_t)ctx->n_chain * ctx->n_alpha, hi.data() + iR)) return MXE_ERR_ARG;
     if (longest > mxe::RQ_MAX_ROWS) return MXE_ERR_LIMIT;
     int padded = 2;
     while (padded < longest) padded <<= 1;
     const size_t lds = (size_t)padded * mxe::RQ_COLS * sizeof(double);
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    // doubles: q [nq] | H [rows][nw] (when handed in) | quantiles [ng][nq][nw]
-    const size_t oH = nq, oQ = oH + (H ? rows * nw : 0), total = oQ + ng * nq * nw;
-    HIPCHK(ctx, ctx->rr_d.ensure(total));
-    HIPCHK(ctx, ctx->rr_i.ensure(itotal));
+    Stage sg;
+    if (int rc = sg.open(ctx); rc != MXE_OK) return rc;
+    Block b;                                                  // rr_d
+    const size_t oQ = b.add(nq);                              // q [nq]
+    const size_t oH = b.add(H ? rows * nw : 0);               // H [rows][nw], when handed in
+    const size_t oO = b.add(ng * nq * nw);                    // quantiles [ng][nq][nw]
+    STGCHK(sg, ctx->rr_d.ensure(b.total));
+    STGCHK(sg, ctx->rr_i.ensure(bi.total));
     double* d = ctx->rr_d.p;
     int* di = ctx->rr_i.p;
-    HIPCHK(ctx, hipMemcpyAsync(d, q, nq * 8, hipMemcpyHostToDevice, ctx->stream));
-    if (H && rows) HIPCHK(ctx, hipMemcpyAsync(d + oH, H, rows * nw * 8, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(di, hi.data(), itotal * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    STGCHK(sg, sg.upload(d + oQ, q, nq)); STGCHK(sg, sg.upload(d + oH, H, rows * nw));
+    STGCHK(sg, sg.upload(di, hi.data(), bi.total));
     mxe::QuantileParams qp;
     qp.H = H ? d + oH : ctx->dout_H.p; qp.row = H ? nullptr : di + iR;
-    qp.off = di + iO; qp.q = d; qp.nw = (int)nw; qp.n_q = n_q; qp.rows = (int)rows; qp.padded = padded;
-    qp.ok = di + iK; qp.out = d + oQ; qp.used = di + iU;
-    HIPCHK(ctx, hipFuncSetAttribute((const void*)mxe::resample_quantile_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    SvdScratch sc;                    // (the two events of the timing, released on every path)
-    if (out_ms) {
-        HIPCHK(ctx, hipEventCreate(&sc.e0)); HIPCHK(ctx, hipEventCreate(&sc.e1));
-        HIPCHK(ctx, hipEventRecord(sc.e0, ctx->stream));
-    }
+    qp.off = di + iO; qp.q = d + oQ; qp.nw = (int)nw; qp.n_q = n_q; qp.rows = (int)rows; qp.padded = padded;
+    qp.ok = di + iK; qp.out = d + oO; qp.used = di + iU;
+    STGCHK(sg, hipFuncSetAttribute((const void*)mxe::resample_quantile_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    STGCHK(sg, sg.time_begin(out_ms != nullptr));
     if (rows) {
         hipLaunchKernelGGL(mxe::rows_finite_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, ctx->stream, qp);
-        HIPCHK(ctx, hipGetLastError());
+        STGCHK(sg, hipGetLastError());
     }
     hipLaunchKernelGGL(mxe::resample_quantile_kernel, dim3((unsigned)n_groups, (unsigned)((nw + mxe::RQ_COLS - 1) / mxe::RQ_COLS)),
                        dim3(256), lds, ctx->stream, qp);
-    HIPCHK(ctx, hipGetLastError());
-    if (out_ms) HIPCHK(ctx, hipEventRecord(sc.e1, ctx->stream));
+    STGCHK(sg, hipGetLastError());
+    STGCHK(sg, sg.time_end());
     std::vector<double> hq(out_q ? ng * nq * nw : 0);    // (nothing is written to the caller's arrays before the stream is through)
-    std::vector<int> hused(ng);
-    if (out_q) HIPCHK(ctx, hipMemcpyAsync(hq.data(), d + oQ, ng * nq * nw * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (out_used) HIPCHK(ctx, hipMemcpyAsync(hused.data(), di + iU, ng * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, stream_wait(ctx->stream));
-    if (out_q) std::copy(hq.begin(), hq.end(), out_q);
-    if (out_used) for (size_t g = 0; g < ng; ++g) out_used[g] = hused[g];
-    if (out_ms) HIPCHK(ctx, hipEventElapsedTime(out_ms, sc.e0, sc.e1));
+    std::vector<int> hused(out_used ? ng : 0);
+    STGCHK(sg, sg.fetch(hq.data(), d + oO, hq.size())); STGCHK(sg, sg.fetch(hused.data(), di + iU, hused.size()));
+    STGCHK(sg, sg.finish(out_ms));
+    std::copy(hq.begin(), hq.end(), out_q);
+    std::copy(hused.begin(), hused.end(), out_used);
     return MXE_OK;
 }
 MXE_CATCH_ALL
@@ -3504,47 +3363,33 @@ try {
         for (size_t s = 0; s < ns; ++s) if (rank[s] < 0 || rank[s] > n_data) return MXE_ERR_ARG;
         if (!all_finite(T, ns * n * n)) return MXE_ERR_ARG;
     }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return MXE_ERR_NODEVICE;
-    if (device < 0 || device >= ndev) return MXE_ERR_ARG;
+    Stage sg;
+    if (int rc = sg.open(device); rc != MXE_OK) return rc;
     // chunks of mocks: MOCK_CHUNK each, more where gridDim.y would pass 1024
     size_t chunk = mxe::MOCK_CHUNK;
     while ((nm + chunk - 1) / chunk > 1024) chunk *= 2;
     const size_t gy = (nm + chunk - 1) / chunk, gx = (ns + 15) / 16;
     if (16 * chunk * ((n + 1) / 2) > 0x7fffffffull || gy * ns * n > 0x7fffffffull) return MXE_ERR_ARG;
-    SVDCHK(hipSetDevice(device));
-    SvdScratch sc;
-    SVDCHK(hipStreamCreateWithFlags(&sc.stream, hipStreamNonBlocking));
     mxe::MockParams p;
     p.n_sets = n_sets; p.n_mock = n_mock; p.n_data = n_data; p.nw = n_omega; p.chunk = (int)chunk; p.seed = seed;
     double *dK, *dH0, *derr, *dT = nullptr;
     int* drank = nullptr;
     uint64_t* dstream;
-    SVDCHK(sc.alloc(&dK, n * nw)); SVDCHK(sc.alloc(&dH0, ns * nw)); SVDCHK(sc.alloc(&derr, ns * n));
-    SVDCHK(sc.alloc(&dstream, ns));
-    if (T) { SVDCHK(sc.alloc(&dT, ns * n * n)); SVDCHK(sc.alloc(&drank, ns)); }
-    SVDCHK(sc.alloc(&p.kh, T ? gy * ns * n : 1)); SVDCHK(sc.alloc(&p.mdl, gy * ns * n));
-    SVDCHK(sc.alloc(&p.out_model, ns * n)); SVDCHK(sc.alloc(&p.out_G, ns * nm * n));
+    STGCHK(sg, sg.alloc(&dK, n * nw)); STGCHK(sg, sg.alloc(&dH0, ns * nw)); STGCHK(sg, sg.alloc(&derr, ns * n));
+    STGCHK(sg, sg.alloc(&dstream, ns));
+    if (T) { STGCHK(sg, sg.alloc(&dT, ns * n * n)); STGCHK(sg, sg.alloc(&drank, ns)); }
+    STGCHK(sg, sg.alloc(&p.kh, T ? gy * ns * n : 1)); STGCHK(sg, sg.alloc(&p.mdl, gy * ns * n));
+    STGCHK(sg, sg.alloc(&p.out_model, ns * n)); STGCHK(sg, sg.alloc(&p.out_G, ns * nm * n));
     p.K = dK; p.H0 = dH0; p.err = derr; p.T = dT; p.rank = drank; p.stream = dstream;
-    SVDCHK(hipMemcpyAsync(dK, K, n * nw * 8, hipMemcpyHostToDevice, sc.stream));
-    SVDCHK(hipMemcpyAsync(dH0, H0, ns * nw * 8, hipMemcpyHostToDevice, sc.stream));
-    SVDCHK(hipMemcpyAsync(derr, err, ns * n * 8, hipMemcpyHostToDevice, sc.stream));
-    SVDCHK(hipMemcpyAsync(dstream, stream, ns * 8, hipMemcpyHostToDevice, sc.stream));
-    if (T) {
-        SVDCHK(hipMemcpyAsync(dT, T, ns * n * n * 8, hipMemcpyHostToDevice, sc.stream));
-        SVDCHK(hipMemcpyAsync(drank, rank, ns * 4, hipMemcpyHostToDevice, sc.stream));
-    }
-    if (out_ms) {
-        SVDCHK(hipEventCreate(&sc.e0)); SVDCHK(hipEventCreate(&sc.e1));
-        SVDCHK(hipEventRecord(sc.e0, sc.stream));
-    }
-    hipLaunchKernelGGL(mxe::mock_data_kernel, dim3((unsigned)gx, (unsigned)gy), dim3(mxe::MOCK_T), 0, sc.stream, p);
-    SVDCHK(hipGetLastError());
-    if (out_ms) SVDCHK(hipEventRecord(sc.e1, sc.stream));
-    SVDCHK(hipMemcpyAsync(out_model, p.out_model, ns * n * 8, hipMemcpyDeviceToHost, sc.stream));
-    SVDCHK(hipMemcpyAsync(out_G, p.out_G, ns * nm * n * 8, hipMemcpyDeviceToHost, sc.stream));
-    SVDCHK(hipStreamSynchronize(sc.stream));
-    if (out_ms) SVDCHK(hipEventElapsedTime(out_ms, sc.e0, sc.e1));
+    STGCHK(sg, sg.upload(dK, K, n * nw)); STGCHK(sg, sg.upload(dH0, H0, ns * nw)); STGCHK(sg, sg.upload(derr, err, ns * n));
+    STGCHK(sg, sg.upload(dstream, stream, ns));
+    STGCHK(sg, sg.upload(dT, T, ns * n * n)); STGCHK(sg, sg.upload(drank, rank, ns));
+    STGCHK(sg, sg.time_begin(out_ms != nullptr));
+    hipLaunchKernelGGL(mxe::mock_data_kernel, dim3((unsigned)gx, (unsigned)gy), dim3(mxe::MOCK_T), 0, sg.stream, p);
+    STGCHK(sg, hipGetLastError());
+    STGCHK(sg, sg.time_end());
+    STGCHK(sg, sg.fetch(out_model, p.out_model, ns * n)); STGCHK(sg, sg.fetch(out_G, p.out_G, ns * nm * n));
+    STGCHK(sg, sg.finish(out_ms));
     return MXE_OK;
 }
 MXE_CATCH_ALL
@@ -3562,9 +3407,7 @@ extern "C" int mxe_evidence_reduce(mxe_ctx* ctx, int n_groups, const int32_t* gr
 try {
     if (!ctx || n_groups < 1 || !group_offset || n_alpha < 1 || !logp || !log_quad || !log_mix || n_f < 0 || (n_f > 0 && !F) ||
         row_mode < 0 || row_mode > 2 || (row_mode == 2 && !pick)) return MXE_ERR_ARG;
-    if (group_offset[0] != 0) return MXE_ERR_ARG;
-    for (int g = 0; g < n_groups; ++g)
-        if (group_offset[g + 1] < group_offset[g]) return MXE_ERR_ARG;
+    if (!group_offsets_ok(group_offset, n_groups)) return MXE_ERR_ARG;
     const size_t ns = (size_t)group_offset[n_groups], na = n_alpha, nw = ctx->n_omega, nf = n_f, ng = n_groups;
     const size_t lim = 0x7fffffffull;
     if (ns * na > lim || (H && ns * na * nw > lim) || ns * nw > lim || ns * std::max<size_t>(nf, 1) > lim || nf * nw > lim ||
@@ -3583,22 +3426,39 @@ try {
     }
     if (row_mode == 2)
         for (size_t s = 0; s < ns; ++s) if (pick[s] >= n_alpha) return MXE_ERR_ARG;
-    if (!all_finite(log_quad, na) || !all_finite(log_mix, na) || (nf && !all_finite(F, nf * nw))) return MXE_ERR_ARG;
+    if (!all_finite(log_quad, na) || !all_finite(log_mix, na) || !all_finite(F, nf * nw)) return MXE_ERR_ARG;
     if (log_prior)
         for (size_t s = 0; s < ns; ++s)
             if (std::isnan(log_prior[s]) || log_prior[s] == INFINITY) return MXE_ERR_ARG;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    // doubles: H [ns][na][nw] (when handed in; first: its rows start on 16 bytes where nw is even) | logp [ns][na] | log_quad,
-    // log_mix [na] | log_prior [ns] | F [nf][nw] | logZ [ns] | walpha [ns][na] | row [ns][nw] | fval [ns][nf] | wmodel [ns] |
-    // mean, between [ng][nw] | fmean [ng][nf] | fcov [ng][nf][nf]
-    const size_t oP = H ? ns * na * nw : 0, oQ = oP + ns * na, oX = oQ + na, oPr = oX + na, oF = oPr + ns, oZ = oF + nf * nw,
-                 oW = oZ + ns, oR = oW + ns * na, oV = oR + ns * nw, oU = oV + ns * nf, oM = oU + ns, oB = oM + ng * nw,
-                 oFm = oB + ng * nw, oFc = oFm + ng * nf, total = oFc + ng * nf * nf;
-    // integers: offsets [ng + 1] | pick [ns] | good [ns][na] | usable, kmax, ngood [ns] | used [ng]
-    const size_t iP = ng + 1, iG = iP + ns, iUs = iG + ns * na, iK = iUs + ns, iN = iK + ns, iU = iN + ns, itotal = iU + ng;
-    HIPCHK(ctx, ctx->er_d.ensure(total));
-    HIPCHK(ctx, ctx->er_i.ensure(itotal));
-    HIPCHK(ctx, ctx->er_l.ensure(hrow0.size()));
+    Stage sg;
+    if (int rc = sg.open(ctx); rc != MXE_OK) return rc;
+    Block b;                                                  // er_d
+    const size_t oH = b.add(H ? ns * na * nw : 0);            // H [ns][na][nw], when handed in (first: its rows start on 16 bytes where nw is even)
+    const size_t oP = b.add(ns * na);                         // logp [ns][na]
+    const size_t oQ = b.add(na);                              // log_quad [na]
+    const size_t oX = b.add(na);                              // log_mix [na]
+    const size_t oPr = b.add(ns);                             // log_prior [ns]
+    const size_t oF = b.add(nf * nw);                         // F [nf][nw]
+    const size_t oZ = b.add(ns);                              // logZ [ns]
+    const size_t oW = b.add(ns * na);                         // walpha [ns][na]
+    const size_t oR = b.add(ns * nw);                         // row [ns][nw]
+    const size_t oV = b.add(ns * nf);                         // fval [ns][nf]
+    const size_t oU = b.add(ns);                              // wmodel [ns]
+    const size_t oM = b.add(ng * nw);                         // mean [ng][nw]
+    const size_t oB = b.add(ng * nw);                         // between [ng][nw]
+    const size_t oFm = b.add(ng * nf);                        // fmean [ng][nf]
+    const size_t oFc = b.add(ng * nf * nf);                   // fcov [ng][nf][nf]
+    Block bi;                                                 // er_i
+    const size_t iO = bi.add(ng + 1);                         // offsets [ng + 1]
+    const size_t iP = bi.add(ns);                             // pick [ns]
+    const size_t iG = bi.add(ns * na);                        // good [ns][na]
+    const size_t iUs = bi.add(ns);                            // usable [ns]
+    const size_t iK = bi.add(ns);                             // kmax [ns]
+    const size_t iN = bi.add(ns);                             // ngood [ns], behind kmax: fetched with it
+    const size_t iU = bi.add(ng);                             // used [ng]
+    STGCHK(sg, ctx->er_d.ensure(b.total));
+    STGCHK(sg, ctx->er_i.ensure(bi.total));
+    STGCHK(sg, ctx->er_l.ensure(hrow0.size()));
     double* d = ctx->er_d.p;
     int* di = ctx->er_i.p;
     std::vector<int> hi(group_offset, group_offset + ng + 1);
@@ -3606,52 +3466,38 @@ try {
     if (row_mode == 2) for (size_t s = 0; s < ns; ++s) hi[iP + s] = pick[s];
     std::vector<double> hprior(std::max<size_t>(ns, 1), 0.0);
     if (log_prior) for (size_t s = 0; s < ns; ++s) hprior[s] = log_prior[s];
-    if (H && ns) HIPCHK(ctx, hipMemcpyAsync(d, H, ns * na * nw * 8, hipMemcpyHostToDevice, ctx->stream));
-    if (ns) HIPCHK(ctx, hipMemcpyAsync(d + oP, logp, ns * na * 8, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(d + oQ, log_quad, na * 8, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(d + oX, log_mix, na * 8, hipMemcpyHostToDevice, ctx->stream));
-    if (ns) HIPCHK(ctx, hipMemcpyAsync(d + oPr, hprior.data(), ns * 8, hipMemcpyHostToDevice, ctx->stream));
-    if (nf) HIPCHK(ctx, hipMemcpyAsync(d + oF, F, nf * nw * 8, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(di, hi.data(), iG * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->er_l.p, hrow0.data(), hrow0.size() * sizeof(long long), hipMemcpyHostToDevice, ctx->stream));
+    STGCHK(sg, sg.upload(d + oH, H, ns * na * nw)); STGCHK(sg, sg.upload(d + oP, logp, ns * na));
+    STGCHK(sg, sg.upload(d + oQ, log_quad, na)); STGCHK(sg, sg.upload(d + oX, log_mix, na));
+    STGCHK(sg, sg.upload(d + oPr, hprior.data(), ns)); STGCHK(sg, sg.upload(d + oF, F, nf * nw));
+    STGCHK(sg, sg.upload(di + iO, hi.data(), iG)); STGCHK(sg, sg.upload(ctx->er_l.p, hrow0.data(), hrow0.size()));
     mxe::EvidenceParams ep;
-    ep.H = H ? d : ctx->dout_H.p; ep.row0 = ctx->er_l.p;
-    ep.logp = d + oP; ep.log_quad = d + oQ; ep.log_mix = d + oX; ep.log_prior = d + oPr; ep.pick = di + iP; ep.off = di;
+    ep.H = H ? d + oH : ctx->dout_H.p; ep.row0 = ctx->er_l.p;
+    ep.logp = d + oP; ep.log_quad = d + oQ; ep.log_mix = d + oX; ep.log_prior = d + oPr; ep.pick = di + iP; ep.off = di + iO;
     ep.F = d + oF; ep.n_alpha = n_alpha; ep.nw = (int)nw; ep.n_f = n_f; ep.row_mode = row_mode;
     ep.good = di + iG; ep.usable = di + iUs; ep.logZ = d + oZ; ep.kmax = di + iK; ep.ngood = di + iN; ep.walpha = d + oW;
     ep.row = d + oR; ep.fval = d + oV; ep.wmodel = d + oU; ep.mean = d + oM; ep.between = d + oB; ep.fmean = d + oFm;
     ep.fcov = d + oFc; ep.used = di + iU;
-    SvdScratch sc;                    // (the two events of the timing, released on every path)
-    if (out_ms) {
-        HIPCHK(ctx, hipEventCreate(&sc.e0)); HIPCHK(ctx, hipEventCreate(&sc.e1));
-        HIPCHK(ctx, hipEventRecord(sc.e0, ctx->stream));
-    }
+    STGCHK(sg, sg.time_begin(out_ms != nullptr));
     if (ns) {
         hipLaunchKernelGGL(mxe::evidence_scan_kernel, dim3((unsigned)ns), dim3(mxe::EV_T), 0, ctx->stream, ep);
-        HIPCHK(ctx, hipGetLastError());
+        STGCHK(sg, hipGetLastError());
     }
     hipLaunchKernelGGL(mxe::evidence_group_kernel, dim3((unsigned)ng), dim3(mxe::EV_T), 0, ctx->stream, ep);
-    HIPCHK(ctx, hipGetLastError());
-    if (out_ms) HIPCHK(ctx, hipEventRecord(sc.e1, ctx->stream));
-    if (out_logZ && ns) HIPCHK(ctx, hipMemcpyAsync(out_logZ, d + oZ, ns * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (out_walpha && ns) HIPCHK(ctx, hipMemcpyAsync(out_walpha, d + oW, ns * na * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (out_row && ns) HIPCHK(ctx, hipMemcpyAsync(out_row, d + oR, ns * nw * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (out_fval && ns * nf) HIPCHK(ctx, hipMemcpyAsync(out_fval, d + oV, ns * nf * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (out_wmodel && ns) HIPCHK(ctx, hipMemcpyAsync(out_wmodel, d + oU, ns * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (out_mean) HIPCHK(ctx, hipMemcpyAsync(out_mean, d + oM, ng * nw * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (out_between) HIPCHK(ctx, hipMemcpyAsync(out_between, d + oB, ng * nw * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (out_fmean && nf) HIPCHK(ctx, hipMemcpyAsync(out_fmean, d + oFm, ng * nf * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (out_fcov && nf) HIPCHK(ctx, hipMemcpyAsync(out_fcov, d + oFc, ng * nf * nf * 8, hipMemcpyDeviceToHost, ctx->stream));
+    STGCHK(sg, hipGetLastError());
+    STGCHK(sg, sg.time_end());
+    STGCHK(sg, sg.fetch(out_logZ, d + oZ, ns)); STGCHK(sg, sg.fetch(out_walpha, d + oW, ns * na));
+    STGCHK(sg, sg.fetch(out_row, d + oR, ns * nw)); STGCHK(sg, sg.fetch(out_fval, d + oV, ns * nf));
+    STGCHK(sg, sg.fetch(out_wmodel, d + oU, ns)); STGCHK(sg, sg.fetch(out_mean, d + oM, ng * nw));
+    STGCHK(sg, sg.fetch(out_between, d + oB, ng * nw)); STGCHK(sg, sg.fetch(out_fmean, d + oFm, ng * nf));
+    STGCHK(sg, sg.fetch(out_fcov, d + oFc, ng * nf * nf));
     std::vector<int> hout(2 * ns + ng);                   // kmax | ngood (back to back on the device) | used
-    if (ns) HIPCHK(ctx, hipMemcpyAsync(hout.data(), di + iK, 2 * ns * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(hout.data() + 2 * ns, di + iU, ng * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, stream_wait(ctx->stream));
+    STGCHK(sg, sg.fetch(hout.data(), di + iK, 2 * ns)); STGCHK(sg, sg.fetch(hout.data() + 2 * ns, di + iU, ng));
+    STGCHK(sg, sg.finish(out_ms));
     for (size_t s = 0; s < ns; ++s) {
         if (out_kmax) out_kmax[s] = hout[s];
         if (out_ngood) out_ngood[s] = hout[ns + s];
     }
     if (out_used) for (size_t g = 0; g < ng; ++g) out_used[g] = hout[2 * ns + g];
-    if (out_ms) HIPCHK(ctx, hipEventElapsedTime(out_ms, sc.e0, sc.e1));
     return MXE_OK;
 }
 MXE_CATCH_ALL
@@ -3673,42 +3519,28 @@ try {
     if (!all_finite(bins, nel) || (T && !all_finite(T, ns * n * n))) return MXE_ERR_ARG;
     int L = 0;
     while ((n_bins >> (L + 1)) >= 1) ++L;                             // floor(log2 n_bins): every level has two blocks or more
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return MXE_ERR_NODEVICE;
-    if (device < 0 || device >= ndev) return MXE_ERR_ARG;
-    SVDCHK(hipSetDevice(device));
-    SvdScratch sc;
-    SVDCHK(hipStreamCreateWithFlags(&sc.stream, hipStreamNonBlocking));
+    Stage sg;
+    if (int rc = sg.open(device); rc != MXE_OK) return rc;
     mxe::BinCheckParams p;
     p.m = n_bins; p.n = n_data; p.L = L;
     const size_t nout = ns * (size_t)L * n;
     double *dbins, *dT = nullptr;
     int* drank = nullptr;
-    SVDCHK(sc.alloc(&dbins, nel));
-    if (T) { SVDCHK(sc.alloc(&dT, ns * n * n)); SVDCHK(sc.alloc(&drank, ns)); }
-    SVDCHK(sc.alloc(&p.part, ns * mxe::BINS_NWAVE * n * 2)); SVDCHK(sc.alloc(&p.part2, ns * mxe::BINS_NWAVE * n * 3));
-    SVDCHK(sc.alloc(&p.Y0, nel)); SVDCHK(sc.alloc(&p.Y1, std::max<size_t>(ns * (m >> 1) * n, 1)));
-    SVDCHK(sc.alloc(&p.out_mean, ns * n)); SVDCHK(sc.alloc(&p.out_err2, nout));
-    SVDCHK(sc.alloc(&p.out_skew, nout)); SVDCHK(sc.alloc(&p.out_kurt, nout));
+    STGCHK(sg, sg.alloc(&dbins, nel));
+    if (T) { STGCHK(sg, sg.alloc(&dT, ns * n * n)); STGCHK(sg, sg.alloc(&drank, ns)); }
+    STGCHK(sg, sg.alloc(&p.part, ns * mxe::BINS_NWAVE * n * 2)); STGCHK(sg, sg.alloc(&p.part2, ns * mxe::BINS_NWAVE * n * 3));
+    STGCHK(sg, sg.alloc(&p.Y0, nel)); STGCHK(sg, sg.alloc(&p.Y1, ns * (m >> 1) * n));
+    STGCHK(sg, sg.alloc(&p.out_mean, ns * n)); STGCHK(sg, sg.alloc(&p.out_err2, nout));
+    STGCHK(sg, sg.alloc(&p.out_skew, nout)); STGCHK(sg, sg.alloc(&p.out_kurt, nout));
     p.bins = dbins; p.T = dT; p.rank = drank;
-    SVDCHK(hipMemcpyAsync(dbins, bins, nel * 8, hipMemcpyHostToDevice, sc.stream));
-    if (T) {
-        SVDCHK(hipMemcpyAsync(dT, T, ns * n * n * 8, hipMemcpyHostToDevice, sc.stream));
-        SVDCHK(hipMemcpyAsync(drank, rank, ns * 4, hipMemcpyHostToDevice, sc.stream));
-    }
-    if (out_ms) {
-        SVDCHK(hipEventCreate(&sc.e0)); SVDCHK(hipEventCreate(&sc.e1));
-        SVDCHK(hipEventRecord(sc.e0, sc.stream));
-    }
-    hipLaunchKernelGGL(mxe::bins_check_kernel, dim3(n_sets), dim3(mxe::BINS_T), 0, sc.stream, p);
-    SVDCHK(hipGetLastError());
-    if (out_ms) SVDCHK(hipEventRecord(sc.e1, sc.stream));
-    SVDCHK(hipMemcpyAsync(out_mean, p.out_mean, ns * n * 8, hipMemcpyDeviceToHost, sc.stream));
-    SVDCHK(hipMemcpyAsync(out_err2, p.out_err2, nout * 8, hipMemcpyDeviceToHost, sc.stream));
-    SVDCHK(hipMemcpyAsync(out_skew, p.out_skew, nout * 8, hipMemcpyDeviceToHost, sc.stream));
-    SVDCHK(hipMemcpyAsync(out_kurt, p.out_kurt, nout * 8, hipMemcpyDeviceToHost, sc.stream));
-    SVDCHK(hipStreamSynchronize(sc.stream));
-    if (out_ms) SVDCHK(hipEventElapsedTime(out_ms, sc.e0, sc.e1));
+    STGCHK(sg, sg.upload(dbins, bins, nel)); STGCHK(sg, sg.upload(dT, T, ns * n * n)); STGCHK(sg, sg.upload(drank, rank, ns));
+    STGCHK(sg, sg.time_begin(out_ms != nullptr));
+    hipLaunchKernelGGL(mxe::bins_check_kernel, dim3(n_sets), dim3(mxe::BINS_T), 0, sg.stream, p);
+    STGCHK(sg, hipGetLastError());
+    STGCHK(sg, sg.time_end());
+    STGCHK(sg, sg.fetch(out_mean, p.out_mean, ns * n)); STGCHK(sg, sg.fetch(out_err2, p.out_err2, nout));
+    STGCHK(sg, sg.fetch(out_skew, p.out_skew, nout)); STGCHK(sg, sg.fetch(out_kurt, p.out_kurt, nout));
+    STGCHK(sg, sg.finish(out_ms));
     out_levels[0] = L;
     return MXE_OK;
 }
@@ -3726,56 +3558,37 @@ try {
     if (m > mxe::HERMEIG_MAX_M) return MXE_ERR_LIMIT;
     const size_t nm = n_mat, mm = (size_t)m * m, w = is_complex ? 2 : 1;
     if (nm * mm * w > 0x7fffffffull) return MXE_ERR_ARG;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return MXE_ERR_NODEVICE;
-    if (device < 0 || device >= ndev) return MXE_ERR_ARG;
-    SVDCHK(hipSetDevice(device));
-    SvdScratch sc;
-    SVDCHK(hipStreamCreateWithFlags(&sc.stream, hipStreamNonBlocking));
+    Stage sg;
+    if (int rc = sg.open(device); rc != MXE_OK) return rc;
     mxe::HermEigParams p;
     std::memset(&p, 0, sizeof(p));
     p.n_mat = n_mat; p.m = m; p.floor = floor;
     double* dA;
-    SVDCHK(sc.alloc(&dA, nm * mm * w));
+    STGCHK(sg, sg.alloc(&dA, nm * mm * w));
     p.A = dA;
-    if (out_lambda) SVDCHK(sc.alloc(&p.lambda, nm * m));
-    if (out_vec) SVDCHK(sc.alloc(&p.vec, nm * mm * w));
-    if (out_proj) SVDCHK(sc.alloc(&p.proj, nm * mm * w));
-    if (out_neg) SVDCHK(sc.alloc(&p.neg, nm));
-    if (out_dist) SVDCHK(sc.alloc(&p.dist, nm));
-    if (out_pair) SVDCHK(sc.alloc(&p.pair, nm));
-    if (out_asym) SVDCHK(sc.alloc(&p.asym, nm));
-    if (out_info) SVDCHK(sc.alloc(&p.info, nm));
-    SVDCHK(hipMemcpyAsync(dA, A, nm * mm * w * 8, hipMemcpyHostToDevice, sc.stream));
-    if (out_ms) {
-        SVDCHK(hipEventCreate(&sc.e0)); SVDCHK(hipEventCreate(&sc.e1));
-        SVDCHK(hipEventRecord(sc.e0, sc.stream));
-    }
+    if (out_lambda) STGCHK(sg, sg.alloc(&p.lambda, nm * m));
+    if (out_vec) STGCHK(sg, sg.alloc(&p.vec, nm * mm * w));
+    if (out_proj) STGCHK(sg, sg.alloc(&p.proj, nm * mm * w));
+    if (out_neg) STGCHK(sg, sg.alloc(&p.neg, nm));
+    if (out_dist) STGCHK(sg, sg.alloc(&p.dist, nm));
+    if (out_pair) STGCHK(sg, sg.alloc(&p.pair, nm));
+    if (out_asym) STGCHK(sg, sg.alloc(&p.asym, nm));
+    if (out_info) STGCHK(sg, sg.alloc(&p.info, nm));
+    STGCHK(sg, sg.upload(dA, A, nm * mm * w));
+    STGCHK(sg, sg.time_begin(out_ms != nullptr));
     const bool wave = m <= mxe::HERMEIG_WAVE_M;
     const size_t slots = wave ? mxe::HERMEIG_T / 64 : 1;
     const size_t lds = slots * mxe::hermeig_slot_doubles(m, is_complex != 0) * sizeof(double);
     if (lds > 160 * 1024) return MXE_ERR_LIMIT;
-    const unsigned grid = (unsigned)((nm + slots - 1) / slots);
-    hipError_t e;
-#define MXE_LAUNCH_HERMEIG(C_, T_) do { \
-        e = hipFuncSetAttribute((const void*)mxe::hermeig_kernel<C_, T_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        if (e == hipSuccess) { hipLaunchKernelGGL((mxe::hermeig_kernel<C_, T_>), dim3(grid), dim3(mxe::HERMEIG_T), lds, sc.stream, p); \
-                               e = hipGetLastError(); } } while (0)
-    if (is_complex) { if (wave) MXE_LAUNCH_HERMEIG(true, 64); else MXE_LAUNCH_HERMEIG(true, 256); }
-    else            { if (wave) MXE_LAUNCH_HERMEIG(false, 64); else MXE_LAUNCH_HERMEIG(false, 256); }
-#undef MXE_LAUNCH_HERMEIG
-    SVDCHK(e);
-    if (out_ms) SVDCHK(hipEventRecord(sc.e1, sc.stream));
-    if (out_lambda) SVDCHK(hipMemcpyAsync(out_lambda, p.lambda, nm * m * 8, hipMemcpyDeviceToHost, sc.stream));
-    if (out_vec) SVDCHK(hipMemcpyAsync(out_vec, p.vec, nm * mm * w * 8, hipMemcpyDeviceToHost, sc.stream));
-    if (out_proj) SVDCHK(hipMemcpyAsync(out_proj, p.proj, nm * mm * w * 8, hipMemcpyDeviceToHost, sc.stream));
-    if (out_neg) SVDCHK(hipMemcpyAsync(out_neg, p.neg, nm * 8, hipMemcpyDeviceToHost, sc.stream));
-    if (out_dist) SVDCHK(hipMemcpyAsync(out_dist, p.dist, nm * 8, hipMemcpyDeviceToHost, sc.stream));
-    if (out_pair) SVDCHK(hipMemcpyAsync(out_pair, p.pair, nm * 8, hipMemcpyDeviceToHost, sc.stream));
-    if (out_asym) SVDCHK(hipMemcpyAsync(out_asym, p.asym, nm * 8, hipMemcpyDeviceToHost, sc.stream));
-    if (out_info) SVDCHK(hipMemcpyAsync(out_info, p.info, nm * 4, hipMemcpyDeviceToHost, sc.stream));
-    SVDCHK(hipStreamSynchronize(sc.stream));
-    if (out_ms) SVDCHK(hipEventElapsedTime(out_ms, sc.e0, sc.e1));
+    const auto kernel = is_complex ? (wave ? mxe::hermeig_kernel<true, 64> : mxe::hermeig_kernel<true, 256>)
+                                   : (wave ? mxe::hermeig_kernel<false, 64> : mxe::hermeig_kernel<false, 256>);
+    STGCHK(sg, launch_lds(kernel, dim3((unsigned)((nm + slots - 1) / slots)), dim3(mxe::HERMEIG_T), lds, sg.stream, p));
+    STGCHK(sg, sg.time_end());
+    STGCHK(sg, sg.fetch(out_lambda, p.lambda, nm * m)); STGCHK(sg, sg.fetch(out_vec, p.vec, nm * mm * w));
+    STGCHK(sg, sg.fetch(out_proj, p.proj, nm * mm * w)); STGCHK(sg, sg.fetch(out_neg, p.neg, nm));
+    STGCHK(sg, sg.fetch(out_dist, p.dist, nm)); STGCHK(sg, sg.fetch(out_pair, p.pair, nm));
+    STGCHK(sg, sg.fetch(out_asym, p.asym, nm)); STGCHK(sg, sg.fetch(out_info, p.info, nm));
+    STGCHK(sg, sg.finish(out_ms));
     return MXE_OK;
 }
 MXE_CATCH_ALL
