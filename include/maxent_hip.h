@@ -61,6 +61,8 @@
  *                                                          |   (percentile bands of the H rows of resamples or mocks)
  *   (nothing: users rebin by hand until the errors settle) | mxe_bins_check (blocking ladder, skewness and
  *                                                          |   kurtosis of the block means of the bins)
+ *   (nothing: few bins give a biased covariance)           | mxe_bins_eig_shrunk (shrinkage intensity from the
+ *                                                          |   bins, eigenbasis of the shrunk covariance)
  *   (nothing: users loop run() over their default models)  | mxe_evidence_reduce (evidence of every default
  *                                                          |   model, model-averaged image, spread between models)
  *   (nothing: positivity of the matrix is not checked)     | mxe_hermitian_eig (eigenvalues of A(w) as a matrix,
@@ -684,6 +686,32 @@ int  mxe_kramers_kronig(int device, int n_w, const double* w, const double* weig
  * not converge in 60 sweeps, or whose squares overflow. */
 int  mxe_bins_eig(int device, int n_sets, int n_bins, int n_data, const double* bins, double threshold,
                   double* out_mean, double* out_var, double* out_T, int32_t* out_rank, int32_t* out_sweeps);
+
+/* ---- few bins: the shrinkage covariance of the mean (no counterpart in the reference) ---- */
+/* mxe_bins_eig with the covariance of the mean replaced by the shrinkage estimator of Schaefer & Strimmer (2005), target
+ * "diagonal, unequal variances":  C* = (1 - lambda) X^T X + lambda diag(c),  c_j = (X^T X)_jj  -- the variances are kept,
+ * the correlations shrunk towards zero.  With x = bins - mean, s_j^2 = sum_k x_kj^2 / (m - 1), z = x / s (columns with
+ * s_j = 0 left out), w_ij = sum_k z_ki z_kj / m, r_ij = m / (m - 1) w_ij (m = n_bins):
+ *   lambda_raw = sum_{i != j} Var(r_ij) / sum_{i != j} r_ij^2,   Var(r_ij) = m / (m - 1)^3 sum_k (z_ki z_kj - w_ij)^2,
+ *   lambda     = min(1, max(0, lambda_raw));  a zero denominator (one column, no correlation at all): lambda = 1 and
+ *                lambda_raw = NaN (C* = C whatever lambda).
+ * The two Gram matrices behind the sums run as v_mfma_f64_16x16x4_f64 tiles, every sum over the bins in index order inside
+ * one wavefront, the tile sums added in tile order: no atomics.  C* is never formed: it is Y^T Y of
+ * Y = [sqrt(1 - lambda) X ; sqrt(lambda) diag(sqrt(c))], which goes through the pivoted QR and the one-sided Jacobi SVD of
+ * mxe_bins_eig; lambda is read from device memory, there is no host round trip between the kernels.
+ *   bins, threshold, out_mean, out_var, out_T, out_rank, out_sweeps   as for mxe_bins_eig (out_mean: the same bits); the
+ *               noise floor of the selection is ((n_bins + n_data) eps)^2 lambda_max, Y having n_bins + n_data rows.
+ *   lambda_in   < 0: lambda is estimated per set;  0 <= lambda_in <= 1: it is that value for every set
+ *   out_lambda      n_sets: the intensity used
+ *   out_lambda_raw  n_sets: the unclipped estimate (NaN with a fixed lambda_in)
+ *   out_diag    n_sets x n_data: c_j, the variances of the mean
+ *   out_ms      device time of all kernels of the call (may be NULL)
+ * A set's output does not depend on the other sets of the launch and repeats bit for bit.  MXE_ERR_ARG (nothing is
+ * launched): what mxe_bins_eig refuses, lambda_in > 1 or NaN, n_bins < 4 with lambda_in < 0, a NULL out_lambda,
+ * out_lambda_raw or out_diag;  MXE_ERR_NUMERIC as for mxe_bins_eig. */
+int  mxe_bins_eig_shrunk(int device, int n_sets, int n_bins, int n_data, const double* bins, double threshold,
+                         double lambda_in, double* out_mean, double* out_var, double* out_T, int32_t* out_rank,
+                         int32_t* out_sweeps, double* out_lambda, double* out_lambda_raw, double* out_diag, float* out_ms);
 
 /* ---- jackknife / bootstrap resampling of the bins (no counterpart in the reference) ---- */
 /* The rotated data of every resample of every set, one launch (one workgroup per set).

@@ -42,7 +42,7 @@ from .maxent_util import (ArrayGf, get_G_w_from_A_w, get_G_tau_from_A_w,   # noq
                           kramers_kronig)
 from .sigma_continuator import (SigmaContinuator, InversionSigmaContinuator,   # noqa: F401
                                 DirectSigmaContinuator)
-from .bin_checks import check_bins, rebin_bins      # noqa: F401
+from .bin_checks import check_bins, rebin_bins, shrink_bins      # noqa: F401
 from .positivity import matrix_positivity           # noqa: F401
 from . import _layout as _layout        # the reference's sub-module paths (analyzers.linefit_analyzer, ...)
 _layout.register(__name__)

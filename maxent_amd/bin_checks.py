@@ -108,6 +108,27 @@ def check_bins(bins, basis='data', T=None, rank=None, device=0):
     return out
 
 
+def shrink_bins(bins, shrinkage='auto', threshold=0.0, device=0):
+    """The shrinkage covariance of the mean of real ``bins`` (n_bins, n_data) from anywhere, or of several sets
+    (n_sets, n_bins, n_data): C* = (1 - lambda) C + lambda diag(C) (Schaefer and Strimmer 2005), for
+    jobs with fewer than about twice as many bins as data values.  ``shrinkage``: ``'auto'`` (lambda* is estimated from the
+    bins, at least 4) or a number in [0, 1].  Returns what ``bin_statistics`` holds after
+    ``set_G_tau_bins(..., shrinkage=...)``: ``mean``, ``sigma`` and ``T`` (eigenvalues of C* as their square roots,
+    ascending, and eigenvector rows), ``rank``, ``sweeps``, ``n_bins``, ``shrinkage``, ``shrinkage_raw`` and ``variance``
+    (the diagonal of C); a list of such dicts for several sets.  ``C* = T.T @ diag(sigma**2) @ T``."""
+    from . import device as dev
+    b = np.asarray(bins)
+    if b.ndim not in (2, 3):
+        raise ValueError('shrink_bins: bins must be (n_bins, n_data) or (n_sets, n_bins, n_data); their shape is {}'.format(b.shape))
+    if shrinkage is None:
+        raise ValueError("shrink_bins: shrinkage must be 'auto' or a number in [0, 1]")
+    dev.shrinkage_argument(shrinkage, b.shape[-2])
+    got = dev.bins_eig_shrunk(b, float(threshold), shrinkage, device=device)
+    if b.ndim == 2:
+        return dict(got, n_bins=b.shape[0])
+    return [dict(st, n_bins=b.shape[1]) for st in got]
+
+
 def _padded(T, rank, n_data):
     """eigenvector rows as ``mxe_bins_eig`` wrote them: zero rows behind the kept ones"""
     T = np.asarray(T, dtype=float)

@@ -3178,6 +3178,88 @@ try {
 }
 MXE_CATCH_ALL
 
+// ---- few bins: shrinkage intensity and the eigenbasis of the shrunk covariance of the mean (mxe_shrink.hip.h) ----
+#include "mxe_shrink.hip.h"
+
+extern "C" int mxe_bins_eig_shrunk(int device, int n_sets, int n_bins, int n_data, const double* bins, double threshold,
+                                   double lambda_in, double* out_mean, double* out_var, double* out_T, int32_t* out_rank,
+                                   int32_t* out_sweeps, double* out_lambda, double* out_lambda_raw, double* out_diag,
+                                   float* out_ms)
+try {
+    if (n_sets < 1 || n_bins < 2 || n_data < 1 || n_data > mxe::BINS_NMAX || !bins || !out_mean || !out_var || !out_T ||
+        !out_rank || !out_sweeps || !(threshold >= 0.0) || !std::isfinite(threshold)) return MXE_ERR_ARG;
+    if (!out_lambda || !out_lambda_raw || !out_diag || !(lambda_in <= 1.0)) return MXE_ERR_ARG;   // (a NaN fails the comparison)
+    const bool estimate = lambda_in < 0.0;
+    if (estimate && n_bins < 4) return MXE_ERR_ARG;
+    if ((int64_t)n_bins * n_data > INT32_MAX) return MXE_ERR_ARG;
+    const size_t m = n_bins, n = n_data, ns = n_sets, nel = ns * m * n;
+    const size_t M = m + n;                                   // rows of Y
+    if (!all_finite(bins, nel)) return MXE_ERR_ARG;
+    mxe::ShrinkParams sp;
+    sp.m = n_bins; sp.n = n_data;
+    sp.mp = (n_bins + 3) & ~3; sp.np = (n_data + 15) & ~15;
+    const int ct = sp.np / 16;
+    sp.nt = ct * (ct + 1) / 2;
+    sp.wgs = (sp.nt + mxe::SHRINK_TW - 1) / mxe::SHRINK_TW;
+    if ((int64_t)sp.wgs * n_sets > INT32_MAX) return MXE_ERR_ARG;
+    Stage sg;
+    if (int rc = sg.open(device); rc != MXE_OK) return rc;
+    mxe::BinsParams p;
+    p.m = n_bins; p.n = n_data;
+    p.rcap = (n_data + 1) & ~1;
+    p.scale = 1.0 / std::sqrt((double)n_bins * (double)(n_bins - 1));
+    p.threshold = threshold;
+    const double floor1 = (double)(n_bins + n_data) * 2.220446049250313e-16;
+    p.floor2 = floor1 * floor1;
+    double *dbins, *dlam, *draw, *ddiag;
+    STGCHK(sg, sg.alloc(&dbins, nel));
+    p.bins = dbins;
+    STGCHK(sg, sg.alloc(&p.A, ns * n * M));
+    STGCHK(sg, sg.alloc(&p.Rm, ns * p.rcap * n)); STGCHK(sg, sg.alloc(&p.vk, ns * M));
+    STGCHK(sg, sg.alloc(&p.part, ns * mxe::BINS_NWAVE * n * 2)); STGCHK(sg, sg.alloc(&p.cn2, ns * n));
+    STGCHK(sg, sg.alloc(&p.perm, ns * n));
+    STGCHK(sg, sg.alloc(&p.out_mean, ns * n)); STGCHK(sg, sg.alloc(&p.out_var, ns * n));
+    STGCHK(sg, sg.alloc(&p.out_T, ns * n * n)); STGCHK(sg, sg.alloc(&p.out_info, ns * 4));
+    STGCHK(sg, sg.alloc(&dlam, ns)); STGCHK(sg, sg.alloc(&draw, ns)); STGCHK(sg, sg.alloc(&ddiag, ns * n));
+    std::vector<double> hlam;                                 // (a fixed lambda: lives until the stream is waited for)
+    if (estimate) {
+        sp.bins = dbins; sp.part = p.part; sp.out_mean = p.out_mean; sp.lambda = dlam; sp.lambda_raw = draw;
+        STGCHK(sg, sg.alloc(&sp.Z, ns * sp.mp * sp.np)); STGCHK(sg, sg.alloc(&sp.tpart, ns * sp.nt * 2));
+    } else {
+        hlam.assign(2 * ns, lambda_in);
+        std::fill(hlam.begin() + ns, hlam.end(), std::nan(""));
+        STGCHK(sg, sg.upload(dlam, hlam.data(), ns)); STGCHK(sg, sg.upload(draw, hlam.data() + ns, ns));
+    }
+    STGCHK(sg, sg.upload(dbins, bins, nel));
+    STGCHK(sg, sg.time_begin(out_ms != nullptr));
+    if (estimate) {
+        hipLaunchKernelGGL(mxe::shrink_prep_kernel, dim3(n_sets), dim3(mxe::BINS_T), 0, sg.stream, sp);
+        STGCHK(sg, hipGetLastError());
+        hipLaunchKernelGGL(mxe::shrink_gram_kernel, dim3((unsigned)(sp.wgs * n_sets)), dim3(64 * mxe::SHRINK_TW), 0, sg.stream, sp);
+        STGCHK(sg, hipGetLastError());
+        hipLaunchKernelGGL(mxe::shrink_lambda_kernel, dim3(n_sets), dim3(64), 0, sg.stream, sp);
+        STGCHK(sg, hipGetLastError());
+    }
+    hipLaunchKernelGGL(mxe::bins_eig_shrunk_kernel, dim3(n_sets), dim3(mxe::BINS_T), 0, sg.stream, p,
+                       (const double*)dlam, ddiag);
+    STGCHK(sg, hipGetLastError());
+    STGCHK(sg, sg.time_end());
+    std::vector<int> hinfo(ns * 4);
+    STGCHK(sg, sg.fetch(out_mean, p.out_mean, ns * n)); STGCHK(sg, sg.fetch(out_var, p.out_var, ns * n));
+    STGCHK(sg, sg.fetch(out_T, p.out_T, ns * n * n)); STGCHK(sg, sg.fetch(hinfo.data(), p.out_info, hinfo.size()));
+    STGCHK(sg, sg.fetch(out_lambda, dlam, ns)); STGCHK(sg, sg.fetch(out_lambda_raw, draw, ns));
+    STGCHK(sg, sg.fetch(out_diag, ddiag, ns * n));
+    STGCHK(sg, sg.finish(out_ms));
+    int rc = MXE_OK;
+    for (size_t s = 0; s < ns; ++s) {
+        out_rank[s] = hinfo[s * 4];
+        out_sweeps[s] = hinfo[s * 4 + 2];
+        if (hinfo[s * 4 + 3] != 0) rc = MXE_ERR_NUMERIC;
+    }
+    return rc;
+}
+MXE_CATCH_ALL
+
 // ---- resampling of the bins: the rotated data of every jackknife / bootstrap resample, and the reduction of the
 // ---- H rows they were continued to (mxe_resample.hip.h) ----
 #include "mxe_resample.hip.h"

@@ -115,16 +115,24 @@ __device__ __forceinline__ void bins_mean(const double* bins, int m, int n, doub
     __syncthreads();
 }
 
-__global__ __launch_bounds__(BINS_T)
-void bins_eig_kernel(const BinsParams p)
+// The stages of a set's decomposition, by its workgroup of BINS_T threads.  SHRUNK = false: bins_eig_kernel, as described
+// above.  SHRUNK = true (bins_eig_shrunk_kernel, mxe_shrink.hip.h): the matrix whose right singular vectors are asked for
+// is Y = [sqrt(1 - lambda) X ; sqrt(lambda) diag(sqrt(c))], c_j = sum_k X_kj^2 (written to ``diag``), lambda = *lam read
+// from device memory: Y^T Y = (1 - lambda) X^T X + lambda diag(c).  The n diagonal rows are appended to the columns of
+// X^T (M = m + n rows; A: [n][M], vk: [M]) and Y always goes through the QR stage.  With SHRUNK = false M is m and every
+// operation is the one bins_eig_kernel has always done: its outputs keep their bits.
+template <bool SHRUNK>
+__device__ __forceinline__ void bins_eig_body(const BinsParams& p, const double* lam, double* diag)
 {
     const int set = blockIdx.x;
     const int m = p.m, n = p.n;
+    const int M = SHRUNK ? m + n : m;                    // rows of the matrix the QR stage works on
+    const bool tall = SHRUNK || m > n;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const double* bins = p.bins + (size_t)set * m * n;
-    double* A = p.A + ((m > n) ? (size_t)set * n * m : 0);
+    double* A = p.A + (tall ? (size_t)set * n * M : 0);
     double* Rm = p.Rm + (size_t)set * p.rcap * n;
-    double* vk = p.vk + (size_t)set * m;
+    double* vk = p.vk + (size_t)set * M;
     double* part = p.part + (size_t)set * BINS_NWAVE * n * 2;
     double* cn2 = p.cn2 + (size_t)set * n;
     int* perm = p.perm + (size_t)set * n;
@@ -147,7 +155,7 @@ void bins_eig_kernel(const BinsParams p)
 
     // ---- 2. X = (bins - mean) * scale ----
     int r = 0;
-    if (m > n) {
+    if (tall) {
         // transposed into A (column j = m contiguous values) through a 64 x 64 tile: reads and writes along the fast index
         const int tx = tid & 63, ty = tid >> 6;
         for (int i0 = 0; i0 < m; i0 += 64) {
@@ -161,7 +169,7 @@ void bins_eig_kernel(const BinsParams p)
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
                     const int j = j0 + ty + 16 * q, i = i0 + tx;
-                    if (i < m && j < n) A[(size_t)j * m + i] = tile[tx][ty + 16 * q];
+                    if (i < m && j < n) A[(size_t)j * M + i] = tile[tx][ty + 16 * q];
                 }
                 __syncthreads();
             }
@@ -169,11 +177,29 @@ void bins_eig_kernel(const BinsParams p)
         // column norms
         for (int j = wave; j < n; j += BINS_NWAVE) {
             double s = 0.0;
-            for (int i = lane; i < m; i += 64) { const double x = A[(size_t)j * m + i]; s = fma(x, x, s); }
+            for (int i = lane; i < m; i += 64) { const double x = A[(size_t)j * M + i]; s = fma(x, x, s); }
             s = bins_wave_sum(s);
             if (lane == 0) { cn2[j] = s; perm[j] = j; }
         }
         __syncthreads();
+        if constexpr (SHRUNK) {
+            // Y: the rows of X times sqrt(1 - lambda), below them sqrt(lambda c_j) on the diagonal; the column norms again
+            const double lm = lam[set];
+            const double wx = sqrt(1.0 - lm), wd = sqrt(lm);
+            for (int j = wave; j < n; j += BINS_NWAVE) {
+                double* col = A + (size_t)j * M;
+                const double cj = cn2[j];
+                double s = 0.0;
+                for (int i = lane; i < M; i += 64) {
+                    const double x = (i < m) ? wx * col[i] : ((i - m == j) ? wd * sqrt(cj) : 0.0);
+                    col[i] = x;
+                    s = fma(x, x, s);
+                }
+                s = bins_wave_sum(s);
+                if (lane == 0) { diag[(size_t)set * n + j] = cj; cn2[j] = s; }
+            }
+            __syncthreads();
+        }
 
         // ---- Householder QR with column pivoting, early stop (mxe_svd.hip.h, without its cap on the rows of R) ----
         for (int k = 0; k < n; ++k) {
@@ -199,10 +225,10 @@ void bins_eig_kernel(const BinsParams p)
             if (sh_stop) break;
             const int piv = sh_piv;
             if (piv != k) {
-                for (int i = tid; i < m; i += BINS_T) {
-                    const double x = A[(size_t)k * m + i];
-                    A[(size_t)k * m + i] = A[(size_t)piv * m + i];
-                    A[(size_t)piv * m + i] = x;
+                for (int i = tid; i < M; i += BINS_T) {
+                    const double x = A[(size_t)k * M + i];
+                    A[(size_t)k * M + i] = A[(size_t)piv * M + i];
+                    A[(size_t)piv * M + i] = x;
                 }
                 if (tid == 0) {
                     const int t = perm[k]; perm[k] = perm[piv]; perm[piv] = t;
@@ -213,16 +239,16 @@ void bins_eig_kernel(const BinsParams p)
             // Householder vector of column k, rows k..m-1 (wave 0)
             if (wave == 0) {
                 double s = 0.0;
-                for (int i = k + lane; i < m; i += 64) { const double x = A[(size_t)k * m + i]; s = fma(x, x, s); }
+                for (int i = k + lane; i < M; i += 64) { const double x = A[(size_t)k * M + i]; s = fma(x, x, s); }
                 s = bins_wave_sum(s);
-                const double x0 = A[(size_t)k * m + k];
+                const double x0 = A[(size_t)k * M + k];
                 const double nrm = sqrt(s);
                 const double alpha = (x0 >= 0.0) ? -nrm : nrm;
                 const double vn = sqrt(2.0 * (s - alpha * x0));       // |x - alpha e0|
                 const double inv = (vn > 0.0) ? 1.0 / vn : 0.0;
-                for (int i = k + lane; i < m; i += 64) {
-                    vk[i] = ((i == k) ? (x0 - alpha) : A[(size_t)k * m + i]) * inv;
-                    A[(size_t)k * m + i] = (i == k) ? alpha : 0.0;
+                for (int i = k + lane; i < M; i += 64) {
+                    vk[i] = ((i == k) ? (x0 - alpha) : A[(size_t)k * M + i]) * inv;
+                    A[(size_t)k * M + i] = (i == k) ? alpha : 0.0;
                 }
             }
             __syncthreads();
@@ -233,8 +259,8 @@ void bins_eig_kernel(const BinsParams p)
                 for (int q = 0; q < 4; ++q) {
                     s[q] = 0.0;
                     const int j = min(j0 + q * BINS_NWAVE, n - 1);
-                    const double* col = A + (size_t)j * m;
-                    for (int i = k + lane; i < m; i += 64) s[q] = fma(vk[i], col[i], s[q]);
+                    const double* col = A + (size_t)j * M;
+                    for (int i = k + lane; i < M; i += 64) s[q] = fma(vk[i], col[i], s[q]);
                 }
 #pragma unroll
                 for (int q = 0; q < 4; ++q) s[q] = 2.0 * bins_wave_sum(s[q]);
@@ -243,8 +269,8 @@ void bins_eig_kernel(const BinsParams p)
                     rem[q] = 0.0;
                     const int j = j0 + q * BINS_NWAVE;
                     if (j < n) {
-                        double* col = A + (size_t)j * m;
-                        for (int i = k + lane; i < m; i += 64) {
+                        double* col = A + (size_t)j * M;
+                        for (int i = k + lane; i < M; i += 64) {
                             const double x = fma(-s[q], vk[i], col[i]);
                             col[i] = x;
                             if (i > k) rem[q] = fma(x, x, rem[q]);
@@ -266,7 +292,7 @@ void bins_eig_kernel(const BinsParams p)
         const int rr0 = (r + 1) & ~1;
         for (int idx = tid; idx < rr0 * n; idx += BINS_T) {
             const int kk = idx / n, j = idx - kk * n;
-            Rm[idx] = (kk < r && j >= kk) ? A[(size_t)j * m + kk] : 0.0;
+            Rm[idx] = (kk < r && j >= kk) ? A[(size_t)j * M + kk] : 0.0;
         }
     } else {
         // the short side: the m rows of X are the rows to orthogonalise (row-major, as the bins come)
@@ -315,12 +341,30 @@ void bins_eig_kernel(const BinsParams p)
                         const double az = fabs(zeta);
                         const double t = ((zeta >= 0.0) ? 1.0 : -1.0) / ((az < 1.0e150) ? az + sqrt(1.0 + zeta * zeta) : 2.0 * az);
                         const double cs = 1.0 / sqrt(1.0 + t * t), sn = cs * t;
+                        if constexpr (SHRUNK) {
+                            // x - sn (y + tau x), tau = sn / (1 + cs) = (1 - cs) / sn: below |t| ~ 1e-8 cs rounds to 1 and
+                            // (cs, sn) stretches the pair by 1 + t^2 -- always up, and a row sees n - 1 such rotations per
+                            // late sweep (measured: eigenvalues high by 1.7e-13 at 512 rows).  This form carries 1 - cs
+                            // as a term of its own.  bins_eig_kernel keeps the form (and the bits) it has always had.
+                            const double tau = sn / (1.0 + cs);
 #pragma unroll
-                        for (int c = 0; c < BINS_NC; ++c) {
-                            const int j = lane + 64 * c;
-                            if (j < n) {
-                                x[j] = cs * xv[c] - sn * yv[c];
-                                y[j] = sn * xv[c] + cs * yv[c];
+                            for (int c = 0; c < BINS_NC; ++c) {
+                                const int j = lane + 64 * c;
+                                if (j < n) {
+                                    x[j] = xv[c] - sn * fma(tau, xv[c], yv[c]);
+                                    y[j] = yv[c] + sn * fma(-tau, yv[c], xv[c]);
+                                }
+                            }
+                        } else {
+#pragma unroll
+                            for (int c = 0; c < BINS_NC; ++c) {
+                                const int j = lane + 64 * c;
+                                if (j < n) {
+                                    // (the fused forms this kernel has always been compiled to, spelled out: its bits
+                                    // do not hang on which product the compiler picks to fuse)
+                                    x[j] = fma(cs, xv[c], -(sn * yv[c]));
+                                    y[j] = fma(sn, xv[c], cs * yv[c]);
+                                }
                             }
                         }
                         if (lane == 0) atomicAdd(&sh_rot, 1);
@@ -388,6 +432,12 @@ void bins_eig_kernel(const BinsParams p)
         for (int j = lane; j < n; j += 64) trow[perm[j]] = rrow[j] * inv;
     }
     if (tid == 0) { out_info[0] = ns; out_info[1] = r; out_info[2] = sweeps; out_info[3] = status; }
+}
+
+__global__ __launch_bounds__(BINS_T)
+void bins_eig_kernel(const BinsParams p)
+{
+    bins_eig_body<false>(p, nullptr, nullptr);
 }
 
 } // namespace mxe

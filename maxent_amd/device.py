@@ -172,6 +172,9 @@ SYMBOLS = [
                                           ctypes.c_int, _dp, _dp, ctypes.POINTER(ctypes.c_float)]),
     ('mxe_bins_eig', ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, ctypes.c_double,
                                     _dp, _dp, _dp, _ip, _ip]),
+    ('mxe_bins_eig_shrunk', ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, ctypes.c_double,
+                                           ctypes.c_double, _dp, _dp, _dp, _ip, _ip, _dp, _dp, _dp,
+                                           ctypes.POINTER(ctypes.c_float)]),
     ('mxe_bins_resample', ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, ctypes.c_int, _ip, _dp, _ip,
                                          _dp, _dp, _dp, ctypes.POINTER(ctypes.c_float)]),
     ('mxe_resample_reduce', ctypes.c_int, [_vp, ctypes.c_int, _ip, _dp, _ip, _dp, ctypes.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _ip,
@@ -550,6 +553,83 @@ def bins_eig(bins, threshold, device=0):
         out.append(dict(mean=mean[s].copy(), sigma=np.sqrt(var[s, :k]), T=T[s, :k].copy(), rank=k, sweeps=int(sweeps[s])))
     return out[0] if single else out
 
+
+def shrinkage_argument(shrinkage, n_bins):
+    """The ``shrinkage`` argument of the bins setters as ``lambda_in`` of ``mxe_bins_eig_shrunk``: None for ``None`` and
+    ``0.0`` (the sample covariance, ``mxe_bins_eig``), -1.0 for ``'auto'`` (the intensity is estimated from the bins, which
+    takes four of them), the value itself for a number in (0, 1].  Anything else is a ValueError; nothing is touched."""
+    if shrinkage is None:
+        return None
+    if isinstance(shrinkage, str):
+        if shrinkage != 'auto':
+            raise ValueError("shrinkage must be None, 'auto' or a number in [0, 1]; got %r" % (shrinkage,))
+        if int(n_bins) < 4:
+            raise ValueError("shrinkage='auto' estimates the variance of every correlation and needs at least 4 bins; "
+                             "got %d" % int(n_bins))
+        return -1.0
+    if isinstance(shrinkage, (bool, np.bool_)) or not isinstance(shrinkage, (int, float, np.integer, np.floating)):
+        raise ValueError("shrinkage must be None, 'auto' or a number in [0, 1]; got %r" % (shrinkage,))
+    lam = float(shrinkage)
+    if not (0.0 <= lam <= 1.0):
+        raise ValueError("shrinkage must be None, 'auto' or a number in [0, 1]; got %r" % (shrinkage,))
+    return None if lam == 0.0 else lam
+
+
+def bins_eig_shrunk(bins, threshold, shrinkage, device=0, timing=None):
+    """``mxe_bins_eig_shrunk``: :func:`bins_eig` with the shrinkage covariance of the mean
+    C* = (1 - lambda) X^T X + lambda diag(c) in place of X^T X.  ``shrinkage``: ``'auto'`` (lambda* is estimated per set
+    from its bins) or a number in [0, 1] (that lambda for every set).  Returns the dicts of :func:`bins_eig` with three
+    more entries: ``shrinkage`` (the lambda used), ``shrinkage_raw`` (the unclipped estimate; NaN for a fixed lambda and
+    where no two columns are correlated at all) and ``variance`` (n_data: c_j, the variances of the mean, the diagonal
+    of both C and C*).  ``timing``: a dict that receives the device time ``ms`` of the call's kernels."""
+    lib = load_library()
+    b = np.asarray(bins)
+    single = b.ndim == 2
+    if single:
+        b = b[None]
+    if b.ndim != 3 or np.iscomplexobj(b):
+        raise ValueError('bins_eig_shrunk: bins must be real, (n_sets, n_bins, n_data) or (n_bins, n_data); got %s' % (np.shape(bins),))
+    b = _c(b)
+    n_sets, n_bins, n_data = b.shape
+    if n_sets < 1 or n_bins < 2:
+        raise ValueError('bins_eig_shrunk: at least one set and two bins are needed; got %d set(s) of %d bin(s)' % (n_sets, n_bins))
+    lam_in = shrinkage_argument(shrinkage, n_bins)
+    if lam_in is None:
+        if shrinkage is None:
+            raise ValueError("bins_eig_shrunk: shrinkage must be 'auto' or a number in [0, 1]; bins_eig is the call without")
+        lam_in = 0.0
+    if n_data < 1 or n_data > BINS_MAX_DATA:
+        raise MaxEntDeviceError('mxe_bins_eig_shrunk: %d data points per set; the device decomposition takes 1 to %d'
+                                % (n_data, BINS_MAX_DATA))
+    if device_count() < 1:
+        raise MaxEntDeviceError('no HIP device visible; the shrinkage covariance of bins has no CPU fallback')
+    mean = np.empty((n_sets, n_data))
+    var = np.empty((n_sets, n_data))
+    T = np.empty((n_sets, n_data, n_data))
+    rank = np.zeros(n_sets, dtype=np.int32)
+    sweeps = np.zeros(n_sets, dtype=np.int32)
+    lam = np.empty(n_sets)
+    raw = np.empty(n_sets)
+    diag = np.empty((n_sets, n_data))
+    ms = ctypes.c_float(0)
+    rc = lib.mxe_bins_eig_shrunk(int(device), n_sets, n_bins, n_data, _p(b), float(threshold), float(lam_in), _p(mean), _p(var),
+                                 _p(T), _p(rank), _p(sweeps), _p(lam), _p(raw), _p(diag), ctypes.byref(ms))
+    if rc == _MXE_ERR_NUMERIC:
+        raise MaxEntDeviceError('mxe_bins_eig_shrunk: the Jacobi iteration of set(s) %s did not converge (sweeps %s), or the '
+                                'squares of the bins overflow' % (np.nonzero(sweeps >= 60)[0].tolist(), int(sweeps.max())))
+    if rc == _MXE_ERR_ARG:           # (sizes and lambda were checked above: what is left is a NaN or an Inf, or a bad threshold)
+        raise ValueError('bins_eig_shrunk: bins hold %d values that are not finite (threshold %r)'
+                         % (int((~np.isfinite(b)).sum()), threshold))
+    if rc != 0:
+        raise MaxEntDeviceError('mxe_bins_eig_shrunk failed: ' + lib.mxe_strerror(rc).decode())
+    if timing is not None:
+        timing['ms'] = float(ms.value)
+    out = []
+    for s in range(n_sets):
+        k = int(rank[s])
+        out.append(dict(mean=mean[s].copy(), sigma=np.sqrt(var[s, :k]), T=T[s, :k].copy(), rank=k, sweeps=int(sweeps[s]),
+                        shrinkage=float(lam[s]), shrinkage_raw=float(raw[s]), variance=diag[s].copy()))
+    return out[0] if single else out
 
 
 def bins_resample(bins, counts, T, rank, device=0, want_dev=True, timing=None):

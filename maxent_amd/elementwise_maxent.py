@@ -1260,13 +1260,15 @@ class ElementwiseMaxEnt(object):
         self.put_error = lambda maxent, err: maxent.set_cov(err)
 
     # ---- bins: all sets of the run through ONE mxe_bins_eig call ----------------------------------------
-    def _bins_eig(self, shape, sets_of, n_bins):
+    def _bins_eig(self, shape, sets_of, n_bins, shrinkage=None):
         """``sets_of(i, j)``: the real bins (n_bins, n_data) of the real-part problem of element (i, j) and of its
         imaginary-part problem (None: there is none).  Every set the run needs -- with ``use_hermiticity`` only
         i <= j, imaginary parts only with ``use_complex`` and off the diagonal -- goes down in one call, on the first
         of ``device_ids`` (the preparation is not sharded: the elements' solves are).  Returns
-        {(i, j): [statistics of the real part, of the imaginary part or None]}."""
+        {(i, j): [statistics of the real part, of the imaginary part or None]}.  ``shrinkage``: as for
+        :meth:`TauMaxEnt.set_G_tau_bins`; with ``'auto'`` every set gets its own lambda."""
         from . import device
+        lambda_in = device.shrinkage_argument(shrinkage, n_bins)     # (a ValueError before anything is touched)
         M, N = shape
         where, sets = [], []
         for i in range(M):
@@ -1280,9 +1282,13 @@ class ElementwiseMaxEnt(object):
                     where.append((i, j, 1))
                     sets.append(im_set)
         stack = np.ascontiguousarray(np.stack(sets), dtype=float)
-        self.maxent_diagonal._warn_few_bins(n_bins, stack.shape[-1])
         ids = self.device_ids if self.device_ids else (self.maxent_diagonal._device_for_bins(),)
-        stats = device.bins_eig(stack, self.cov_threshold, device=ids[0])
+        if lambda_in is None:
+            self.maxent_diagonal._warn_few_bins(n_bins, stack.shape[-1])
+            stats = device.bins_eig(stack, self.cov_threshold, device=ids[0])
+        else:
+            stats = device.bins_eig_shrunk(stack, self.cov_threshold, shrinkage, device=ids[0])
+            self.maxent_diagonal._note_shrinkage(n_bins, stack.shape[-1], [st['shrinkage'] for st in stats])
         table, public = {}, {}
         for (i, j, c), st in zip(where, stats):
             st = dict(st, n_bins=n_bins)
@@ -1317,12 +1323,13 @@ class ElementwiseMaxEnt(object):
         self.put_error = put
         object.__setattr__(self, '_errors_from_bins', True)
 
-    def set_G_tau_bins(self, tau, bins):
+    def set_G_tau_bins(self, tau, bins, shrinkage=None):
         """``bins``: (n_bins, M, N, n_tau) array of independent estimates of G_ij(tau) (:meth:`TauMaxEnt.set_G_tau_bins`),
         complex with ``use_complex``: real and imaginary parts are then sets of their own, each with the covariance of
         its own mean.  The eigenbases of all elements the run needs come from one ``mxe_bins_eig`` call;
         ``bin_statistics[(i, j)]`` (``[(i, j, c)]`` with ``use_complex``) holds ``mean``, ``sigma``, ``T``, ``rank`` and
-        ``n_bins``.  Not in the reference."""
+        ``n_bins``.  ``shrinkage``: as for :meth:`TauMaxEnt.set_G_tau_bins`, all sets still in one call
+        (``mxe_bins_eig_shrunk``), every set with its own lambda.  Not in the reference."""
         tau = np.asarray(tau, dtype=float)
         bins = TauMaxEnt._check_bins(tau, bins, 'G(tau) bins')
         if bins.ndim != 4:
@@ -1334,11 +1341,11 @@ class ElementwiseMaxEnt(object):
         def sets_of(i, j):
             b = bins[:, i, j, :]
             return b.real, (b.imag if cplx else None)
-        table = self._bins_eig(bins.shape[1:3], sets_of, bins.shape[0])
+        table = self._bins_eig(bins.shape[1:3], sets_of, bins.shape[0], shrinkage)
         self.set_G_tau_data(tau, self._means_of_bins(table, bins.shape[1:3], len(tau)))
         self._put_eigenbases(table)
 
-    def set_G_iw_bins(self, iomega, bins, beta=None):
+    def set_G_iw_bins(self, iomega, bins, beta=None, shrinkage=None):
         """``bins``: complex (n_bins, M, M, n_iw) array of independent estimates of G_ij(i omega_n).  Every bin is split
         as in :meth:`set_G_iw_data` -- (G_ij + G_ji) / 2 = K Re A_ij, (G_ij - G_ji) / (2i) = K Im A_ij (the latter with
         ``use_complex``) -- and unfolded to stacked real values, whose mean and covariance enter as in
@@ -1356,11 +1363,11 @@ class ElementwiseMaxEnt(object):
                 return re_set, None
             im_part = (a - b) / 2j
             return re_set, np.concatenate([im_part.real, im_part.imag], axis=-1)
-        table = self._bins_eig(bins.shape[1:3], sets_of, bins.shape[0])
+        table = self._bins_eig(bins.shape[1:3], sets_of, bins.shape[0], shrinkage)
         self._set_G_iw_stacked(iomega, self._means_of_bins(table, bins.shape[1:3], 2 * len(iomega)), beta)
         self._put_eigenbases(table)
 
-    def set_G_l_bins(self, bins, beta, l=None):
+    def set_G_l_bins(self, bins, beta, l=None, shrinkage=None):
         """``bins``: (n_bins, M, N, n_l) array of independent estimates of the Legendre coefficients of G_ij
         (:meth:`TauMaxEnt.set_G_l_bins`), complex with ``use_complex``; everything else as :meth:`set_G_tau_bins`."""
         bins = np.asarray(bins)
@@ -1375,7 +1382,7 @@ class ElementwiseMaxEnt(object):
         def sets_of(i, j):
             b = bins[:, i, j, :]
             return b.real, (b.imag if cplx else None)
-        table = self._bins_eig(bins.shape[1:3], sets_of, bins.shape[0])
+        table = self._bins_eig(bins.shape[1:3], sets_of, bins.shape[0], shrinkage)
         self.set_G_l_data(self._means_of_bins(table, bins.shape[1:3], len(l)), beta, l)
         self._put_eigenbases(table)
 

@@ -310,12 +310,28 @@ class TauMaxEnt(object):
         if inner._projected or (T is not None and T.shape[0] != T.shape[1]):
             self.K.refill_unrotated()
 
-    def _bins_eig(self, stacked_bins):
-        """mean and covariance eigenbasis of real ``stacked_bins`` (n_bins, n_data) from the device; changes nothing"""
+    def _note_shrinkage(self, n_bins, n_data, lambdas):
+        """in place of the few-bins warning: with shrinkage no direction of the data is lost"""
+        from .logtaker import VerbosityFlags
+        lambdas = np.atleast_1d(np.asarray(lambdas, dtype=float))
+        self.logtaker.message(
+            VerbosityFlags.Header,
+            '{} bins for {} data values: shrinkage covariance of the mean, lambda = {}',
+            n_bins, n_data, '{:.4g}'.format(lambdas[0]) if lambdas.size == 1 else
+            '{:.4g} .. {:.4g} over {} sets'.format(lambdas.min(), lambdas.max(), lambdas.size))
+
+    def _bins_eig(self, stacked_bins, shrinkage=None):
+        """mean and covariance eigenbasis of real ``stacked_bins`` (n_bins, n_data) from the device; changes nothing.
+        ``shrinkage``: see :meth:`set_G_tau_bins` (refused with a ValueError before the device is asked for anything)"""
         from . import device
         n_bins, n_data = stacked_bins.shape
-        self._warn_few_bins(n_bins, n_data)
-        st = device.bins_eig(stacked_bins, self.cov_threshold, device=self._device_for_bins())
+        lambda_in = device.shrinkage_argument(shrinkage, n_bins)
+        if lambda_in is None:
+            self._warn_few_bins(n_bins, n_data)
+            st = device.bins_eig(stacked_bins, self.cov_threshold, device=self._device_for_bins())
+        else:
+            st = device.bins_eig_shrunk(stacked_bins, self.cov_threshold, shrinkage, device=self._device_for_bins())
+            self._note_shrinkage(n_bins, n_data, st['shrinkage'])
         if st['rank'] == 0:
             raise AssertionError('no eigenvalue of the covariance of the mean is above cov_threshold = {}'.format(
                 self.cov_threshold))
@@ -325,38 +341,46 @@ class TauMaxEnt(object):
         object.__setattr__(self, 'bin_statistics', st)
         self._set_eigenbasis(st['sigma'], st['T'], mean=st['mean'])
 
-    def set_G_tau_bins(self, tau, bins):
+    def set_G_tau_bins(self, tau, bins, shrinkage=None):
         """G(tau) as ``bins`` of shape (n_bins, n_tau): independent estimates (Monte Carlo bins).  The data become their
         mean, the errors those of the covariance of the mean C = X^T X, X = (bins - mean) / sqrt(n_bins (n_bins - 1)):
         the job is the one of ``set_G_tau_data(tau, mean)`` and ``set_cov(C)`` on a fresh object, with ``cov_threshold``
         as the cut.  Mean and eigenbasis come from the device (``mxe_bins_eig``: the singular value decomposition of X;
         C is never formed, and small eigenvalues keep their relative accuracy); ``bin_statistics`` holds ``mean``,
         ``sigma``, ``T``, ``rank`` and ``n_bins``.  Bins that are refused leave the object as it was.  Not in the
-        reference."""
+        reference.
+
+        ``shrinkage``: with fewer than about twice as many bins as data values the small eigenvalues of C are biased low
+        (and with ``n_bins <= n_data`` directions of the data are lost).  ``'auto'`` replaces C by the shrinkage estimator
+        C* = (1 - lambda) C + lambda diag(C) of Schaefer and Strimmer with the intensity lambda* estimated from the bins
+        (at least 4), a number in (0, 1] fixes lambda; both on the device (``mxe_bins_eig_shrunk``, DESIGN.md section
+        4y; :func:`maxent_amd.shrink_bins` is the plain function).  ``bin_statistics`` then also holds ``shrinkage``,
+        ``shrinkage_raw`` and ``variance``.  ``None`` or ``0.0``: the sample covariance as before.  Anything else is a
+        ValueError that leaves the object as it was."""
         tau = np.asarray(tau, dtype=float)
         bins = self._check_bins(tau, bins, 'G(tau) bins')
         if bins.ndim != 2:
             raise AssertionError('G(tau) bins must be (n_bins, n_tau); their shape is {}'.format(bins.shape))
         if np.iscomplexobj(bins):
             raise AssertionError('G(tau) bins must be real')
-        st = self._bins_eig(np.asarray(bins, dtype=float))
+        st = self._bins_eig(np.asarray(bins, dtype=float), shrinkage)
         self._use_kernel(kernels.TauKernel, tau)
         self._adopt_bins(st)
 
-    def set_G_iw_bins(self, iomega, bins, beta=None):
-        """G(i omega_n) as complex ``bins`` of shape (n_bins, n_iw), see :meth:`set_G_tau_bins` and
-        :meth:`set_G_iw_data`: every bin is unfolded to the stacked real vector ``[Re G ; Im G]``, mean and covariance
+    def set_G_iw_bins(self, iomega, bins, beta=None, shrinkage=None):
+        """G(i omega_n) as complex ``bins`` of shape (n_bins, n_iw), see :meth:`set_G_tau_bins` (also for ``shrinkage``)
+        and :meth:`set_G_iw_data`: every bin is unfolded to the stacked real vector ``[Re G ; Im G]``, mean and covariance
         are those of the 2 n_iw stacked values."""
         iomega = np.asarray(iomega, dtype=float)
         bins = self._check_bins(iomega, bins, 'G(i omega_n) bins', per_point=2)
         if bins.ndim != 2:
             raise AssertionError('G(i omega_n) bins must be (n_bins, n_iw); their shape is {}'.format(bins.shape))
-        st = self._bins_eig(kernels.stack_complex(bins))                   # (every bin as [Re ; Im])
+        st = self._bins_eig(kernels.stack_complex(bins), shrinkage)        # (every bin as [Re ; Im])
         self._use_kernel(kernels.IOmegaKernel, iomega, beta=beta)
         self._adopt_bins(st)
 
-    def set_G_l_bins(self, bins, beta, l=None):
-        """Legendre coefficients as ``bins`` of shape (n_bins, n_l), see :meth:`set_G_tau_bins` and
+    def set_G_l_bins(self, bins, beta, l=None, shrinkage=None):
+        """Legendre coefficients as ``bins`` of shape (n_bins, n_l), see :meth:`set_G_tau_bins` (also for ``shrinkage``) and
         :meth:`set_G_l_data`: the job is the one of ``set_G_l_data(mean, beta, l)`` and ``set_cov(C)`` on a fresh
         object."""
         bins = np.asarray(bins)
@@ -366,7 +390,7 @@ class TauMaxEnt(object):
         bins = self._check_bins(l, bins, 'G_l bins')
         if np.iscomplexobj(bins):
             raise AssertionError('G_l bins must be real')
-        st = self._bins_eig(np.asarray(bins, dtype=float))
+        st = self._bins_eig(np.asarray(bins, dtype=float), shrinkage)
         self._use_kernel(kernels.LegendreKernel, l, beta=beta)
         self._adopt_bins(st)
 
