@@ -93,7 +93,8 @@ extern "C" {
 #define MXE_ERR_NODEVICE    -3   /* no usable gfx950 device                   */
 #define MXE_ERR_STATE       -4   /* call order (e.g. solve before elements)   */
 #define MXE_ERR_LIMIT       -5   /* n_s > 128 (fp32: > 64); mxe_eval_batch / mxe_audit: w and H of a problem
-                                     exceed the LDS (n_omega > ~7900); the alpha scans themselves take any
+                                     exceed the LDS next to the n_s x n_s matrix (n_omega > 7680 for n_s <= 64,
+                                     n_omega > 1408 for 64 < n_s <= 128); the alpha scans themselves take any
                                      n_omega (state in device memory where the LDS does not hold it) */
 #define MXE_ERR_NUMERIC     -6   /* whitening failed (non-positive error bar) / SVD sweeps exhausted or matrix not finite */
 #define MXE_ERR_NOMEM       -7   /* host allocation failed                     */
@@ -491,7 +492,9 @@ int  mxe_entropy(int device, int kind, int n_omega, int P, const double* H, cons
  * binary16 tiles): at the returned v the exact Newton correction delta of Bryan's system is computed and
  *   out_corr[p] = ||w * V delta||_2 / ||H||_2   -- to first order the relative L2 distance of the
  *                 returned H from the minimiser (the quantity mxe_opts.tol_h bounds by an estimate)
- *   out_gmax[p] = max_k |g_k| / (|c_k rho_k| + |alpha v_k|)  -- the gradient against its cancelling terms
+ *   out_gmax[p] = max_k |g_k| / (|eta c_k rho_k| + |alpha v_k|),  g = eta c rho + alpha v  -- the gradient
+ *                 against its cancelling terms, in the whitened basis of the problem's data set (the audit
+ *                 itself runs with eta = 1 on the alpha / eta the chains iterated on)
  * [n_chain][n_alpha]; either may be NULL. */
 int  mxe_audit(mxe_ctx* ctx, double* out_corr, double* out_gmax);
 
