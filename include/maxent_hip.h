@@ -67,6 +67,8 @@
  *                                                          |   model, model-averaged image, spread between models)
  *   (nothing: positivity of the matrix is not checked)     | mxe_hermitian_eig (eigenvalues of A(w) as a matrix,
  *                                                          |   its nearest positive semi-definite matrix)
+ *   (nothing: "FullMatrixMaxEnt" is announced, not shipped) | mxe_fullmatrix_solve (the matrix A(w) as one unknown,
+ *                                                          |   positive semi-definite by construction)
  *   the arrays of MaxEntResult (numpy allocations)         | mxe_host_alloc / mxe_host_free (optional:
  *     maxent_result.py:835-967                             |   page-locked destinations, one DMA per fetch)
  *
@@ -913,6 +915,43 @@ int  mxe_bins_check(int device, int n_sets, int n_bins, int n_data, const double
 int  mxe_hermitian_eig(int device, int n_mat, int m, int is_complex, const double* A, double floor,
                        double* out_lambda, double* out_vec, double* out_proj, double* out_neg, double* out_dist,
                        double* out_pair, double* out_asym, int32_t* out_info, float* out_ms);
+
+/* Whole-matrix continuation (no counterpart in the reference: its guide announces a FullMatrixMaxEnt, its FAQ says it is
+ * not implemented).  The unknown is the Hermitian matrix H_i = D_i exp(Gamma_i) at every frequency, Gamma_i = sum_p
+ * (V' u)_ip E_p with E_p an orthonormal basis of the Hermitian m x m matrices (P = m (m + 1) / 2 of them for real symmetric
+ * data, m^2 with is_complex: the diagonal units, (e_ab + e_ba) / sqrt 2 for a < b in row order, then i (e_ab - e_ba) /
+ * sqrt 2); x_p = Tr(E_p X) are the coordinates of a Hermitian X.  Minimised is Q = chi2 / 2 - alpha S with
+ * chi2 = sum_p | c o V'^T H_p - g^_p |^2 + c_perp and the matrix entropy S = sum_i Tr[H_i - D_i - H_i log(H_i / D_i)]:
+ * H is Hermitian and positive semi-definite at every frequency and alpha.  n_prob problems share V', c, D and the alpha
+ * mesh; one workgroup per problem walks the mesh in order, warm-started, by a damped Newton iteration on
+ * F = alpha u + c o (c o V'^T H_p - g^_p): a step is taken only if Q does not rise (a Q that is not finite counts as a
+ * rise), a step that makes Q rise is halved up to three times before the damping grows, the damping grows and shrinks
+ * geometrically, an alpha ends converged when a full undamped step was taken whose first-order change of H,
+ * || L V' delta ||_F / || H ||_F, is below tol_h, and unconverged after maxiter trial points.
+ *   V           n_omega x n_s row-major, the (whitened) right singular basis;  c  n_s, > 0: S / sigma
+ *   D           n_omega, > 0: the default model (times delta omega), the same for every diagonal element
+ *   alpha       n_alpha, > 0, already scaled by the number of data of ONE matrix element
+ *   ghat        n_prob x P x n_s: U^T G_p / sigma of the coordinates G_p of the data;  cperp  n_prob: chi2 outside U
+ *   u0          n_prob x P x n_s: the start of the first alpha (NULL: zeros, H = D 1)
+ *   out_u       n_prob x n_alpha x P x n_s
+ *   out_H       n_prob x n_alpha x (is_complex ? 2 : 1) x m x m x n_omega: the real part and (is_complex) the imaginary part
+ *               of every matrix element; the upper triangle is computed, the lower is its conjugate: exactly Hermitian
+ *   out_chi2, out_S, out_Q   n_prob x n_alpha: one cost for the whole matrix
+ *   out_niter   n_prob x n_alpha: the trial points evaluated;  out_conv  n_prob x n_alpha: 1 converged, 0 not
+ *   out_ms      device time of the kernel (may be NULL)
+ * No atomics, fixed summation order: the bits of a problem do not depend on the other problems of the call.
+ * MXE_ERR_ARG (nothing is launched, nothing is written): a size < 1, maxiter < 0, tol_h <= 0, a NULL among the arrays
+ * other than u0 and out_ms, a NaN or an Inf in an input, a c, D or alpha that is not positive, sizes whose products exceed
+ * 2^31 - 1.  MXE_ERR_LIMIT (likewise): m > MXE_FULLMATRIX_MAX_M or n_s > MXE_FULLMATRIX_MAX_NS (the Newton matrix has order
+ * P n_s <= 1024: its panel of 16 columns fills 139 KB of the 160 KB of LDS); cut the singular space.
+ * MXE_ERR_NODEVICE: no device. */
+#define MXE_FULLMATRIX_MAX_M   4
+#define MXE_FULLMATRIX_MAX_NS  64
+int  mxe_fullmatrix_solve(int device, int n_prob, int m, int is_complex, int n_omega, int n_s, int n_alpha,
+                          const double* V, const double* c, const double* D, const double* alpha,
+                          const double* ghat, const double* cperp, const double* u0, int maxiter, double tol_h,
+                          double* out_u, double* out_H, double* out_chi2, double* out_S, double* out_Q,
+                          int32_t* out_niter, int32_t* out_conv, float* out_ms);
 
 #ifdef __cplusplus
 }

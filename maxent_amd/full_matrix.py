@@ -1,0 +1,312 @@
+"""Whole-matrix continuation: ``FullMatrixMaxEnt`` (no counterpart in the reference).
+
+``ElementwiseMaxEnt`` and ``PoormanMaxEnt`` continue a matrix-valued G one element at a time; the matrix A(omega) they give
+is Hermitian but, as a rule, not positive semi-definite (``positivity()`` measures by how much).  The reference's guide names
+the way out -- "treating the spectral function matrix as a whole", a ``FullMatrixMaxEnt`` it announces and never shipped.
+This is it: the unknown is the matrix H_i = D_i exp(Gamma_i) at every frequency, the entropy is the matrix entropy
+S = sum_i Tr[H_i - D_i - H_i log(H_i / D_i)] (Kraberger et al., PRB 96, 155128), chi2 is the Frobenius misfit over all
+matrix elements, and the solution is Hermitian and positive semi-definite at every omega and alpha because it is a matrix
+exponential.  DESIGN 4z has the equations; ``mxe_fullmatrix_solve`` (maxent_amd/csrc/mxe_fullmatrix.hip.h) solves them,
+one workgroup per problem; there is no CPU path (``tests/fullmatrix_ref.py`` is a numpy truth for the tests).
+
+First version, everything else is refused with NotImplementedError or ValueError: G(tau) or Legendre data (a real kernel
+acting on a Hermitian A); one error -- a scalar or one value per tau -- shared by all matrix elements; the default model
+D(omega) times the unit matrix; M <= 4 and n_s <= 64.  Not supported: Matsubara and bosonic data, ``set_cov``, per-element
+errors, bins, preblur, a matrix-valued default model, the probability-based analyzers (Bryan, Classic) and ``probability=``.
+
+alpha is scaled by n_tau, the number of data of ONE matrix element (``scale_alpha='Ndata'``): block-diagonal data then
+decouple into exactly the ``DiagonalMaxEnt`` problems at the same mesh alpha.
+"""
+
+from datetime import datetime
+
+import numpy as np
+
+from . import device as _dev
+from . import kernels
+from .analyzers import BryanAnalyzer, ClassicAnalyzer
+from .maxent_result import MaxEntResult
+from .tau_maxent import TauMaxEnt
+
+MAX_M = _dev.FULLMATRIX_MAX_M
+MAX_NS = _dev.FULLMATRIX_MAX_NS
+RESULT_KEYS = ('u', 'H', 'chi2', 'S', 'Q', 'n_iter', 'converged', 'alpha', 'ms')
+
+
+def hermitian_basis(M, use_complex):
+    """the orthonormal basis E_p (P, M, M) of the Hermitian M x M matrices in the order of the device: the diagonal units,
+    (e_ab + e_ba) / sqrt 2 for a < b in row order, then (``use_complex``) i (e_ab - e_ba) / sqrt 2; Tr E_p E_q = delta_pq"""
+    E = np.zeros((_dev.fullmatrix_P(M, use_complex), M, M), dtype=complex)
+    r = 1.0 / np.sqrt(2.0)
+    pairs = [(a, b) for a in range(M) for b in range(a + 1, M)]
+    for a in range(M):
+        E[a, a, a] = 1.0
+    for k, (a, b) in enumerate(pairs):
+        E[M + k, a, b] = E[M + k, b, a] = r
+        if use_complex:
+            E[M + len(pairs) + k, a, b] = 1.0j * r
+            E[M + len(pairs) + k, b, a] = -1.0j * r
+    return E
+
+
+def _check_G(G, use_complex, what):
+    G = np.asarray(G)
+    if G.ndim != 3 or G.shape[0] != G.shape[1] or G.dtype.kind not in 'biufc':
+        raise ValueError('%s: G must be numeric of shape (M, M, n); got %s' % (what, G.shape,))
+    if G.shape[0] > MAX_M:
+        raise ValueError('%s: a %d x %d matrix; at most %d x %d is supported' % (what, G.shape[0], G.shape[0], MAX_M, MAX_M))
+    if not np.all(np.isfinite(G)):
+        raise ValueError('%s: G is not finite' % what)
+    if np.iscomplexobj(G) and not use_complex:
+        if np.any(G.imag != 0.0):
+            raise ValueError('%s: G is complex; construct FullMatrixMaxEnt(use_complex=True)' % what)
+        G = G.real
+    return np.array(G, dtype=complex if use_complex else float)
+
+
+def _check_hermitian(G, err, what):
+    """G_ij = conj(G_ji) within the error: |G_ij - conj(G_ji)| <= 4 sqrt(2) err at every point"""
+    asym = np.abs(G - np.conj(np.swapaxes(G, 0, 1)))
+    bound = 4.0 * np.sqrt(2.0) * np.asarray(err, dtype=float) * np.ones(G.shape[-1])
+    if np.any(asym > bound):
+        i, j, k = (int(x) for x in np.argwhere(asym > bound)[0])
+        raise ValueError('%s: G is not Hermitian within its error: |G[%d, %d] - conj(G[%d, %d])| = %.3g at point %d (error %.3g)'
+                         % (what, i, j, j, i, asym[i, j, k], k, bound[k] / (4.0 * np.sqrt(2.0))))
+
+
+def whiten(U, S, V, err):
+    """(U^, c, V', Q) of the whitened problem diag(1 / err) U S = U^ diag(c) Q^T, V' = V Q; for one error for all
+    points nothing is rotated: U^ = U, c = S / err, Q = None"""
+    err = np.asarray(err, dtype=float)
+    if err.ndim == 0 or np.all(err == err.flat[0]):
+        return U, S / float(err.flat[0]), V, None
+    Uh, c, Qt = np.linalg.svd((U * S) / err[:, None], full_matrices=False)
+    return Uh, c, np.dot(V, Qt.T), Qt.T
+
+
+def full_matrix_continue(G_batch, U, S, V, D, alpha, err, use_complex=False, maxiter=1000, tol_h=1e-9, u0=None, device=0):
+    """The batch behind :class:`FullMatrixMaxEnt`: every G of ``G_batch`` (n_prob, M, M, n_data) -- k-points, mock data sets,
+    iterations of a self-consistency loop -- is continued as a whole matrix, one workgroup per problem in one launch of
+    ``mxe_fullmatrix_solve``.  They share the truncated SVD ``U`` (n_data, n_s), ``S``, ``V`` (n_omega, n_s) of the kernel
+    that maps H = A delta_omega to the data, the default model ``D`` (n_omega,; times delta omega), the mesh ``alpha``
+    (already scaled by the number of data of one element) and ``err`` (a scalar or one value per data point).  ``u0``: the
+    start of the first alpha, (n_prob, P, n_s) in the basis of ``V``.  A problem's bits do not depend on the batch.
+
+    Returns a dict: ``u`` (n_prob, n_alpha, P, n_s), the coordinates of Gamma = log(H / D) in the basis of ``V`` and of
+    :func:`hermitian_basis`; ``H`` (n_prob, M, M, n_alpha, n_omega), complex with ``use_complex``, exactly Hermitian and
+    positive semi-definite; ``chi2``, ``S``, ``Q`` (n_prob, n_alpha), one cost per matrix; ``n_iter``, ``converged``;
+    ``alpha``; ``ms``, the device time of the kernel."""
+    G = np.asarray(G_batch)
+    if G.ndim != 4:
+        raise ValueError('full_matrix_continue: G_batch must be (n_prob, M, M, n_data); got %s' % (G.shape,))
+    G = np.stack([_check_G(g, use_complex, 'full_matrix_continue') for g in G])
+    U, S, V, D = (np.asarray(x, dtype=float) for x in (U, S, V, D))
+    M, n = G.shape[1], G.shape[-1]
+    if U.ndim != 2 or U.shape[0] != n or S.shape != (U.shape[1],) or V.ndim != 2 or V.shape[1] != U.shape[1]:
+        raise ValueError('full_matrix_continue: U must be (n_data, n_s), S (n_s,), V (n_omega, n_s); got %s, %s, %s for %d data'
+                         % (U.shape, S.shape, V.shape, n))
+    if len(S) > MAX_NS:
+        raise ValueError('full_matrix_continue: %d singular values; at most %d are supported (the Newton matrix has order '
+                         'n_s x %d): cut the singular space with reduce_singular_space' % (len(S), MAX_NS, _dev.fullmatrix_P(M, use_complex)))
+    if D.shape != (V.shape[0],):
+        raise NotImplementedError('full_matrix_continue: the default model must be one D(omega) of shape (%d,), shared by the '
+                                  'diagonal elements; a matrix-valued model is not supported; got %s' % (V.shape[0], D.shape))
+    err = np.asarray(err, dtype=float)
+    if err.ndim > 1 or (err.ndim == 1 and err.shape != (n,)):
+        raise ValueError('full_matrix_continue: one error for all data or one per data point, shared by all matrix elements; '
+                         'per-element errors are not supported; got shape %s' % (err.shape,))
+    if not (np.all(np.isfinite(err)) and np.all(err > 0)):
+        raise ValueError('full_matrix_continue: the error must be positive and finite')
+    for g in G:
+        _check_hermitian(g, err, 'full_matrix_continue')
+    G = 0.5 * (G + np.conj(np.swapaxes(G, 1, 2)))
+    E = hermitian_basis(M, use_complex)
+    Gp = np.einsum('pba,nabt->npt', E, G).real                  # (n_prob, P, n_data): Tr(E_p G)
+    Uh, c, Vw, Q = whiten(U, S, V, err)
+    Gw = Gp / err
+    ghat = np.dot(Gw, Uh)                                       # (n_prob, P, n_s)
+    cperp = np.maximum(np.sum(Gw ** 2, axis=(1, 2)) - np.sum(ghat ** 2, axis=(1, 2)), 0.0)
+    if u0 is not None and Q is not None:
+        u0 = np.dot(np.asarray(u0, dtype=float), Q)             # u' = Q^T u
+    t = {}
+    out = _dev.fullmatrix_solve(Vw, c, D, alpha, ghat, cperp, M, use_complex, u0=u0, maxiter=maxiter, tol_h=tol_h,
+                                device=device, timing=t)
+    if Q is not None:
+        out['u'] = np.dot(out['u'], Q.T)
+    out['alpha'] = np.array(alpha, dtype=float)
+    out['ms'] = t.get('ms', 0.0)
+    return out
+
+
+class FullMatrixResult(MaxEntResult):
+    """the :class:`MaxEntResult` of a whole-matrix job: ``A`` and ``H`` are (M, M, n_alpha, n_omega), ``chi2``, ``S``, ``Q``
+    (n_alpha,) belong to the matrix, ``v`` holds u (n_alpha, P, n_s); an analyzer picks one alpha for the whole matrix and
+    its ``A_out`` is (M, M, n_omega)"""
+
+    def element_row(self, name, matrix_element, idx):
+        arr = np.asarray(self.element_array(name, matrix_element))
+        if name in ('A', 'H'):
+            return arr[:, :, int(idx)]
+        return arr[idx]
+
+
+_REFUSED = dict(set_G_iw_data='Matsubara data', set_G_iw='Matsubara data', set_chi_tau_data='bosonic data',
+                set_chi_iw_data='bosonic data', set_cov='a covariance matrix', set_cov_file='a covariance matrix',
+                set_G_tau_bins='Monte Carlo bins', set_G_iw_bins='Monte Carlo bins', set_G_l_bins='Monte Carlo bins',
+                set_G_tau='TRIQS Green functions (use set_G_tau_data)', set_G_tau_file='a file of one element (use set_G_tau_data)')
+
+
+class FullMatrixMaxEnt(object):
+    """Continue a matrix-valued G(tau) as ONE unknown, the Hermitian positive semi-definite matrix A(omega).  See the
+    module's docstring for what the first version takes.  ``omega``, ``alpha_mesh``, ``D``, ``reduce_singular_space``,
+    ``minimizer`` (its ``maxiter`` bounds the trial points per alpha), ``analyzers``, ``scale_alpha`` and the other
+    attributes of :class:`TauMaxEnt` are forwarded to ``self.maxent``, as ``ElementwiseMaxEnt`` forwards to its workers.
+    ``use_complex``: the matrix is complex Hermitian (P = M^2 unknown functions) instead of real symmetric
+    (P = M (M + 1) / 2).  ``tol_h``: the stopping tolerance, the first-order relative change of H of an undamped step."""
+
+    maxent = None
+
+    def __init__(self, use_complex=False, tol_h=1e-9, **kwargs):
+        if kwargs.get('probability') is not None:
+            raise NotImplementedError('FullMatrixMaxEnt: probability= needs the log-determinant of the whole-matrix problem, '
+                                      'which is not implemented')
+        if isinstance(kwargs.get('cost_function'), str) and kwargs['cost_function'].lower() != 'normal':
+            raise NotImplementedError('FullMatrixMaxEnt: the cost function is the matrix entropy; cost_function=%r is not '
+                                      'supported' % (kwargs['cost_function'],))
+        object.__setattr__(self, 'maxent', TauMaxEnt(**kwargs))
+        object.__setattr__(self, 'use_complex', bool(use_complex))
+        object.__setattr__(self, 'tol_h', float(tol_h))
+        object.__setattr__(self, 'G_mat', None)
+        object.__setattr__(self, 'maxent_result', None)
+        object.__setattr__(self, 'last_info', None)
+
+    def __getattr__(self, name):
+        if name in _REFUSED:
+            def refuse(*args, **kwargs):
+                raise NotImplementedError('FullMatrixMaxEnt: %s not supported yet (G(tau) and Legendre data with one '
+                                          'error for all matrix elements are)' % ('%s: %s is' % (name, _REFUSED[name])))
+            return refuse
+        return getattr(object.__getattribute__(self, 'maxent'), name)
+
+    def __setattr__(self, name, value):
+        if name in self.__dict__ or not hasattr(self.maxent, name):
+            object.__setattr__(self, name, value)
+        else:
+            setattr(self.maxent, name, value)
+
+    # ---- data ---------------------------------------------------------------------------------------------------------
+    def _adopt(self, G):
+        object.__setattr__(self, 'G_mat', G)
+        self.maxent.G = np.array(G[0, 0].real, dtype=float)       # (the worker's own data: what scale_alpha counts)
+        self.maxent._adopt_data()
+
+    def set_G_tau_data(self, tau, G):
+        """G(tau) of shape (M, M, n_tau), M <= 4, Hermitian at every tau within the error (checked in ``run()``, when the
+        error is known); complex data need ``use_complex=True``"""
+        G = _check_G(G, self.use_complex, 'set_G_tau_data')
+        tau = np.asarray(tau, dtype=float)
+        if tau.ndim != 1 or len(tau) != G.shape[-1]:
+            raise ValueError("set_G_tau_data: tau and G don't have the same dimension")
+        self.maxent._use_kernel(kernels.TauKernel, tau)
+        self._adopt(G)
+
+    def set_G_l_data(self, G_l, beta, l=None):
+        """Legendre coefficients of shape (M, M, n_l) (:meth:`TauMaxEnt.set_G_l_data` for the normalisation and ``l``)"""
+        G = _check_G(G_l, self.use_complex, 'set_G_l_data')
+        self.maxent._use_kernel(kernels.LegendreKernel, self.maxent._legendre_orders(l, G.shape[-1]), beta=beta)
+        self._adopt(G)
+
+    def set_error(self, error):
+        """one standard deviation for all data or one per data point, shared by all matrix elements"""
+        if np.ndim(error) > 1:
+            raise ValueError('FullMatrixMaxEnt.set_error: one error for all matrix elements (a scalar or one value per data '
+                             'point); per-element errors are not supported; got shape %s' % (np.shape(error),))
+        if self.G_mat is None:
+            raise ValueError('FullMatrixMaxEnt.set_error: set the data first')
+        self.maxent.set_error(error)
+
+    # ---- the job --------------------------------------------------------------------------------------------------------
+    def _job(self):
+        """the arrays of the present job, after every refusal"""
+        w = self.maxent
+        loop = w.maxent_loop
+        if self.G_mat is None:
+            raise ValueError('FullMatrixMaxEnt: no data; use set_G_tau_data or set_G_l_data')
+        if loop.err is None:
+            raise ValueError('FullMatrixMaxEnt: no error; use set_error')
+        if loop.probability is not None or any(isinstance(a, (BryanAnalyzer, ClassicAnalyzer)) for a in loop.analyzers):
+            raise NotImplementedError('FullMatrixMaxEnt: the probability-based analyzers (BryanAnalyzer, ClassicAnalyzer) and '
+                                      'probability= need the log-determinant of the whole-matrix problem, which is not '
+                                      'implemented; use LineFitAnalyzer, Chi2CurvatureAnalyzer or EntropyAnalyzer')
+        K = w.K
+        if hasattr(K, 'kernel') or type(loop.A_of_H).__name__ != 'IdentityA_of_H':
+            raise NotImplementedError('FullMatrixMaxEnt: preblur is not supported')
+        if getattr(K, 'setter_kind', 'tau') not in ('tau', 'legendre') or getattr(K, 'stacked', False):
+            raise NotImplementedError('FullMatrixMaxEnt: only G(tau) and Legendre data are supported')
+        if K.rotation is not None:
+            raise NotImplementedError('FullMatrixMaxEnt: a covariance matrix (a rotated data space) is not supported')
+        D = np.asarray(loop.D.D, dtype=float)
+        if D.ndim != 1:
+            raise NotImplementedError('FullMatrixMaxEnt: the default model must be one D(omega), shared by the diagonal '
+                                      'elements; a matrix-valued model is not supported')
+        K.reduce_singular_space(loop.reduce_singular_space)
+        if len(K.S) > MAX_NS:
+            raise ValueError('FullMatrixMaxEnt: %d singular values pass reduce_singular_space = %g; at most %d are supported '
+                             '(the Newton matrix has order n_s x %d): raise reduce_singular_space'
+                             % (len(K.S), loop.reduce_singular_space, MAX_NS, _dev.fullmatrix_P(self.G_mat.shape[0], self.use_complex)))
+        scale = loop._alpha_scale()
+        return dict(U=np.asarray(K.U, dtype=float), S=np.asarray(K.S, dtype=float), V=np.asarray(K.V, dtype=float), D=D,
+                    alpha=np.asarray(loop.alpha_mesh, dtype=float) * scale, err=np.asarray(loop.err, dtype=float),
+                    maxiter=int(getattr(loop.minimizer, 'maxiter', 1000)))
+
+    def run(self):
+        """Continue the matrix; returns a :class:`MaxEntResult` (:class:`FullMatrixResult`): ``A`` and ``H`` (M, M, n_alpha,
+        n_omega), complex with ``use_complex``; ``chi2``, ``S``, ``Q``, ``n_iter``, ``converged`` (n_alpha,), one cost for the
+        whole matrix; ``v`` = u (n_alpha, P, n_s); the analyzers pick one alpha for the matrix, ``A_out`` is (M, M, n_omega)."""
+        job = self._job()
+        w = self.maxent
+        loop = w.maxent_loop
+        t0 = datetime.now()
+        sol = full_matrix_continue(self.G_mat[None], job['U'], job['S'], job['V'], job['D'], job['alpha'], job['err'],
+                                   use_complex=self.use_complex, maxiter=job['maxiter'], tol_h=self.tol_h,
+                                   device=loop.device_id)
+        t1 = datetime.now()
+        H = sol['H'][0]
+        delta = np.asarray(w.omega.delta, dtype=float)
+        A = H / delta
+        X = len(job['alpha'])
+        M = H.shape[0]
+        G_rec = np.einsum('ti,abxi->abxt', np.asarray(w.K.K_delta, dtype=float), A)
+        res = FullMatrixResult(matrix_structure=(M, M), element_wise=False, complex_elements=self.use_complex)
+        rec = dict(alpha=job['alpha'], v=sol['u'][0], H=H, A=A, chi2=sol['chi2'][0], S=sol['S'][0], Q=sol['Q'][0],
+                   G=np.array(self.G_mat), G_orig=np.array(self.G_mat), G_rec=G_rec,
+                   data_variable=np.array(w.K.data_variable, dtype=float), omega=w.omega,
+                   probability=np.full(X, np.nan), n_iter=sol['n_iter'][0], converged=sol['converged'][0],
+                   run_times=((t1 - t0) / max(1, X),) * X)
+        res.start_timing(time=t0)
+        res.add_element_results(rec)
+        res.end_timing(time=t1)
+        if loop.analyzers:
+            res._default_analyzer_name = loop.analyzers[0].name
+        res.analyze(loop.analyzers)
+        object.__setattr__(self, 'maxent_result', res)
+        object.__setattr__(self, 'last_info', dict(kernel_ms=sol['ms'], n_iter=sol['n_iter'][0], converged=sol['converged'][0]))
+        return res
+
+    def positivity(self, result=None, alpha=None, floor=0.0, keep_vectors=False):
+        """:func:`maxent_amd.positivity.matrix_positivity` of the result (default: ``run()``): ``alpha`` None -- ``A_out`` of
+        the default analyzer --, an analyzer name, an index into the alpha mesh, or ``'all'``.  The dict also holds ``alpha``,
+        what was taken."""
+        from .positivity import matrix_positivity
+        res = self.run() if result is None else result
+        if isinstance(alpha, str) and alpha == 'all':
+            A, which = np.asarray(res.A), 'all'
+        elif alpha is None or isinstance(alpha, str):
+            A = np.asarray(res.get_A_out(alpha))
+            which = res.default_analyzer_name if alpha is None else alpha
+        else:
+            A, which = np.asarray(res.A)[:, :, int(alpha)], int(alpha)
+        out = matrix_positivity(A, delta=np.asarray(self.maxent.omega.delta, dtype=float), floor=floor,
+                                keep_vectors=keep_vectors, device=self.maxent.maxent_loop.device_id)
+        out['alpha'] = which
+        return out
