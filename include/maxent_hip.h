@@ -280,7 +280,14 @@ int  mxe_solve_chains(mxe_ctx* ctx, int n_chain, int n_alpha,
  * whitened basis with row stride mxe_ns_padded() (use mxe_chains_fetch for
  * caller-basis v).  H, chi2, S, Q are contiguous in that order in ONE
  * allocation of P*n_omega + 3*P doubles starting at d_H, so that one
- * collective moves all per-alpha results. */
+ * collective moves all per-alpha results.
+ * A lock-step launch (chain_kernel_mc) whose pieces come off a queue puts NO reset of the queue counter in front of the
+ * kernel: the counter is a pair of words, launch k of a context draws from word k & 1, and its first thread stores the
+ * start value of launch k + 1 into the other word, which launch k - 1 has finished with (the launches of a context are
+ * ordered by its stream).  mxe_chains_upload sets both words and starts at word 0; a launch that could not be enqueued
+ * does not advance the turn.  The two passes of a launch that starts in chain_kernel_lv keep two words of their own and
+ * their reset.  mxe_chains_upload also tabulates log and log10 of the staged alphas on the device for mxe_select_launch /
+ * mxe_select3_launch (it is the only writer of the staged alphas, so the table cannot go stale). */
 int  mxe_chains_upload(mxe_ctx* ctx, int n_chain, int n_alpha,
                        const int32_t* elem_of_chain, const double* alpha_scaled,
                        const double* v0, const mxe_opts* opts);

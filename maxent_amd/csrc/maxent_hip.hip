@@ -298,8 +298,11 @@ struct mxe_ctx {
     struct View { double* p = nullptr; } dout_H, dout_chi2, dout_S, dout_Q;
     DevBuf<int> dout_niter, dout_nact;       // dout_niter: niter [P] | converged [P] | nevals [P] in ONE block (mxe_chains_fetch: one copy)
     struct IView { int* p = nullptr; } dout_conv, dout_nevals;
-    DevBuf<long long> dprof;
-    DevBuf<int> dqueue, dcounter;
+    DevBuf<long long> dprof, dprof_lf;      // (diagnostic build: stamps of the chain kernels / of linefit_kernel)
+    DevBuf<int> dqueue, dcounter;           // dcounter: the pair of words of MCExtra::counter | two words of chain_kernel_lv's two passes
+    int counter_par = 0;                // word of the pair the next lock-step launch draws from
+    int counter_armed = -1;             // start value both words were set to / the launches re-arm to (-1: not armed)
+    DevBuf<double> dalpha_log;          // [2][P]: log | log10 of dalpha, by alpha_log_kernel behind every write of dalpha (linefit_kernel)
     DevBuf<int> dsub_pre, dsub_init, dsub_walk0;
     DevBuf<double> dwalk_alpha;
     DevBuf<double> dinit_tab;           // start states per class of pieces (KParams::init_tab)
@@ -636,7 +639,7 @@ void mxe_ctx_destroy(mxe_ctx* ctx)
     ctx->dlogdet.release(); ctx->dparent_elem.release(); ctx->dV.release(); ctx->dVt.release(); ctx->dVf.release(); ctx->dVtf.release(); ctx->dc.release(); ctx->dcinv.release();
     ctx->dghat.release(); ctx->dcperp.release(); ctx->dD.release(); ctx->dsumD.release();
     ctx->dalpha.release(); ctx->dv0.release(); ctx->delem_ds.release(); ctx->delem_kind.release();
-    ctx->dchain_elem.release(); ctx->dsub_prob0.release(); ctx->dsub_len.release(); ctx->dsub_v0.release(); ctx->dwg_chains.release(); ctx->dqueue.release(); ctx->dcounter.release(); ctx->dsub_pre.release(); ctx->dsub_init.release(); ctx->dsub_walk0.release(); ctx->dwalk_alpha.release(); ctx->dinit_tab.release(); ctx->dout_v.release(); ctx->dout_pack.release(); ctx->dout_pack2.release();
+    ctx->dchain_elem.release(); ctx->dsub_prob0.release(); ctx->dsub_len.release(); ctx->dsub_v0.release(); ctx->dwg_chains.release(); ctx->dqueue.release(); ctx->dcounter.release(); ctx->dalpha_log.release(); ctx->dprof_lf.release(); ctx->dsub_pre.release(); ctx->dsub_init.release(); ctx->dsub_walk0.release(); ctx->dwalk_alpha.release(); ctx->dinit_tab.release(); ctx->dout_v.release(); ctx->dout_pack.release(); ctx->dout_pack2.release();
     ctx->dout_niter.release(); ctx->dout_conv.p = ctx->dout_nevals.p = nullptr; ctx->dout_nact.release(); ctx->dexcluded.release();
     ctx->dB.release(); ctx->dA.release(); ctx->dprof.release();
     ctx->rows_out.release(); ctx->rows_idx.release();
@@ -1140,7 +1143,14 @@ try {
         if (const hipError_t e = buf.ensure(vec.size()); e != hipSuccess || vec.empty()) return e;
         return hipMemcpyAsync(buf.p, vec.data(), vec.size() * sizeof(vec[0]), hipMemcpyHostToDevice, ctx->stream);
     };
-    HIPCHK(ctx, ctx->dcounter.ensure(2)); HIPCHK(ctx, put(ctx->dqueue, ctx->queue)); HIPCHK(ctx, put(ctx->dwg_chains, ctx->wg_chains));
+    HIPCHK(ctx, ctx->dcounter.ensure(4)); HIPCHK(ctx, put(ctx->dqueue, ctx->queue));
+    // both words of the counter pair start at what a launch of this plan draws from (mxe_chains_launch: counter0); from then on
+    // every launch re-arms the word of the next one
+    const int counter0 = (ctx->n_queue > 0 && ctx->mc_wgpc == 2 && n_solo > 0) ? (ctx->n_wg - n_solo) * 4 : 0;
+    const std::vector<int> counter_words = {counter0, counter0, 0, 0};
+    ctx->counter_armed = -1; ctx->counter_par = 0;
+    HIPCHK(ctx, put(ctx->dcounter, counter_words));
+ HIPCHK(ctx, put(ctx->dwg_chains, ctx->wg_chains));
     HIPCHK(ctx, put(ctx->dchain_elem, ctx->sub_elem)); HIPCHK(ctx, put(ctx->dsub_prob0, ctx->sub_prob0));
     HIPCHK(ctx, put(ctx->dsub_len, ctx->sub_len)); HIPCHK(ctx, put(ctx->dsub_v0, ctx->sub_v0));
     HIPCHK(ctx, ctx->dsub_pre.ensure(n_sub));
@@ -1148,6 +1158,10 @@ try {
     if (ctx->has_walk && ctx->has_pre) { HIPCHK(ctx, put(ctx->dsub_walk0, ctx->sub_walk0)); HIPCHK(ctx, put(ctx->dwalk_alpha, ctx->walk_alpha)); }
     if (!ctx->excluded.empty()) HIPCHK(ctx, put(ctx->dexcluded, ctx->excluded));
     HIPCHK(ctx, put(ctx->dalpha, alpha_dev)); HIPCHK(ctx, put(ctx->dv0, hv0)); HIPCHK(ctx, ctx->dout_v.ensure(P * NP));
+    // the logarithms of the mesh for linefit_kernel: this is the only writer of dalpha, so the table cannot go stale
+    HIPCHK(ctx, ctx->dalpha_log.ensure(2 * P));
+    hipLaunchKernelGGL(mxe::alpha_log_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, ctx->stream, ctx->dalpha.p, ctx->dalpha_log.p, P);
+    HIPCHK(ctx, hipGetLastError());
     // one allocation: H [P][nw] | chi2 S Q [3P] | H of the analyzer's alpha [n_chain][nw] | its index [n_chain]
     // (everything behind H is the COMPACT result pack that a gather between GPUs moves)
     HIPCHK(ctx, ctx->dout_pack.ensure(P * nw + 3 * P + (size_t)n_chain * (nw + 1)));
@@ -1165,6 +1179,7 @@ try {
         HIPCHK(ctx, ctx->dcnt1_niter.ensure(P)); HIPCHK(ctx, ctx->dcnt1_nevals.ensure(P));
     }
     HIPCHK(ctx, stream_wait(ctx->stream));          // (the host vectors go out of scope)
+    ctx->counter_armed = counter0;
     // ---- 8. the start states of the pieces
     { const int rc_init = build_init_table(ctx, n_chain, elem_of_chain, hv0); if (rc_init != MXE_OK) return rc_init; }
     ctx->chains_ready = true;
@@ -1301,8 +1316,10 @@ try {
             const size_t lds1 = mxe::lv_lds_bytes(ctx->n_s, ctx->nwp);
             mxe::MCExtra ex; ex.wg_chains = ctx->dwg_chains.p; ex.n_wg = ctx->n_wg;
             ex.gstate = nullptr; ex.gstate_stride = 0; ex.stagger = 0; ex.n_solo = 0;
-            ex.queue = ctx->dqueue.p; ex.n_queue = ctx->n_queue; ex.counter = ctx->dcounter.p;
-            HIPCHK(ctx, hipMemsetAsync(ctx->dcounter.p, 0, 2 * sizeof(int), ctx->stream));
+            ex.queue = ctx->dqueue.p; ex.n_queue = ctx->n_queue; ex.counter = ctx->dcounter.p + 2;
+            // (words 2 and 3, one per pass, zeroed by a reset node as before: the pair of the lock-step launches is not touched.  The
+            //  second pass -- chain_kernel_mc drawing from word 3 -- stores its 0 into word 2, which the first pass has finished with.)
+            HIPCHK(ctx, hipMemsetAsync(ctx->dcounter.p + 2, 0, 2 * sizeof(int), ctx->stream));
             ctx->rounds_n[0] = ctx->n_wg; ctx->rounds_n[1] = (ctx->lv_mode == 2) ? ctx->n_wg2 : 0;
             HIPCHK(ctx, ctx->drounds.ensure((size_t)ctx->rounds_n[0] + ctx->rounds_n[1]));
             HIPCHK(ctx, hipMemsetAsync(ctx->drounds.p, 0, ((size_t)ctx->rounds_n[0] + ctx->rounds_n[1]) * sizeof(int), ctx->stream));
@@ -1336,7 +1353,7 @@ try {
                 k2.prof = nullptr;                  // (diagnostic build: the stamps of the first pass stay)
                 mxe::MCExtra e2 = ex;
                 e2.n_wg = ctx->n_wg2;
-                e2.queue = ctx->d2_queue.p; e2.n_queue = (int)Pn; e2.counter = ctx->dcounter.p + 1;
+                e2.queue = ctx->d2_queue.p; e2.n_queue = (int)Pn; e2.counter = ctx->dcounter.p + 3;
                 e2.wg_chains = ctx->drounds.p + ctx->rounds_n[0];
 #define MXE_LAUNCH_MC2(WG_, NWV_) do { \
                 e = hipFuncSetAttribute((const void*)mxe::chain_kernel_mc<32, WG_, false, NWV_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
@@ -1366,7 +1383,7 @@ try {
             HIPCHK(ctx, ctx->dgstate_mc.ensure((size_t)ctx->n_wg * ex.gstate_stride + 4096));
             ex.gstate = ctx->dgstate_mc.p;
         }
-        ex.queue = ctx->dqueue.p; ex.n_queue = ctx->n_queue; ex.counter = ctx->dcounter.p;
+        ex.queue = ctx->dqueue.p; ex.n_queue = ctx->n_queue; ex.counter = ctx->dcounter.p + ctx->counter_par;
         // rounds per workgroup (mxe_launch_depth): the builds for launches that do not fill the GPU write them, in the dynamic
         // layout (MCExtra: the pointer is the table of chain ids in the static one).  Not <32, 2> without led pieces -- the batch
         // that fills the GPU: the memset node alone is 1.5 us of its 812 (A/B: profiles/r04_experiments.txt)
@@ -1385,7 +1402,12 @@ try {
             ex.n_solo = ctx->n_solo;
             counter0 = (ctx->n_wg - ex.n_solo) * 4;
         }
-        HIPCHK(ctx, hipMemsetD32Async((hipDeviceptr_t)ctx->dcounter.p, counter0, 1, ctx->stream));
+        // No reset node: launch k draws from word k & 1 of the pair, which mxe_chains_upload (k = 0, 1) or launch k - 1 set to counter0.
+        // (Never taken: a launch whose start value is not the one the pair is armed with sets both words itself.)
+        if (ctx->counter_armed != counter0) {
+            HIPCHK(ctx, hipMemsetD32Async((hipDeviceptr_t)ctx->dcounter.p, counter0, 2, ctx->stream));
+            ctx->counter_armed = counter0;
+        }
         if (!ctx->excluded.empty()) {
             hipLaunchKernelGGL(clear_excluded_kernel, dim3((unsigned)ctx->excluded.size()), dim3(256), 0, ctx->stream,
                                ctx->dexcluded.p, ctx->n_alpha, ctx->n_omega, ctx->NP, ctx->dv0.p, ctx->dout_H.p, ctx->dout_chi2.p,
@@ -1411,6 +1433,7 @@ try {
         else { if (lead) MXE_LAUNCH_MC(32, 1, true, 4); else MXE_LAUNCH_MC(32, 1, false, 4); }
 #undef MXE_LAUNCH_MC
         HIPCHK(ctx, e);
+        ctx->counter_par ^= 1;       // (only behind a launch that was enqueued: a failed one re-armed nothing)
     } else {
         ctx->rounds_n[0] = ctx->rounds_n[1] = 0;
         int NW = std::min(o.waves_per_chain, 4);     // (eight waves per chain: two per SIMD at 256 registers each spilled; not built)
@@ -1909,6 +1932,15 @@ extern "C" int mxe_prof_fetch(mxe_ctx* ctx, long long* out /*[n_sub + 8192][8]*/
     HIPCHK(ctx, hipMemcpy(out, ctx->dprof.p, ((size_t)ctx->n_sub + 8 * 1024) * 64, hipMemcpyDeviceToHost));
     return MXE_OK;
 }
+// the stamps of the last mxe_select_launch / mxe_select3_launch
+extern "C" int mxe_prof_linefit_fetch(mxe_ctx* ctx, long long* out /*[n_chain][4][10]*/)
+{
+    if (!ctx || !out) return MXE_ERR_ARG;
+    if (!ctx->dprof_lf.p) return MXE_ERR_STATE;
+    HIPCHK(ctx, stream_wait(ctx->stream));
+    HIPCHK(ctx, hipMemcpy(out, ctx->dprof_lf.p, (size_t)ctx->n_chain * 40 * sizeof(long long), hipMemcpyDeviceToHost));
+    return MXE_OK;
+}
 #endif
 
 // ---- the kernels that factorise B = c W c + a I per problem (mxe_factor.hip.h): logdet, posterior variances, samples ----
@@ -2377,6 +2409,14 @@ try {
 MXE_CATCH_ALL
 
 // ---- the default analyzer's alpha on the device, and the compact result pack ----------------
+#ifdef MXE_PROFILE
+// (diagnostic build: linefit_kernel stamps its phases, [n_chain][4 waves][10] clock values; mxe_prof_linefit_fetch, tools/profile_linefit.py)
+#define MXE_LINEFIT_PROF_ENSURE(ctx) HIPCHK(ctx, (ctx)->dprof_lf.ensure((size_t)(ctx)->n_chain * 40))
+#define MXE_LINEFIT_PROF_ARG(ctx) , (ctx)->dprof_lf.p
+#else
+#define MXE_LINEFIT_PROF_ENSURE(ctx) do {} while (0)
+#define MXE_LINEFIT_PROF_ARG(ctx)
+#endif
 extern "C" int mxe_select_launch(mxe_ctx* ctx, int p2_deg)
 try {
     if (!ctx || (p2_deg != 0 && p2_deg != 1)) return MXE_ERR_ARG;
@@ -2385,8 +2425,10 @@ try {
     const size_t P = (size_t)ctx->n_chain * ctx->n_alpha;
     double* sel = ctx->dout_Q.p + P;
     double* idx = sel + (size_t)ctx->n_chain * ctx->n_omega;
+    MXE_LINEFIT_PROF_ENSURE(ctx);
     hipLaunchKernelGGL(mxe::linefit_kernel, dim3(ctx->n_chain), dim3(256), ((size_t)11 * ctx->n_alpha + 6 + 28) * sizeof(double), ctx->stream,
-                       ctx->dalpha.p, ctx->dout_chi2.p, ctx->dout_H.p, ctx->n_alpha, ctx->n_omega, p2_deg, sel, idx);
+                       ctx->dalpha_log.p, ctx->dout_chi2.p, ctx->dout_H.p, ctx->n_alpha, ctx->n_omega, p2_deg, sel, idx,
+                       nullptr, 0.2, nullptr, nullptr MXE_LINEFIT_PROF_ARG(ctx));
     HIPCHK(ctx, hipGetLastError());
     return MXE_OK;
 }
@@ -2405,9 +2447,10 @@ try {
     double* idx = sel + nc * nw;
     HIPCHK(ctx, ctx->dsel3.ensure(3 * nc * (nw + 1)));
     ctx->pre_rows = nullptr; ctx->pre_index = false;
+    MXE_LINEFIT_PROF_ENSURE(ctx);
     hipLaunchKernelGGL(mxe::linefit_kernel, dim3(ctx->n_chain), dim3(256), ((size_t)11 * ctx->n_alpha + 6 + 28) * sizeof(double), ctx->stream,
-                       ctx->dalpha.p, ctx->dout_chi2.p, ctx->dout_H.p, ctx->n_alpha, ctx->n_omega, p2_deg, sel, idx,
-                       ctx->dout_S.p, gamma, ctx->dsel3.p, ctx->dsel3.p + 3 * nc);
+                       ctx->dalpha_log.p, ctx->dout_chi2.p, ctx->dout_H.p, ctx->n_alpha, ctx->n_omega, p2_deg, sel, idx,
+                       ctx->dout_S.p, gamma, ctx->dsel3.p, ctx->dsel3.p + 3 * nc MXE_LINEFIT_PROF_ARG(ctx));
     HIPCHK(ctx, hipGetLastError());
     ctx->sel3_nc = ctx->n_chain;
     return MXE_OK;

@@ -353,72 +353,124 @@ void entropy_kernel(int kind, int n, const double* __restrict__ H, const double*
 // ---- the default analyzer on the device: LineFitAnalyzer's alpha (linefit_analyzer.py:28-87, 151-183) --
 // Two-piece fit of log chi2 (log alpha): a line through the first i points, a constant (p2_deg = 0) or a
 // line (p2_deg = 1) through the rest, i = 2 .. n-3 chosen for the smallest summed squared misfit; the answer
-// is the index of the alpha closest to the intersection.  NaN chi2 are left out.  One wavefront per scan:
-// lane t evaluates the break points t, t + 64, ... with the two-pass formulas of the host analyzer
-// (maxent_amd/analyzers.py: _linfit_sse), then the H of the chosen alpha is copied out, so that a caller
-// (or a gather between GPUs) moves one row per scan instead of all of them.
+// is the index of the alpha closest to the intersection.  NaN chi2 are left out.  The break points are evaluated
+// with the two-pass formulas of the host analyzer (maxent_amd/analyzers.py: _linfit_sse), then the H of the
+// chosen alpha is copied out, so that a caller (or a gather between GPUs) moves one row per scan instead of all
+// of them.
 namespace mxe {
+
+// log and log10 of the staged alphas, [2][P]: they change only when the chains are uploaded, so the line fit reads them
+// instead of forming four logarithms per alpha at every launch.  The same device functions as the fit used on the same
+// numbers: the same bits.
+__global__ __launch_bounds__(256)
+void alpha_log_kernel(const double* __restrict__ alpha, double* __restrict__ out, size_t P)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < P) { const double a = alpha[i]; out[i] = log(a); out[P + i] = log10(a); }
+}
 
 struct LineSSE { double slope, icpt, sse; int n; };
 
-// least-squares line (or constant) through the points lo .. hi-1 that are not NaN, by the whole wavefront:
-// lane t takes the points lo + t, lo + t + 64, ...; two-pass formulas (mean first, then centred sums)
-__device__ inline LineSSE line_sse(const double* x, const double* y, int lo, int hi, bool line)
+// least-squares lines through the points 0 .. i-1 (a) and i .. n-1 (b; a constant unless line_b) that are not NaN, by the whole
+// wavefront: lane t takes the points lo + t, lo + t + 64, ...; two-pass formulas (mean first, then centred sums).  Both fits of a
+// break point side by side, so that the wave reductions of the one fill the latency of the other; each fit's own arithmetic is that
+// of a fit made alone.  false: one side has no point (the break point does not count).
+__device__ inline bool line_sse_pair(const double* x, const double* y, int i, int n, bool line_b, LineSSE& a, LineSSE& b)
 {
     const int lane = threadIdx.x & 63;
-    LineSSE r; r.slope = 0.0; r.icpt = 0.0; r.sse = 0.0; r.n = 0;
-    double sx = 0.0, sy = 0.0, cnt = 0.0;
-    for (int k = lo + lane; k < hi; k += 64) if (y[k] == y[k]) { sx += x[k]; sy += y[k]; cnt += 1.0; }
-    sx = wave_sum(sx); sy = wave_sum(sy); cnt = wave_sum(cnt);
-    r.n = (int)cnt;
-    if (r.n < 1) return r;
-    const double xm = sx / cnt, ym = sy / cnt;
-    double sxx = 0.0, sxy = 0.0;
-    for (int k = lo + lane; k < hi; k += 64) if (y[k] == y[k]) { const double dx = x[k] - xm; sxx += dx * dx; sxy += dx * (y[k] - ym); }
-    sxx = wave_sum(sxx); sxy = wave_sum(sxy);
-    if (line && r.n >= 2 && sxx != 0.0) { r.slope = sxy / sxx; r.icpt = ym - r.slope * xm; }
-    else r.icpt = ym;
-    double e = 0.0;
-    for (int k = lo + lane; k < hi; k += 64) if (y[k] == y[k]) { const double d = y[k] - (r.slope * x[k] + r.icpt); e += d * d; }
-    r.sse = wave_sum(e);
-    return r;
+    a.slope = 0.0; a.icpt = 0.0; a.sse = 0.0; b.slope = 0.0; b.icpt = 0.0; b.sse = 0.0;
+    // (one loop for both sides: lane t takes the points t, t + 64, ... of a and i + t, i + t + 64, ... of b, in ascending order)
+    const int trips = max(i, n - i);
+    double sxa = 0.0, sya = 0.0, ca = 0.0, sxb = 0.0, syb = 0.0, cb = 0.0;
+    for (int j = lane; j < trips; j += 64) {
+        const bool ina = j < i, inb = i + j < n;
+        const int ka = ina ? j : 0, kb = inb ? i + j : 0;
+        const double xa = x[ka], ya = y[ka], xb = x[kb], yb = y[kb];
+        if (ina && ya == ya) { sxa += xa; sya += ya; ca += 1.0; }
+        if (inb && yb == yb) { sxb += xb; syb += yb; cb += 1.0; }
+    }
+    sxa = wave_sum(sxa); sya = wave_sum(sya); ca = wave_sum(ca);
+    sxb = wave_sum(sxb); syb = wave_sum(syb); cb = wave_sum(cb);
+    a.n = (int)ca; b.n = (int)cb;
+    if (a.n < 1 || b.n < 1) return false;
+    const double xma = sxa / ca, yma = sya / ca, xmb = sxb / cb, ymb = syb / cb;
+    double sxxa = 0.0, sxya = 0.0, sxxb = 0.0, sxyb = 0.0;
+    for (int j = lane; j < trips; j += 64) {
+        const bool ina = j < i, inb = i + j < n;
+        const int ka = ina ? j : 0, kb = inb ? i + j : 0;
+        const double xa = x[ka], ya = y[ka], xb = x[kb], yb = y[kb];
+        if (ina && ya == ya) { const double dx = xa - xma; sxxa += dx * dx; sxya += dx * (ya - yma); }
+        if (inb && yb == yb) { const double dx = xb - xmb; sxxb += dx * dx; sxyb += dx * (yb - ymb); }
+    }
+    sxxa = wave_sum(sxxa); sxya = wave_sum(sxya); sxxb = wave_sum(sxxb); sxyb = wave_sum(sxyb);
+    if (a.n >= 2 && sxxa != 0.0) { a.slope = sxya / sxxa; a.icpt = yma - a.slope * xma; }
+    else a.icpt = yma;
+    if (line_b && b.n >= 2 && sxxb != 0.0) { b.slope = sxyb / sxxb; b.icpt = ymb - b.slope * xmb; }
+    else b.icpt = ymb;
+    double ea = 0.0, eb = 0.0;
+    for (int j = lane; j < trips; j += 64) {
+        const bool ina = j < i, inb = i + j < n;
+        const int ka = ina ? j : 0, kb = inb ? i + j : 0;
+        const double xa = x[ka], ya = y[ka], xb = x[kb], yb = y[kb];
+        if (ina && ya == ya) { const double d = ya - (a.slope * xa + a.icpt); ea += d * d; }
+        if (inb && yb == yb) { const double d = yb - (b.slope * xb + b.icpt); eb += d * d; }
+    }
+    a.sse = wave_sum(ea); b.sse = wave_sum(eb);
+    return true;
 }
 
-// One workgroup of FOUR waves per scan (round 5; one wave until then: 19.4 us per launch of 256 scans, a serial chain of
-// running sums, candidate fits and row copies in one wave).  Every number that decides a pick is formed by the arithmetic of the
-// one-wave version in the same order -- the running sums per quantity, the exact misfits per candidate -- so the picks are the
-// same; what is spread over the waves is WHICH quantity / candidate / analyzer a wave takes, and the row copies.
+#ifdef MXE_PROFILE
+// (diagnostic build: lane 0 of every wave stamps the clock behind each phase, [n_chain][4 waves][10]: 0 entry, 1 logarithms + barrier,
+//  2 running sums + barrier, 3 ranking + barrier, 4 candidate fits and the other analyzers, 5 their barrier, 6 the pick, 7 rows copied
+//  -- shader clock --, 8 and 9 the constant 100 MHz clock at entry and exit; tools/profile_linefit.py)
+#define MXE_LF_STAMP(i) do { if ((threadIdx.x & 63) == 0) prof[((size_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 10 + (i)] = ((i) < 8) ? clock64() : wall_clock64(); } while (0)
+#define MXE_LF_PROF_PARAM , long long* __restrict__ prof
+#else
+#define MXE_LF_STAMP(i) do {} while (0)
+#define MXE_LF_PROF_PARAM
+#endif
+
+// One workgroup of FOUR waves per scan.  Every number that decides a pick is formed by the arithmetic of the one-wave version of
+// round 4 in the same order -- the running sums per quantity, the approximate misfits, the tolerance, the exact misfits per
+// candidate, the tie rules -- so the picks are the same; what is spread over the waves is WHICH quantity / candidate / analyzer a
+// wave takes, and the row copies.  What is left of the launch is one dependent pass:
+//   read chi2, ONE logarithm per alpha (those of alpha come from alpha_log_kernel's table; log10 chi2 only under out3_idx, by the
+//   wave that uses it, off the path of the others) | barrier | running sums, the two quantities of a wave side by side | barrier |
+//   ranking | barrier | candidates found with a ballot per 64 break points, both lines of a candidate side by side | barrier |
+//   every wave forms the pick for itself (no barrier in front of the rows) | rows.
 __global__ __launch_bounds__(256)
-void linefit_kernel(const double* __restrict__ alpha, const double* __restrict__ chi2, const double* __restrict__ H,
+void linefit_kernel(const double* __restrict__ alog /*[2][n_chain][n_alpha]: log alpha | log10 alpha (alpha_log_kernel)*/,
+                    const double* __restrict__ chi2, const double* __restrict__ H,
                     int n_alpha, int nw, int p2_deg, double* __restrict__ out_sel /*[n_chain][nw] or null*/,
                     double* __restrict__ out_idx /*[n_chain], as doubles (they travel in the result pack)*/,
                     // the two other default analyzers of the reference, when out3_idx is given (mxe_select3_launch):
-                    const double* __restrict__ S = nullptr, double gamma = 0.2,
-                    double* __restrict__ out3_idx = nullptr /*[3][n_chain]: line fit, chi2 curvature, entropy*/,
-                    double* __restrict__ out3_sel = nullptr /*[3][n_chain][nw]: the H rows of the three*/)
+                    const double* __restrict__ S, double gamma,
+                    double* __restrict__ out3_idx /*[3][n_chain]: line fit, chi2 curvature, entropy*/,
+                    double* __restrict__ out3_sel /*[3][n_chain][nw]: the H rows of the three*/ MXE_LF_PROF_PARAM)
 {
     // Break points are first ranked with running sums (O(n) for all of them; centred, like the host
     // analyzer's fit_piecewise), then only those within a whisker of the best are evaluated exactly with the
     // two-pass formulas -- the same two stages, with the same tolerance, as the host code.
     extern __shared__ double sm[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = n_alpha;
+    MXE_LF_STAMP(8); MXE_LF_STAMP(0);
     double* x = sm;                  // log alpha
     double* y = x + n;               // log chi2
     double* cs = y + n;              // [6][n + 1] running sums of w, w x0, yc, w x0^2, x0 yc, yc^2
     double* ap = cs + 6 * (n + 1);   // [n] approximate misfit of break point i
     double* x10 = ap + n;            // [n] gamma log10 alpha   (chi2 curvature)
-    double* y10 = x10 + n;           // [n] log10 chi2
+    double* y10 = x10 + n;           // [n] log10 chi2          (wave 1 alone writes and reads it)
     double* wbest = y10 + n;         // [4] smallest approximate misfit seen by a wave
     double* wfit = wbest + 4;        // [4][6] a wave's best exact candidate: misfit, index, the two lines
     __shared__ int s_pick[3];
-    const size_t c = blockIdx.x;
+    const size_t c = blockIdx.x, P = (size_t)gridDim.x * n;
     for (int k = tid; k < n; k += 256) {
-        const double a = alpha[c * n + k], q = chi2[c * n + k];
-        x[k] = log(a); y[k] = log(q);
-        x10[k] = gamma * log10(a); y10[k] = log10(q);
+        x[k] = alog[c * n + k]; y[k] = log(chi2[c * n + k]);
+        if (out3_idx) x10[k] = gamma * alog[P + c * n + k];
     }
     if (tid < 3) s_pick[tid] = -1;
     __syncthreads();
+    MXE_LF_STAMP(1);
     const bool fit = n > 4;
     double xm = 0.0, ym = 0.0;
     if (fit) {
@@ -427,28 +479,49 @@ void linefit_kernel(const double* __restrict__ alpha, const double* __restrict__
         for (int k = lane; k < n; k += 64) { sx += x[k]; if (y[k] == y[k]) { sy += y[k]; sw += 1.0; } }
         sx = wave_sum(sx); sy = wave_sum(sy); sw = wave_sum(sw);
         xm = sx / n; ym = sy / fmax(sw, 1.0);
-        // running sums of the six quantities, quantity q by wave q & 3: lane t holds element c0 + t of a chunk of 64,
-        // inclusive scan over the lanes (six shuffle steps), carry from chunk to chunk
-        for (int q = wave; q < 6; q += 4) {
-            double carry = 0.0;
-            if (lane == 0) cs[q * (n + 1)] = 0.0;
-            for (int c0 = 0; c0 < n; c0 += 64) {
-                const int k = c0 + lane;
-                const bool in = k < n, ok = in && y[in ? k : 0] == y[in ? k : 0];
-                const double w = ok ? 1.0 : 0.0, x0 = in ? x[k] - xm : 0.0, yc = ok ? y[k] - ym : 0.0;
-                double v = q == 0 ? w : q == 1 ? w * x0 : q == 2 ? yc : q == 3 ? w * x0 * x0 : q == 4 ? x0 * yc : yc * yc;
+        // running sums of the six quantities, quantities q and q + 4 by wave q (waves 2 and 3 carry an idle second): lane t holds
+        // element c0 + t of a chunk of 64, inclusive scan over the lanes (six shuffle steps), carry from chunk to chunk.  The
+        // shuffles of two quantities and two chunks are in flight together -- four scans that do not depend on one another
+        // until the carry is added, each with the additions of a scan made alone.
+        const int qs[2] = {wave, wave + 4 < 6 ? wave + 4 : wave};
+        double carry[2] = {0.0, 0.0};
+        if (lane == 0) { cs[qs[0] * (n + 1)] = 0.0; cs[qs[1] * (n + 1)] = 0.0; }
+        for (int c0 = 0; c0 < n; c0 += 128) {
+            double v[2][2];
+            bool in[2];
 #pragma unroll
-                for (int off = 1; off < 64; off <<= 1) {
-                    const double up = __shfl_up(v, off);
-                    if (lane >= off) v += up;
+            for (int h = 0; h < 2; ++h) {
+                const int k = c0 + 64 * h + lane;
+                in[h] = k < n;
+                const bool ok = in[h] && y[in[h] ? k : 0] == y[in[h] ? k : 0];
+                const double w = ok ? 1.0 : 0.0, x0 = in[h] ? x[k] - xm : 0.0, yc = ok ? y[k] - ym : 0.0;
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    const int q = qs[j];
+                    v[h][j] = q == 0 ? w : q == 1 ? w * x0 : q == 2 ? yc : q == 3 ? w * x0 * x0 : q == 4 ? x0 * yc : yc * yc;
                 }
-                v += carry;
-                if (in) cs[q * (n + 1) + k + 1] = v;
-                carry = __shfl(v, 63);
+            }
+#pragma unroll
+            for (int off = 1; off < 64; off <<= 1) {
+                double up[2][2];
+#pragma unroll
+                for (int h = 0; h < 2; ++h) { up[h][0] = __shfl_up(v[h][0], off); up[h][1] = __shfl_up(v[h][1], off); }
+                if (lane >= off) { v[0][0] += up[0][0]; v[0][1] += up[0][1]; v[1][0] += up[1][0]; v[1][1] += up[1][1]; }
+            }
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const int k = c0 + 64 * h + lane;
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    v[h][j] += carry[j];
+                    if (in[h] && (j == 0 || qs[1] != qs[0])) cs[qs[j] * (n + 1) + k + 1] = v[h][j];
+                    carry[j] = wave_bcast(v[h][j], 63);
+                }
             }
         }
     }
     __syncthreads();
+    MXE_LF_STAMP(2);
     auto sse = [&](int lo, int hi, bool line) -> double {
         const double m = cs[hi] - cs[lo], s1 = cs[(n + 1) + hi] - cs[(n + 1) + lo], s2 = cs[2 * (n + 1) + hi] - cs[2 * (n + 1) + lo];
         const double sxx = cs[3 * (n + 1) + hi] - cs[3 * (n + 1) + lo], sxy = cs[4 * (n + 1) + hi] - cs[4 * (n + 1) + lo];
@@ -470,58 +543,49 @@ void linefit_kernel(const double* __restrict__ alpha, const double* __restrict__
         if (lane == 0) wbest[wave] = best;
     }
     __syncthreads();
+    MXE_LF_STAMP(3);
     if (fit) {
         const double best = fmin(fmin(wbest[0], wbest[1]), fmin(wbest[2], wbest[3]));
         const double tol = best + 1e-9 * (fabs(cs[5 * (n + 1) + n]) + 1e-300) + 1e-6 * fabs(best);
         const bool rank_ok = best < 1.7e308 && n > 8;
         // exact misfit of the candidates, candidate number j by wave j & 3, each by its whole wave; the smallest wins,
-        // the lowest index among equals (np.nanargmin)
+        // the lowest index among equals (np.nanargmin).  The candidates of 64 break points at a time come out of one ballot, in
+        // ascending order.
         double ebest = __builtin_inf(); int ebest_i = -1, seen = 0;
         LineSSE abest, bbest;
         abest.slope = abest.icpt = bbest.slope = bbest.icpt = 0.0;
-        for (int i = 2; i < n - 2; ++i) {
-            const bool cand = rank_ok ? (ap[i] == ap[i] && ap[i] <= tol) : true;      // wave-uniform
-            if (!cand) continue;
-            const bool mine = (seen & 3) == wave;
-            ++seen;
-            if (!mine) continue;
-            const LineSSE a = line_sse(x, y, 0, i, true), b = line_sse(x, y, i, n, p2_deg == 1);
-            if (a.n < 1 || b.n < 1) continue;
-            const double m = a.sse + b.sse;
-            if (m == m && m < ebest) { ebest = m; ebest_i = i; abest = a; bbest = b; }
+        for (int c0 = 2; c0 < n - 2; c0 += 64) {
+            const int i0 = c0 + lane;
+            bool cand = i0 < n - 2;
+            if (cand && rank_ok) { const double a = ap[i0]; cand = a == a && a <= tol; }
+            unsigned long long mask = __ballot(cand);
+            while (mask) {
+                const int i = c0 + __builtin_ctzll(mask);
+                mask &= mask - 1;
+                const bool mine = (seen & 3) == wave;
+                ++seen;
+                if (!mine) continue;
+                LineSSE a, b;
+                if (!line_sse_pair(x, y, i, n, p2_deg == 1, a, b)) continue;
+                const double m = a.sse + b.sse;
+                if (m == m && m < ebest) { ebest = m; ebest_i = i; abest = a; bbest = b; }
+            }
         }
         if (lane == 0) {
             double* f = wfit + wave * 6;
             f[0] = ebest; f[1] = (double)ebest_i; f[2] = abest.slope; f[3] = abest.icpt; f[4] = bbest.slope; f[5] = bbest.icpt;
         }
     }
-    __syncthreads();
-    if (wave == 0 && fit) {
-        double ebest = __builtin_inf(); int ebest_i = -1, wv = -1;
-        for (int w = 0; w < 4; ++w) {
-            const double m = wfit[w * 6]; const int i = (int)wfit[w * 6 + 1];
-            if (i >= 0 && (m < ebest || (m == ebest && i < ebest_i))) { ebest = m; ebest_i = i; wv = w; }
-        }
-        if (ebest_i >= 0) {
-            const double* f = wfit + wv * 6;
-            const double xc = (f[5] - f[3]) / (f[2] - f[4]);
-            double dbest = __builtin_inf(); int di = -1;
-            for (int k = lane; k < n; k += 64) {
-                const double d = fabs(x[k] - xc);
-                if (d == d && (d < dbest || (d == dbest && k < di))) { dbest = d; di = k; }
-            }
-            for (int off = 32; off >= 1; off >>= 1) {
-                const double od = __shfl_xor(dbest, off); const int oi = __shfl_xor(di, off);
-                if (oi >= 0 && (di < 0 || od < dbest || (od == dbest && oi < di))) { dbest = od; di = oi; }
-            }
-            if (lane == 0) s_pick[0] = di;
-        }
-    }
     // ---- Chi2CurvatureAnalyzer (reference analyzers/chi2_curvature_analyzer.py:25-49, 101-131): the alpha of the
     //      largest curvature y'' / (1 + y'^2)^(3/2) of y = log10 chi2 over x = gamma log10 alpha, second-order
     //      central differences on the (non-uniform) mesh, NaN ignored, the first of equal maxima.          (wave 1)
     // ---- EntropyAnalyzer (entropy_analyzer.py:72-103): the alpha where (dS / dlog alpha)^2 is smallest.   (wave 2)
+    // Both in front of the barrier that wave 0 passes with the line fit's candidates: beside the exact fits, not behind them.
     if (out3_idx && (wave == 1 || wave == 2)) {
+        if (wave == 1) {
+            for (int k = lane; k < n; k += 64) y10[k] = log10(chi2[c * n + k]);
+            wave_sync();
+        }
         double vbest = (wave == 1) ? -__builtin_inf() : __builtin_inf();
         int vi = -1;
         for (int k = 1 + lane; k < n - 1; k += 64) {
@@ -546,25 +610,53 @@ void linefit_kernel(const double* __restrict__ alpha, const double* __restrict__
         }
         if (lane == 0) s_pick[wave] = vi;
     }
+    MXE_LF_STAMP(4);
     __syncthreads();
-    const int idx = s_pick[0];
+    MXE_LF_STAMP(5);
+    // the pick, by every wave for itself (the same numbers in the same order in all four): no barrier between it and the rows
+    int idx = -1;
+    if (fit) {
+        double ebest = __builtin_inf(); int ebest_i = -1, wv = -1;
+        for (int w = 0; w < 4; ++w) {
+            const double m = wfit[w * 6]; const int i = (int)wfit[w * 6 + 1];
+            if (i >= 0 && (m < ebest || (m == ebest && i < ebest_i))) { ebest = m; ebest_i = i; wv = w; }
+        }
+        if (ebest_i >= 0) {
+            const double* f = wfit + wv * 6;
+            const double xc = (f[5] - f[3]) / (f[2] - f[4]);
+            double dbest = __builtin_inf(); int di = -1;
+            // (parallel lines, xc infinite: every distance is infinite and the first alpha is the closest, as np.nanargmin has it)
+            for (int k = lane; k < n; k += 64) {
+                const double d = fabs(x[k] - xc);
+                if (d == d && (di < 0 || d < dbest || (d == dbest && k < di))) { dbest = d; di = k; }
+            }
+            // the smallest distance, the lowest index among equals: comparisons only, so two reductions in the order wave_max has
+            const double dmin = -wave_max(di >= 0 ? -dbest : -__builtin_inf());
+            const double imin = -wave_max(di >= 0 && dbest == dmin ? -(double)di : -__builtin_inf());
+            idx = imin < __builtin_inf() ? (int)imin : -1;
+        }
+    }
+    MXE_LF_STAMP(6);
     if (tid == 0) out_idx[c] = (double)idx;
     if (out_sel) {
         const double* row = H + (c * n + (idx >= 0 ? idx : 0)) * nw;
         for (int k = tid; k < nw; k += 256) out_sel[c * nw + k] = (idx >= 0) ? row[k] : __builtin_nan("");
     }
-    if (!out3_idx) return;
-    const size_t nc = gridDim.x;
-    if (tid < 3) out3_idx[tid * nc + c] = (double)s_pick[tid];
-    if (out3_sel) {
+    if (out3_idx) {
+        const size_t nc = gridDim.x;
+        const int pick[3] = {idx, s_pick[1], s_pick[2]};
+        if (tid < 3) out3_idx[tid * nc + c] = (double)(tid == 0 ? idx : s_pick[tid]);
+        if (out3_sel) {
 #pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            const int pk = s_pick[a];
-            const double* row = H + (c * n + (pk >= 0 ? pk : 0)) * nw;
-            double* dst = out3_sel + ((size_t)a * nc + c) * nw;
-            for (int k = tid; k < nw; k += 256) dst[k] = (pk >= 0) ? row[k] : __builtin_nan("");
+            for (int a = 0; a < 3; ++a) {
+                const int pk = pick[a];
+                const double* row = H + (c * n + (pk >= 0 ? pk : 0)) * nw;
+                double* dst = out3_sel + ((size_t)a * nc + c) * nw;
+                for (int k = tid; k < nw; k += 256) dst[k] = (pk >= 0) ? row[k] : __builtin_nan("");
+            }
         }
     }
+    MXE_LF_STAMP(7); MXE_LF_STAMP(9);
 }
 
 } // namespace mxe

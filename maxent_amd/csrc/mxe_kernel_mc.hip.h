@@ -39,7 +39,10 @@ struct MCExtra {
     int n_wg;
     const int* queue;             // dynamic layout: chain ids in the order they are handed out
     int n_queue;                  //   (0 = static layout)
-    int* counter;                 //   next queue position (zeroed before every launch)
+    int* counter;                 //   next queue position.  One word of an 8-byte aligned pair: launch k of a context draws from word
+                                  //   k & 1, and its first thread stores the start value of launch k + 1 -- 0, or the entries the solo
+                                  //   rule hands out by position -- into the other word, which launch k - 1 has finished with (stream
+                                  //   order).  No reset node in front of the launch; no new field either (see below).
     int stagger;                  // WGPC = 2: the second half of the grid starts this many units of 4096 cycles late
     int n_solo;                   // WGPC = 2, dynamic layout, gridDim = 2 x CUs: workgroups b and b + gridDim / 2 share a CU
                                   //   (tools/wg_placement.hip); the first n_solo workgroups get their CU to themselves --
@@ -199,6 +202,24 @@ void chain_kernel_mc(const KParams p, const MCExtra x)
     constexpr int NPAIR = NT * (NT + 1) / 2;
     typedef double d4 __attribute__((ext_vector_type(4)));
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    // re-arm the queue counter of the NEXT launch (MCExtra::counter): the other word of the pair, which the launch before this one
+    // drew from and which nothing of this launch reads
+    // (the four arguments it needs are read through the kernarg segment pointer, made opaque: loads of this branch alone.  Written
+    //  with `x.` the compiler merged them into its argument loads and re-allocated the scalar registers of the whole kernel: <32, 2>
+    //  lost 0.5 %, profiles/r07_experiments.txt)
+    if (blockIdx.x == 0 && tid == 0) {
+        typedef const char __attribute__((address_space(4))) KA;
+        typedef const int __attribute__((address_space(4))) KInt;
+        typedef int* const __attribute__((address_space(4))) KPtr;
+        KA* ka = (KA*)__builtin_amdgcn_kernarg_segment_ptr();
+        asm volatile("" : "+s"(ka));
+        static_assert(sizeof(KParams) % alignof(MCExtra) == 0, "MCExtra follows KParams without padding");
+        KA* xa = ka + sizeof(KParams);
+        int* const ctr = *(KPtr*)(xa + offsetof(MCExtra, counter));
+        const int nq = *(KInt*)(xa + offsetof(MCExtra, n_queue)), nso = *(KInt*)(xa + offsetof(MCExtra, n_solo));
+        const int nwg = *(KInt*)(xa + offsetof(MCExtra, n_wg));
+        if (ctr) *(int*)((uintptr_t)ctr ^ sizeof(int)) = (WGPC == 2 && nq > 0 && nso > 0) ? (nwg - nso) * MCC : 0;
+    }
     if ((int)blockIdx.x >= x.n_wg) return;
     const int half_grid = (int)gridDim.x / 2;
     if (WGPC == 2 && x.n_solo > 0 && (int)blockIdx.x >= half_grid && (int)blockIdx.x < half_grid + x.n_solo) return;
