@@ -95,7 +95,18 @@ def full_matrix_continue(G_batch, U, S, V, D, alpha, err, use_complex=False, max
     Returns a dict: ``u`` (n_prob, n_alpha, P, n_s), the coordinates of Gamma = log(H / D) in the basis of ``V`` and of
     :func:`hermitian_basis`; ``H`` (n_prob, M, M, n_alpha, n_omega), complex with ``use_complex``, exactly Hermitian and
     positive semi-definite; ``chi2``, ``S``, ``Q`` (n_prob, n_alpha), one cost per matrix; ``n_iter``, ``converged``;
-    ``alpha``; ``ms``, the device time of the kernel."""
+    ``alpha``; ``ms``, the device time of the kernel.
+
+    ``maxiter`` bounds the trial points of one alpha -- full steps and halved steps alike; ``n_iter`` counts them -- and an
+    alpha that uses them up returns the last accepted point with ``converged`` False.  With a start ``u0`` this shows single
+    steps of the iteration (tested contract, tests/test_gpu_fullmatrix_steps.py), delta being the solution of J delta = F
+    at u0 with the undamped J of the first alpha:
+
+    * ``maxiter=1``, the full step does not raise Q: ``u`` = u0 - delta, ``n_iter`` 1;
+    * ``maxiter=1``, the full step raises Q: there is no trial point left for a halved step, ``u`` is u0 bit for bit,
+      ``n_iter`` 1, ``converged`` False, and ``H``, ``chi2``, ``S``, ``Q`` are those of u0;
+    * ``maxiter=2``, the full step raises Q and half of it does not: ``u`` = u0 - delta / 2, ``n_iter`` 2, ``converged``
+      False (a halved step never ends an alpha)."""
     G = np.asarray(G_batch)
     if G.ndim != 4:
         raise ValueError('full_matrix_continue: G_batch must be (n_prob, M, M, n_data); got %s' % (G.shape,))

@@ -128,7 +128,9 @@ def test_a_spectrum_whose_matrices_do_not_commute():
     assert np.linalg.eigvalsh(np.moveaxis(H, (0, 1), (-2, -1))).min() >= -16 * EPS * np.max(np.abs(H))
 
 
-@pytest.mark.parametrize('M,cx,n_tau,n_omega,n_alpha,cut', [(3, False, 40, 48, 4, None), (4, True, 40, 32, 2, 12)])
+# (M = 4 real runs end to end in tests/test_gpu_fullmatrix_steps.py, at n_s = 64)
+@pytest.mark.parametrize('M,cx,n_tau,n_omega,n_alpha,cut', [(3, False, 40, 48, 4, None), (4, True, 40, 32, 2, 12),
+                                                          (3, True, 40, 32, 2, 12)])
 def test_other_sizes(M, cx, n_tau, n_omega, n_alpha, cut):
     tau, omega, K, G, _ = synthetic.matrix_G(M, n_tau, n_omega)
     sigma = 1e-3
