@@ -243,7 +243,7 @@ DEVICE_DIRECTIONS = 64          # singular directions the lock-step kernels hold
 KEEP_BOUND = 1e-7               # largest |delta u| = |delta H / H| the dropped directions may cause (the parity gate is 1e-6; the bound overestimates tenfold)
 
 
-def directions_to_keep(K, specs=None, arrays=None):
+def directions_to_keep(K, specs=None, arrays=None, chi2_factor=1.0):
     """How many singular directions of ``K`` the device has to solve this job with: ``None`` (all), or 64 when there are more and
     the others cannot be told from zero in it.
 
@@ -256,12 +256,20 @@ def directions_to_keep(K, specs=None, arrays=None):
     unit length).  The job keeps 64 directions -- or 128, where 64 are too few and there are more: a mesh of 2 000 frequencies on
     1 000 data points leaves 991 'singular values' above 1e-14, the rounding floor of that decomposition -- when that norm, with
     the smallest alpha of the job, stays below ``KEEP_BOUND`` for every element; the v it returns are zero in the others.  Only for ONE error bar per element and an
-    unrotated kernel: there M = S U^T diag(1 / err^2) U S is diagonal and rho_k is the direction's own."""
+    unrotated kernel: there M = S U^T diag(1 / err^2) U S is diagonal and rho_k is the direction's own.
+
+    ``chi2_factor``: the eta of the job's cost function, Q = eta chi2 / 2 - alpha S.  The device iterates on alpha / eta, and so
+    does the minimiser obey  (alpha / eta) v_k = -c_k rho_k:  the alpha of the bound is the job's smallest alpha / eta (a bound
+    formed with alpha alone promised eta times too much; tests/test_keep_bound_host.py measures the claim against the
+    extended-precision fixed points of all and of the kept directions).  A factor that is not a positive finite number keeps all."""
     S = np.asarray(K.S, dtype=float)
     n_s = S.shape[0]
     if n_s <= DEVICE_DIRECTIONS or K.rotation is not None or os.environ.get('MAXENT_AMD_ALL_DIRECTIONS'):
         return None
     try:
+        eta = float(chi2_factor)
+        if not (np.isfinite(eta) and eta > 0.0):
+            return None
         if arrays is not None:
             G = np.asarray(arrays['G'], dtype=float)
             err = np.asarray(arrays['err'], dtype=float) * np.ones((1, G.shape[1]))
@@ -286,7 +294,7 @@ def directions_to_keep(K, specs=None, arrays=None):
             if keep >= n_s:
                 break
             # u = V v and the rows of V are at most of unit length: |delta u_i| <= |v_dropped|_2
-            bound = np.sqrt(np.sum(per[:, keep - DEVICE_DIRECTIONS:] ** 2, axis=1)) / amin
+            bound = np.sqrt(np.sum(per[:, keep - DEVICE_DIRECTIONS:] ** 2, axis=1)) / (amin / eta)
             if np.all(np.isfinite(bound)) and float(np.max(bound)) <= KEEP_BOUND:
                 return keep
     except Exception:
@@ -581,7 +589,8 @@ class BatchSolver(object):
             maps = {r: self.ctxs[r].apply_output_map(output_map) for r in active} if output_map is not None else {}
             ms = [self.ctxs[r].last_kernel_ms() for r in active]
             info = dict(kernel_ms=max(ms), kernel_ms_per_device=ms, devices=[self.device_ids[r] for r in active],
-                        n_datasets=[self._n_datasets.get(id(self.ctxs[r]), 0) for r in active])
+                        n_datasets=[self._n_datasets.get(id(self.ctxs[r]), 0) for r in active],
+                        keep=self._keep)        # (None: all singular directions; 64 or 128: directions_to_keep)
             info.update(self.ctxs[active[0]].last_launch_info())
             if os.environ.get('MAXENT_AMD_AUDIT'):
                 # on request (the parity tests): mxe_audit over every problem of this launch -- the exact binary64 Newton correction
@@ -696,7 +705,7 @@ class BatchSolver(object):
                 c.select3_fetch_rows(first=eager, count=1, idx=picks[0], rows=picks[2])
             ms = c.last_kernel_ms()
             info = dict(kernel_ms=ms, kernel_ms_per_device=[ms], devices=[self.device_ids[0]],
-                        n_datasets=[self._n_datasets.get(id(c), 0)], eager=eager)
+                        n_datasets=[self._n_datasets.get(id(c), 0)], eager=eager, keep=self._keep)
             info.update(c.last_launch_info())
             if os.environ.get('MAXENT_AMD_AUDIT'):
                 corr = c.audit()['corr'].ravel()

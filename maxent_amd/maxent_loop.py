@@ -84,7 +84,7 @@ def solve_elements(K, specs, minimizer, device_id=0, waves_per_chain=0,
         return (lambda: done) if defer else done
     from .batch_solver import BatchSolver, directions_to_keep
     solver = BatchSolver.for_kernel(K, (device_id,) if device_ids is None else device_ids,
-                                    keep=directions_to_keep(K, specs, arrays))
+                                    keep=directions_to_keep(K, specs, arrays, chi2_factor=chi2_factor))
     extra = dict(in_flight=int(in_flight)) if in_flight and in_flight > 1 else {}
     opts = minimizer.to_opts(waves_per_chain=waves_per_chain, chi2_factor=float(chi2_factor), **extra)
     if arrays is not None:

@@ -137,7 +137,7 @@ def element_model_scan(K, omega, loop, templates, models, prior=None, alpha='bry
             if not per_dev[r]:
                 continue
             specs = [loop.spec_with_model(templates[e], D) for e in per_dev[r] for D in models]
-            solver = BatchSolver.for_kernel(K, (dev,), keep=directions_to_keep(K, specs, None))
+            solver = BatchSolver.for_kernel(K, (dev,), keep=directions_to_keep(K, specs, None, chi2_factor=loop.cost_function.chi2_factor))
             solver._lock.acquire()              # (until this device's rows are reduced: nobody else launches on its contexts)
             begun.append([r, solver, specs, None])
             begun[-1][3] = solve_elements(K, specs, loop.minimizer, device_ids=(dev,),

@@ -167,7 +167,7 @@ def element_resamples(K, omega, loop, templates, G_rows, method, alpha=None, alp
             if not per_dev[r]:
                 continue
             specs = [loop.spec_like(templates[e], G_rows[e][k], templates[e]['err']) for e in per_dev[r] for k in range(n_tot)]
-            solver = BatchSolver.for_kernel(K, (dev,), keep=directions_to_keep(K, specs, None))
+            solver = BatchSolver.for_kernel(K, (dev,), keep=directions_to_keep(K, specs, None, chi2_factor=loop.cost_function.chi2_factor))
             solver._lock.acquire()              # (until this device's rows are reduced: nobody else launches on its contexts)
             begun.append([r, solver, specs, None])
             begun[-1][3] = solve_elements(K, specs, loop.minimizer, device_ids=(dev,),

@@ -907,3 +907,11 @@ def test_the_device_keeps_64_singular_directions_only_where_the_others_cannot_ma
     assert bs.directions_to_keep(K3, [sp3], None) == 64
     assert bs.directions_to_keep(K3, [dict(sp3, err=1e-9 * np.ones(1000))], None) is None
     assert len(K2.S) <= 64 and bs.directions_to_keep(K2, None, dict(arrays, G=Gmat2.reshape(-1, 100), err=1e-4 * np.ones((1, 100)))) is None
+    # chi2_factor = eta: the device iterates on alpha / eta, and that is the alpha of the bound.  The bound of this job is 1.6e-11
+    # (the rounding floor of LAPACK's decomposition), KEEP_BOUND / 6 400: eta = 1 is the default, 1e6 lifts it over the edge, and
+    # alpha and eta scaled together change nothing
+    for form in (dict(specs=specs), dict(arrays=arrays)):
+        assert bs.directions_to_keep(K, chi2_factor=1.0, **form) == 64
+        assert bs.directions_to_keep(K, chi2_factor=1e6, **form) is None
+    assert bs.directions_to_keep(K, None, dict(arrays, alpha=alpha * 2.0 ** 20), chi2_factor=2.0 ** 20) == 64
+    assert bs.directions_to_keep(K3, [sp3], None, chi2_factor=1e6) is None
