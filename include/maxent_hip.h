@@ -68,7 +68,9 @@
  *   (nothing: positivity of the matrix is not checked)     | mxe_hermitian_eig (eigenvalues of A(w) as a matrix,
  *                                                          |   its nearest positive semi-definite matrix)
  *   (nothing: "FullMatrixMaxEnt" is announced, not shipped) | mxe_fullmatrix_solve (the matrix A(w) as one unknown,
- *                                                          |   positive semi-definite by construction)
+ *                                                          |   positive semi-definite by construction),
+ *                                                          |   mxe_fullmatrix_solve_metric (the same with one
+ *                                                          |   error bar per matrix element)
  *   the arrays of MaxEntResult (numpy allocations)         | mxe_host_alloc / mxe_host_free (optional:
  *     maxent_result.py:835-967                             |   page-locked destinations, one DMA per fetch)
  *
@@ -959,6 +961,25 @@ int  mxe_fullmatrix_solve(int device, int n_prob, int m, int is_complex, int n_o
                           const double* ghat, const double* cperp, const double* u0, int maxiter, double tol_h,
                           double* out_u, double* out_H, double* out_chi2, double* out_S, double* out_Q,
                           int32_t* out_niter, int32_t* out_conv, float* out_ms);
+
+/* The same continuation with one error bar per matrix element: sigma_ab(t) = sigma_ba(t) is the standard deviation of the
+ * real and of the imaginary part of the symmetrised G_ab(t).  In the coordinates of E_p the misfit stays a sum over the
+ * components, chi2 = sum_p sum_t (g_p - (K h_p))_t^2 / sigma_p(t)^2 with sigma_p = sigma_aa for a diagonal unit and
+ * sigma_ab for both components of a pair a < b, and the diagonal metric c, shared by all components, becomes a dense
+ * n_s x n_s factor per component: diag(1 / sigma_p) U S = Q^_p R_p (thin, any sign convention), A_p = R_p^T R_p,
+ *   rho_p = R_p V^T H_p - g^_p    chi2 = sum_p |rho_p|^2 + c_perp    F_p = alpha u_p + R_p^T rho_p
+ *   J = alpha I + blockdiag_p(A_p) W
+ * V is not rotated and u stays in its basis.  The iteration, the outputs and their layouts are those of
+ * mxe_fullmatrix_solve; block row p of J - alpha I is formed as A_p W[(p, .), :] by a phase of its own, in a fixed order.
+ *   V           n_omega x n_s row-major, the right singular basis itself
+ *   R, A        P x n_s x n_s row-major, shared by the problems: R_p and A_p = R_p^T R_p (finite; no sign is asked for)
+ *   ghat        n_prob x P x n_s: Q^_p^T (G_p / sigma_p);  cperp  n_prob: sum_p (|G_p / sigma_p|^2 - |ghat_p|^2), >= 0
+ * Everything else, the return codes and the limits as for mxe_fullmatrix_solve (with R, A in the place of c). */
+int  mxe_fullmatrix_solve_metric(int device, int n_prob, int m, int is_complex, int n_omega, int n_s, int n_alpha,
+                                 const double* V, const double* R, const double* A, const double* D, const double* alpha,
+                                 const double* ghat, const double* cperp, const double* u0, int maxiter, double tol_h,
+                                 double* out_u, double* out_H, double* out_chi2, double* out_S, double* out_Q,
+                                 int32_t* out_niter, int32_t* out_conv, float* out_ms);
 
 #ifdef __cplusplus
 }

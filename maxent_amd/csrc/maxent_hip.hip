@@ -3721,31 +3721,34 @@ MXE_CATCH_ALL
 // ---- whole-matrix continuation: H(omega) = D exp(Gamma(omega)), positive by construction (mxe_fullmatrix.hip.h) ----
 #include "mxe_fullmatrix.hip.h"
 
-extern "C" int mxe_fullmatrix_solve(int device, int n_prob, int m, int is_complex, int n_omega, int n_s, int n_alpha,
-                                    const double* V, const double* c, const double* D, const double* alpha,
-                                    const double* ghat, const double* cperp, const double* u0, int maxiter, double tol_h,
-                                    double* out_u, double* out_H, double* out_chi2, double* out_S, double* out_Q,
-                                    int32_t* out_niter, int32_t* out_conv, float* out_ms)
-try {
+// the two entries: c [n_s] (R and A NULL; the diagonal metric shared by all components) or R, A [P][n_s][n_s] (c NULL)
+static int fullmatrix_solve_any(int device, int n_prob, int m, int is_complex, int n_omega, int n_s, int n_alpha,
+                                const double* V, const double* c, const double* R, const double* A, bool metric,
+                                const double* D, const double* alpha,
+                                const double* ghat, const double* cperp, const double* u0, int maxiter, double tol_h,
+                                double* out_u, double* out_H, double* out_chi2, double* out_S, double* out_Q,
+                                int32_t* out_niter, int32_t* out_conv, float* out_ms)
+{
     static_assert(MXE_FULLMATRIX_MAX_M == mxe::FM_MAX_M && MXE_FULLMATRIX_MAX_NS == mxe::FM_MAX_NS,
                   "the header and the kernel disagree on the limits");
     if (n_prob < 1 || m < 1 || (is_complex != 0 && is_complex != 1) || n_omega < 1 || n_s < 1 || n_alpha < 1 || maxiter < 0 ||
-        !V || !c || !D || !alpha || !ghat || !cperp || !out_u || !out_H || !out_chi2 || !out_S || !out_Q || !out_niter ||
+        !V || (metric ? (!R || !A) : !c) || !D || !alpha || !ghat || !cperp || !out_u || !out_H || !out_chi2 || !out_S || !out_Q || !out_niter ||
         !out_conv || !(tol_h > 0.0) || !std::isfinite(tol_h))
         return MXE_ERR_ARG;
     if (m > mxe::FM_MAX_M || n_s > mxe::FM_MAX_NS) return MXE_ERR_LIMIT;
     const bool cplx = is_complex != 0;
     const size_t np = n_prob, nw = n_omega, ns = n_s, na = n_alpha, P = mxe::fm_P(m, cplx), d = P * ns;
     const size_t mm = (size_t)m * m, hplanes = (cplx ? 2 : 1) * mm;
-    const size_t scr = mxe::fm_scratch_doubles(m, cplx, n_omega, n_s);
+    const size_t scr = metric ? mxe::fm_scratch_doubles_metric(m, cplx, n_omega, n_s) : mxe::fm_scratch_doubles(m, cplx, n_omega, n_s);
+    const size_t nc = metric ? 0 : ns, nr = metric ? P * ns * ns : 0;
     if (nw * ns > 0x7fffffffull || np * na * hplanes * nw > 0x7fffffffull || np * na * d > 0x7fffffffull ||
         P * (P + 1) / 2 * nw > 0x7fffffffull)
         return MXE_ERR_ARG;
-    if (!all_finite(V, nw * ns) || !all_finite(c, ns) || !all_finite(D, nw) || !all_finite(alpha, na) ||
+    if (!all_finite(V, nw * ns) || (metric ? (!all_finite(R, nr) || !all_finite(A, nr)) : !all_finite(c, ns)) || !all_finite(D, nw) || !all_finite(alpha, na) ||
         !all_finite(ghat, np * d) || !all_finite(cperp, np) || (u0 && !all_finite(u0, np * d)))
         return MXE_ERR_ARG;
     for (size_t i = 0; i < nw; ++i) if (!(D[i] > 0.0)) return MXE_ERR_ARG;
-    for (size_t k = 0; k < ns; ++k) if (!(c[k] > 0.0)) return MXE_ERR_ARG;
+    for (size_t k = 0; k < nc; ++k) if (!(c[k] > 0.0)) return MXE_ERR_ARG;
     for (size_t a = 0; a < na; ++a) if (!(alpha[a] > 0.0)) return MXE_ERR_ARG;
     const size_t lds = mxe::fm_lds_doubles((int)d) * sizeof(double);
     if (lds > 160 * 1024) return MXE_ERR_LIMIT;
@@ -3756,16 +3759,18 @@ try {
     p.n_prob = n_prob; p.n_omega = n_omega; p.n_s = n_s; p.n_alpha = n_alpha; p.maxiter = maxiter;
     p.tol_h = tol_h; p.mu_first = 1e-3; p.mu_grow = 4.0; p.mu_max = 1e12;
     Block in;
-    const size_t oV = in.add(nw * ns), oc = in.add(ns), oD = in.add(nw), oa = in.add(na), og = in.add(np * d),
-                 op = in.add(np), o0 = in.add(u0 ? np * d : 0);
+    const size_t oV = in.add(nw * ns), oc = in.add(nc), oD = in.add(nw), oa = in.add(na), og = in.add(np * d),
+                 op = in.add(np), o0 = in.add(u0 ? np * d : 0), oR = in.add(nr), oA = in.add(nr);
     double* din;
     STGCHK(sg, sg.alloc(&din, in.total));
-    STGCHK(sg, sg.upload(din + oV, V, nw * ns)); STGCHK(sg, sg.upload(din + oc, c, ns));
+    STGCHK(sg, sg.upload(din + oV, V, nw * ns)); STGCHK(sg, sg.upload(din + oc, c, nc));
     STGCHK(sg, sg.upload(din + oD, D, nw)); STGCHK(sg, sg.upload(din + oa, alpha, na));
     STGCHK(sg, sg.upload(din + og, ghat, np * d)); STGCHK(sg, sg.upload(din + op, cperp, np));
     STGCHK(sg, sg.upload(din + o0, u0, np * d));
+    STGCHK(sg, sg.upload(din + oR, R, nr)); STGCHK(sg, sg.upload(din + oA, A, nr));
     p.V = din + oV; p.c = din + oc; p.D = din + oD; p.alpha = din + oa; p.ghat = din + og; p.cperp = din + op;
     p.u0 = u0 ? din + o0 : nullptr;
+    if (metric) { p.c = nullptr; p.R = din + oR; p.A = din + oA; }
     STGCHK(sg, sg.alloc(&p.scratch, np * scr));
     Block out;
     const size_t ou = out.add(np * na * d), oH = out.add(np * na * hplanes * nw), ox = out.add(np * na), oS = out.add(np * na),
@@ -3782,8 +3787,13 @@ try {
          mxe::fullmatrix_kernel<4, false>},
         {mxe::fullmatrix_kernel<1, true>, mxe::fullmatrix_kernel<2, true>, mxe::fullmatrix_kernel<3, true>,
          mxe::fullmatrix_kernel<4, true>}};
+    static const kernel_t metric_kernels[2][4] = {
+        {mxe::fullmatrix_kernel<1, false, true>, mxe::fullmatrix_kernel<2, false, true>, mxe::fullmatrix_kernel<3, false, true>,
+         mxe::fullmatrix_kernel<4, false, true>},
+        {mxe::fullmatrix_kernel<1, true, true>, mxe::fullmatrix_kernel<2, true, true>, mxe::fullmatrix_kernel<3, true, true>,
+         mxe::fullmatrix_kernel<4, true, true>}};
     STGCHK(sg, sg.time_begin(out_ms != nullptr));
-    STGCHK(sg, launch_lds(kernels[cplx ? 1 : 0][m - 1], dim3((unsigned)np), dim3(mxe::FM_T), lds, sg.stream, p));
+    STGCHK(sg, launch_lds((metric ? metric_kernels : kernels)[cplx ? 1 : 0][m - 1], dim3((unsigned)np), dim3(mxe::FM_T), lds, sg.stream, p));
     STGCHK(sg, sg.time_end());
     STGCHK(sg, sg.fetch(out_u, p.out_u, np * na * d)); STGCHK(sg, sg.fetch(out_H, p.out_H, np * na * hplanes * nw));
     STGCHK(sg, sg.fetch(out_chi2, p.out_chi2, np * na)); STGCHK(sg, sg.fetch(out_S, p.out_S, np * na));
@@ -3791,5 +3801,26 @@ try {
     STGCHK(sg, sg.fetch(out_niter, (int32_t*)p.out_niter, np * na)); STGCHK(sg, sg.fetch(out_conv, (int32_t*)p.out_conv, np * na));
     STGCHK(sg, sg.finish(out_ms));
     return MXE_OK;
+}
+
+extern "C" int mxe_fullmatrix_solve(int device, int n_prob, int m, int is_complex, int n_omega, int n_s, int n_alpha,
+                                    const double* V, const double* c, const double* D, const double* alpha,
+                                    const double* ghat, const double* cperp, const double* u0, int maxiter, double tol_h,
+                                    double* out_u, double* out_H, double* out_chi2, double* out_S, double* out_Q,
+                                    int32_t* out_niter, int32_t* out_conv, float* out_ms)
+try {
+    return fullmatrix_solve_any(device, n_prob, m, is_complex, n_omega, n_s, n_alpha, V, c, nullptr, nullptr, false, D, alpha,
+                                ghat, cperp, u0, maxiter, tol_h, out_u, out_H, out_chi2, out_S, out_Q, out_niter, out_conv, out_ms);
+}
+MXE_CATCH_ALL
+
+extern "C" int mxe_fullmatrix_solve_metric(int device, int n_prob, int m, int is_complex, int n_omega, int n_s, int n_alpha,
+                                           const double* V, const double* R, const double* A, const double* D,
+                                           const double* alpha, const double* ghat, const double* cperp, const double* u0,
+                                           int maxiter, double tol_h, double* out_u, double* out_H, double* out_chi2,
+                                           double* out_S, double* out_Q, int32_t* out_niter, int32_t* out_conv, float* out_ms)
+try {
+    return fullmatrix_solve_any(device, n_prob, m, is_complex, n_omega, n_s, n_alpha, V, nullptr, R, A, true, D, alpha,
+                                ghat, cperp, u0, maxiter, tol_h, out_u, out_H, out_chi2, out_S, out_Q, out_niter, out_conv, out_ms);
 }
 MXE_CATCH_ALL

@@ -26,6 +26,15 @@
 //      the forward substitution is the elimination of column d; the back substitution runs in blocks of 16 rows.
 // No atomics; every sum has one order that depends on the sizes alone: the bits of a problem do not depend on the batch.
 // All arrays of a problem other than the panel live in its slice of a device-memory scratch (fm_scratch_doubles).
+//
+// fullmatrix_kernel<M, C, true> (mxe_fullmatrix_solve_metric): one error bar per matrix element.  The diagonal metric c, the
+// same for all components, becomes a dense n_s x n_s factor per component, diag(1 / sigma_p) U S = Q^_p R_p, A_p = R_p^T R_p,
+// shared by the batch; V is not rotated.  c stood in three places, and only they differ:
+//   rho_p = R_p V^T H_p - g^_p      F_p = alpha u_p + R_p^T rho_p      J = alpha I + blockdiag_p(A_p) W
+// The Gram epilogue writes the unscaled W (into the array LU works on, which is filled only afterwards); a phase of its own
+// then forms block row p of J - alpha I as A_p W[(p, .), :] on the same MFMA: one wavefront per 16 x 16 tile (the row tile
+// inside one p, the column tiles over all of d), the n_s-long sum in index order inside one chain, zeros beyond n_s and d.
+// The other instantiations do not contain any of this: their code is that of the two-parameter template before it.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -44,7 +53,9 @@ struct FullMatrixParams {
     int n_prob, n_omega, n_s, n_alpha, maxiter;
     double tol_h, mu_first, mu_grow, mu_max;
     const double* V;         // [n_omega][n_s]
-    const double* c;         // [n_s]
+    const double* c;         // [n_s]                      (METRIC: unused)
+    const double* R;         // [P][n_s][n_s] row-major     (METRIC only)
+    const double* A;         // [P][n_s][n_s] = R_p^T R_p   (METRIC only)
     const double* D;         // [n_omega]
     const double* alpha;     // [n_alpha]
     const double* ghat;      // [n_prob][P][n_s]
@@ -66,6 +77,11 @@ __host__ __device__ inline size_t fm_scratch_doubles(int m, bool cplx, int nw, i
     const size_t P = fm_P(m, cplx), d = P * ns, npair = P * (P + 1) / 2, mm = (size_t)m * m;
     // u, u_t, rho, rho_t, delta | Gamma coordinates, H coordinates | W_i | D phi | L | J - alpha I | the matrix LU works on
     return 5 * d + 2 * P * nw + (cplx ? 2 : 1) * mm * nw + mm * nw + npair * nw + d * d + d * (d + 1);
+}
+// the metric variant: the above, then V^T H_p [d]
+__host__ __device__ inline size_t fm_scratch_doubles_metric(int m, bool cplx, int nw, int ns)
+{
+    return fm_scratch_doubles(m, cplx, nw, ns) + (size_t)fm_P(m, cplx) * ns;
 }
 // doubles of dynamic LDS: the panel (or, in the back substitution, x and 256 partial sums) | reductions | scalars
 __host__ __device__ inline size_t fm_lds_doubles(int d)
@@ -201,7 +217,7 @@ __device__ __forceinline__ void fm_jacobi(double (&ar)[M][M], double (&ai)[M][M]
     }
 }
 
-template <int M, bool C>
+template <int M, bool C, bool METRIC = false>
 __global__ __launch_bounds__(FM_T)
 void fullmatrix_kernel(const FullMatrixParams p)
 {
@@ -220,7 +236,7 @@ void fullmatrix_kernel(const FullMatrixParams p)
     int* piv = (int*)(bc + 8);                       // [16] pivot rows of the panel (relative to the panel), [16] ok flag
 
     // ---- the problem's slice of the scratch ----
-    double* sc = p.scratch + prob * fm_scratch_doubles(M, C, nw, ns);
+    double* sc = p.scratch + prob * (METRIC ? fm_scratch_doubles_metric(M, C, nw, ns) : fm_scratch_doubles(M, C, nw, ns));
     double* u = sc;            sc += d;
     double* ut = sc;           sc += d;
     double* rho = sc;          sc += d;
@@ -232,7 +248,8 @@ void fullmatrix_kernel(const FullMatrixParams p)
     double* phiD = sc;         sc += (size_t)MM * nw;        // [nw][M][M]
     double* Lp = sc;           sc += (size_t)NPAIR * nw;     // [NPAIR][nw]
     double* Jb = sc;           sc += (size_t)d * d;          // [d][d]  (c^2 (x) 1) W
-    double* Aw = sc;                                         // [d][d + 1]
+    double* Aw = sc;           sc += (size_t)d * lda;        // [d][d + 1]  (METRIC: before it is filled, the unscaled W [d][d])
+    double* hv = sc;                                         // [d] V^T H_p (METRIC only)
 
     const double* V = p.V;
     const double* cc = p.c;
@@ -346,11 +363,28 @@ void fullmatrix_kernel(const FullMatrixParams p)
             const double* hp = hc + (size_t)pp * nw;
             double s = 0.0;
             for (int i = 0; i < nw; ++i) s = fma(V[(size_t)i * ns + k], hp[i], s);
-            const double r = cc[k] * s - ghat[idx];
-            rho_x[idx] = r;
-            c_part = fma(r, r, c_part);
+            if constexpr (METRIC) {
+                hv[idx] = s;
+            } else {
+                const double r = cc[k] * s - ghat[idx];
+                rho_x[idx] = r;
+                c_part = fma(r, r, c_part);
+            }
         }
         __syncthreads();
+        if constexpr (METRIC) {
+            for (int idx = tid; idx < d; idx += FM_T) {
+                const int pp = idx / ns;
+                const double* Rr = p.R + (size_t)idx * ns;           // row k of R_p
+                const double* hp = hv + (size_t)pp * ns;
+                double s = 0.0;
+                for (int t = 0; t < ns; ++t) s = fma(Rr[t], hp[t], s);
+                const double r = s - ghat[idx];
+                rho_x[idx] = r;
+                c_part = fma(r, r, c_part);
+            }
+            __syncthreads();
+        }
         const double chi2_x = hermeig_reduce<FM_T, false>(c_part, red) + cperp;
 
         // ================= the state machine =================
@@ -461,12 +495,56 @@ void fullmatrix_kernel(const FullMatrixParams p)
                     if (s >= ns || t >= ns || (ti == tj && s > t)) continue;
                     const double w = acc[r];
                     const size_t ps = (size_t)pp * ns + s, pt = (size_t)pp * ns + t, qs = (size_t)qq * ns + s, qt = (size_t)qq * ns + t;
-                    const double c2s = cc[s] * cc[s], c2t = cc[t] * cc[t];
-                    Jb[ps * d + qt] = c2s * w;
-                    Jb[pt * d + qs] = c2t * w;
-                    if (pp != qq) {
-                        Jb[qs * d + pt] = c2s * w;
-                        Jb[qt * d + ps] = c2t * w;
+                    if constexpr (METRIC) {
+                        Aw[ps * d + qt] = w;
+                        Aw[pt * d + qs] = w;
+                        if (pp != qq) {
+                            Aw[qs * d + pt] = w;
+                            Aw[qt * d + ps] = w;
+                        }
+                    } else {
+                        const double c2s = cc[s] * cc[s], c2t = cc[t] * cc[t];
+                        Jb[ps * d + qt] = c2s * w;
+                        Jb[pt * d + qs] = c2t * w;
+                        if (pp != qq) {
+                            Jb[qs * d + pt] = c2s * w;
+                            Jb[qt * d + ps] = c2t * w;
+                        }
+                    }
+                }
+            }
+            if constexpr (METRIC) {
+                // block row p of J - alpha I = A_p W[(p, .), :]: W [d][d] in Aw; the row tile lies inside one p, the column
+                // tiles run over all of d; rows and the sum beyond n_s and columns beyond d are fed as zeros, never stored
+                __syncthreads();
+                const int nct = (d + 15) >> 4, nkg = (ns + 3) >> 2;
+                for (int item = wave; item < P * ntile * nct; item += 4) {
+                    const int pp = item / (ntile * nct), rem = item - pp * ntile * nct;
+                    const int ti = rem / nct, tc = rem - ti * nct;
+                    const double* Ap = p.A + (size_t)pp * ns * ns;
+                    const double* Wp = Aw + (size_t)pp * ns * d;
+                    const int row = 16 * ti + cn, col = 16 * tc + cn;
+                    // the operands of eight links of the chain are loaded before the eight run, so that their loads overlap;
+                    // the chain itself is the same values in the same order
+                    constexpr int NKG = 8;
+                    d4 acc = d4{0.0, 0.0, 0.0, 0.0};
+                    for (int g0 = 0; g0 < nkg; g0 += NKG) {
+                        double av[NKG], bv[NKG];
+#pragma unroll
+                        for (int g = 0; g < NKG; ++g) {
+                            const int s = 4 * (g0 + g) + kq;
+                            const bool sv = g0 + g < nkg && s < ns;
+                            av[g] = (sv && row < ns) ? Ap[(size_t)row * ns + s] : 0.0;
+                            bv[g] = (sv && col < d) ? Wp[(size_t)s * d + col] : 0.0;
+                        }
+#pragma unroll
+                        for (int g = 0; g < NKG; ++g)
+                            if (g0 + g < nkg) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av[g], bv[g], acc, 0, 0, 0);
+                    }
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int k = 16 * ti + kq + 4 * r;
+                        if (k < ns && col < d) Jb[((size_t)pp * ns + k) * d + col] = acc[r];
                     }
                 }
             }
@@ -479,8 +557,21 @@ void fullmatrix_kernel(const FullMatrixParams p)
             const int r = idx / lda, c = idx - r * lda;
             double v;
             if (c < d) { v = Jb[(size_t)r * d + c]; if (r == c) v += alpha + mu; }
+            else if constexpr (METRIC) continue;                     // (column d: below)
             else v = alpha * u[r] + cc[r % ns] * rho[r];
             Aw[idx] = v;
+        }
+        if constexpr (METRIC) {
+            // column d, F_p = alpha u_p + R_p^T rho_p: a thread per (p, k) in a loop of its own (inside the loop above the
+            // n_s-long sum would stall its wavefront once per row)
+            for (int r = tid; r < d; r += FM_T) {
+                const int pp = r / ns, k = r - pp * ns;
+                const double* Rc = p.R + (size_t)pp * ns * ns + k;   // column k of R_p
+                const double* rp = rho + (size_t)pp * ns;
+                double s = 0.0;
+                for (int t = 0; t < ns; ++t) s = fma(Rc[(size_t)t * ns], rp[t], s);
+                Aw[(size_t)r * lda + d] = alpha * u[r] + s;
+            }
         }
         if (tid == 0) piv[16] = 1;
         __syncthreads();

@@ -192,6 +192,8 @@ SYMBOLS = [
                                          _dp, _dp, _dp, _dp, _dp, _dp, _dp, _ip, ctypes.POINTER(ctypes.c_float)]),
     ('mxe_fullmatrix_solve', ctypes.c_int, [ctypes.c_int] * 7 + [_dp] * 7 + [ctypes.c_int, ctypes.c_double] + [_dp] * 5 +
                                            [_ip, _ip, ctypes.POINTER(ctypes.c_float)]),
+    ('mxe_fullmatrix_solve_metric', ctypes.c_int, [ctypes.c_int] * 7 + [_dp] * 8 + [ctypes.c_int, ctypes.c_double] +
+                                                  [_dp] * 5 + [_ip, _ip, ctypes.POINTER(ctypes.c_float)]),
 ]
 
 
@@ -975,6 +977,69 @@ def fullmatrix_solve(V, c, D, alpha, ghat, cperp, m, use_complex, u0=None, maxit
                                   _p(Q), _p(n_iter), _p(conv), ctypes.byref(ms))
     if rc != 0:
         raise MaxEntDeviceError('mxe_fullmatrix_solve failed: ' + lib.mxe_strerror(rc).decode())
+    if timing is not None:
+        timing['ms'] = float(ms.value)
+    Hm = H[:, :, 0] + 1.0j * H[:, :, 1] if use_complex else H[:, :, 0]          # (n_prob, n_alpha, m, m, n_omega)
+    return dict(u=u, H=np.ascontiguousarray(np.moveaxis(Hm, 1, 3)), chi2=chi2, S=S, Q=Q, n_iter=n_iter,
+                converged=conv != 0)
+
+
+def fullmatrix_solve_metric(V, R, A, D, alpha, ghat, cperp, m, use_complex, u0=None, maxiter=1000, tol_h=1e-9, device=0,
+                            timing=None):
+    """``mxe_fullmatrix_solve_metric``: :func:`fullmatrix_solve` with one error bar per matrix element.  In the place of
+    ``c`` stand the dense factors ``R`` (P, n_s, n_s), diag(1 / sigma_p) U S = Q^_p R_p, and ``A`` (P, n_s, n_s),
+    A_p = R_p^T R_p, of every component E_p, shared by the problems; ``V`` (n_omega, n_s) is the right singular basis itself
+    and ``ghat`` (n_prob, P, n_s) = Q^_p^T (G_p / sigma_p).  Returns what :func:`fullmatrix_solve` returns.  Arguments the
+    library would refuse raise ValueError before it is called."""
+    V, R, A, D, alpha = _c(V), _c(R), _c(A), _c(D), _c(alpha)
+    ghat, cperp = _c(ghat), _c(cperp)
+    m, use_complex = int(m), bool(use_complex)
+    if m < 1 or m > FULLMATRIX_MAX_M:
+        raise ValueError('fullmatrix_solve_metric: matrices of %d x %d; 1 to %d are supported' % (m, m, FULLMATRIX_MAX_M))
+    if V.ndim != 2 or V.shape[0] < 1 or V.shape[1] < 1:
+        raise ValueError('fullmatrix_solve_metric: V must be (n_omega, n_s); got %s' % (V.shape,))
+    n_omega, n_s = V.shape
+    if n_s > FULLMATRIX_MAX_NS:
+        raise ValueError('fullmatrix_solve_metric: %d singular values; at most %d are supported: cut the singular space with '
+                         'reduce_singular_space' % (n_s, FULLMATRIX_MAX_NS))
+    P = fullmatrix_P(m, use_complex)
+    if R.shape != (P, n_s, n_s) or A.shape != (P, n_s, n_s):
+        raise ValueError('fullmatrix_solve_metric: R and A must be (%d, %d, %d); got %s and %s' % (P, n_s, n_s, R.shape, A.shape))
+    if D.shape != (n_omega,) or alpha.ndim != 1 or alpha.size < 1:
+        raise ValueError('fullmatrix_solve_metric: D must be (n_omega,), alpha one-dimensional and not empty')
+    if ghat.ndim != 3 or ghat.shape[0] < 1 or ghat.shape[1:] != (P, n_s) or cperp.shape != (ghat.shape[0],):
+        raise ValueError('fullmatrix_solve_metric: ghat must be (n_prob, %d, %d) and cperp (n_prob,); got %s and %s'
+                         % (P, n_s, ghat.shape, cperp.shape))
+    n_prob, n_alpha = ghat.shape[0], alpha.size
+    if u0 is not None:
+        u0 = _c(u0)
+        if u0.shape != ghat.shape:
+            raise ValueError('fullmatrix_solve_metric: u0 must have the shape of ghat, %s; got %s' % (ghat.shape, u0.shape))
+    for name, a in (('V', V), ('R', R), ('A', A), ('D', D), ('alpha', alpha), ('ghat', ghat), ('cperp', cperp), ('u0', u0)):
+        if a is not None and not np.all(np.isfinite(a)):
+            raise ValueError('fullmatrix_solve_metric: %s is not finite' % name)
+    if not (np.all(D > 0) and np.all(alpha > 0)):
+        raise ValueError('fullmatrix_solve_metric: D and alpha must be positive')
+    maxiter, tol_h = int(maxiter), float(tol_h)
+    if maxiter < 0 or not (tol_h > 0 and np.isfinite(tol_h)):
+        raise ValueError('fullmatrix_solve_metric: maxiter must be >= 0 and tol_h positive and finite')
+    planes = 2 if use_complex else 1
+    if max(n_prob * n_alpha * planes * m * m * n_omega, n_prob * n_alpha * P * n_s, n_omega * n_s,
+           P * (P + 1) // 2 * n_omega) > 2 ** 31 - 1:
+        raise ValueError('fullmatrix_solve_metric: the arrays of this call hold more than 2^31 - 1 numbers')
+    lib = load_library()
+    if device_count() < 1:
+        raise MaxEntDeviceError('no HIP device visible; mxe_fullmatrix_solve_metric has no CPU fallback')
+    u = np.empty((n_prob, n_alpha, P, n_s))
+    H = np.empty((n_prob, n_alpha, planes, m, m, n_omega))
+    chi2, S, Q = (np.empty((n_prob, n_alpha)) for _ in range(3))
+    n_iter, conv = (np.empty((n_prob, n_alpha), dtype=np.int32) for _ in range(2))
+    ms = ctypes.c_float(0)
+    rc = lib.mxe_fullmatrix_solve_metric(int(device), n_prob, m, 1 if use_complex else 0, n_omega, n_s, n_alpha, _p(V), _p(R),
+                                         _p(A), _p(D), _p(alpha), _p(ghat), _p(cperp), _p(u0), maxiter, tol_h, _p(u), _p(H),
+                                         _p(chi2), _p(S), _p(Q), _p(n_iter), _p(conv), ctypes.byref(ms))
+    if rc != 0:
+        raise MaxEntDeviceError('mxe_fullmatrix_solve_metric failed: ' + lib.mxe_strerror(rc).decode())
     if timing is not None:
         timing['ms'] = float(ms.value)
     Hm = H[:, :, 0] + 1.0j * H[:, :, 1] if use_complex else H[:, :, 0]          # (n_prob, n_alpha, m, m, n_omega)

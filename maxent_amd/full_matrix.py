@@ -9,10 +9,13 @@ matrix elements, and the solution is Hermitian and positive semi-definite at eve
 exponential.  DESIGN 4z has the equations; ``mxe_fullmatrix_solve`` (maxent_amd/csrc/mxe_fullmatrix.hip.h) solves them,
 one workgroup per problem; there is no CPU path (``tests/fullmatrix_ref.py`` is a numpy truth for the tests).
 
-First version, everything else is refused with NotImplementedError or ValueError: G(tau) or Legendre data (a real kernel
-acting on a Hermitian A); one error -- a scalar or one value per tau -- shared by all matrix elements; the default model
-D(omega) times the unit matrix; M <= 4 and n_s <= 64.  Not supported: Matsubara and bosonic data, ``set_cov``, per-element
-errors, bins, preblur, a matrix-valued default model, the probability-based analyzers (Bryan, Classic) and ``probability=``.
+What it takes, everything else is refused with NotImplementedError or ValueError: G(tau) or Legendre data (a real kernel
+acting on a Hermitian A); one error -- a scalar or one value per tau -- shared by all matrix elements (``set_error``,
+``err=``), or one error bar per matrix element, sigma_ab or sigma_ab(tau) with sigma_ab = sigma_ba (``set_element_errors``,
+``element_err=``; ``mxe_fullmatrix_solve_metric``: a dense n_s x n_s metric per Hermitian component in the place of the
+diagonal S / sigma); the default model D(omega) times the unit matrix; M <= 4 and n_s <= 64.  Not supported: Matsubara and
+bosonic data, ``set_cov``, bins, preblur, a matrix-valued default model, the probability-based analyzers (Bryan, Classic)
+and ``probability=``.
 
 alpha is scaled by n_tau, the number of data of ONE matrix element (``scale_alpha='Ndata'``): block-diagonal data then
 decouple into exactly the ``DiagonalMaxEnt`` problems at the same mesh alpha.
@@ -65,13 +68,14 @@ def _check_G(G, use_complex, what):
 
 
 def _check_hermitian(G, err, what):
-    """G_ij = conj(G_ji) within the error: |G_ij - conj(G_ji)| <= 4 sqrt(2) err at every point"""
+    """G_ij = conj(G_ji) within the error: |G_ij - conj(G_ji)| <= 4 sqrt(2) err at every point; ``err``: a scalar, one
+    value per point, or (M, M, n), one per element and point"""
     asym = np.abs(G - np.conj(np.swapaxes(G, 0, 1)))
-    bound = 4.0 * np.sqrt(2.0) * np.asarray(err, dtype=float) * np.ones(G.shape[-1])
+    bound = np.broadcast_to(4.0 * np.sqrt(2.0) * np.asarray(err, dtype=float) * np.ones(G.shape[-1]), asym.shape)
     if np.any(asym > bound):
         i, j, k = (int(x) for x in np.argwhere(asym > bound)[0])
         raise ValueError('%s: G is not Hermitian within its error: |G[%d, %d] - conj(G[%d, %d])| = %.3g at point %d (error %.3g)'
-                         % (what, i, j, j, i, asym[i, j, k], k, bound[k] / (4.0 * np.sqrt(2.0))))
+                         % (what, i, j, j, i, asym[i, j, k], k, bound[i, j, k] / (4.0 * np.sqrt(2.0))))
 
 
 def whiten(U, S, V, err):
@@ -84,13 +88,70 @@ def whiten(U, S, V, err):
     return Uh, c, np.dot(V, Qt.T), Qt.T
 
 
-def full_matrix_continue(G_batch, U, S, V, D, alpha, err, use_complex=False, maxiter=1000, tol_h=1e-9, u0=None, device=0):
+def component_errors(err, M, use_complex, n=None):
+    """The error bars of the Hermitian components from those of the matrix elements.  ``err``: sigma_ab of shape (M, M) or
+    sigma_ab(t) of shape (M, M, n), positive, finite and symmetric, err[a, b] == err[b, a]: the standard deviation of the
+    real and of the imaginary part of the symmetrised G_ab(t).  Returns (P, n) in the order of :func:`hermitian_basis`
+    ((P, 1) for an (M, M) input when ``n`` is not given): sigma_aa for the diagonal units, sigma_ab for BOTH the symmetric
+    and the antisymmetric component of a pair a < b (the sqrt 2 of the basis cancels), so that the Frobenius misfit
+    sum_ab sum_t |G_ab - (K H)_ab|^2 / sigma_ab^2 is sum_p sum_t (g_p - K h_p)_t^2 / sigma_p(t)^2."""
+    e = np.asarray(err)
+    M = int(M)
+    if e.dtype.kind not in 'biuf' or e.ndim not in (2, 3) or e.shape[:2] != (M, M) or (e.ndim == 3 and e.shape[2] < 1):
+        raise ValueError('component_errors: the element errors must be real of shape (%d, %d) or (%d, %d, n); got %s %s'
+                         % (M, M, M, M, e.dtype, e.shape))
+    e = np.array(e, dtype=float)
+    if e.ndim == 2:
+        e = e[:, :, None]
+    if n is not None:
+        if e.shape[2] not in (1, int(n)):
+            raise ValueError('component_errors: %d data points, but the element errors have shape %s' % (n, np.shape(err)))
+        e = np.broadcast_to(e, (M, M, int(n)))
+    if not (np.all(np.isfinite(e)) and np.all(e > 0)):
+        raise ValueError('component_errors: the element errors must be positive and finite')
+    if not np.array_equal(e, np.swapaxes(e, 0, 1)):
+        raise ValueError('component_errors: the element errors must be symmetric, err[a, b] == err[b, a]')
+    pairs = [(a, b) for a in range(M) for b in range(a + 1, M)]
+    rows = [e[a, a] for a in range(M)] + [e[a, b] for a, b in pairs] * (2 if use_complex else 1)
+    return np.array(rows, dtype=float)
+
+
+def whiten_components(U, S, errp):
+    """The whitened problem of every component: diag(1 / sigma_p) U S = Q^_p R_p (thin QR), A_p = R_p^T R_p.  ``errp``:
+    (P, n) or (P, 1) from :func:`component_errors`.  Returns ``R`` (P, n_s, n_s), ``A`` (P, n_s, n_s), ``Qh`` (P, n, n_s).
+    V is not rotated: rho_p = R_p V^T H_p - Qh_p^T (G_p / sigma_p).  Components with the same errors share one
+    factorisation (the same bits)."""
+    U, S = np.asarray(U, dtype=float), np.asarray(S, dtype=float)
+    n, n_s = U.shape
+    if n < n_s:
+        raise ValueError('whiten_components: U must be (n_data, n_s) with n_data >= n_s; got %s' % (U.shape,))
+    errp = np.asarray(errp, dtype=float)
+    if errp.ndim != 2 or errp.shape[1] not in (1, n):
+        raise ValueError('whiten_components: the component errors must be (P, %d) or (P, 1); got %s' % (n, errp.shape))
+    P = errp.shape[0]
+    R, Qh = np.empty((P, n_s, n_s)), np.empty((P, n, n_s))
+    done = {}
+    for p in range(P):
+        key = errp[p].tobytes()
+        if key not in done:
+            done[key] = np.linalg.qr((U * S) / (errp[p] * np.ones(n))[:, None])
+        Qh[p], R[p] = done[key]
+    return R, np.einsum('pks,pkt->pst', R, R), Qh
+
+
+def full_matrix_continue(G_batch, U, S, V, D, alpha, err=None, use_complex=False, maxiter=1000, tol_h=1e-9, u0=None, device=0,
+                         element_err=None):
     """The batch behind :class:`FullMatrixMaxEnt`: every G of ``G_batch`` (n_prob, M, M, n_data) -- k-points, mock data sets,
     iterations of a self-consistency loop -- is continued as a whole matrix, one workgroup per problem in one launch of
     ``mxe_fullmatrix_solve``.  They share the truncated SVD ``U`` (n_data, n_s), ``S``, ``V`` (n_omega, n_s) of the kernel
     that maps H = A delta_omega to the data, the default model ``D`` (n_omega,; times delta omega), the mesh ``alpha``
     (already scaled by the number of data of one element) and ``err`` (a scalar or one value per data point).  ``u0``: the
     start of the first alpha, (n_prob, P, n_s) in the basis of ``V``.  A problem's bits do not depend on the batch.
+
+    ``element_err`` in the place of ``err`` (giving both is an error): one error bar per matrix element, (M, M) or
+    (M, M, n_data), symmetric (:func:`component_errors`).  The job then always runs on ``mxe_fullmatrix_solve_metric``, also
+    when all errors are equal; ``V`` is never rotated, so ``u`` and ``u0`` are in the basis of ``V`` as given; everything
+    below holds unchanged.
 
     Returns a dict: ``u`` (n_prob, n_alpha, P, n_s), the coordinates of Gamma = log(H / D) in the basis of ``V`` and of
     :func:`hermitian_basis`; ``H`` (n_prob, M, M, n_alpha, n_omega), complex with ``use_complex``, exactly Hermitian and
@@ -122,10 +183,31 @@ def full_matrix_continue(G_batch, U, S, V, D, alpha, err, use_complex=False, max
     if D.shape != (V.shape[0],):
         raise NotImplementedError('full_matrix_continue: the default model must be one D(omega) of shape (%d,), shared by the '
                                   'diagonal elements; a matrix-valued model is not supported; got %s' % (V.shape[0], D.shape))
+    if element_err is not None:
+        if err is not None:
+            raise ValueError('full_matrix_continue: give err (one error for all matrix elements) or element_err (one per '
+                             'element), not both')
+        errp = component_errors(element_err, M, use_complex, n)            # (P, n)
+        sigma = np.broadcast_to(np.asarray(element_err, dtype=float).reshape(M, M, -1), (M, M, n))
+        for g in G:
+            _check_hermitian(g, sigma, 'full_matrix_continue')
+        G = 0.5 * (G + np.conj(np.swapaxes(G, 1, 2)))
+        Gw = np.einsum('pba,nabt->npt', hermitian_basis(M, use_complex), G).real / errp
+        Rm, Am, Qh = whiten_components(U, S, errp)
+        ghat = np.einsum('pts,npt->nps', Qh, Gw)                           # (n_prob, P, n_s)
+        cperp = np.maximum(np.sum(Gw ** 2, axis=(1, 2)) - np.sum(ghat ** 2, axis=(1, 2)), 0.0)
+        t = {}
+        out = _dev.fullmatrix_solve_metric(V, Rm, Am, D, alpha, ghat, cperp, M, use_complex, u0=u0, maxiter=maxiter,
+                                           tol_h=tol_h, device=device, timing=t)
+        out['alpha'] = np.array(alpha, dtype=float)
+        out['ms'] = t.get('ms', 0.0)
+        return out
+    if err is None:
+        raise ValueError('full_matrix_continue: no error; give err or element_err')
     err = np.asarray(err, dtype=float)
     if err.ndim > 1 or (err.ndim == 1 and err.shape != (n,)):
         raise ValueError('full_matrix_continue: one error for all data or one per data point, shared by all matrix elements; '
-                         'per-element errors are not supported; got shape %s' % (err.shape,))
+                         'per-element errors are not supported here (use element_err=); got shape %s' % (err.shape,))
     if not (np.all(np.isfinite(err)) and np.all(err > 0)):
         raise ValueError('full_matrix_continue: the error must be positive and finite')
     for g in G:
@@ -188,6 +270,7 @@ class FullMatrixMaxEnt(object):
         object.__setattr__(self, 'use_complex', bool(use_complex))
         object.__setattr__(self, 'tol_h', float(tol_h))
         object.__setattr__(self, 'G_mat', None)
+        object.__setattr__(self, 'element_err', None)
         object.__setattr__(self, 'maxent_result', None)
         object.__setattr__(self, 'last_info', None)
 
@@ -195,7 +278,7 @@ class FullMatrixMaxEnt(object):
         if name in _REFUSED:
             def refuse(*args, **kwargs):
                 raise NotImplementedError('FullMatrixMaxEnt: %s not supported yet (G(tau) and Legendre data with one '
-                                          'error for all matrix elements are)' % ('%s: %s is' % (name, _REFUSED[name])))
+                                          'error for all matrix elements, or one per element, are)' % ('%s: %s is' % (name, _REFUSED[name])))
             return refuse
         return getattr(object.__getattribute__(self, 'maxent'), name)
 
@@ -231,10 +314,24 @@ class FullMatrixMaxEnt(object):
         """one standard deviation for all data or one per data point, shared by all matrix elements"""
         if np.ndim(error) > 1:
             raise ValueError('FullMatrixMaxEnt.set_error: one error for all matrix elements (a scalar or one value per data '
-                             'point); per-element errors are not supported; got shape %s' % (np.shape(error),))
+                             'point); per-element errors are not supported here (use set_element_errors); got shape %s'
+                             % (np.shape(error),))
         if self.G_mat is None:
             raise ValueError('FullMatrixMaxEnt.set_error: set the data first')
         self.maxent.set_error(error)
+        object.__setattr__(self, 'element_err', None)
+
+    def set_element_errors(self, error):
+        """one standard deviation per matrix element, (M, M) or (M, M, n) with error[a, b] == error[b, a]: that of the real
+        and of the imaginary part of the symmetrised G_ab (:func:`component_errors`).  Replaces an earlier ``set_error``, as
+        a later ``set_error`` replaces this.  The job runs on ``mxe_fullmatrix_solve_metric``."""
+        if self.G_mat is None:
+            raise ValueError('FullMatrixMaxEnt.set_element_errors: set the data first')
+        M, n = self.G_mat.shape[0], self.G_mat.shape[-1]
+        component_errors(error, M, self.use_complex, n)                      # (every refusal)
+        e = np.array(np.broadcast_to(np.asarray(error, dtype=float).reshape(M, M, -1), (M, M, n)))
+        self.maxent.set_error(np.array(e[0, 0]))      # (the worker's own error: what scale_alpha and _job look at)
+        object.__setattr__(self, 'element_err', e)
 
     # ---- the job --------------------------------------------------------------------------------------------------------
     def _job(self):
@@ -267,7 +364,9 @@ class FullMatrixMaxEnt(object):
                              % (len(K.S), loop.reduce_singular_space, MAX_NS, _dev.fullmatrix_P(self.G_mat.shape[0], self.use_complex)))
         scale = loop._alpha_scale()
         return dict(U=np.asarray(K.U, dtype=float), S=np.asarray(K.S, dtype=float), V=np.asarray(K.V, dtype=float), D=D,
-                    alpha=np.asarray(loop.alpha_mesh, dtype=float) * scale, err=np.asarray(loop.err, dtype=float),
+                    alpha=np.asarray(loop.alpha_mesh, dtype=float) * scale,
+                    err=None if self.element_err is not None else np.asarray(loop.err, dtype=float),
+                    element_err=self.element_err,
                     maxiter=int(getattr(loop.minimizer, 'maxiter', 1000)))
 
     def run(self):
@@ -280,7 +379,7 @@ class FullMatrixMaxEnt(object):
         t0 = datetime.now()
         sol = full_matrix_continue(self.G_mat[None], job['U'], job['S'], job['V'], job['D'], job['alpha'], job['err'],
                                    use_complex=self.use_complex, maxiter=job['maxiter'], tol_h=self.tol_h,
-                                   device=loop.device_id)
+                                   device=loop.device_id, element_err=job['element_err'])
         t1 = datetime.now()
         H = sol['H'][0]
         delta = np.asarray(w.omega.delta, dtype=float)
@@ -301,7 +400,9 @@ class FullMatrixMaxEnt(object):
             res._default_analyzer_name = loop.analyzers[0].name
         res.analyze(loop.analyzers)
         object.__setattr__(self, 'maxent_result', res)
-        object.__setattr__(self, 'last_info', dict(kernel_ms=sol['ms'], n_iter=sol['n_iter'][0], converged=sol['converged'][0]))
+        object.__setattr__(self, 'last_info', dict(kernel_ms=sol['ms'], n_iter=sol['n_iter'][0], converged=sol['converged'][0],
+                                                      kernel='mxe_fullmatrix_solve' if job['element_err'] is None
+                                                      else 'mxe_fullmatrix_solve_metric'))
         return res
 
     def positivity(self, result=None, alpha=None, floor=0.0, keep_vectors=False):
