@@ -312,8 +312,6 @@ struct mxe_ctx {
     DevBuf<int> dfin_elem, dfin_prob0, dfin_len, dfin_v0;       // mxe_chains_finish: one piece per alpha that is solved again
     DevBuf<double> dfin_start;          //   and its start vector (the state the lock-step kernel left)
     int sel3_nc = 0;                    // scans of the launch the last mxe_select3_launch chose for (0: none since the chains were uploaded)
-    int last_finished = 0;              // alphas the last mxe_chains_finish solved again
-    int last_rungs = 0;                 //   rungs it laid between them (coarse meshes)
     bool has_init = false;
     // mxe_eval_batch / mxe_audit scratch
     DevBuf<double> ev_x, ev_alpha, ev_scal, ev_vecw, ev_vecs, ev_mat;
@@ -535,6 +533,13 @@ template <int NW>
 hipError_t launch_nab(int NP, const KParams& kp, size_t lds, hipStream_t s)
 {
     return (NP == 64) ? launch_t<NW, 2>(kp, lds, s) : launch_t<NW, 4>(kp, lds, s);
+}
+
+// a host vector into a buffer of the context, on its stream (the vector has to outlive the copy: stream_wait)
+template <class Buf, class Vec> hipError_t put(mxe_ctx* ctx, Buf& buf, const Vec& vec)
+{
+    if (const hipError_t e = buf.ensure(vec.size()); e != hipSuccess || vec.empty()) return e;
+    return hipMemcpyAsync(buf.p, vec.data(), vec.size() * sizeof(vec[0]), hipMemcpyHostToDevice, ctx->stream);
 }
 
 } // namespace
@@ -1058,6 +1063,13 @@ void read_plan_env(mxe::PlanEnv& env)
     env.no_lds_basis = getenv("MXE_NO_LDS_BASIS") != nullptr; env.no_split_by_kind = getenv("MXE_NO_SPLIT_BY_KIND") != nullptr;
     env.no_ladder = getenv("MXE_NO_LADDER") != nullptr; env.no_na64 = getenv("MXE_NO_NA64") != nullptr; env.no_sorted_static = getenv("MXE_NO_SORTED_STATIC") != nullptr;
 }
+// ... and of the plan of the finishing pass: the only environment reads of mxe_chains_finish's decisions (plan_finish clamps)
+void read_finish_env(mxe::FinishEnv& env)
+{
+    if (const char* e = getenv("MXE_FIN_RATIO")) env.ratio = atof(e);
+    if (const char* e = getenv("MXE_FIN_RUNG_ITERS")) env.rung_iters = atoi(e);
+    env.no_ladder = getenv("MXE_NO_FINISH_LADDER") != nullptr;
+}
 }  // namespace
 
 // Stages the chains of a launch.  What is launched -- pieces, kernel, layout, order -- is decided by mxe::plan_launch
@@ -1139,25 +1151,21 @@ try {
     ctx->wgpc_auto = plan.wgpc_auto; ctx->mc_wgpc_hint = plan.mc_wgpc_hint; ctx->n_wg = plan.n_wg; ctx->n_wg2 = plan.n_wg2; ctx->wgpc2 = plan.wgpc2;
     ctx->n_solo = n_solo; ctx->placement_checked = placement_checked;
     // ---- 7. buffers
-    auto put = [&](auto& buf, const auto& vec) -> hipError_t {
-        if (const hipError_t e = buf.ensure(vec.size()); e != hipSuccess || vec.empty()) return e;
-        return hipMemcpyAsync(buf.p, vec.data(), vec.size() * sizeof(vec[0]), hipMemcpyHostToDevice, ctx->stream);
-    };
-    HIPCHK(ctx, ctx->dcounter.ensure(4)); HIPCHK(ctx, put(ctx->dqueue, ctx->queue));
+    HIPCHK(ctx, ctx->dcounter.ensure(4)); HIPCHK(ctx, put(ctx, ctx->dqueue, ctx->queue));
     // both words of the counter pair start at what a launch of this plan draws from (mxe_chains_launch: counter0); from then on
     // every launch re-arms the word of the next one
     const int counter0 = (ctx->n_queue > 0 && ctx->mc_wgpc == 2 && n_solo > 0) ? (ctx->n_wg - n_solo) * 4 : 0;
     const std::vector<int> counter_words = {counter0, counter0, 0, 0};
     ctx->counter_armed = -1; ctx->counter_par = 0;
-    HIPCHK(ctx, put(ctx->dcounter, counter_words));
- HIPCHK(ctx, put(ctx->dwg_chains, ctx->wg_chains));
-    HIPCHK(ctx, put(ctx->dchain_elem, ctx->sub_elem)); HIPCHK(ctx, put(ctx->dsub_prob0, ctx->sub_prob0));
-    HIPCHK(ctx, put(ctx->dsub_len, ctx->sub_len)); HIPCHK(ctx, put(ctx->dsub_v0, ctx->sub_v0));
+    HIPCHK(ctx, put(ctx, ctx->dcounter, counter_words));
+    HIPCHK(ctx, put(ctx, ctx->dwg_chains, ctx->wg_chains));
+    HIPCHK(ctx, put(ctx, ctx->dchain_elem, ctx->sub_elem)); HIPCHK(ctx, put(ctx, ctx->dsub_prob0, ctx->sub_prob0));
+    HIPCHK(ctx, put(ctx, ctx->dsub_len, ctx->sub_len)); HIPCHK(ctx, put(ctx, ctx->dsub_v0, ctx->sub_v0));
     HIPCHK(ctx, ctx->dsub_pre.ensure(n_sub));
-    if (ctx->has_pre || ctx->mc_gst) HIPCHK(ctx, put(ctx->dsub_pre, ctx->sub_pre));     // (the device-memory-state build is the LEAD build: it reads the array)
-    if (ctx->has_walk && ctx->has_pre) { HIPCHK(ctx, put(ctx->dsub_walk0, ctx->sub_walk0)); HIPCHK(ctx, put(ctx->dwalk_alpha, ctx->walk_alpha)); }
-    if (!ctx->excluded.empty()) HIPCHK(ctx, put(ctx->dexcluded, ctx->excluded));
-    HIPCHK(ctx, put(ctx->dalpha, alpha_dev)); HIPCHK(ctx, put(ctx->dv0, hv0)); HIPCHK(ctx, ctx->dout_v.ensure(P * NP));
+    if (ctx->has_pre || ctx->mc_gst) HIPCHK(ctx, put(ctx, ctx->dsub_pre, ctx->sub_pre));     // (the device-memory-state build is the LEAD build: it reads the array)
+    if (ctx->has_walk && ctx->has_pre) { HIPCHK(ctx, put(ctx, ctx->dsub_walk0, ctx->sub_walk0)); HIPCHK(ctx, put(ctx, ctx->dwalk_alpha, ctx->walk_alpha)); }
+    if (!ctx->excluded.empty()) HIPCHK(ctx, put(ctx, ctx->dexcluded, ctx->excluded));
+    HIPCHK(ctx, put(ctx, ctx->dalpha, alpha_dev)); HIPCHK(ctx, put(ctx, ctx->dv0, hv0)); HIPCHK(ctx, ctx->dout_v.ensure(P * NP));
     // the logarithms of the mesh for linefit_kernel: this is the only writer of dalpha, so the table cannot go stale
     HIPCHK(ctx, ctx->dalpha_log.ensure(2 * P));
     hipLaunchKernelGGL(mxe::alpha_log_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, ctx->stream, ctx->dalpha.p, ctx->dalpha_log.p, P);
@@ -1174,8 +1182,8 @@ try {
     if (ctx->lv_mode == 2) {
         e2.resize(P); p2.resize(P); l2.assign(P, 1);
         for (size_t i = 0; i < P; ++i) { e2[i] = elem_of_chain[i / n_alpha]; p2[i] = (int)i; }
-        HIPCHK(ctx, put(ctx->d2_elem, e2)); HIPCHK(ctx, put(ctx->d2_len, l2));
-        HIPCHK(ctx, put(ctx->d2_prob0, p2)); HIPCHK(ctx, put(ctx->d2_v0, p2)); HIPCHK(ctx, put(ctx->d2_queue, p2));
+        HIPCHK(ctx, put(ctx, ctx->d2_elem, e2)); HIPCHK(ctx, put(ctx, ctx->d2_len, l2));
+        HIPCHK(ctx, put(ctx, ctx->d2_prob0, p2)); HIPCHK(ctx, put(ctx, ctx->d2_v0, p2)); HIPCHK(ctx, put(ctx, ctx->d2_queue, p2));
         HIPCHK(ctx, ctx->dcnt1_niter.ensure(P)); HIPCHK(ctx, ctx->dcnt1_nevals.ensure(P));
     }
     HIPCHK(ctx, stream_wait(ctx->stream));          // (the host vectors go out of scope)
@@ -1223,6 +1231,58 @@ static void fill_kparams(mxe_ctx* ctx, KParams& kp)
     kp.out_index = nullptr;
     kp.dbg_hist = nullptr;
     { const char* e = getenv("MXE_STUCK_SKIP"); kp.stuck_skip = e ? atoi(e) : 1; }
+}
+// other pieces for the kernel parameters of the staged chains (the second pass of a two-pass launch, the finishing pass): n
+// plain pieces -- nothing led, no walk, no start states -- whose start vectors are the rows v0[v0_row[.]]
+static void set_pieces(KParams& kp, int n, const int* elem, const int* prob0, const int* len, const int* v0_row, const double* v0)
+{
+    kp.chain_elem = elem; kp.chain_prob0 = prob0; kp.chain_len = len; kp.chain_v0 = v0_row; kp.v0 = v0;
+    kp.chain_lead = nullptr; kp.init_tab = nullptr; kp.chain_init = nullptr; kp.chain_walk0 = nullptr; kp.walk_alpha = nullptr;
+    kp.n_chain = n;
+}
+// Waves of a lock-step workgroup.  Eight (four helpers for the streaming passes) where the launch runs one workgroup per
+// CU, i.e. does not fill the GPU and is as long as its deepest chain of rounds; mxe_opts.waves_per_chain = 4 / 8
+// overrides (the passes of that build want n_omega_pad in units of 256)
+static int lockstep_waves(int NA, int nwp, int wgpc, bool gst, int waves_per_chain = 0)
+{
+    return (NA == 32 && wgpc == 1 && nwp % 256 == 0 && waves_per_chain != 4 && mc_lds_bytes(NA, nwp, 1, 8, gst) <= mxe::LDS_MC1) ? 8 : 4;
+}
+// The build of the one-chain kernel for kp.n_chain chains: NW waves per chain, halved down to nw_min until the LDS takes
+// the chain.  A frequency mesh whose omega-space state (five arrays per chain) does not fit it even then: the state goes to
+// device memory (four waves per chain; one where the 128 x 128 Newton matrix leaves no room for more) -- kp.gstate.
+struct OneChainBuild { int NW; bool gst; size_t lds; };
+static int one_chain_build(mxe_ctx* ctx, KParams& kp, int NW, int nw_min, bool f32, OneChainBuild& b)
+{
+    size_t lds = lds_bytes(ctx->NP, ctx->nwp, NW, f32);
+    while (lds > mxe::LDS_CU && NW > nw_min) { NW /= 2; lds = lds_bytes(ctx->NP, ctx->nwp, NW, f32); }
+    const bool gst = lds > mxe::LDS_CU;
+    if (gst) {
+        NW = (ctx->NP == 64) ? 4 : 1;
+        lds = lds_bytes(ctx->NP, ctx->nwp, NW, f32, true);
+        if (lds > mxe::LDS_CU) return MXE_ERR_LIMIT;
+        HIPCHK(ctx, ctx->dgstate.ensure((size_t)kp.n_chain * 5 * ctx->nwp));     // (binary32 build: half of it used)
+        kp.gstate = ctx->dgstate.p;
+    }
+    b = OneChainBuild{NW, gst, lds};
+    return MXE_OK;
+}
+static hipError_t launch_one_chain(const mxe_ctx* ctx, const KParams& kp, const OneChainBuild& b, bool f32)
+{
+    hipStream_t s = ctx->stream;
+    if (b.gst) {
+        if (f32) return launch_t<4, 2, float, true>(kp, b.lds, s);
+        return (ctx->NP == 64) ? launch_t<4, 2, double, true>(kp, b.lds, s) : launch_t<1, 4, double, true>(kp, b.lds, s);
+    }
+    if (f32) switch (b.NW) {
+        case 1: return launch_t<1, 2, float>(kp, b.lds, s);
+        case 2: return launch_t<2, 2, float>(kp, b.lds, s);
+        default: return launch_t<4, 2, float>(kp, b.lds, s);
+    }
+    switch (b.NW) {
+        case 1: return launch_nab<1>(ctx->NP, kp, b.lds, s);
+        case 2: return launch_nab<2>(ctx->NP, kp, b.lds, s);
+        default: return launch_nab<4>(ctx->NP, kp, b.lds, s);
+    }
 }
 
 namespace {
@@ -1307,9 +1367,6 @@ try {
     hipError_t e;
     if (ctx->mc_na > 0) {
         // four chains per workgroup, lock-step (mxe_kernel_mc.hip.h)
-        // Eight waves per workgroup (four helpers for the streaming passes) where the launch runs one workgroup per
-        // CU, i.e. does not fill the GPU and is as long as its deepest chain of rounds; mxe_opts.waves_per_chain = 4 / 8
-        // overrides (the passes of that build want n_omega_pad in units of 256)
         if (ctx->lv_mode != 0) {
             // V^T resident in LDS as binary32 (mxe_kernel_lv.hip.h): the launch itself (precision = F32) or the first pass
             // of a binary64 launch that does not fill the GPU
@@ -1342,14 +1399,11 @@ try {
                 // second pass: every alpha a piece of its own in the binary64 lock-step kernel, from the v of the first
                 const size_t Pn = (size_t)ctx->n_chain * ctx->n_alpha;
                 const int W2 = ctx->wgpc2;
-                const int NWV2 = (W2 == 1 && ctx->nwp % 256 == 0 && mc_lds_bytes(32, ctx->nwp, 1, 8) <= 160 * 1024 - 6144) ? 8 : 4;
+                const int NWV2 = lockstep_waves(32, ctx->nwp, W2, false);
                 const size_t lds = mc_lds_bytes(32, ctx->nwp, W2, NWV2);
-                if (lds > 160 * 1024 - 6144) return MXE_ERR_LIMIT;
+                if (lds > mxe::LDS_MC1) return MXE_ERR_LIMIT;
                 KParams k2 = kp;
-                k2.chain_elem = ctx->d2_elem.p; k2.chain_prob0 = ctx->d2_prob0.p; k2.chain_len = ctx->d2_len.p;
-                k2.chain_v0 = ctx->d2_v0.p; k2.v0 = ctx->dout_v.p;
-                k2.chain_lead = nullptr; k2.init_tab = nullptr; k2.chain_init = nullptr; k2.chain_walk0 = nullptr; k2.walk_alpha = nullptr;
-                k2.n_chain = (int)Pn;
+                set_pieces(k2, (int)Pn, ctx->d2_elem.p, ctx->d2_prob0.p, ctx->d2_len.p, ctx->d2_v0.p, ctx->dout_v.p);
                 k2.prof = nullptr;                  // (diagnostic build: the stamps of the first pass stay)
                 mxe::MCExtra e2 = ex;
                 e2.n_wg = ctx->n_wg2;
@@ -1372,10 +1426,9 @@ try {
         }
         const int NA = ctx->mc_na, WGPC = ctx->mc_wgpc;
         const bool GST = ctx->mc_gst;
-        const int NWV = (NA == 32 && WGPC == 1 && ctx->nwp % 256 == 0 && o.waves_per_chain != 4 &&
-                         mc_lds_bytes(NA, ctx->nwp, 1, 8, GST) <= 160 * 1024 - 6144) ? 8 : 4;
+        const int NWV = lockstep_waves(NA, ctx->nwp, WGPC, GST, o.waves_per_chain);
         const size_t lds = mc_lds_bytes(NA, ctx->nwp, WGPC, NWV, GST);
-        if (lds > 160 * 1024 - 6144) return MXE_ERR_LIMIT;
+        if (lds > mxe::LDS_MC1) return MXE_ERR_LIMIT;
         mxe::MCExtra ex; ex.wg_chains = ctx->dwg_chains.p; ex.n_wg = ctx->n_wg;
         ex.gstate = nullptr; ex.gstate_stride = 0;
         if (GST) {
@@ -1443,40 +1496,12 @@ try {
             NW = (nc >= 2048) ? 1 : (nc >= 1024) ? 2 : 4;
         }
         const bool f32 = (o.precision == MXE_PRECISION_F32);
-        size_t lds = lds_bytes(ctx->NP, ctx->nwp, NW, f32);
-        while (lds > 160 * 1024 && NW > 1) { NW /= 2; lds = lds_bytes(ctx->NP, ctx->nwp, NW, f32); }
-        // a frequency mesh whose omega-space state (five arrays per chain) does not fit the LDS: the state goes to
-        // device memory (four waves per chain; one where the 128 x 128 Newton matrix leaves no room for more)
-        const bool gst = lds > 160 * 1024;
-        if (gst) {
-            NW = (ctx->NP == 64) ? 4 : 1;
-            lds = lds_bytes(ctx->NP, ctx->nwp, NW, f32, true);
-            if (lds > 160 * 1024) return MXE_ERR_LIMIT;
-            HIPCHK(ctx, ctx->dgstate.ensure((size_t)ctx->n_sub * 5 * ctx->nwp));     // (binary32 build: half of it used)
-            kp.gstate = ctx->dgstate.p;
-        }
-        ctx->last_nw = NW; ctx->last_lds = (int)lds;
-        ctx->last_kernel = "mxe::chain_kernel<" + std::to_string(NW) + ", " + std::to_string(ctx->NP / 32) + (f32 ? ", float" : ", double") + (gst ? ", device-memory state>" : ">");
+        OneChainBuild b;
+        if (const int rc = one_chain_build(ctx, kp, NW, 1, f32, b); rc != MXE_OK) return rc;
+        ctx->last_nw = b.NW; ctx->last_lds = (int)b.lds;
+        ctx->last_kernel = "mxe::chain_kernel<" + std::to_string(b.NW) + ", " + std::to_string(ctx->NP / 32) + (f32 ? ", float" : ", double") + (b.gst ? ", device-memory state>" : ">");
         HIPCHK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-        if (gst) {
-            if (f32) e = launch_t<4, 2, float, true>(kp, lds, ctx->stream);
-            else e = (ctx->NP == 64) ? launch_t<4, 2, double, true>(kp, lds, ctx->stream) : launch_t<1, 4, double, true>(kp, lds, ctx->stream);
-        } else
-        if (f32) {
-            switch (NW) {
-                case 1: e = launch_t<1, 2, float>(kp, lds, ctx->stream); break;
-                case 2: e = launch_t<2, 2, float>(kp, lds, ctx->stream); break;
-                case 4: e = launch_t<4, 2, float>(kp, lds, ctx->stream); break;
-                default: e = launch_t<4, 2, float>(kp, lds, ctx->stream); break;
-            }
-        } else
-        switch (NW) {
-            case 1: e = launch_nab<1>(ctx->NP, kp, lds, ctx->stream); break;
-            case 2: e = launch_nab<2>(ctx->NP, kp, lds, ctx->stream); break;
-            case 4: e = launch_nab<4>(ctx->NP, kp, lds, ctx->stream); break;
-            default: e = launch_nab<4>(ctx->NP, kp, lds, ctx->stream); break;
-        }
-        HIPCHK(ctx, e);
+        HIPCHK(ctx, launch_one_chain(ctx, kp, b, f32));
     }
     HIPCHK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
     ctx->launched = true;
@@ -1497,142 +1522,61 @@ int mxe_sync(mxe_ctx* ctx)
 // Newton matrix that costs nothing where the system is well conditioned and stalls the iteration where it is not
 // (few data points, small alpha: tens to hundreds of iterations per alpha where the binary64 Gram matrix of the
 // one-chain kernel takes five); it stops an alpha after MC_MAXITER iterations.  Blocking; a no-op after a launch of
-// the one-chain layout and when everything converged.
+// the one-chain layout and when everything converged.  Which alphas, as which warm chains, over which rungs and with what
+// budgets is decided by mxe::plan_finish (mxe_plan.h) from numbers alone; this function checks, reads the records back,
+// asks, and carries the plan out.
 int mxe_chains_finish(mxe_ctx* ctx, int32_t* n_resolved)
 try {
+    // ---- 1. checks
     if (n_resolved) *n_resolved = 0;
     if (!ctx) return MXE_ERR_ARG;
     if (!ctx->launched) return MXE_ERR_STATE;
-    ctx->last_finished = 0;
     if (ctx->mc_na == 0) return MXE_OK;                       // the launch was in the one-chain layout
     HIPCHK(ctx, hipSetDevice(ctx->device));
     HIPCHK(ctx, stream_wait(ctx->stream));
-    const mxe_opts& o = ctx->opts;
+    // ---- 2. the records of the lock-step pass (the flags first: when everything converged nothing else is read)
     const size_t P = (size_t)ctx->n_chain * ctx->n_alpha;
+    const int NP = ctx->NP;
     std::vector<int> conv(P), nit(P), nev(P);
     HIPCHK(ctx, hipMemcpy(conv.data(), ctx->dout_conv.p, P * sizeof(int), hipMemcpyDeviceToHost));
-    std::vector<int> todo;
-    for (size_t i = 0; i < P; ++i) if (!conv[i]) todo.push_back((int)i);
-    if (todo.empty()) return MXE_OK;
+    if (std::find(conv.begin(), conv.end(), 0) == conv.end()) return MXE_OK;
+    std::vector<double> halpha(P);
     HIPCHK(ctx, hipMemcpy(nit.data(), ctx->dout_niter.p, P * sizeof(int), hipMemcpyDeviceToHost));
     HIPCHK(ctx, hipMemcpy(nev.data(), ctx->dout_nevals.p, P * sizeof(int), hipMemcpyDeviceToHost));
-    // (an alpha that used up the caller's own maxiter stays as it is)
-    std::vector<char> open(P, 0);
-    int n = 0;
-    for (int i : todo) if (nit[i] < o.maxiter) { open[i] = 1; ++n; }
-    if (n == 0) return MXE_OK;
-    ctx->pre_d = nullptr; ctx->pre_i = nullptr; ctx->pre_rows = nullptr; ctx->pre_index = false;   // (what was copied out behind the launch is about to change)
-    // The alphas to solve again, as the reference would have reached them: every run of consecutive open alphas of a scan is
-    // ONE warm-started chain that begins at the solution of the alpha before it (a converged neighbour: 3-5 iterations
-    // per alpha, where the cold-started piece the lock-step kernel gave up on was stuck far from the minimiser -- on inputs
-    // whose error bar lies far below their noise a cold start does not get there in thousands of evaluations, the
-    // reference's warm scan does: tests/golden/stress_reference.npz); a run at the head of a scan starts from the state its
-    // first alpha was left in.
-    const int NP = ctx->NP, na = ctx->n_alpha;
-    std::vector<int> f_elem, f_prob0, f_len, f_v0;
-    std::vector<size_t> f_src;                       // row of dout_v the run starts from
-    // The entries of the chains: the open alphas of the mesh and -- where the mesh is too coarse to step on (round 5) -- RUNGS in
-    // between.  What is left to this pass lies deep in the region where the entropy term no longer holds the solution (or couples
-    // more directions than the lock-step layout takes); there a warm step over the factor 1.9 of the reference's default mesh
-    // (alpha_meshes.py:81: 20 alphas from 20 down to 1e-4) took 500-2 300 evaluations where ten steps of 10 % take 35 each
-    // (profiles/r05_b_coarse_mesh.txt, tools/stress.py case 17).  A step over more than FIN_COARSE is therefore cut into equal
-    // rungs of at most FIN_RATIO; a rung gets FIN_RUNG_ITERS iterations, no record, and its cost is counted with the alpha it leads to.
-    constexpr double FIN_COARSE = 1.6;
-    const double FIN_RATIO = getenv("MXE_FIN_RATIO") ? std::max(1.05, atof(getenv("MXE_FIN_RATIO"))) : 1.3;
-    const int FIN_RUNG_ITERS = getenv("MXE_FIN_RUNG_ITERS") ? std::max(1, atoi(getenv("MXE_FIN_RUNG_ITERS"))) : 10;
-    constexpr int FIN_RUNGS_MAX = 40;
-    const bool rungs_ok = !getenv("MXE_NO_FINISH_LADDER");
-    std::vector<double> halpha(P);
     HIPCHK(ctx, hipMemcpy(halpha.data(), ctx->dalpha.p, P * sizeof(double), hipMemcpyDeviceToHost));
-    std::vector<double> e_alpha;                     // per entry
-    std::vector<int> e_out, e_budget;
-    int n_rungs = 0;
-    for (int c = 0; c < ctx->n_chain; ++c)
-        for (int i = 0; i < na; ) {
-            if (!open[(size_t)c * na + i]) { ++i; continue; }
-            int j = i;
-            while (j < na && open[(size_t)c * na + j]) ++j;
-            f_elem.push_back(ctx->chain_elem[c]); f_prob0.push_back((int)e_alpha.size());
-            f_v0.push_back((int)f_v0.size());
-            // (a run at the head of a scan starts from the state its first alpha was left in -- if it was ever evaluated: a led piece
-            //  that gives up during its WALK leaves no record of its own alpha, and the vector in the result buffer is then whatever
-            //  the block held before: the start vector of the scan instead.  SIZE_MAX marks that)
-            const size_t p_head = (size_t)c * na + i;
-            f_src.push_back(i > 0 ? p_head - 1 : ((nit[p_head] > 0 || nev[p_head] > 0) ? p_head : (size_t)-1 - (size_t)c));
-            if (rungs_ok && i == 0 && f_src.back() > (size_t)-1 - (size_t)ctx->n_chain - 1) {
-                // a run that begins at the head of a scan from the default model, deep in the hard region (an ascending mesh, or a
-                // mesh that lies there altogether): rungs from N_data / 4 down to its first alpha, like the led pieces of the
-                // lock-step kernel (mxe_plan.h: emit_scan) -- the cold start at alpha~ = 0.5 of tools/stress.py case 17 ran
-                // into maxiter
-                const double a_to = halpha[p_head];
-                const double a_from = 0.25 * ctx->ds[ctx->elem_ds[ctx->chain_elem[c]]].n_rows;
-                // (only where the mesh goes on FINE from there -- the rising mesh of case 17: 148 -> 150 of 150 converged, 61 -> 8 ms;
-                //  case 5: 29 -> 4.5 ms.  With three alphas five decades apart, alpha~ = 0.06 at sigma = 1e-5 on 40 data points, the
-                //  cold start with its full budget converged 129 of 192 and the rungs 99-108 at any ratio and budget tried: case 93)
-                const bool fine_head = na > 1 && std::max(halpha[p_head + 1] / a_to, a_to / halpha[p_head + 1]) <= FIN_COARSE;
-                if (fine_head && a_to * FIN_RATIO * FIN_RATIO < a_from) {
-                    int m = (int)std::ceil(std::log(a_from / a_to) / std::log(FIN_RATIO) - 1e-9);
-                    m = std::max(2, std::min(m, FIN_RUNGS_MAX + 1));
-                    const double q = std::pow(a_to / a_from, 1.0 / m);
-                    for (int s2 = 0; s2 < m; ++s2) {
-                        e_alpha.push_back(a_from * std::pow(q, s2)); e_out.push_back(-1); e_budget.push_back(s2 == 0 ? 3 * FIN_RUNG_ITERS : FIN_RUNG_ITERS);
-                        ++n_rungs;
-                    }
-                }
-            }
-            for (int k = i; k < j; ++k) {
-                const size_t pk = (size_t)c * na + k;
-                if (rungs_ok && k > 0) {
-                    const double a_from = halpha[pk - 1], a_to = halpha[pk];
-                    const double r = a_from > a_to ? a_from / a_to : a_to / a_from;
-                    if (r > FIN_COARSE) {
-                        int m = (int)std::ceil(std::log(r) / std::log(FIN_RATIO) - 1e-9);          // steps, the last of them the alpha itself
-                        m = std::max(2, std::min(m, FIN_RUNGS_MAX + 1));
-                        const double q = std::pow(a_to / a_from, 1.0 / m);
-                        for (int s2 = 1; s2 < m; ++s2) {
-                            e_alpha.push_back(a_from * std::pow(q, s2)); e_out.push_back(-1); e_budget.push_back(FIN_RUNG_ITERS);
-                            ++n_rungs;
-                        }
-                    }
-                }
-                e_alpha.push_back(halpha[pk]); e_out.push_back((int)pk);
-                // the caller's maxiter bounds the iterations of an alpha over BOTH passes, alpha by alpha as the reference caps them
-                // (levenberg_minimizer.py:155): every open alpha gets what the lock-step pass left of ITS budget -- an alpha that pass
-                // never touched (the rest of an abandoned piece, an excluded alpha: nit = 0) the whole of it.  (Until round 5 the pass had
-                // ONE budget, that of the open alpha with the most iterations behind it: ADVICE r04.)
-                e_budget.push_back(std::max(1, o.maxiter - nit[pk]));
-            }
-            f_len.push_back((int)e_alpha.size() - f_prob0.back());
-            i = j;
-        }
-    const int nr = (int)f_elem.size();
-    const size_t ne = e_alpha.size();
-    HIPCHK(ctx, ctx->dfin_elem.ensure(nr)); HIPCHK(ctx, ctx->dfin_prob0.ensure(nr));
-    HIPCHK(ctx, ctx->dfin_len.ensure(nr)); HIPCHK(ctx, ctx->dfin_v0.ensure(nr));
+    // ---- 3. the plan
+    std::vector<int> chain_rows(ctx->n_chain);
+    for (int c = 0; c < ctx->n_chain; ++c) chain_rows[c] = ctx->ds[ctx->elem_ds[ctx->chain_elem[c]]].n_rows;
+    mxe::FinishInput in;
+    in.n_chain = ctx->n_chain; in.n_alpha = ctx->n_alpha; in.maxiter = ctx->opts.maxiter;
+    in.alpha = halpha.data(); in.converged = conv.data(); in.n_iter = nit.data(); in.n_evals = nev.data();
+    in.chain_elem = ctx->chain_elem.data(); in.chain_rows = chain_rows.data();
+    read_finish_env(in.env);
+    mxe::FinishPlan plan;
+    mxe::plan_finish(in, plan);
+    if (plan.n_open == 0) return MXE_OK;
+    ctx->pre_d = nullptr; ctx->pre_i = nullptr; ctx->pre_rows = nullptr; ctx->pre_index = false;   // (what was copied out behind the launch is about to change)
+    // ---- 4. the runs as pieces of the one-chain kernel: one upload per array, start vectors (whitened basis, row stride NP)
+    const int nr = (int)plan.runs.size();
+    std::vector<int> f_elem(nr), f_prob0(nr), f_len(nr), f_v0(nr);
+    for (int k = 0; k < nr; ++k) { const mxe::FinishRun& r = plan.runs[k]; f_elem[k] = r.elem; f_prob0[k] = r.entry0; f_len[k] = r.len; f_v0[k] = k; }
+    HIPCHK(ctx, put(ctx, ctx->dfin_elem, f_elem)); HIPCHK(ctx, put(ctx, ctx->dfin_prob0, f_prob0));
+    HIPCHK(ctx, put(ctx, ctx->dfin_len, f_len)); HIPCHK(ctx, put(ctx, ctx->dfin_v0, f_v0));
+    HIPCHK(ctx, put(ctx, ctx->dfin_alpha, plan.entry_alpha)); HIPCHK(ctx, put(ctx, ctx->dfin_out, plan.entry_out));
+    HIPCHK(ctx, put(ctx, ctx->dfin_budget, plan.entry_budget));
     HIPCHK(ctx, ctx->dfin_start.ensure((size_t)nr * NP));
-    HIPCHK(ctx, ctx->dfin_alpha.ensure(ne)); HIPCHK(ctx, ctx->dfin_out.ensure(ne)); HIPCHK(ctx, ctx->dfin_budget.ensure(ne));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->dfin_elem.p, f_elem.data(), nr * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->dfin_prob0.p, f_prob0.data(), nr * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->dfin_len.p, f_len.data(), nr * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->dfin_v0.p, f_v0.data(), nr * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->dfin_alpha.p, e_alpha.data(), ne * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->dfin_out.p, e_out.data(), ne * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->dfin_budget.p, e_budget.data(), ne * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    for (int k = 0; k < nr; ++k) {       // start vectors (whitened basis, row stride NP)
-        const bool from_v0 = f_src[k] > (size_t)-1 - (size_t)ctx->n_chain - 1;
-        const double* from = from_v0 ? ctx->dv0.p + ((size_t)-1 - f_src[k]) * NP : ctx->dout_v.p + f_src[k] * NP;
+    for (int k = 0; k < nr; ++k) {
+        const mxe::FinishStart& st = plan.runs[k].start;
+        const double* from = (st.from_v0 ? ctx->dv0.p : ctx->dout_v.p) + (size_t)st.index * NP;
         HIPCHK(ctx, hipMemcpyAsync(ctx->dfin_start.p + (size_t)k * NP, from, NP * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
     }
     HIPCHK(ctx, stream_wait(ctx->stream));          // (the host vectors are locals)
     KParams kp;
     fill_kparams(ctx, kp);
-    kp.chain_elem = ctx->dfin_elem.p; kp.chain_prob0 = ctx->dfin_prob0.p; kp.chain_len = ctx->dfin_len.p;
-    kp.chain_v0 = ctx->dfin_v0.p; kp.v0 = ctx->dfin_start.p;
-    kp.chain_lead = nullptr; kp.init_tab = nullptr; kp.chain_init = nullptr; kp.chain_walk0 = nullptr; kp.walk_alpha = nullptr;
-    kp.n_chain = nr;
+    set_pieces(kp, nr, ctx->dfin_elem.p, ctx->dfin_prob0.p, ctx->dfin_len.p, ctx->dfin_v0.p, ctx->dfin_start.p);
     kp.alpha = ctx->dfin_alpha.p; kp.out_index = ctx->dfin_out.p; kp.prob_maxiter = ctx->dfin_budget.p;
-    ctx->last_rungs = n_rungs;
 #ifdef MXE_DEBUG_HIST
+    const size_t ne = plan.entry_alpha.size();
     DevBuf<double> dhist;
     if (getenv("MXE_DEBUG_HIST_FILE")) {
         HIPCHK(ctx, dhist.ensure(ne * 48));
@@ -1647,21 +1591,12 @@ try {
         kp.prof = ctx->dprof.p;
     }
 #endif
-    const int NW = 4;
-    size_t lds = lds_bytes(NP, ctx->nwp, NW, false);
-    hipError_t e;
+    // ---- 5. the launch: binary64, four waves per chain whatever the mesh (a frequency mesh beyond the LDS -- the lock-step
+    // launch kept its state in device memory --: so does this one)
     HIPCHK(ctx, scribble_lds(ctx->stream));      // (diagnostic, MXE_POISON_LDS)
-    if (lds > 160 * 1024) {
-        // (a frequency mesh beyond the LDS -- the lock-step launch kept its state in device memory --: so does this one)
-        lds = lds_bytes(NP, ctx->nwp, NW, false, true);
-        if (lds > 160 * 1024) return MXE_ERR_LIMIT;
-        HIPCHK(ctx, ctx->dgstate.ensure((size_t)nr * 5 * ctx->nwp));
-        kp.gstate = ctx->dgstate.p;
-        e = launch_t<4, 2, double, true>(kp, lds, ctx->stream);
-    } else {
-        e = launch_t<4, 2>(kp, lds, ctx->stream);
-    }
-    HIPCHK(ctx, e);
+    OneChainBuild b;
+    if (const int rc = one_chain_build(ctx, kp, 4, 4, false, b); rc != MXE_OK) return rc;
+    HIPCHK(ctx, launch_one_chain(ctx, kp, b, false));
     HIPCHK(ctx, stream_wait(ctx->stream));
 #ifdef MXE_DEBUG_HIST
     if (kp.dbg_hist) {
@@ -1673,8 +1608,9 @@ try {
         HIPCHK(ctx, hipMemcpy(ni.data(), ctx->dout_niter.p, P * sizeof(int), hipMemcpyDeviceToHost));
         if (FILE* f = fopen(getenv("MXE_DEBUG_HIST_FILE"), "a")) {
             for (size_t en = 0; en < ne; ++en) {
-                if (e_out[en] < 0) continue;
-                fprintf(f, "%d %d %d %.6e", e_out[en], cv[e_out[en]], ni[e_out[en]], e_alpha[en]);
+                const int out = plan.entry_out[en];
+                if (out < 0) continue;
+                fprintf(f, "%d %d %d %.6e", out, cv[out], ni[out], plan.entry_alpha[en]);
                 for (int m = 0; m < 48; ++m) fprintf(f, "%s%.3e", (m % 16 == 0) ? " | " : " ", hh[en * 48 + m]);
                 fprintf(f, "\n");
             }
@@ -1683,15 +1619,14 @@ try {
         dhist.release();
     }
 #endif
-    // the counters of the records: both passes (whole arrays: one copy each way)
+    // ---- 6. the counters of the records: both passes (whole arrays: one copy each way)
     std::vector<int> nit2(P), nev2(P);
     HIPCHK(ctx, hipMemcpy(nit2.data(), ctx->dout_niter.p, P * sizeof(int), hipMemcpyDeviceToHost));
     HIPCHK(ctx, hipMemcpy(nev2.data(), ctx->dout_nevals.p, P * sizeof(int), hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < P; ++i) if (open[i]) { nit2[i] += nit[i]; nev2[i] += nev[i]; }
+    for (size_t i = 0; i < P; ++i) if (plan.open[i]) { nit2[i] += nit[i]; nev2[i] += nev[i]; }
     HIPCHK(ctx, hipMemcpy(ctx->dout_niter.p, nit2.data(), P * sizeof(int), hipMemcpyHostToDevice));
     HIPCHK(ctx, hipMemcpy(ctx->dout_nevals.p, nev2.data(), P * sizeof(int), hipMemcpyHostToDevice));
-    ctx->last_finished = n;
-    if (n_resolved) *n_resolved = n;
+    if (n_resolved) *n_resolved = plan.n_open;
     return MXE_OK;
 }
 MXE_CATCH_ALL

@@ -2,6 +2,7 @@
 // block and layout run them, and in what order.  Plain C++17 on the host: no device call, no context, no environment, no
 // I/O -- everything the decision reads is in PlanInput, everything it produces in LaunchPlan (tools/plan_dump.cpp runs it
 // stand-alone).  plan_launch() runs the stages below in order; DESIGN.md section 4 lists them.
+// At the end of the file, under the same rules: plan_finish(), the plan of mxe_chains_finish (FinishInput -> FinishPlan).
 #pragma once
 #include "../../include/maxent_hip.h"
 #include <algorithm>
@@ -16,6 +17,10 @@ constexpr double MC_DEPTH_TARGET = 20.0;     // evaluations of one piece of a la
 constexpr double MC_LADDER_COARSE = 2.0;     // a step between neighbouring alphas beyond this factor is not taken in one go (measured: up to a factor ~1.5 a warm step is safe, over a factor 2 single scans took 100-300 evaluations; 1.6 here cost stress case 51 -- ratio 1.66, sigma 1e-5 -- two converged flags and 3 x the time)
 constexpr int MC_LADDER_MAX = 28;            // rungs per piece (the slot's alpha table holds 32 entries)
 constexpr size_t LDS_CU = 160 * 1024;        // bytes of LDS of a CU
+constexpr size_t LDS_MC1 = LDS_CU - 6144;    // dynamic LDS of a lock-step workgroup that has a CU to itself (the rest: the static arrays of chain_kernel_mc)
+constexpr size_t LDS_MC2 = LDS_CU / 2 - 2048;      // ... of one that shares it with a second
+constexpr double FIN_COARSE = 1.6;           // finishing pass: a step between neighbouring alphas beyond this factor, in either direction, is cut into rungs (plan_finish)
+constexpr int FIN_RUNGS_MAX = 40;            // rungs of one such step (beyond: equal rungs of more than FinishEnv::ratio)
 
 // the environment overrides of the plan (A/B runs and tests); read_plan_env() of maxent_hip.hip is the one place that reads them
 struct PlanEnv {
@@ -418,7 +423,7 @@ inline int choose_layout(const PlanInput& in, State& st, LaunchPlan& lp)
             // correction up to 9e-7, p99 1e-7, against 4e-8 / 2e-9) and time in the 64-row build (pieces of 10 alphas x 32
             // iterations: launch 8-9 ms).  Not when more than a third of the alphas would be left to the finishing pass
             // (sigma = 5e-7 without the 64-row build: 197 against 150 ms).  profiles/r03_c_cut_pieces.txt, r03_e_na64.txt
-            const bool have64 = !in.env.no_na64 && in.n_s > 32 && o.wg_per_cu != 2 && in.lds_mc64x1 <= LDS_CU - 6144;
+            const bool have64 = !in.env.no_na64 && in.n_s > 32 && o.wg_per_cu != 2 && in.lds_mc64x1 <= LDS_MC1;
             bool need64 = false;
             std::vector<char> bad(P, 0); size_t n_bad = 0;
             for (int c = 0; c < in.n_chain; ++c) {
@@ -446,8 +451,8 @@ inline int choose_layout(const PlanInput& in, State& st, LaunchPlan& lp)
     }
     if (layout == 4) {
         lp.mc_wgpc = (o.wg_per_cu != 1 && (o.wg_per_cu == 2 || lp.wgpc_auto == 2) && lp.mc_na == 32 && in.n_omega_pad <= 512 &&
-                      in.lds_mc32x2 <= LDS_CU / 2 - 2048) ? 2 : 1;
-        if ((lp.mc_na == 64 ? in.lds_mc64x1 : lp.mc_wgpc == 2 ? in.lds_mc32x2 : in.lds_mc32x1) > LDS_CU - 6144) {
+                      in.lds_mc32x2 <= LDS_MC2) ? 2 : 1;
+        if ((lp.mc_na == 64 ? in.lds_mc64x1 : lp.mc_wgpc == 2 ? in.lds_mc32x2 : in.lds_mc32x1) > LDS_MC1) {
             // a frequency mesh whose state (u, H, sw of four slots: 80 B per omega) does not fit the LDS beside the
             // rest: the state goes to device memory (chain_kernel_mc<.., GSTATE>, one workgroup per CU)
             lp.mc_wgpc = 1; lp.mc_gst = true;
@@ -534,7 +539,7 @@ inline void order_pieces(const PlanInput& in, const State& st, LaunchPlan& lp)
     if (st.lv_fits && st.precision == MXE_PRECISION_F64 && lp.mc_na == 32 && !lp.mc_gst && lp.excluded.empty() && o.lds_basis == 1) {
         const int P2 = in.n_chain * n_alpha;
         lp.lv_mode = 2; lp.mc_wgpc = 1; lp.n_wg = std::min((n_sub + 3) / 4, n_cu);
-        lp.wgpc2 = (o.wg_per_cu != 1 && (P2 + 3) / 4 >= 2 * n_cu && in.lds_mc32x2 <= LDS_CU / 2 - 2048) ? 2 : 1;
+        lp.wgpc2 = (o.wg_per_cu != 1 && (P2 + 3) / 4 >= 2 * n_cu && in.lds_mc32x2 <= LDS_MC2) ? 2 : 1;
         lp.n_wg2 = std::min((P2 + 3) / 4, n_cu * lp.wgpc2);
     }
 }
@@ -566,6 +571,121 @@ inline int plan_launch(const PlanInput& in, LaunchPlan& lp)
     lp.precision = st.precision;
     plan::order_pieces(in, st, lp);
     return plan::check_coverage(in, lp) ? MXE_OK : MXE_ERR_STATE;
+}
+
+// ---- The plan of mxe_chains_finish: which alphas the one-chain kernel solves again behind a lock-step launch, as which warm
+// chains, from where, over which rungs and with what budgets.  The same rules as above: numbers in, numbers out.
+// the environment overrides (read_finish_env() of maxent_hip.hip is the one place that reads them)
+struct FinishEnv {
+    double ratio = 1.3;                // MXE_FIN_RATIO: largest ratio between two rungs (plan_finish: at least 1.05)
+    int rung_iters = 10;               // MXE_FIN_RUNG_ITERS: iterations a rung gets (plan_finish: at least 1)
+    bool no_ladder = false;            // MXE_NO_FINISH_LADDER: no rungs
+};
+struct FinishInput {
+    int n_chain = 0, n_alpha = 0, maxiter = 0;   // maxiter: the caller's, over both passes
+    const double* alpha = nullptr;               // [n_chain][n_alpha] as the device has them (alpha / eta)
+    const int *converged = nullptr, *n_iter = nullptr, *n_evals = nullptr;      // [n_chain][n_alpha]: the records of the lock-step pass
+    const int* chain_elem = nullptr;             // [n_chain]
+    const int* chain_rows = nullptr;             // [n_chain]: data points of the scan's data set
+    FinishEnv env;
+};
+// where a run starts from: row `index` of the result vectors of the launch, or -- from_v0 -- the start vector of scan `index`
+struct FinishStart { bool from_v0; int index; };
+struct FinishRun { int elem, entry0, len; FinishStart start; };      // one warm chain: entries [entry0, entry0 + len)
+struct FinishPlan {
+    std::vector<FinishRun> runs;
+    std::vector<double> entry_alpha;             // per entry: an open alpha of the mesh or a rung on the way to one,
+    std::vector<int> entry_out, entry_budget;    //   the problem whose record it writes (-1: a rung, no record), the iterations it may spend
+    std::vector<char> open;                      // per problem: solved again (its counters are those of both passes)
+    int n_open = 0, n_rungs = 0;                 // n_open == 0: nothing to do, the plan is empty
+};
+namespace plan {
+// The rungs of ONE step of a chain from a_from to a_to, either direction: m equal steps of at most env.ratio (at most
+// FIN_RUNGS_MAX + 1 of them), the last of them a_to itself, which the caller lays.  Steps first .. m - 1 are laid; step 0 is
+// a_from -- a cold start, three times a rung's budget.  A rung has no record; its cost is counted with the alpha it leads to.
+inline void lay_rungs(double a_from, double a_to, int first, const FinishEnv& env, FinishPlan& fp)
+{
+    const double r = a_from > a_to ? a_from / a_to : a_to / a_from;
+    int m = (int)std::ceil(std::log(r) / std::log(env.ratio) - 1e-9);
+    m = std::max(2, std::min(m, FIN_RUNGS_MAX + 1));
+    const double q = std::pow(a_to / a_from, 1.0 / m);
+    for (int s = first; s < m; ++s) {
+        fp.entry_alpha.push_back(a_from * std::pow(q, s)); fp.entry_out.push_back(-1);
+        fp.entry_budget.push_back(s == 0 ? 3 * env.rung_iters : env.rung_iters);
+        ++fp.n_rungs;
+    }
+}
+// ---- finish stage 1: what is open: not converged, and iterations of the caller's maxiter left (an alpha that used them up
+// stays as it is)
+inline void open_problems(const FinishInput& in, FinishPlan& fp)
+{
+    const size_t P = (size_t)in.n_chain * in.n_alpha;
+    fp.open.assign(P, 0);
+    for (size_t i = 0; i < P; ++i) if (!in.converged[i] && in.n_iter[i] < in.maxiter) { fp.open[i] = 1; ++fp.n_open; }
+}
+// ---- finish stage 2: the run of the open alphas [i, j) of scan c.
+// The alphas to solve again, as the reference would have reached them: every run of consecutive open alphas of a scan is
+// ONE warm-started chain that begins at the solution of the alpha before it (a converged neighbour: 3-5 iterations
+// per alpha, where the cold-started piece the lock-step kernel gave up on was stuck far from the minimiser -- on inputs
+// whose error bar lies far below their noise a cold start does not get there in thousands of evaluations, the
+// reference's warm scan does: tests/golden/stress_reference.npz); a run at the head of a scan starts from the state its
+// first alpha was left in.
+// Its entries: the open alphas of the mesh and -- where the mesh is too coarse to step on (round 5) -- RUNGS in between.
+// What is left to this pass lies deep in the region where the entropy term no longer holds the solution (or couples
+// more directions than the lock-step layout takes); there a warm step over the factor 1.9 of the reference's default mesh
+// (alpha_meshes.py:81: 20 alphas from 20 down to 1e-4) took 500-2 300 evaluations where ten steps of 10 % take 35 each
+// (profiles/r05_b_coarse_mesh.txt, tools/stress.py case 17).  A step over more than FIN_COARSE is therefore cut into equal
+// rungs of at most env.ratio; a rung gets env.rung_iters iterations.
+inline void emit_run(const FinishInput& in, int c, int i, int j, FinishPlan& fp)
+{
+    const int na = in.n_alpha, head = c * na + i;
+    const double* ac = in.alpha + (size_t)c * na;
+    // (a run at the head of a scan starts from the state its first alpha was left in -- if it was ever evaluated: a led piece
+    //  that gives up during its WALK leaves no record of its own alpha, and the vector in the result buffer is then whatever
+    //  the block held before: the start vector of the scan instead)
+    const bool from_v0 = i == 0 && in.n_iter[head] == 0 && in.n_evals[head] == 0;
+    const FinishStart start = from_v0 ? FinishStart{true, c} : FinishStart{false, i > 0 ? head - 1 : head};
+    const int entry0 = (int)fp.entry_alpha.size();
+    if (!in.env.no_ladder && from_v0) {
+        // a run that begins at the head of a scan from the default model, deep in the hard region (an ascending mesh, or a
+        // mesh that lies there altogether): rungs from N_data / 4 down to its first alpha, like the led pieces of the
+        // lock-step kernel (emit_scan) -- the cold start at alpha~ = 0.5 of tools/stress.py case 17 ran into maxiter
+        const double a_to = ac[0], a_from = 0.25 * in.chain_rows[c];
+        // (only where the mesh goes on FINE from there -- the rising mesh of case 17: 148 -> 150 of 150 converged, 61 -> 8 ms;
+        //  case 5: 29 -> 4.5 ms.  With three alphas five decades apart, alpha~ = 0.06 at sigma = 1e-5 on 40 data points, the
+        //  cold start with its full budget converged 129 of 192 and the rungs 99-108 at any ratio and budget tried: case 93)
+        const bool fine_head = na > 1 && std::max(ac[1] / a_to, a_to / ac[1]) <= FIN_COARSE;
+        if (fine_head && a_to * in.env.ratio * in.env.ratio < a_from) lay_rungs(a_from, a_to, 0, in.env, fp);
+    }
+    for (int k = i; k < j; ++k) {
+        if (!in.env.no_ladder && k > 0 && std::max(ac[k - 1] / ac[k], ac[k] / ac[k - 1]) > FIN_COARSE) lay_rungs(ac[k - 1], ac[k], 1, in.env, fp);
+        fp.entry_alpha.push_back(ac[k]); fp.entry_out.push_back(c * na + k);
+        // the caller's maxiter bounds the iterations of an alpha over BOTH passes, alpha by alpha as the reference caps them
+        // (levenberg_minimizer.py:155): every open alpha gets what the lock-step pass left of ITS budget -- an alpha that pass
+        // never touched (the rest of an abandoned piece, an excluded alpha: n_iter = 0) the whole of it.  (Until round 5 the pass had
+        // ONE budget, that of the open alpha with the most iterations behind it: ADVICE r04.)
+        fp.entry_budget.push_back(std::max(1, in.maxiter - in.n_iter[c * na + k]));
+    }
+    fp.runs.push_back(FinishRun{in.chain_elem[c], entry0, (int)fp.entry_alpha.size() - entry0, start});
+}
+}  // namespace plan
+// the plan of the finishing pass of (input); empty (n_open == 0) when nothing is open
+inline void plan_finish(const FinishInput& input, FinishPlan& fp)
+{
+    FinishInput in = input;
+    in.env.ratio = std::max(1.05, in.env.ratio); in.env.rung_iters = std::max(1, in.env.rung_iters);
+    fp = FinishPlan();
+    plan::open_problems(in, fp);
+    if (fp.n_open == 0) return;
+    for (int c = 0; c < in.n_chain; ++c)
+        for (int i = 0; i < in.n_alpha; ) {
+            const char* oc = fp.open.data() + (size_t)c * in.n_alpha;
+            if (!oc[i]) { ++i; continue; }
+            int j = i;
+            while (j < in.n_alpha && oc[j]) ++j;
+            plan::emit_run(in, c, i, j, fp);
+            i = j;
+        }
 }
 
 }  // namespace mxe

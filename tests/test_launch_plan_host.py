@@ -4,13 +4,15 @@ synthetic PlanInputs -- n_cu = 256 as data -- and its LaunchPlan is checked: the
 DESIGN.md section 4 states, derived by hand from the rules."""
 import math
 import os
-import shutil
-import subprocess
+import sys
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+from plan_dump_build import plan_dump_binary, run_plan_dump as run_text
+
 NORMAL, PM = 0, 1
 N_CU = 256
 LADDER_RATIO = 1.56
@@ -22,15 +24,7 @@ TOO_BIG = 200000
 
 @pytest.fixture(scope='session')
 def plan_dump(tmp_path_factory):
-    cxx = shutil.which('c++') or shutil.which('g++') or shutil.which('clang++')
-    assert cxx, 'no C++ compiler'
-    out = str(tmp_path_factory.mktemp('plan_dump') / 'plan_dump')
-    base = [cxx, '-std=c++17', '-O1', '-g', os.path.join(ROOT, 'tools', 'plan_dump.cpp'), '-o', out]
-    r = subprocess.run(base + ['-fsanitize=address,undefined', '-fno-sanitize-recover=all'], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    if r.returncode != 0:
-        print('plan_dump: built WITHOUT sanitizers (%s)' % r.stdout.strip().splitlines()[-1:])
-        subprocess.check_call(base)
-    return out
+    return plan_dump_binary(tmp_path_factory)
 
 
 def mesh(n_alpha, hi=1e4, lo=1e-2, n_tau=200):
@@ -60,12 +54,6 @@ def text_of(c):
     w.append('elem_of_chain ' + ' '.join(str(i) for i in range(n_chain)))
     w.append('alpha ' + ' '.join(repr(float(x)) for x in c['alpha'].ravel()))
     return '\n'.join(w) + '\n'
-
-
-def run_text(binary, text):
-    r = subprocess.run([binary], input=text, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
-    assert r.returncode == 0, (r.returncode, r.stderr[-2000:])
-    return r.stdout
 
 
 def parse(out):

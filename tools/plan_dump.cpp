@@ -1,5 +1,7 @@
-// Runs the launch planner of mxe_chains_upload (maxent_amd/csrc/mxe_plan.h) stand-alone, on the host: reads one PlanInput from
-// stdin, prints the LaunchPlan.  tests/test_launch_plan_host.py builds and drives it;
+// Runs the planners of maxent_amd/csrc/mxe_plan.h stand-alone, on the host.  `plan_dump`: the launch planner of
+// mxe_chains_upload -- reads one PlanInput from stdin, prints the LaunchPlan (tests/test_launch_plan_host.py).  `plan_dump finish`:
+// the planner of mxe_chains_finish -- reads one FinishInput, prints the FinishPlan (tests/test_finish_plan_host.py; below).
+// tests/plan_dump_build.py builds it:
 //   c++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all tools/plan_dump.cpp -o plan_dump
 //
 // Input: words separated by white space, `key value...`, in any order except that the counts come before their lists:
@@ -13,10 +15,71 @@
 #include "../maxent_amd/csrc/mxe_plan.h"
 #include <cstdio>
 #include <iostream>
+#include <cstring>
 #include <string>
 
-int main()
+static int fail(const std::string& what) { std::fprintf(stderr, "plan_dump: %s\n", what.c_str()); return 2; }
+
+// `plan_dump finish`.  Input, `key value...` as above, the counts before their lists:
+//   n_chain N  n_alpha M  maxiter K
+//   env NAME VALUE                                  (ratio rung_iters no_ladder)
+//   rows  then n_chain integers (data points of the scan's data set)       chain_elem  then n_chain integers
+//   alpha  then n_chain x n_alpha numbers           converged, n_iter, n_evals  then n_chain x n_alpha integers each
+// Output: n_open, n_rungs, runs (elem entry0 len from_v0 index), entries (alpha out budget), open (one flag per problem).
+static int finish_main()
 {
+    mxe::FinishInput in;
+    std::vector<double> alpha;
+    std::vector<int> rows, chain_elem, converged, n_iter, n_evals;
+    std::string key, name;
+    auto per_chain = [&](std::vector<int>& v) { if (in.n_chain < 1 || in.n_chain > (1 << 24)) return false; v.resize(in.n_chain); for (int& x : v) std::cin >> x; return true; };
+    auto per_problem = [&](auto& v) {
+        if (in.n_chain < 1 || in.n_alpha < 1 || (long long)in.n_chain * in.n_alpha > (1 << 26)) return false;
+        v.resize((size_t)in.n_chain * in.n_alpha); for (auto& x : v) std::cin >> x; return true;
+    };
+    while (std::cin >> key) {
+        bool counts_first = true;
+        if (key == "n_chain") std::cin >> in.n_chain;
+        else if (key == "n_alpha") std::cin >> in.n_alpha;
+        else if (key == "maxiter") std::cin >> in.maxiter;
+        else if (key == "env") {
+            double v; std::cin >> name >> v;
+            if (name == "ratio") in.env.ratio = v; else if (name == "rung_iters") in.env.rung_iters = (int)v;
+            else if (name == "no_ladder") in.env.no_ladder = v != 0;
+            else return fail("unknown override " + name);
+        } else if (key == "rows") counts_first = per_chain(rows);
+        else if (key == "chain_elem") counts_first = per_chain(chain_elem);
+        else if (key == "alpha") counts_first = per_problem(alpha);
+        else if (key == "converged") counts_first = per_problem(converged);
+        else if (key == "n_iter") counts_first = per_problem(n_iter);
+        else if (key == "n_evals") counts_first = per_problem(n_evals);
+        else return fail("unknown key " + key);
+        if (!counts_first) return fail("n_chain and n_alpha come before " + key);
+        if (!std::cin) return fail("bad value for " + key);
+    }
+    const size_t P = (size_t)in.n_chain * in.n_alpha;
+    if (in.n_chain < 1 || in.n_alpha < 1 || in.maxiter < 1) return fail("n_chain, n_alpha or maxiter missing");
+    if (rows.size() != (size_t)in.n_chain || chain_elem.size() != rows.size()) return fail("rows or chain_elem missing");
+    if (alpha.size() != P || converged.size() != P || n_iter.size() != P || n_evals.size() != P) return fail("a list per problem is missing");
+    for (double a : alpha) if (!(a > 0.0) || !std::isfinite(a)) return fail("alpha not positive");
+    for (int r : rows) if (r < 1) return fail("rows not positive");
+    in.alpha = alpha.data(); in.converged = converged.data(); in.n_iter = n_iter.data(); in.n_evals = n_evals.data();
+    in.chain_elem = chain_elem.data(); in.chain_rows = rows.data();
+
+    mxe::FinishPlan fp;
+    mxe::plan_finish(in, fp);
+    std::printf("n_open %d\nn_rungs %d\nruns %zu\n", fp.n_open, fp.n_rungs, fp.runs.size());
+    for (const mxe::FinishRun& r : fp.runs) std::printf("%d %d %d %d %d\n", r.elem, r.entry0, r.len, (int)r.start.from_v0, r.start.index);
+    std::printf("entries %zu\n", fp.entry_alpha.size());
+    for (size_t i = 0; i < fp.entry_alpha.size(); ++i) std::printf("%.17g %d %d\n", fp.entry_alpha[i], fp.entry_out[i], fp.entry_budget[i]);
+    std::printf("open %zu\n", fp.open.size());
+    for (char o : fp.open) std::printf("%d\n", (int)o);
+    return 0;
+}
+
+int main(int argc, char** argv)
+{
+    if (argc > 1) return std::strcmp(argv[1], "finish") == 0 ? finish_main() : fail(std::string("unknown mode ") + argv[1]);
     mxe::PlanInput in;
     in.opts = mxe_opts();
     in.opts.decouple_tol = 1e-5;
@@ -24,7 +87,6 @@ int main()
     std::vector<double> alpha, sumD, c32;
     std::vector<int> kind, eds, rows;
     std::string key, name;
-    auto fail = [&](const std::string& what) { std::fprintf(stderr, "plan_dump: %s\n", what.c_str()); return 2; };
     while (std::cin >> key) {
         if (key == "n_chain") std::cin >> in.n_chain;
         else if (key == "n_alpha") std::cin >> in.n_alpha;
