@@ -24,7 +24,6 @@
 #include <vector>
 #include <mutex>
 #include <thread>
-#include <tuple>
 
 using mxe::KParams;
 
@@ -495,46 +494,59 @@ int upload_bases(mxe_ctx* ctx)
     return MXE_OK;
 }
 
-// dynamic LDS of chain_kernel_mc<NA, WGPC> in bytes (the carve at the top of the kernel)
-size_t mc_lds_bytes(int NA, int nwp, int wgpc, int nwv = 4, bool gst = false)
+// ---- From a build (mxe::KernelBuild, chosen in mxe_plan.h) to its kernel.  Entry i of a table is the instantiation of entry i
+// of mxe::LOCKSTEP_BUILDS / mxe::ONE_CHAIN_BUILDS: those lists are what is instantiated, and a build that is not in them has
+// no kernel (nullptr) -- never a neighbouring one.
+using LockstepFn = void (*)(KParams, mxe::MCExtra);
+using OneChainFn = void (*)(KParams);
+template <int I> constexpr LockstepFn lockstep_entry()
 {
-    const int NT = NA / 16, NPAIR = NT * (NT + 1) / 2;
-    if (gst) nwp = 0;                        // (u, H, sw in device memory: MCExtra::gstate)
-    const size_t doubles = 8 * 4 * 64 + 2 * 64 + 64 * 4 + (wgpc == 2 ? 2 : nwv) * 4 * 64 + nwv * 32 + 2 * 4 * 64 +   // vectors, c, 1/c, step, h, sums, solve scales
-                           (wgpc == 2 ? (size_t)MXE_X_UL * 256 + (size_t)nwp * 4 : (size_t)2 * nwp * 4) +
-                           (size_t)4 * NPAIR * 256;                                                  // u, H, Gram tiles
-    const size_t floats = (size_t)nwp * 4;                                              // sw
-    return doubles * 8 + floats * 4;
+    constexpr mxe::LockstepKey k = mxe::LOCKSTEP_BUILDS[I];
+    return mxe::chain_kernel_mc<k.NA, k.WGPC, k.lead, k.NWV, k.gst>;
 }
-
-// LDS bytes of chain_kernel<NW, NAB, TS>: stream arrays (u, ut, w, wt, Hs, vecs) in the stream
-// type, the Gram staging area only in the binary64 build
-// (gst: the five omega arrays live in device memory, KParams::gstate)
-size_t lds_bytes(int NP, int nwp, int NW, bool f32, bool gst = false)
+template <int I> constexpr OneChainFn one_chain_entry()
 {
-    const int SROW = (NP / 4) * mxe::GBLK;
-    const size_t fixed = (size_t)NP * (NP + 1) + (NP == 64 ? 13 : 11) * (size_t)NP + (size_t)NW * NP + (size_t)NW * 8;
-    const size_t stream = (gst ? 0 : 5 * (size_t)nwp) + NP;
-    const size_t stage = f32 ? 0 : (size_t)NW * 2 * mxe::GRAM_R * SROW;
-    return (fixed + stage) * 8 + stream * (f32 ? 4 : 8);
+    constexpr mxe::OneChainKey k = mxe::ONE_CHAIN_BUILDS[I];
+    return mxe::chain_kernel<k.NW, k.NAB, std::conditional_t<k.f32, float, double>, k.gst>;
 }
-
-template <int NW, int NAB, typename TS = double, bool GST = false>
-hipError_t launch_t(const KParams& kp, size_t lds, hipStream_t s)
+template <int... I> LockstepFn lockstep_at(int i, std::integer_sequence<int, I...>) { static const LockstepFn tab[] = {lockstep_entry<I>()...}; return tab[i]; }
+template <int... I> OneChainFn one_chain_at(int i, std::integer_sequence<int, I...>) { static const OneChainFn tab[] = {one_chain_entry<I>()...}; return tab[i]; }
+// the twelve chain_kernel builds
+OneChainFn one_chain_kernel(const mxe::KernelBuild& b)
 {
-    hipError_t e = hipFuncSetAttribute((const void*)mxe::chain_kernel<NW, NAB, TS, GST>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((mxe::chain_kernel<NW, NAB, TS, GST>), dim3(kp.n_chain), dim3(64 * NW), lds, s, kp);
-    return hipGetLastError();
+    const int i = mxe::build_index(b);
+    if (i < 0 || b.kind != mxe::KernelBuild::ONE_CHAIN) return nullptr;
+    return one_chain_at(i, std::make_integer_sequence<int, mxe::N_ONE_CHAIN_BUILDS>());
 }
-
-template <int NW>
-hipError_t launch_nab(int NP, const KParams& kp, size_t lds, hipStream_t s)
+// the ten chain_kernel_mc builds and chain_kernel_lv
+LockstepFn lockstep_kernel(const mxe::KernelBuild& b)
 {
-    return (NP == 64) ? launch_t<NW, 2>(kp, lds, s) : launch_t<NW, 4>(kp, lds, s);
+    const int i = mxe::build_index(b);
+    if (i < 0 || b.kind == mxe::KernelBuild::ONE_CHAIN) return nullptr;
+    return b.kind == mxe::KernelBuild::LV ? mxe::chain_kernel_lv : lockstep_at(i, std::make_integer_sequence<int, mxe::N_LOCKSTEP_BUILDS>());
 }
-
+// The one launch of a chain kernel: build b on `grid` workgroups of b.waves() wavefronts.  A lock-step or lv build takes
+// (kp, *ex), a one-chain build kp alone.  MXE_ERR_STATE: the build has no kernel (nothing is enqueued then)
+int launch_build(mxe_ctx* ctx, const mxe::LaunchEnv& env, const mxe::KernelBuild& b, int grid, const KParams& kp, const mxe::MCExtra* ex)
+{
+    const dim3 g((unsigned)grid), block(64 * b.waves());
+    if (b.kind == mxe::KernelBuild::ONE_CHAIN) {
+        const OneChainFn k = one_chain_kernel(b);
+        if (!k) return MXE_ERR_STATE;
+        HIPCHK(ctx, launch_lds(k, g, block, b.lds, ctx->stream, kp));
+        return MXE_OK;
+    }
+    const LockstepFn k = lockstep_kernel(b);
+    if (!k || !ex) return MXE_ERR_STATE;
+    if (env.debug_occ && b.kind == mxe::KernelBuild::LOCKSTEP) {
+        int resident = 0;
+        HIPCHK(ctx, hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b.lds));
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&resident, (const void*)k, 64 * b.NWV, b.lds);
+        fprintf(stderr, "[mxe] lock-step kernel NA=%d NWV=%d lds=%zu: %d workgroup(s) per CU resident\n", b.NA, b.NWV, b.lds, resident);
+    }
+    HIPCHK(ctx, launch_lds(k, g, block, b.lds, ctx->stream, kp, *ex));
+    return MXE_OK;
+}
 // a host vector into a buffer of the context, on its stream (the vector has to outlive the copy: stream_wait)
 template <class Buf, class Vec> hipError_t put(mxe_ctx* ctx, Buf& buf, const Vec& vec)
 {
@@ -1070,6 +1082,16 @@ void read_finish_env(mxe::FinishEnv& env)
     if (const char* e = getenv("MXE_FIN_RUNG_ITERS")) env.rung_iters = atoi(e);
     env.no_ladder = getenv("MXE_NO_FINISH_LADDER") != nullptr;
 }
+// ... and of a launch of a chain kernel (mxe_chains_launch, mxe_chains_finish): the only environment reads of either.  Once per
+// launch -- tests set MXE_COUNT_ROUNDS for a single one --, except MXE_POISON_LDS, which is read once per process as ever
+void read_launch_env(mxe::LaunchEnv& env)
+{
+    static const int poison = getenv("MXE_POISON_LDS") ? atoi(getenv("MXE_POISON_LDS")) : 0;
+    env.poison_lds = poison;
+    env.count_rounds = getenv("MXE_COUNT_ROUNDS") != nullptr; env.debug_occ = getenv("MXE_DEBUG_OCC") != nullptr;
+    if (const char* e = getenv("MXE_MC_MAXEVALS")) { env.has_mc_maxevals = true; env.mc_maxevals = atoi(e); }
+    if (const char* e = getenv("MXE_STUCK_SKIP")) env.stuck_skip = atoi(e);
+}
 }  // namespace
 
 // Stages the chains of a launch.  What is launched -- pieces, kernel, layout, order -- is decided by mxe::plan_launch
@@ -1116,8 +1138,6 @@ try {
     in.elem_kind = ctx->elem_kind.data(); in.elem_ds = ctx->elem_ds.data(); in.elem_sumD = ctx->h_sumD.data();
     in.n_ds = (int)ctx->ds.size(); in.ds_rows = ds_rows.data(); in.ds_c32 = ds_c32.data();
     in.n_s = ns; in.NP = NP; in.n_omega_pad = nwp; in.n_cu = ctx->n_cu; in.opts = o;
-    in.lds_lv = mxe::lv_lds_bytes(ns, nwp) + mxe::LV_STATIC_LDS; in.lds_mc64x1 = mc_lds_bytes(64, nwp, 1);
-    in.lds_mc32x1 = mc_lds_bytes(32, nwp, 1); in.lds_mc32x2 = mc_lds_bytes(32, nwp, 2);
     in.wgpc_auto = ctx->wgpc_auto; in.mc_wgpc_hint = ctx->mc_wgpc_hint;
     read_plan_env(in.env);
     mxe::LaunchPlan plan;       // ---- 4. the plan
@@ -1197,7 +1217,7 @@ MXE_CATCH_ALL
 
 // the kernel parameters of the staged chains (mxe_chains_launch; mxe_chains_finish replaces the chain arrays)
 constexpr int MC_MAXITER = 32;       // iterations the lock-step kernel spends on one alpha before it gives it up (mxe_chains_finish)
-static void fill_kparams(mxe_ctx* ctx, KParams& kp)
+static void fill_kparams(mxe_ctx* ctx, const mxe::LaunchEnv& env, KParams& kp)
 {
     const mxe_opts& o = ctx->opts;
     kp.n_omega = ctx->n_omega; kp.n_omega_pad = ctx->nwp; kp.n_s = ctx->n_s; kp.NP = ctx->NP;
@@ -1226,11 +1246,11 @@ static void fill_kparams(mxe_ctx* ctx, KParams& kp)
     kp.gstate = nullptr;
     kp.mc_maxiter = std::min(o.maxiter, std::max(MC_MAXITER, o.miniter + 8));     // (a caller's miniter above the limit moves it)
     kp.mc_abandon = 1;
-    { const char* e = getenv("MXE_MC_MAXEVALS"); kp.mc_maxevals = e ? atoi(e) : 3 * kp.mc_maxiter; }
+    kp.mc_maxevals = env.has_mc_maxevals ? env.mc_maxevals : 3 * kp.mc_maxiter;
     kp.prob_maxiter = nullptr;
     kp.out_index = nullptr;
     kp.dbg_hist = nullptr;
-    { const char* e = getenv("MXE_STUCK_SKIP"); kp.stuck_skip = e ? atoi(e) : 1; }
+    kp.stuck_skip = env.stuck_skip;
 }
 // other pieces for the kernel parameters of the staged chains (the second pass of a two-pass launch, the finishing pass): n
 // plain pieces -- nothing led, no walk, no start states -- whose start vectors are the rows v0[v0_row[.]]
@@ -1240,49 +1260,13 @@ static void set_pieces(KParams& kp, int n, const int* elem, const int* prob0, co
     kp.chain_lead = nullptr; kp.init_tab = nullptr; kp.chain_init = nullptr; kp.chain_walk0 = nullptr; kp.walk_alpha = nullptr;
     kp.n_chain = n;
 }
-// Waves of a lock-step workgroup.  Eight (four helpers for the streaming passes) where the launch runs one workgroup per
-// CU, i.e. does not fill the GPU and is as long as its deepest chain of rounds; mxe_opts.waves_per_chain = 4 / 8
-// overrides (the passes of that build want n_omega_pad in units of 256)
-static int lockstep_waves(int NA, int nwp, int wgpc, bool gst, int waves_per_chain = 0)
+// a one-chain build with its state in device memory: five omega arrays per chain (binary32 build: half of it used)
+static int one_chain_state(mxe_ctx* ctx, const mxe::KernelBuild& b, KParams& kp)
 {
-    return (NA == 32 && wgpc == 1 && nwp % 256 == 0 && waves_per_chain != 4 && mc_lds_bytes(NA, nwp, 1, 8, gst) <= mxe::LDS_MC1) ? 8 : 4;
-}
-// The build of the one-chain kernel for kp.n_chain chains: NW waves per chain, halved down to nw_min until the LDS takes
-// the chain.  A frequency mesh whose omega-space state (five arrays per chain) does not fit it even then: the state goes to
-// device memory (four waves per chain; one where the 128 x 128 Newton matrix leaves no room for more) -- kp.gstate.
-struct OneChainBuild { int NW; bool gst; size_t lds; };
-static int one_chain_build(mxe_ctx* ctx, KParams& kp, int NW, int nw_min, bool f32, OneChainBuild& b)
-{
-    size_t lds = lds_bytes(ctx->NP, ctx->nwp, NW, f32);
-    while (lds > mxe::LDS_CU && NW > nw_min) { NW /= 2; lds = lds_bytes(ctx->NP, ctx->nwp, NW, f32); }
-    const bool gst = lds > mxe::LDS_CU;
-    if (gst) {
-        NW = (ctx->NP == 64) ? 4 : 1;
-        lds = lds_bytes(ctx->NP, ctx->nwp, NW, f32, true);
-        if (lds > mxe::LDS_CU) return MXE_ERR_LIMIT;
-        HIPCHK(ctx, ctx->dgstate.ensure((size_t)kp.n_chain * 5 * ctx->nwp));     // (binary32 build: half of it used)
-        kp.gstate = ctx->dgstate.p;
-    }
-    b = OneChainBuild{NW, gst, lds};
+    if (!b.gst) return MXE_OK;
+    HIPCHK(ctx, ctx->dgstate.ensure((size_t)kp.n_chain * 5 * ctx->nwp));
+    kp.gstate = ctx->dgstate.p;
     return MXE_OK;
-}
-static hipError_t launch_one_chain(const mxe_ctx* ctx, const KParams& kp, const OneChainBuild& b, bool f32)
-{
-    hipStream_t s = ctx->stream;
-    if (b.gst) {
-        if (f32) return launch_t<4, 2, float, true>(kp, b.lds, s);
-        return (ctx->NP == 64) ? launch_t<4, 2, double, true>(kp, b.lds, s) : launch_t<1, 4, double, true>(kp, b.lds, s);
-    }
-    if (f32) switch (b.NW) {
-        case 1: return launch_t<1, 2, float>(kp, b.lds, s);
-        case 2: return launch_t<2, 2, float>(kp, b.lds, s);
-        default: return launch_t<4, 2, float>(kp, b.lds, s);
-    }
-    switch (b.NW) {
-        case 1: return launch_nab<1>(ctx->NP, kp, b.lds, s);
-        case 2: return launch_nab<2>(ctx->NP, kp, b.lds, s);
-        default: return launch_nab<4>(ctx->NP, kp, b.lds, s);
-    }
 }
 
 namespace {
@@ -1324,9 +1308,8 @@ void scribble_lds_kernel(unsigned long long pattern, int words, unsigned long lo
     if (sink && sl[(threadIdx.x * 7) % words] == 1) sink[0] = 1;       // (keeps the stores)
     __builtin_amdgcn_s_sleep(64);
 }
-hipError_t scribble_lds(hipStream_t s)
+hipError_t scribble_lds(hipStream_t s, int mode)
 {
-    static const int mode = getenv("MXE_POISON_LDS") ? atoi(getenv("MXE_POISON_LDS")) : 0;
     if (!mode) return hipSuccess;
     static unsigned long long launches = 0;
     const int bytes = 160 * 1024;
@@ -1343,17 +1326,150 @@ hipError_t scribble_lds(hipStream_t s)
 // (~2e-7 of |H|) to be reached without crawling, close enough for ONE binary64 Newton step to land below 1e-9
 constexpr double LV_TOL1 = 1e-5;
 
+// ---- What the three paths of mxe_chains_launch share.
+// what a lock-step or lv kernel is handed besides KParams; the path sets the counter word, the rounds table and the state
+static mxe::MCExtra mc_extra(const mxe_ctx* ctx)
+{
+    mxe::MCExtra ex;
+    ex.wg_chains = ctx->dwg_chains.p; ex.n_wg = ctx->n_wg;
+    ex.queue = ctx->dqueue.p; ex.n_queue = ctx->n_queue; ex.counter = nullptr;
+    ex.stagger = 0;              // (a late start of the second half of the grid never paid: 0 ... 14 units measured; 5 cost 0.4 %; with the wave priorities of r03: 0 ... 24 units all within 0.5 %)
+    ex.n_solo = 0; ex.gstate = nullptr; ex.gstate_stride = 0;
+    return ex;
+}
+// sizes and clears the rounds per workgroup (mxe_launch_depth) of a launch of n0 workgroups and a second pass of n1; none: no node
+static int arm_rounds(mxe_ctx* ctx, int n0, int n1)
+{
+    ctx->rounds_n[0] = n0; ctx->rounds_n[1] = n1;
+    if (n0 + n1 == 0) return MXE_OK;
+    HIPCHK(ctx, ctx->drounds.ensure((size_t)n0 + n1));
+    HIPCHK(ctx, hipMemsetAsync(ctx->drounds.p, 0, ((size_t)n0 + n1) * sizeof(int), ctx->stream));
+    return MXE_OK;
+}
+// what mxe_last_launch_info and mxe_last_kernel_name report (a two-pass launch: the waves and the LDS of its first pass)
+static void record_build(mxe_ctx* ctx, const mxe::KernelBuild& b, const std::string& name)
+{
+    ctx->last_nw = b.waves(); ctx->last_lds = (int)b.lds; ctx->last_kernel = name;
+}
+
+// V^T resident in LDS as binary32 (mxe_kernel_lv.hip.h): the launch itself (precision = F32) or the first pass of a binary64
+// launch that does not fill the GPU, whose second pass takes every alpha as a piece of its own in the binary64 lock-step
+// kernel, from the v of the first
+static int launch_lv(mxe_ctx* ctx, const mxe::LaunchEnv& env, const KParams& kp)
+{
+    const bool two_pass = ctx->lv_mode == 2;
+    const mxe::KernelBuild b1 = mxe::lv_build(ctx->n_s, ctx->nwp);
+    mxe::KernelBuild b2;
+    if (two_pass) {
+        if (const int rc = mxe::lockstep_build(32, ctx->wgpc2, false, false, ctx->nwp, 0, b2); rc != MXE_OK) return rc;
+        if (mxe::build_index(b2) < 0) return MXE_ERR_STATE;
+    }
+    mxe::MCExtra ex = mc_extra(ctx);
+    // (words 2 and 3, one per pass, zeroed by a reset node as before: the pair of the lock-step launches is not touched.  The
+    //  second pass -- chain_kernel_mc drawing from word 3 -- stores its 0 into word 2, which the first pass has finished with.)
+    ex.counter = ctx->dcounter.p + 2;
+    HIPCHK(ctx, hipMemsetAsync(ctx->dcounter.p + 2, 0, 2 * sizeof(int), ctx->stream));
+    if (const int rc = arm_rounds(ctx, ctx->n_wg, two_pass ? ctx->n_wg2 : 0); rc != MXE_OK) return rc;
+    if (ex.n_queue > 0) ex.wg_chains = ctx->drounds.p;          // (dynamic layout: the rounds of every workgroup come back here)
+    else ctx->rounds_n[0] = 0;
+    KParams k1 = kp;
+    if (two_pass) {
+        k1.tol_h = std::max(kp.tol_h, LV_TOL1);
+        k1.out_H = nullptr;
+        k1.out_niter = ctx->dcnt1_niter.p; k1.out_nevals = ctx->dcnt1_nevals.p;
+    }
+    record_build(ctx, b1, two_pass ? mxe::two_pass_name(b1, b2) : mxe::build_name(b1));
+    HIPCHK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+    if (const int rc = launch_build(ctx, env, b1, ctx->n_wg, k1, &ex); rc != MXE_OK) return rc;
+    if (!two_pass) return MXE_OK;
+    const size_t Pn = (size_t)ctx->n_chain * ctx->n_alpha;
+    KParams k2 = kp;
+    set_pieces(k2, (int)Pn, ctx->d2_elem.p, ctx->d2_prob0.p, ctx->d2_len.p, ctx->d2_v0.p, ctx->dout_v.p);
+    k2.prof = nullptr;                  // (diagnostic build: the stamps of the first pass stay)
+    mxe::MCExtra e2 = ex;
+    e2.n_wg = ctx->n_wg2;
+    e2.queue = ctx->d2_queue.p; e2.n_queue = (int)Pn; e2.counter = ctx->dcounter.p + 3;
+    e2.wg_chains = ctx->drounds.p + ctx->rounds_n[0];
+    if (const int rc = launch_build(ctx, env, b2, ctx->n_wg2, k2, &e2); rc != MXE_OK) return rc;
+    hipLaunchKernelGGL(add_counts_kernel, dim3((unsigned)((Pn + 255) / 256)), dim3(256), 0, ctx->stream,
+                       ctx->dout_niter.p, ctx->dout_nevals.p, ctx->dcnt1_niter.p, ctx->dcnt1_nevals.p, (int)Pn);
+    HIPCHK(ctx, hipGetLastError());
+    return MXE_OK;
+}
+
+// four chains per workgroup, lock-step (mxe_kernel_mc.hip.h)
+static int launch_lockstep(mxe_ctx* ctx, const mxe::LaunchEnv& env, const KParams& kp)
+{
+    const bool lead = kp.chain_lead != nullptr;
+    mxe::KernelBuild b;
+    if (const int rc = mxe::lockstep_build(ctx->mc_na, ctx->mc_wgpc, lead, ctx->mc_gst, ctx->nwp, ctx->opts.waves_per_chain, b); rc != MXE_OK) return rc;
+    if (mxe::build_index(b) < 0) return MXE_ERR_STATE;
+    mxe::MCExtra ex = mc_extra(ctx);
+    if (b.gst) {
+        ex.gstate_stride = mxe::mc_gstate_doubles(ctx->nwp);
+        HIPCHK(ctx, ctx->dgstate_mc.ensure((size_t)ctx->n_wg * ex.gstate_stride + 4096));
+        ex.gstate = ctx->dgstate_mc.p;
+    }
+    ex.counter = ctx->dcounter.p + ctx->counter_par;
+    // rounds per workgroup (mxe_launch_depth): the builds for launches that do not fill the GPU write them, in the dynamic
+    // layout (MCExtra: the pointer is the table of chain ids in the static one).  Not <32, 2> without led pieces -- the batch
+    // that fills the GPU: the memset node alone is 1.5 us of its 812 (A/B: profiles/r04_experiments.txt)
+    // (MXE_COUNT_ROUNDS: there as well -- a diagnostic launch, bench.py: launch_depth)
+    const bool counts = ex.n_queue > 0 && (lead || b.WGPC == 1 || env.count_rounds);
+    if (const int rc = arm_rounds(ctx, counts ? ctx->n_wg : 0, 0); rc != MXE_OK) return rc;
+    if (counts) ex.wg_chains = ctx->drounds.p;
+    int counter0 = 0;
+    if (ex.n_queue > 0 && b.WGPC == 2 && ctx->n_solo > 0) {
+        ex.n_solo = ctx->n_solo;
+        counter0 = (ctx->n_wg - ex.n_solo) * 4;
+    }
+    // No reset node: launch k draws from word k & 1 of the pair, which mxe_chains_upload (k = 0, 1) or launch k - 1 set to counter0.
+    // (Never taken: a launch whose start value is not the one the pair is armed with sets both words itself.)
+    if (ctx->counter_armed != counter0) {
+        HIPCHK(ctx, hipMemsetD32Async((hipDeviceptr_t)ctx->dcounter.p, counter0, 2, ctx->stream));
+        ctx->counter_armed = counter0;
+    }
+    if (!ctx->excluded.empty()) {
+        hipLaunchKernelGGL(clear_excluded_kernel, dim3((unsigned)ctx->excluded.size()), dim3(256), 0, ctx->stream,
+                           ctx->dexcluded.p, ctx->n_alpha, ctx->n_omega, ctx->NP, ctx->dv0.p, ctx->dout_H.p, ctx->dout_chi2.p,
+                           ctx->dout_S.p, ctx->dout_Q.p, ctx->dout_v.p, ctx->dout_niter.p, ctx->dout_conv.p,
+                           ctx->dout_nevals.p, ctx->dout_nact.p);
+        HIPCHK(ctx, hipGetLastError());
+    }
+    record_build(ctx, b, mxe::build_name(b));
+    HIPCHK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+    if (const int rc = launch_build(ctx, env, b, ctx->n_wg, kp, &ex); rc != MXE_OK) return rc;
+    ctx->counter_par ^= 1;       // (only behind a launch that was enqueued: a failed one re-armed nothing)
+    return MXE_OK;
+}
+
+// one chain per workgroup (mxe_kernel.hip.h)
+static int launch_one_chain(mxe_ctx* ctx, const mxe::LaunchEnv& env, KParams& kp)
+{
+    mxe::KernelBuild b;
+    const bool f32 = ctx->opts.precision == MXE_PRECISION_F32;
+    if (const int rc = mxe::one_chain_build(ctx->NP, ctx->nwp, mxe::first_waves(ctx->opts.waves_per_chain, ctx->n_sub), 1, f32, b); rc != MXE_OK) return rc;
+    if (mxe::build_index(b) < 0) return MXE_ERR_STATE;
+    if (const int rc = arm_rounds(ctx, 0, 0); rc != MXE_OK) return rc;
+    if (const int rc = one_chain_state(ctx, b, kp); rc != MXE_OK) return rc;
+    record_build(ctx, b, mxe::build_name(b));
+    HIPCHK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+    return launch_build(ctx, env, b, kp.n_chain, kp, nullptr);
+}
+
+// Launches the staged chains: check, choose the build (mxe_plan.h), arm what the kernel draws from, launch
 int mxe_chains_launch(mxe_ctx* ctx)
 try {
     if (!ctx) return MXE_ERR_ARG;
     if (!ctx->chains_ready) return MXE_ERR_STATE;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     ctx->pre_d = nullptr; ctx->pre_i = nullptr; ctx->pre_rows = nullptr; ctx->pre_index = false;
-    const mxe_opts& o = ctx->opts;
+    mxe::LaunchEnv env;
+    read_launch_env(env);
     KParams kp;
-    fill_kparams(ctx, kp);
-    HIPCHK(ctx, scribble_lds(ctx->stream));      // (diagnostic, MXE_POISON_LDS)
-    if (getenv("MXE_COUNT_ROUNDS") && ctx->mc_na > 0 && kp.chain_lead == nullptr && ctx->lv_mode == 0) {
+    fill_kparams(ctx, env, kp);
+    HIPCHK(ctx, scribble_lds(ctx->stream, env.poison_lds));      // (diagnostic, MXE_POISON_LDS)
+    if (env.count_rounds && ctx->mc_na > 0 && kp.chain_lead == nullptr && ctx->lv_mode == 0) {
         // a diagnostic launch that counts the rounds of its workgroups (mxe_launch_depth) also where the shipped build does not --
         // <32, 2> without led pieces compiles the store out --: the build for led pieces with no piece led, the same schedule
         HIPCHK(ctx, hipMemsetAsync(ctx->dsub_pre.p, 0, (size_t)std::max(ctx->n_sub, 1) * sizeof(int), ctx->stream));
@@ -1364,145 +1480,8 @@ try {
     HIPCHK(ctx, hipMemsetAsync(ctx->dprof.p, 0, ((size_t)ctx->n_sub + 8 * 1024) * 64, ctx->stream));
     kp.prof = ctx->dprof.p;
 #endif
-    hipError_t e;
-    if (ctx->mc_na > 0) {
-        // four chains per workgroup, lock-step (mxe_kernel_mc.hip.h)
-        if (ctx->lv_mode != 0) {
-            // V^T resident in LDS as binary32 (mxe_kernel_lv.hip.h): the launch itself (precision = F32) or the first pass
-            // of a binary64 launch that does not fill the GPU
-            const size_t lds1 = mxe::lv_lds_bytes(ctx->n_s, ctx->nwp);
-            mxe::MCExtra ex; ex.wg_chains = ctx->dwg_chains.p; ex.n_wg = ctx->n_wg;
-            ex.gstate = nullptr; ex.gstate_stride = 0; ex.stagger = 0; ex.n_solo = 0;
-            ex.queue = ctx->dqueue.p; ex.n_queue = ctx->n_queue; ex.counter = ctx->dcounter.p + 2;
-            // (words 2 and 3, one per pass, zeroed by a reset node as before: the pair of the lock-step launches is not touched.  The
-            //  second pass -- chain_kernel_mc drawing from word 3 -- stores its 0 into word 2, which the first pass has finished with.)
-            HIPCHK(ctx, hipMemsetAsync(ctx->dcounter.p + 2, 0, 2 * sizeof(int), ctx->stream));
-            ctx->rounds_n[0] = ctx->n_wg; ctx->rounds_n[1] = (ctx->lv_mode == 2) ? ctx->n_wg2 : 0;
-            HIPCHK(ctx, ctx->drounds.ensure((size_t)ctx->rounds_n[0] + ctx->rounds_n[1]));
-            HIPCHK(ctx, hipMemsetAsync(ctx->drounds.p, 0, ((size_t)ctx->rounds_n[0] + ctx->rounds_n[1]) * sizeof(int), ctx->stream));
-            if (ex.n_queue > 0) ex.wg_chains = ctx->drounds.p;          // (dynamic layout: the rounds of every workgroup come back here)
-            else ctx->rounds_n[0] = 0;
-            KParams k1 = kp;
-            if (ctx->lv_mode == 2) {
-                k1.tol_h = std::max(kp.tol_h, LV_TOL1);
-                k1.out_H = nullptr;
-                k1.out_niter = ctx->dcnt1_niter.p; k1.out_nevals = ctx->dcnt1_nevals.p;
-            }
-            ctx->last_nw = mxe::LV_NWV; ctx->last_lds = (int)lds1;
-            ctx->last_kernel = "mxe::chain_kernel_lv";
-            HIPCHK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-            e = hipFuncSetAttribute((const void*)mxe::chain_kernel_lv, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1);
-            HIPCHK(ctx, e);
-            hipLaunchKernelGGL(mxe::chain_kernel_lv, dim3(ctx->n_wg), dim3(64 * mxe::LV_NWV), lds1, ctx->stream, k1, ex);
-            HIPCHK(ctx, hipGetLastError());
-            if (ctx->lv_mode == 2) {
-                // second pass: every alpha a piece of its own in the binary64 lock-step kernel, from the v of the first
-                const size_t Pn = (size_t)ctx->n_chain * ctx->n_alpha;
-                const int W2 = ctx->wgpc2;
-                const int NWV2 = lockstep_waves(32, ctx->nwp, W2, false);
-                const size_t lds = mc_lds_bytes(32, ctx->nwp, W2, NWV2);
-                if (lds > mxe::LDS_MC1) return MXE_ERR_LIMIT;
-                KParams k2 = kp;
-                set_pieces(k2, (int)Pn, ctx->d2_elem.p, ctx->d2_prob0.p, ctx->d2_len.p, ctx->d2_v0.p, ctx->dout_v.p);
-                k2.prof = nullptr;                  // (diagnostic build: the stamps of the first pass stay)
-                mxe::MCExtra e2 = ex;
-                e2.n_wg = ctx->n_wg2;
-                e2.queue = ctx->d2_queue.p; e2.n_queue = (int)Pn; e2.counter = ctx->dcounter.p + 3;
-                e2.wg_chains = ctx->drounds.p + ctx->rounds_n[0];
-#define MXE_LAUNCH_MC2(WG_, NWV_) do { \
-                e = hipFuncSetAttribute((const void*)mxe::chain_kernel_mc<32, WG_, false, NWV_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-                if (e == hipSuccess) { hipLaunchKernelGGL((mxe::chain_kernel_mc<32, WG_, false, NWV_>), dim3(ctx->n_wg2), dim3(64 * NWV_), lds, ctx->stream, k2, e2); e = hipGetLastError(); } } while (0)
-                if (W2 == 2) MXE_LAUNCH_MC2(2, 4); else if (NWV2 == 8) MXE_LAUNCH_MC2(1, 8); else MXE_LAUNCH_MC2(1, 4);
-#undef MXE_LAUNCH_MC2
-                HIPCHK(ctx, e);
-                hipLaunchKernelGGL(add_counts_kernel, dim3((unsigned)((Pn + 255) / 256)), dim3(256), 0, ctx->stream,
-                                   ctx->dout_niter.p, ctx->dout_nevals.p, ctx->dcnt1_niter.p, ctx->dcnt1_nevals.p, (int)Pn);
-                HIPCHK(ctx, hipGetLastError());
-                ctx->last_kernel += " + mxe::chain_kernel_mc<32, " + std::to_string(W2) + (NWV2 == 8 ? ", 8 waves>" : ">") + " per alpha";
-            }
-            HIPCHK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-            ctx->launched = true;
-            return MXE_OK;
-        }
-        const int NA = ctx->mc_na, WGPC = ctx->mc_wgpc;
-        const bool GST = ctx->mc_gst;
-        const int NWV = lockstep_waves(NA, ctx->nwp, WGPC, GST, o.waves_per_chain);
-        const size_t lds = mc_lds_bytes(NA, ctx->nwp, WGPC, NWV, GST);
-        if (lds > mxe::LDS_MC1) return MXE_ERR_LIMIT;
-        mxe::MCExtra ex; ex.wg_chains = ctx->dwg_chains.p; ex.n_wg = ctx->n_wg;
-        ex.gstate = nullptr; ex.gstate_stride = 0;
-        if (GST) {
-            ex.gstate_stride = mxe::mc_gstate_doubles(ctx->nwp);
-            HIPCHK(ctx, ctx->dgstate_mc.ensure((size_t)ctx->n_wg * ex.gstate_stride + 4096));
-            ex.gstate = ctx->dgstate_mc.p;
-        }
-        ex.queue = ctx->dqueue.p; ex.n_queue = ctx->n_queue; ex.counter = ctx->dcounter.p + ctx->counter_par;
-        // rounds per workgroup (mxe_launch_depth): the builds for launches that do not fill the GPU write them, in the dynamic
-        // layout (MCExtra: the pointer is the table of chain ids in the static one).  Not <32, 2> without led pieces -- the batch
-        // that fills the GPU: the memset node alone is 1.5 us of its 812 (A/B: profiles/r04_experiments.txt)
-        ctx->rounds_n[0] = ctx->rounds_n[1] = 0;
-        // (MXE_COUNT_ROUNDS: there as well -- a diagnostic launch, bench.py: launch_depth)
-        if (ex.n_queue > 0 && (kp.chain_lead != nullptr || WGPC == 1 || getenv("MXE_COUNT_ROUNDS"))) {
-            ctx->rounds_n[0] = ctx->n_wg;
-            HIPCHK(ctx, ctx->drounds.ensure((size_t)ctx->n_wg));
-            HIPCHK(ctx, hipMemsetAsync(ctx->drounds.p, 0, (size_t)ctx->n_wg * sizeof(int), ctx->stream));
-            ex.wg_chains = ctx->drounds.p;
-        }
-        ex.stagger = 0;              // (a late start of the second half of the grid never paid: 0 ... 14 units measured; 5 cost 0.4 %; with the wave priorities of r03: 0 ... 24 units all within 0.5 %)
-        ex.n_solo = 0;
-        int counter0 = 0;
-        if (ex.n_queue > 0 && WGPC == 2 && ctx->n_solo > 0) {
-            ex.n_solo = ctx->n_solo;
-            counter0 = (ctx->n_wg - ex.n_solo) * 4;
-        }
-        // No reset node: launch k draws from word k & 1 of the pair, which mxe_chains_upload (k = 0, 1) or launch k - 1 set to counter0.
-        // (Never taken: a launch whose start value is not the one the pair is armed with sets both words itself.)
-        if (ctx->counter_armed != counter0) {
-            HIPCHK(ctx, hipMemsetD32Async((hipDeviceptr_t)ctx->dcounter.p, counter0, 2, ctx->stream));
-            ctx->counter_armed = counter0;
-        }
-        if (!ctx->excluded.empty()) {
-            hipLaunchKernelGGL(clear_excluded_kernel, dim3((unsigned)ctx->excluded.size()), dim3(256), 0, ctx->stream,
-                               ctx->dexcluded.p, ctx->n_alpha, ctx->n_omega, ctx->NP, ctx->dv0.p, ctx->dout_H.p, ctx->dout_chi2.p,
-                               ctx->dout_S.p, ctx->dout_Q.p, ctx->dout_v.p, ctx->dout_niter.p, ctx->dout_conv.p,
-                               ctx->dout_nevals.p, ctx->dout_nact.p);
-            HIPCHK(ctx, hipGetLastError());
-        }
-        ctx->last_nw = NWV; ctx->last_lds = (int)lds;
-        const bool lead = kp.chain_lead != nullptr;
-        ctx->last_kernel = "mxe::chain_kernel_mc<" + std::to_string(NA) + ", " + std::to_string(WGPC) + (lead ? ", lead" : "") +
-                           (NWV == 8 ? ", 8 waves" : "") + (GST ? ", device-memory state>" : ">");
-        HIPCHK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-#define MXE_LAUNCH_MC(NA_, WG_, LD_, ...) do { constexpr int NWV_ = std::get<0>(std::make_tuple(__VA_ARGS__)); \
-        e = hipFuncSetAttribute((const void*)mxe::chain_kernel_mc<NA_, WG_, LD_, __VA_ARGS__>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        if (e == hipSuccess && getenv("MXE_DEBUG_OCC")) { int nb__ = 0; \
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb__, (const void*)mxe::chain_kernel_mc<NA_, WG_, LD_, __VA_ARGS__>, 64 * NWV_, lds); \
-            fprintf(stderr, "[mxe] lock-step kernel NA=%d NWV=%d lds=%zu: %d workgroup(s) per CU resident\n", NA_, NWV_, (size_t)lds, nb__); } \
-        if (e == hipSuccess) { hipLaunchKernelGGL((mxe::chain_kernel_mc<NA_, WG_, LD_, __VA_ARGS__>), dim3(ctx->n_wg), dim3(64 * NWV_), lds, ctx->stream, kp, ex); e = hipGetLastError(); } } while (0)
-        if (NA == 64) { if (lead) MXE_LAUNCH_MC(64, 1, true, 4); else MXE_LAUNCH_MC(64, 1, false, 4); }
-        else if (GST) { if (NWV == 8) MXE_LAUNCH_MC(32, 1, true, 8, true); else MXE_LAUNCH_MC(32, 1, true, 4, true); }
-        else if (NA == 32 && WGPC == 2) { if (lead) MXE_LAUNCH_MC(32, 2, true, 4); else MXE_LAUNCH_MC(32, 2, false, 4); }
-        else if (NWV == 8) { if (lead) MXE_LAUNCH_MC(32, 1, true, 8); else MXE_LAUNCH_MC(32, 1, false, 8); }
-        else { if (lead) MXE_LAUNCH_MC(32, 1, true, 4); else MXE_LAUNCH_MC(32, 1, false, 4); }
-#undef MXE_LAUNCH_MC
-        HIPCHK(ctx, e);
-        ctx->counter_par ^= 1;       // (only behind a launch that was enqueued: a failed one re-armed nothing)
-    } else {
-        ctx->rounds_n[0] = ctx->rounds_n[1] = 0;
-        int NW = std::min(o.waves_per_chain, 4);     // (eight waves per chain: two per SIMD at 256 registers each spilled; not built)
-        if (NW == 0) {
-            // fill the 256 CUs x 4 SIMDs: few chains -> more waves per chain
-            const int nc = ctx->n_sub;
-            NW = (nc >= 2048) ? 1 : (nc >= 1024) ? 2 : 4;
-        }
-        const bool f32 = (o.precision == MXE_PRECISION_F32);
-        OneChainBuild b;
-        if (const int rc = one_chain_build(ctx, kp, NW, 1, f32, b); rc != MXE_OK) return rc;
-        ctx->last_nw = b.NW; ctx->last_lds = (int)b.lds;
-        ctx->last_kernel = "mxe::chain_kernel<" + std::to_string(b.NW) + ", " + std::to_string(ctx->NP / 32) + (f32 ? ", float" : ", double") + (b.gst ? ", device-memory state>" : ">");
-        HIPCHK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-        HIPCHK(ctx, launch_one_chain(ctx, kp, b, f32));
-    }
+    const int rc = ctx->mc_na == 0 ? launch_one_chain(ctx, env, kp) : ctx->lv_mode != 0 ? launch_lv(ctx, env, kp) : launch_lockstep(ctx, env, kp);
+    if (rc != MXE_OK) return rc;
     HIPCHK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
     ctx->launched = true;
     return MXE_OK;
@@ -1571,8 +1550,10 @@ try {
         HIPCHK(ctx, hipMemcpyAsync(ctx->dfin_start.p + (size_t)k * NP, from, NP * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
     }
     HIPCHK(ctx, stream_wait(ctx->stream));          // (the host vectors are locals)
+    mxe::LaunchEnv env;
+    read_launch_env(env);
     KParams kp;
-    fill_kparams(ctx, kp);
+    fill_kparams(ctx, env, kp);
     set_pieces(kp, nr, ctx->dfin_elem.p, ctx->dfin_prob0.p, ctx->dfin_len.p, ctx->dfin_v0.p, ctx->dfin_start.p);
     kp.alpha = ctx->dfin_alpha.p; kp.out_index = ctx->dfin_out.p; kp.prob_maxiter = ctx->dfin_budget.p;
 #ifdef MXE_DEBUG_HIST
@@ -1593,10 +1574,11 @@ try {
 #endif
     // ---- 5. the launch: binary64, four waves per chain whatever the mesh (a frequency mesh beyond the LDS -- the lock-step
     // launch kept its state in device memory --: so does this one)
-    HIPCHK(ctx, scribble_lds(ctx->stream));      // (diagnostic, MXE_POISON_LDS)
-    OneChainBuild b;
-    if (const int rc = one_chain_build(ctx, kp, 4, 4, false, b); rc != MXE_OK) return rc;
-    HIPCHK(ctx, launch_one_chain(ctx, kp, b, false));
+    HIPCHK(ctx, scribble_lds(ctx->stream, env.poison_lds));      // (diagnostic, MXE_POISON_LDS)
+    mxe::KernelBuild b;
+    if (const int rc = mxe::one_chain_build(NP, ctx->nwp, 4, 4, false, b); rc != MXE_OK) return rc;
+    if (const int rc = one_chain_state(ctx, b, kp); rc != MXE_OK) return rc;
+    if (const int rc = launch_build(ctx, env, b, kp.n_chain, kp, nullptr); rc != MXE_OK) return rc;
     HIPCHK(ctx, stream_wait(ctx->stream));
 #ifdef MXE_DEBUG_HIST
     if (kp.dbg_hist) {

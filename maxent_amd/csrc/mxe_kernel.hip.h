@@ -29,12 +29,11 @@
 #include <stdint.h>
 #include <type_traits>
 #include <utility>
+#include "mxe_shapes.h"       // GRAM_R, GBLK and the LDS bytes of every build
 
 namespace mxe {
 
 constexpr int WAVE = 64;
-constexpr int GRAM_R = 4;         // rows staged per wave per Gram tile
-constexpr int GBLK = 6;           // staged doubles per 4-column block (16-B aligned, bank spread)
 
 struct KParams {
     int n_omega;        // number of frequencies

@@ -35,7 +35,6 @@
 
 namespace mxe {
 
-constexpr int LV_NWV = 8;
 #ifndef MXE_X_LV_PARTNER_PRIO
 #define MXE_X_LV_PARTNER_PRIO 1
 #endif
@@ -44,19 +43,7 @@ constexpr int LV_NWV = 8;
 #endif
 constexpr int LV_ACAP = 16;             // alphas of a slot's piece kept in LDS (longer pieces read the mesh from memory)
 constexpr double LV_FLOOR = 2e-5;       // corrections below this that no longer halve: the binary32 rounding floor
-constexpr int LV_STATIC_LDS = 2304;     // bound on the __shared__ arrays of the kernel (host side: fits-the-LDS test)
-
-// rows of V^T the kernel keeps: the 32 columns of the active block at least, a multiple of eight (row-pass unroll)
-inline int lv_rows(int ns) { const int r = (ns + 7) & ~7; return r < 32 ? 32 : r; }
-// dynamic LDS in bytes (the carve at the top of the kernel)
-inline size_t lv_lds_bytes(int ns, int nwp)
-{
-    const size_t S32 = (size_t)nwp + 4;
-    const size_t stage = 4 * S32 * 4;                                   // H or sw of the four slots
-    const size_t solve = 4 * 4 * 64 * 8;                                // rhs, z, two scale vectors (alias sw)
-    return (size_t)lv_rows(ns) * S32 * 4 + (4 * 4 * 64 + 2 * 64 + 4 * 64 + 64) * 8 + 3 * 4 * 64 * 4 +
-           stage + (stage > solve ? stage : solve) + 4 * 3 * 256 * 4;
-}
+// (LV_NWV, LV_STATIC_LDS, lv_rows and lv_lds_bytes: mxe_shapes.h)
 
 // exp(x) in binary32: k = rint(x log2 e), the remainder in two pieces (log2 e split), v_exp_f32, ldexp.
 // Overflow / underflow come out as inf / 0 like fast_exp.

@@ -54,9 +54,7 @@ struct MCExtra {
     //  mxe_launch_depth.  A field of its own changed the kernel-argument layout and cost the <32, 2> build 0.25 %.)
 };
 
-// omega-space state of one workgroup of a GSTATE build, in doubles: u [nwp][4] | H [nwp][4] + look-ahead | sw [nwp][4] floats + look-ahead
-constexpr int MC_GSTATE_PAD = 1024;
-inline size_t mc_gstate_doubles(int nwp) { return (size_t)nwp * 4 + ((size_t)nwp * 4 + MC_GSTATE_PAD) + ((size_t)nwp * 4 + MC_GSTATE_PAD) / 2; }
+// (MC_GSTATE_PAD, mc_gstate_doubles and MXE_X_UL: mxe_shapes.h)
 
 // NA    capacity of the active block: 32 or 48
 // WGPC  workgroups per CU the kernel is built for:
@@ -137,9 +135,6 @@ constexpr int MC_LOOKAHEAD_LDS = (8 + 2) * 4 * 4 * 4 + 64;       // entries
 #endif
 #ifndef MXE_X_RD1
 #define MXE_X_RD1 4        // (8: the shards of an 8-GPU job 0.593 / 0.653 -> 0.617 / 0.688 ms)
-#endif
-#ifndef MXE_X_UL
-#define MXE_X_UL 0            // u elements per lane kept in LDS instead of registers (0: all eight in registers)
 #endif
 // LEAD  pieces may be led by an earlier alpha of their scan (KParams::chain_lead); a build of its own, because the
 //       two extra instructions of start_piece cost the schedule without such pieces 1.6 % (register allocation)

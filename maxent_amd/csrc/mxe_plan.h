@@ -2,12 +2,16 @@
 // block and layout run them, and in what order.  Plain C++17 on the host: no device call, no context, no environment, no
 // I/O -- everything the decision reads is in PlanInput, everything it produces in LaunchPlan (tools/plan_dump.cpp runs it
 // stand-alone).  plan_launch() runs the stages below in order; DESIGN.md section 4 lists them.
-// At the end of the file, under the same rules: plan_finish(), the plan of mxe_chains_finish (FinishInput -> FinishPlan).
+// At the end of the file, under the same rules: plan_finish(), the plan of mxe_chains_finish (FinishInput -> FinishPlan), and
+// KernelBuild with its choosers: which instantiation of a chain kernel a launch runs (mxe_chains_launch, mxe_chains_finish).
+// The LDS bytes of every build come from mxe_shapes.h.
 #pragma once
 #include "../../include/maxent_hip.h"
+#include "mxe_shapes.h"
 #include <algorithm>
 #include <array>
 #include <cmath>
+#include <string>
 #include <utility>
 #include <vector>
 
@@ -37,7 +41,8 @@ struct PlanInput {
     const int* ds_rows = nullptr;                // per data set: data points,
     const double* ds_c32 = nullptr;              //   the singular value c[32] (0 when n_s <= 32)
     mxe_opts opts;
-    size_t lds_lv = 0, lds_mc32x1 = 0, lds_mc32x2 = 0, lds_mc64x1 = 0;      // dynamic LDS of chain_kernel_lv (+ its static arrays) and chain_kernel_mc<NA, WGPC>
+    size_t lds_override[4] = {0, 0, 0, 0};       // tests only (plan_dump's `lds` key): bytes to take instead of the formulas of mxe_shapes.h for chain_kernel_lv with
+                                                 //   its static arrays, chain_kernel_mc<32, 1>, <32, 2>, <64, 1>, so that "does not fit" is expressible; 0: the formula
     int wgpc_auto = 2, mc_wgpc_hint = 1;         // what the auto rule chose last: a launch with alpha_split > 0 keeps it
     PlanEnv env;
 };
@@ -66,6 +71,13 @@ struct State {
 inline bool normal_elem(const PlanInput& in, int e) { return in.elem_kind[e] == MXE_ENTROPY_NORMAL; }
 // (what every lock-step build needs of the options)
 inline bool lockstep_opts(const PlanInput& in) { return in.NP == 64 && in.opts.chains_per_wg != 1 && in.opts.tol_d <= 0.0 && in.opts.decouple_tol > 0.0; }
+// dynamic LDS of the candidate builds at the mesh of the input: chain_kernel_lv with its static arrays, chain_kernel_mc<NA, wgpc> at four waves
+inline size_t lds_lv(const PlanInput& in) { return in.lds_override[0] ? in.lds_override[0] : lv_lds_bytes(in.n_s, in.n_omega_pad) + LV_STATIC_LDS; }
+inline size_t lds_mc(const PlanInput& in, int NA, int wgpc)
+{
+    const size_t over = in.lds_override[NA == 64 ? 3 : wgpc == 2 ? 2 : 1];
+    return over ? over : mc_lds_bytes(NA, in.n_omega_pad, wgpc);
+}
 inline double piece_amin(const PlanInput& in, const Piece& p) { return *std::min_element(in.alpha + p.prob0, in.alpha + p.prob0 + p.len); }
 // alpha x the relative coupling of the first direction a 32-row active block leaves out, for element e: c_32^2 wmax, wmax <= max(1, sum D)
 inline double coupling32(const PlanInput& in, int e) { const double c = in.ds_c32[in.elem_ds[e]]; return c * c * std::max(1.0, in.elem_sumD[e]); }
@@ -77,7 +89,7 @@ inline void choose_precision(const PlanInput& in, State& st)
     const mxe_opts& o = in.opts;
     st.precision = o.precision;
     const bool lds_basis_ok = o.lds_basis != 2 && !in.env.no_lds_basis && lockstep_opts(in);
-    st.lv_fits = in.n_omega_pad <= 512 && lds_basis_ok && in.lds_lv <= LDS_CU;
+    st.lv_fits = in.n_omega_pad <= 512 && lds_basis_ok && lds_lv(in) <= LDS_CU;
     st.f32_lv = st.precision == MXE_PRECISION_F32 && st.lv_fits;
     if (st.f32_lv && in.n_s > 32) {
         // (chain_kernel_lv has the plain 32-row build only: a job with an alpha that couples more than 32 directions -- the criterion
@@ -423,7 +435,7 @@ inline int choose_layout(const PlanInput& in, State& st, LaunchPlan& lp)
             // correction up to 9e-7, p99 1e-7, against 4e-8 / 2e-9) and time in the 64-row build (pieces of 10 alphas x 32
             // iterations: launch 8-9 ms).  Not when more than a third of the alphas would be left to the finishing pass
             // (sigma = 5e-7 without the 64-row build: 197 against 150 ms).  profiles/r03_c_cut_pieces.txt, r03_e_na64.txt
-            const bool have64 = !in.env.no_na64 && in.n_s > 32 && o.wg_per_cu != 2 && in.lds_mc64x1 <= LDS_MC1;
+            const bool have64 = !in.env.no_na64 && in.n_s > 32 && o.wg_per_cu != 2 && lds_mc(in, 64, 1) <= LDS_MC1;
             bool need64 = false;
             std::vector<char> bad(P, 0); size_t n_bad = 0;
             for (int c = 0; c < in.n_chain; ++c) {
@@ -451,8 +463,8 @@ inline int choose_layout(const PlanInput& in, State& st, LaunchPlan& lp)
     }
     if (layout == 4) {
         lp.mc_wgpc = (o.wg_per_cu != 1 && (o.wg_per_cu == 2 || lp.wgpc_auto == 2) && lp.mc_na == 32 && in.n_omega_pad <= 512 &&
-                      in.lds_mc32x2 <= LDS_MC2) ? 2 : 1;
-        if ((lp.mc_na == 64 ? in.lds_mc64x1 : lp.mc_wgpc == 2 ? in.lds_mc32x2 : in.lds_mc32x1) > LDS_MC1) {
+                      lds_mc(in, 32, 2) <= LDS_MC2) ? 2 : 1;
+        if (lds_mc(in, lp.mc_na, lp.mc_wgpc) > LDS_MC1) {
             // a frequency mesh whose state (u, H, sw of four slots: 80 B per omega) does not fit the LDS beside the
             // rest: the state goes to device memory (chain_kernel_mc<.., GSTATE>, one workgroup per CU)
             lp.mc_wgpc = 1; lp.mc_gst = true;
@@ -539,7 +551,7 @@ inline void order_pieces(const PlanInput& in, const State& st, LaunchPlan& lp)
     if (st.lv_fits && st.precision == MXE_PRECISION_F64 && lp.mc_na == 32 && !lp.mc_gst && lp.excluded.empty() && o.lds_basis == 1) {
         const int P2 = in.n_chain * n_alpha;
         lp.lv_mode = 2; lp.mc_wgpc = 1; lp.n_wg = std::min((n_sub + 3) / 4, n_cu);
-        lp.wgpc2 = (o.wg_per_cu != 1 && (P2 + 3) / 4 >= 2 * n_cu && in.lds_mc32x2 <= LDS_MC2) ? 2 : 1;
+        lp.wgpc2 = (o.wg_per_cu != 1 && (P2 + 3) / 4 >= 2 * n_cu && lds_mc(in, 32, 2) <= LDS_MC2) ? 2 : 1;
         lp.n_wg2 = std::min((P2 + 3) / 4, n_cu * lp.wgpc2);
     }
 }
@@ -687,5 +699,113 @@ inline void plan_finish(const FinishInput& input, FinishPlan& fp)
             i = j;
         }
 }
+
+// ---- The build of a chain kernel: which instantiation a launch runs, with how much dynamic LDS.  mxe_chains_launch and
+// mxe_chains_finish ask the choosers below; maxent_hip.hip instantiates exactly the builds listed here (LOCKSTEP_BUILDS,
+// ONE_CHAIN_BUILDS, and chain_kernel_lv) and finds the kernel of a build in those lists, so a build that is not listed has
+// no kernel and is an error, never a neighbouring one.
+struct KernelBuild {
+    enum Kind { ONE_CHAIN, LOCKSTEP, LV } kind = ONE_CHAIN;
+    int NA = 0, WGPC = 0, NWV = 0; bool lead = false, gst = false;      // LOCKSTEP: chain_kernel_mc<NA, WGPC, lead, NWV, gst>
+    int NW = 0, NAB = 0; bool f32 = false;                              // ONE_CHAIN: chain_kernel<NW, NAB, float / double, gst>
+    size_t lds = 0;                                                     // dynamic LDS of the launch
+    int waves() const { return kind == ONE_CHAIN ? NW : NWV; }          // wavefronts of a workgroup
+};
+// the environment overrides of a launch (diagnostics and A/B runs; read_launch_env() of maxent_hip.hip is the one place that reads them)
+struct LaunchEnv {
+    bool count_rounds = false;         // MXE_COUNT_ROUNDS: the rounds of every workgroup also where the shipped build does not count them
+    bool debug_occ = false;            // MXE_DEBUG_OCC: print how many workgroups of the build a CU holds
+    bool has_mc_maxevals = false; int mc_maxevals = 0;       // MXE_MC_MAXEVALS: evaluations the lock-step kernel spends on one alpha (default: 3 x its iterations)
+    int stuck_skip = 1;                // MXE_STUCK_SKIP
+    int poison_lds = 0;                // MXE_POISON_LDS: 1 / 2, every CU's LDS is written over before the kernel starts
+};
+struct LockstepKey { int NA, WGPC; bool lead; int NWV; bool gst; };
+struct OneChainKey { int NW, NAB; bool f32, gst; };
+// (the device-memory-state build is the LEAD build; the 64-row build and two workgroups per CU have four waves)
+constexpr LockstepKey LOCKSTEP_BUILDS[] = {
+    {32, 2, false, 4, false}, {32, 1, false, 8, false}, {32, 1, false, 4, false}, {64, 1, true, 4, false}, {64, 1, false, 4, false},
+    {32, 1, true, 8, true}, {32, 1, true, 4, true}, {32, 2, true, 4, false}, {32, 1, true, 8, false}, {32, 1, true, 4, false}};
+// (binary32 only with the 64-row Newton matrix, NAB = 2; device-memory state: four waves, one where NAB = 4 leaves no room for more)
+constexpr OneChainKey ONE_CHAIN_BUILDS[] = {
+    {4, 2, true, true}, {4, 2, false, true}, {1, 4, false, true}, {1, 2, true, false}, {2, 2, true, false}, {4, 2, true, false},
+    {1, 2, false, false}, {1, 4, false, false}, {2, 2, false, false}, {2, 4, false, false}, {4, 2, false, false}, {4, 4, false, false}};
+constexpr int N_LOCKSTEP_BUILDS = sizeof(LOCKSTEP_BUILDS) / sizeof(LOCKSTEP_BUILDS[0]), N_ONE_CHAIN_BUILDS = sizeof(ONE_CHAIN_BUILDS) / sizeof(ONE_CHAIN_BUILDS[0]);
+// where build b stands in its list (chain_kernel_lv: 0), -1: there is no such kernel
+inline int build_index(const KernelBuild& b)
+{
+    if (b.kind == KernelBuild::LV) return 0;
+    if (b.kind == KernelBuild::LOCKSTEP) {
+        for (int i = 0; i < N_LOCKSTEP_BUILDS; ++i) {
+            const LockstepKey& k = LOCKSTEP_BUILDS[i];
+            if (k.NA == b.NA && k.WGPC == b.WGPC && k.lead == b.lead && k.NWV == b.NWV && k.gst == b.gst) return i;
+        }
+        return -1;
+    }
+    for (int i = 0; i < N_ONE_CHAIN_BUILDS; ++i) {
+        const OneChainKey& k = ONE_CHAIN_BUILDS[i];
+        if (k.NW == b.NW && k.NAB == b.NAB && k.f32 == b.f32 && k.gst == b.gst) return i;
+    }
+    return -1;
+}
+// The lock-step build of (active block, workgroups per CU, led pieces, device-memory state).  Eight waves (four helpers for
+// the streaming passes) where the launch runs one workgroup per CU, i.e. does not fill the GPU and is as long as its deepest
+// chain of rounds; mxe_opts.waves_per_chain = 4 / 8 overrides (the passes of that build want n_omega_pad in units of 256).
+// MXE_ERR_LIMIT: the build does not fit the LDS
+inline int lockstep_build(int NA, int wgpc, bool lead, bool gst, int n_omega_pad, int waves_per_chain, KernelBuild& b)
+{
+    b = KernelBuild();
+    b.kind = KernelBuild::LOCKSTEP; b.NA = NA; b.WGPC = wgpc; b.lead = lead; b.gst = gst;
+    b.NWV = (NA == 32 && wgpc == 1 && n_omega_pad % 256 == 0 && waves_per_chain != 4 && mc_lds_bytes(NA, n_omega_pad, 1, 8, gst) <= LDS_MC1) ? 8 : 4;
+    b.lds = mc_lds_bytes(NA, n_omega_pad, wgpc, b.NWV, gst);
+    return b.lds <= LDS_MC1 ? MXE_OK : MXE_ERR_LIMIT;
+}
+// The build of the one-chain kernel: NW waves per chain, halved down to nw_min until the LDS takes the chain (the launch: 1;
+// the finishing pass never halved: 4).  A frequency mesh whose omega-space state (five arrays per chain) does not fit it even
+// then: the state goes to device memory (four waves per chain; one where the 128 x 128 Newton matrix leaves no room for
+// more) -- b.gst, the caller provides KParams::gstate.  MXE_ERR_LIMIT: not even that fits, or binary32 with NP = 128
+inline int one_chain_build(int NP, int n_omega_pad, int NW, int nw_min, bool f32, KernelBuild& b)
+{
+    b = KernelBuild();
+    b.kind = KernelBuild::ONE_CHAIN; b.NAB = NP / 32; b.f32 = f32;
+    if (f32 && NP != 64) return MXE_ERR_LIMIT;
+    b.lds = lds_bytes(NP, n_omega_pad, NW, f32);
+    while (b.lds > LDS_CU && NW > nw_min) { NW /= 2; b.lds = lds_bytes(NP, n_omega_pad, NW, f32); }
+    b.gst = b.lds > LDS_CU;
+    if (b.gst) {
+        NW = (NP == 64) ? 4 : 1;
+        b.lds = lds_bytes(NP, n_omega_pad, NW, f32, true);
+    }
+    b.NW = NW;
+    return b.lds <= LDS_CU ? MXE_OK : MXE_ERR_LIMIT;
+}
+// waves per chain the one-chain launch asks one_chain_build for: the caller's (eight waves per chain -- two per SIMD at 256
+// registers each -- spilled and are not built: four), else enough to fill the 256 CUs x 4 SIMDs: few chains -> more waves per chain
+inline int first_waves(int waves_per_chain, int n_sub)
+{
+    if (waves_per_chain != 0) return std::min(waves_per_chain, 4);
+    return (n_sub >= 2048) ? 1 : (n_sub >= 1024) ? 2 : 4;
+}
+// chain_kernel_lv: one build (32-row active block, led pieces, one workgroup of LV_NWV waves per CU)
+inline KernelBuild lv_build(int n_s, int n_omega_pad)
+{
+    KernelBuild b;
+    b.kind = KernelBuild::LV; b.NA = 32; b.WGPC = 1; b.NWV = LV_NWV; b.lead = true; b.lds = lv_lds_bytes(n_s, n_omega_pad);
+    return b;
+}
+// the one place that spells the name of a kernel (mxe_last_kernel_name)
+inline std::string build_name(const KernelBuild& b)
+{
+    switch (b.kind) {
+        case KernelBuild::LV: return "mxe::chain_kernel_lv";
+        case KernelBuild::LOCKSTEP:
+            return "mxe::chain_kernel_mc<" + std::to_string(b.NA) + ", " + std::to_string(b.WGPC) + (b.lead ? ", lead" : "") +
+                   (b.NWV == 8 ? ", 8 waves" : "") + (b.gst ? ", device-memory state>" : ">");
+        default:
+            return "mxe::chain_kernel<" + std::to_string(b.NW) + ", " + std::to_string(b.NAB) + (b.f32 ? ", float" : ", double") +
+                   (b.gst ? ", device-memory state>" : ">");
+    }
+}
+// ... and of a two-pass launch: chain_kernel_lv, then every alpha a piece of its own in build `second`
+inline std::string two_pass_name(const KernelBuild& first, const KernelBuild& second) { return build_name(first) + " + " + build_name(second) + " per alpha"; }
 
 }  // namespace mxe

@@ -1,5 +1,5 @@
 """The stand-alone build of tools/plan_dump.cpp that the host tests of the planners share (test_launch_plan_host.py,
-test_finish_plan_host.py): the system compiler, with the address and undefined-behaviour sanitizers where it links them.
+test_finish_plan_host.py, test_kernel_build_host.py): the system compiler, with the address and undefined-behaviour sanitizers where it links them.
 Built once per session, whichever file asks first."""
 import os
 import shutil

@@ -1,12 +1,14 @@
 // Runs the planners of maxent_amd/csrc/mxe_plan.h stand-alone, on the host.  `plan_dump`: the launch planner of
 // mxe_chains_upload -- reads one PlanInput from stdin, prints the LaunchPlan (tests/test_launch_plan_host.py).  `plan_dump finish`:
 // the planner of mxe_chains_finish -- reads one FinishInput, prints the FinishPlan (tests/test_finish_plan_host.py; below).
+// `plan_dump build`: the choosers of the kernel build -- answers queries with the KernelBuild and its name
+// (tests/test_kernel_build_host.py; below).
 // tests/plan_dump_build.py builds it:
 //   c++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all tools/plan_dump.cpp -o plan_dump
 //
 // Input: words separated by white space, `key value...`, in any order except that the counts come before their lists:
 //   n_chain N  n_alpha M  n_s K  NP K  n_omega_pad K  n_cu K  wgpc_auto K  mc_wgpc_hint K
-//   lds LV MC32x1 MC32x2 MC64x1                     (bytes)
+//   lds LV MC32x1 MC32x2 MC64x1                     (optional override, bytes; 0: what the formulas of mxe_shapes.h give)
 //   opt NAME VALUE                                  (alpha_split wg_per_cu in_flight chains_per_wg precision lds_basis tol_d decouple_tol)
 //   env NAME VALUE                                  (taper ladder_ratio no_lds_basis no_split_by_kind no_ladder no_na64 no_sorted_static)
 //   elems E  then E x (kind data_set sumD)          ds D  then D x (n_rows c32)
@@ -77,9 +79,41 @@ static int finish_main()
     return 0;
 }
 
+// `plan_dump build`.  The choosers of the kernel build (KernelBuild).  Input: any number of queries, each answered by one line:
+//   lockstep NA WGPC LEAD GST N_OMEGA_PAD WAVES_PER_CHAIN        one_chain NP N_OMEGA_PAD NW NW_MIN F32
+//   lv N_S N_OMEGA_PAD                                           two_pass N_S N_OMEGA_PAD WGPC2   (lv, then lockstep 32 WGPC2 0 0 .. 0)
+//     -> rc kind NA WGPC NWV lead gst NW NAB f32 lds listed | name      (listed: the build has a kernel, build_index >= 0;
+//        two_pass: the second build and the name of both)
+//   first_waves WAVES_PER_CHAIN N_SUB  -> the waves
+static int build_main()
+{
+    auto print = [](int rc, const mxe::KernelBuild& b, const std::string& name) {
+        std::printf("%d %d %d %d %d %d %d %d %d %d %zu %d | %s\n", rc, (int)b.kind, b.NA, b.WGPC, b.NWV, (int)b.lead, (int)b.gst, b.NW, b.NAB,
+                    (int)b.f32, b.lds, (int)(mxe::build_index(b) >= 0), name.c_str());
+    };
+    std::string q;
+    while (std::cin >> q) {
+        int a[6] = {0, 0, 0, 0, 0, 0};
+        const int n = q == "lockstep" ? 6 : q == "one_chain" ? 5 : q == "two_pass" ? 3 : (q == "lv" || q == "first_waves") ? 2 : -1;
+        if (n < 0) return fail("unknown query " + q);
+        for (int i = 0; i < n; ++i) std::cin >> a[i];
+        if (!std::cin) return fail("bad value for " + q);
+        mxe::KernelBuild b;
+        if (q == "first_waves") { std::printf("%d\n", mxe::first_waves(a[0], a[1])); continue; }
+        if (q != "one_chain" && (a[q == "lockstep" ? 4 : 1] < 0 || a[q == "lockstep" ? 4 : 1] > (1 << 24))) return fail("n_omega_pad out of range");
+        if (q == "lockstep") { const int rc = mxe::lockstep_build(a[0], a[1], a[2] != 0, a[3] != 0, a[4], a[5], b); print(rc, b, mxe::build_name(b)); }
+        else if (q == "one_chain") {
+            if ((a[0] != 64 && a[0] != 128) || a[1] < 0 || a[1] > (1 << 24) || a[2] < 1 || a[2] > 4 || a[3] < 1) return fail("one_chain: NP 64 or 128, NW 1 .. 4, NW_MIN >= 1");
+            const int rc = mxe::one_chain_build(a[0], a[1], a[2], a[3], a[4] != 0, b); print(rc, b, mxe::build_name(b));
+        } else if (q == "lv") { b = mxe::lv_build(a[0], a[1]); print(0, b, mxe::build_name(b)); }
+        else { const int rc = mxe::lockstep_build(32, a[2], false, false, a[1], 0, b); print(rc, b, mxe::two_pass_name(mxe::lv_build(a[0], a[1]), b)); }
+    }
+    return 0;
+}
+
 int main(int argc, char** argv)
 {
-    if (argc > 1) return std::strcmp(argv[1], "finish") == 0 ? finish_main() : fail(std::string("unknown mode ") + argv[1]);
+    if (argc > 1) return std::strcmp(argv[1], "finish") == 0 ? finish_main() : std::strcmp(argv[1], "build") == 0 ? build_main() : fail(std::string("unknown mode ") + argv[1]);
     mxe::PlanInput in;
     in.opts = mxe_opts();
     in.opts.decouple_tol = 1e-5;
@@ -96,7 +130,7 @@ int main(int argc, char** argv)
         else if (key == "n_cu") std::cin >> in.n_cu;
         else if (key == "wgpc_auto") std::cin >> in.wgpc_auto;
         else if (key == "mc_wgpc_hint") std::cin >> in.mc_wgpc_hint;
-        else if (key == "lds") std::cin >> in.lds_lv >> in.lds_mc32x1 >> in.lds_mc32x2 >> in.lds_mc64x1;
+        else if (key == "lds") std::cin >> in.lds_override[0] >> in.lds_override[1] >> in.lds_override[2] >> in.lds_override[3];
         else if (key == "opt") {
             double v; std::cin >> name >> v;
             mxe_opts& o = in.opts;
