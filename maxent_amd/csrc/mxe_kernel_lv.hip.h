@@ -41,9 +41,8 @@ namespace mxe {
 #ifndef MXE_X_LV_HIONLY
 #define MXE_X_LV_HIONLY 0        // 1: Gram tiles from the leading binary16 parts only (11 bits) -- experiment
 #endif
-constexpr int LV_ACAP = 16;             // alphas of a slot's piece kept in LDS (longer pieces read the mesh from memory)
 constexpr double LV_FLOOR = 2e-5;       // corrections below this that no longer halve: the binary32 rounding floor
-// (LV_NWV, LV_STATIC_LDS, lv_rows and lv_lds_bytes: mxe_shapes.h)
+// (LV_NWV, LV_STATIC_LDS, LV_ACAP, lv_rows and lv_lds_bytes: mxe_shapes.h)
 
 // exp(x) in binary32: k = rint(x log2 e), the remainder in two pieces (log2 e split), v_exp_f32, ldexp.
 // Overflow / underflow come out as inf / 0 like fast_exp.
@@ -188,6 +187,7 @@ void chain_kernel_lv(const KParams p, const MCExtra x)
             }
         }
     };
+    // (a piece beyond the table reads the scan's mesh, i < 0 included: the planner lays no ladder that long for this kernel, emit_scan)
     auto alpha_at = [&](const Slot& t, int i) -> double {
         return (t.clen + t.lead <= ACAP) ? s_alpha[wave][i + t.lead] : p.alpha[(size_t)t.prob0 + i];
     };

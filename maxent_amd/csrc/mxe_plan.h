@@ -66,6 +66,7 @@ namespace plan {
 struct State {
     int precision = MXE_PRECISION_F64, split = 0, split_pm = 0;       // split: pieces per scan; split_pm: per plus-minus scan where that differs (0: the same)
     bool lv_fits = false, f32_lv = false, ladder_ok = false;
+    bool fits32 = true;                // no alpha of the job couples more than 32 directions (choose_precision)
     bool cut_by_cost = false;          // launches that do not fill the GPU: pieces of equal COST, one per slot (decided once for the launch)
 };
 inline bool normal_elem(const PlanInput& in, int e) { return in.elem_kind[e] == MXE_ENTROPY_NORMAL; }
@@ -91,14 +92,16 @@ inline void choose_precision(const PlanInput& in, State& st)
     const bool lds_basis_ok = o.lds_basis != 2 && !in.env.no_lds_basis && lockstep_opts(in);
     st.lv_fits = in.n_omega_pad <= 512 && lds_basis_ok && lds_lv(in) <= LDS_CU;
     st.f32_lv = st.precision == MXE_PRECISION_F32 && st.lv_fits;
+    // (the criterion of choose_layout, per scan: no alpha of the job couples more than 32 directions)
+    for (int c = 0; c < in.n_chain && st.fits32 && in.n_s > 32; ++c) {
+        const double* ac = in.alpha + (size_t)c * in.n_alpha;
+        const double amin = *std::min_element(ac, ac + in.n_alpha);
+        if (!(coupling32(in, in.elem_of_chain[c]) / amin <= MC_COUPLING_MAX)) st.fits32 = false;
+    }
     if (st.f32_lv && in.n_s > 32) {
-        // (chain_kernel_lv has the plain 32-row build only: a job with an alpha that couples more than 32 directions -- the criterion
-        //  of choose_layout, per scan -- keeps the one-chain binary32 kernel AND its pieces of six alphas)
-        for (int c = 0; c < in.n_chain && st.f32_lv; ++c) {
-            const double* ac = in.alpha + (size_t)c * in.n_alpha;
-            const double amin = *std::min_element(ac, ac + in.n_alpha);
-            if (!(coupling32(in, in.elem_of_chain[c]) / amin <= MC_COUPLING_MAX)) st.f32_lv = false;
-        }
+        // (chain_kernel_lv has the plain 32-row build only: a job with an alpha that couples more than 32 directions keeps the
+        //  one-chain binary32 kernel AND its pieces of six alphas)
+        st.f32_lv = st.fits32;
         // Binary32 is asked for as the cheaper arithmetic; for such a job the cheaper arithmetic is the binary64 lock-step
         // build with the 64-row block (and the hand-over of what it leaves): the one-chain binary32 kernel took 0.7-1.5 s
         // where that takes 4-5 ms, and stops at its rounding floor besides (STRESS_F32=1 tools/stress.py, cases 24 / 25:
@@ -339,12 +342,19 @@ inline void emit_scan(const PlanInput& in, const State& st, int c, const std::ve
         const double r = ac[i - 1] / ac[i];
         return r > MC_LADDER_COARSE || r < 1.0 / MC_LADDER_COARSE;
     };
+    // (chain_kernel_lv keeps LV_ACAP alphas per slot, and a piece that does not fit that table reads every entry from the scan's
+    //  mesh: right for a piece the mesh leads, wrong for rungs.  Until this rule such a launch got the ladders of chain_kernel_mc
+    //  -- four alphas from alpha~ = 1e2 down to 1e-4 on 100 data points: 18 and 23 rungs + 1 alpha -- and walked the mesh BEFORE
+    //  the piece instead, for the first scan from in front of the alpha array.  The second line is what order_pieces asks of a
+    //  two-pass launch, short of a state in device memory, which no mesh that fits this kernel needs.)
+    const bool lv_table = st.f32_lv ||
+                          (st.lv_fits && st.precision == MXE_PRECISION_F64 && in.opts.lds_basis == 1 && st.fits32);
     auto emit_ladder = [&](int i, int len = 1) {
         const double a = ac[i];
         const double top = std::max(hard_below, a * ladder_ratio);
         int rungs = (int)std::ceil(std::log(top / a) / std::log(ladder_ratio) - 1e-9);
-        rungs = std::max(1, std::min(rungs, std::min(MC_LADDER_MAX, 30 - len)));      // (rungs + alphas of the piece: the slot's table of 32)
-        const double ratio = std::pow(top / a, 1.0 / rungs);          // (equal rungs; more than MC_LADDER_MAX would not fit the slot's table)
+        rungs = std::max(1, std::min(rungs, lv_table ? LV_ACAP - len : std::min(MC_LADDER_MAX, 30 - len)));      // (rungs + alphas of the piece: the slot's table of 32, of LV_ACAP in chain_kernel_lv)
+        const double ratio = std::pow(top / a, 1.0 / rungs);          // (equal rungs; more than that would not fit the slot's table)
         const int w0 = (int)lp.walk_alpha.size();
         for (int k = 0; k < rungs; ++k) lp.walk_alpha.push_back(a * std::pow(ratio, rungs - k));
         emit(i, len, rungs, w0);
@@ -354,7 +364,7 @@ inline void emit_scan(const PlanInput& in, const State& st, int c, const std::ve
     // sigma = 4e-5 the head took 2 989 evaluations and did not converge, tools/stress.py case 17).  It is led down a ladder from
     // N_data / 4 to its first alpha and goes on up its own mesh from there.
     auto emit_plain = [&](int first, int len) {
-        const bool deep = st.ladder_ok && len <= 24 && ac[first] * (ladder_ratio * ladder_ratio) < hard_below &&
+        const bool deep = st.ladder_ok && len <= (lv_table ? LV_ACAP : 32) - 8 && ac[first] * (ladder_ratio * ladder_ratio) < hard_below &&
                           (first == 0 || ac[first - 1] < ac[first]);
         if (deep) emit_ladder(first, len); else emit(first, len, 0, -1);
     };

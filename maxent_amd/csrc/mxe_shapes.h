@@ -14,6 +14,8 @@ constexpr int GRAM_R = 4;         // chain_kernel: rows staged per wave per Gram
 constexpr int GBLK = 6;           //   staged doubles per 4-column block (16-B aligned, bank spread)
 constexpr int LV_NWV = 8;         // chain_kernel_lv: wavefronts per workgroup
 constexpr int LV_STATIC_LDS = 2304;     //   bound on the __shared__ arrays of the kernel (host side: fits-the-LDS test)
+constexpr int LV_ACAP = 16;             //   alphas of a slot's piece kept in LDS: a laddered piece walks its rungs from that table only, so rungs + alphas
+                                        //   of such a piece stay within it (emit_scan of mxe_plan.h); longer pieces read the scan's mesh from memory
 
 // omega-space state of one workgroup of a GSTATE build of chain_kernel_mc, in doubles: u [nwp][4] | H [nwp][4] + look-ahead | sw [nwp][4] floats + look-ahead
 constexpr int MC_GSTATE_PAD = 1024;

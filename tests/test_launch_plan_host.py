@@ -16,6 +16,7 @@ from plan_dump_build import plan_dump_binary, run_plan_dump as run_text
 NORMAL, PM = 0, 1
 N_CU = 256
 LADDER_RATIO = 1.56
+LV_ACAP = 16             # alphas of a slot's piece that chain_kernel_lv keeps in LDS (mxe_shapes.h)
 # dynamic LDS of chain_kernel_lv with its static arrays and of chain_kernel_mc<32, 1>, <32, 2>, <64, 1>: 0 = what the planner's own
 # formulas give (mxe_shapes.h; at n_omega_pad = 512, n_s = 56: 161 536, 98 304, 77 824, 155 648 -- all of them fit 160 KB, 160 KB - 6 KB,
 # 80 KB - 2 KB, 160 KB - 6 KB; tests/test_kernel_build_host.py derives them).  A case overrides one with TOO_BIG to say "does not fit"
@@ -102,17 +103,25 @@ def check_invariants(c, p):
             assert b['prob0'] >= a['prob0'] + a['len']
             assert all(x in excluded for x in range(a['prob0'] + a['len'], b['prob0']))
     # led and laddered pieces fit the slot's table of 32 alphas; the ladders
+    in_lv = p['lv_mode'] in (1, 2)
     for q in pieces:
         assert q['pre'] >= 0 and (q['pre'] > 0 or q['walk0'] == -1)
         if q['pre'] > 0:
             assert q['pre'] + q['len'] <= 32
         if q['walk0'] >= 0:
             assert 1 <= q['pre'] <= 28
+            # chain_kernel_lv walks rungs from its table of LV_ACAP alphas only (alpha_at: a piece beyond the table reads the scan's mesh)
+            if in_lv:
+                assert q['pre'] + q['len'] <= LV_ACAP, (q, p['lv_mode'])
             rungs = p['walk_alpha'][q['walk0']:q['walk0'] + q['pre']]
             assert len(rungs) == q['pre']
             a = alpha[q['prob0']]
             assert all(x > y for x, y in zip(rungs, rungs[1:])) and rungs[-1] > a
-            assert rungs[-1] / a <= LADDER_RATIO * (1 + 1e-12)
+            # equal rungs from max(N_data / 4, a x LADDER_RATIO) down to a: of at most LADDER_RATIO unless the table cuts their number
+            top = max(0.25 * c['rows'][c['ds'][q['elem']]], a * LADDER_RATIO)
+            np.testing.assert_allclose(rungs, a * (top / a) ** (np.arange(q['pre'], 0, -1) / q['pre']), rtol=1e-12)
+            if q['pre'] + q['len'] < LV_ACAP if in_lv else (q['pre'] < 28 and q['pre'] + q['len'] < 30):
+                assert rungs[-1] / a <= LADDER_RATIO * (1 + 1e-12)
         elif q['pre'] > 0:
             assert q['prob0'] - q['pre'] >= q['v0'] * n_alpha          # led by an alpha of its own scan
     layout, n = p['layout'], len(pieces)
@@ -233,6 +242,50 @@ def test_a_coarse_mesh_gets_ladders(plan_dump):
         assert head['prob0'] == scan * 5 and head['pre'] == 0 and head['walk0'] == -1
     off = plan(plan_dump, case([NORMAL, PM], a, env=dict(no_ladder=1)))
     assert not off['walk_alpha']
+
+
+def rungs_wanted(a, n_data):
+    return max(1, math.ceil(math.log(max(0.25 * n_data, a * LADDER_RATIO) / a) / math.log(LADDER_RATIO) - 1e-9))
+
+
+@pytest.mark.parametrize('n_tau', [30, 100, 200])
+@pytest.mark.parametrize('n_alpha,lo', [(4, 1e-4), (8, 1e-5)])
+@pytest.mark.parametrize('opts,lv_mode', [(dict(precision=1), 1), (dict(lds_basis=1), 2)])
+def test_ladders_of_a_launch_in_chain_kernel_lv_fit_its_table_of_16(plan_dump, opts, lv_mode, n_alpha, lo, n_tau):
+    """A coarse mesh (alpha~ from 1e2 down to 1e-4 on 4 points, to 1e-5 on 8) in chain_kernel_lv, as the launch (precision = F32)
+    and as the first pass (lds_basis = 1).  chain_kernel_mc holds 32 alphas per slot and gets up to 28 rungs; chain_kernel_lv holds
+    LV_ACAP = 16, and alpha_at sends a piece with more entries to the scan's mesh, where no rung is: rungs + alphas of a laddered
+    piece are at most 16 there (check_invariants), and exactly 16 where a ratio of 1.56 would want more.  The same mesh without
+    the option keeps the long ladders.  (Until the planner knew the table the lv plans held the pieces of the other kernel: n_tau
+    = 100, four alphas: 18 and 23 rungs + 1.)"""
+    a = mesh(n_alpha, hi=1e2, lo=lo, n_tau=n_tau)
+    p = plan(plan_dump, case([NORMAL, PM], a, rows=(n_tau,), opts=opts))
+    assert (p['rc'], p['lv_mode'], p['layout'], p['mc_na']) == (0, lv_mode, 4, 32)
+    mc = plan(plan_dump, case([NORMAL, PM], a, rows=(n_tau,)))
+    assert mc['lv_mode'] == 0 and len(mc['pieces']) == len(p['pieces'])
+    laddered, longest = 0, 0
+    for q, q_mc in zip(p['pieces'], mc['pieces']):
+        assert (q['prob0'], q['len'], q['walk0'] >= 0) == (q_mc['prob0'], q_mc['len'], q_mc['walk0'] >= 0)
+        if q['walk0'] >= 0:
+            want = rungs_wanted(a[q['prob0'] % n_alpha], n_tau)
+            assert q['pre'] == min(want, LV_ACAP - q['len']) and q_mc['pre'] == min(want, 28, 30 - q_mc['len'])
+            laddered += 1
+            longest = max(longest, want + q['len'])
+    # every alpha below N_data / 4 but the head of a scan is such a piece, and some of them wanted more than the table holds
+    assert laddered == 2 * int(np.sum(a[1:] < 0.25 * n_tau)) and longest > LV_ACAP
+
+
+def test_a_long_piece_deep_in_the_hard_region_is_laddered_in_chain_kernel_lv_only_where_the_table_takes_it(plan_dump):
+    """an ascending scan in the hard region: every piece is led down a ladder to its first alpha -- in chain_kernel_lv pieces of up
+    to LV_ACAP - 8 alphas (the other kernels: 32 - 8), so that at least eight rungs fit; a longer piece starts cold"""
+    a = 0.5 * 1.09 ** np.arange(40)
+    for split, laddered in ((5, True), (4, False)):            # pieces of 8 and of 10 alphas
+        p = plan(plan_dump, case([NORMAL, PM], a, opts=dict(precision=1, alpha_split=split)))
+        assert p['lv_mode'] == 1 and all(q['len'] == 40 // split for q in p['pieces'])
+        assert all((q['walk0'] >= 0) == laddered for q in p['pieces'])
+        assert all(q['pre'] == (min(rungs_wanted(a[q['prob0'] % 40], 200), LV_ACAP - q['len']) if laddered else 0) for q in p['pieces'])
+    p = plan(plan_dump, case([NORMAL, PM], a, opts=dict(alpha_split=4)))
+    assert p['lv_mode'] == 0 and all(q['walk0'] >= 0 and q['len'] == 10 for q in p['pieces'])
 
 
 def test_an_ascending_scan_in_the_hard_region_starts_every_piece_with_a_ladder(plan_dump):
