@@ -981,6 +981,36 @@ int  mxe_fullmatrix_solve_metric(int device, int n_prob, int m, int is_complex, 
                                  double* out_u, double* out_H, double* out_chi2, double* out_S, double* out_Q,
                                  int32_t* out_niter, int32_t* out_conv, float* out_ms);
 
+/* Posterior (Gaussian) variances of the whole-matrix continuation with one error for all matrix elements, around the u of
+ * mxe_fullmatrix_solve (the same V', c, D, scaled alpha and basis E_p).  In the coordinates h_p,i = Tr(E_p H_i) the matrix
+ * entropy has the Hessian -L^-1, L_i (P x P) the Frechet derivative of D exp at Gamma_i, and the covariance of h is
+ *   Gamma = (alpha L^-1 + (V' c^2 V'^T) (x) 1_P)^-1,   B = alpha I + c W c = L_B L_B^T of order d = P n_s (W: the solver's Gram matrix)
+ *   var(x)     = (1 / alpha) [ sum_i f_i^T L_i f_i - |L_B^-1 y|^2 ],  y_(p,s) = c_s sum_i V'_is (L_i f_i)_p,  x = sum_p,i f_p,i h_p,i
+ *   var(h_p,i) = (1 / alpha) [ L_i,pp - |L_B^-1 y|^2 ],               y_(q,s) = c_s V'_is L_i,qp
+ * formed as written (differences of sums of non-negative terms; a negative difference is returned as 0, a NaN stays one).
+ * One workgroup per job, a job being one (u, alpha) pair; jobs share V', c, D and F.  For m = 1 this is mxe_posterior_var
+ * with w = H.
+ *   alpha       n_job, > 0;   u  n_job x P x n_s
+ *   F           n_f x P x n_omega: the coordinates f_p,i = Tr(E_p F_i) of Hermitian weights on H (NULL with n_f == 0)
+ *   want_diag   1: also the variance of every coordinate
+ *   out_value, out_var, out_prior   n_job x n_f: x, var(x), and the variance sum_i f_i^T L_i f_i / alpha the entropy alone leaves
+ *   out_diag_var, out_diag_prior, out_h   n_job x P x n_omega (want_diag): var(h_p,i), L_i,pp / alpha, h_p,i
+ *   out_ms      device time of the kernel (may be NULL)
+ * A job whose u or H is not finite, or whose B is not positive definite in binary64, gets NaN in all its outputs; the other
+ * jobs are not touched.  No atomics, fixed summation order: the bits of a job do not depend on the batch, on n_f or on a
+ * functional's place in F.  The device scratch is one slice per workgroup; the workgroups take the jobs in strides over as
+ * many slices as fit below MXE_FULLMATRIX_POSTVAR_SCRATCH_BYTES (one at least); results do not depend on their number.
+ * MXE_ERR_ARG (nothing is launched): a size < 1, n_f < 0, nothing asked for (n_f == 0 without want_diag), a NULL among the
+ * arrays that are needed, a NaN or an Inf in V, c, D, alpha or F, a c, D or alpha that is not positive, sizes whose products
+ * exceed 2^31 - 1.  MXE_ERR_LIMIT: m > MXE_FULLMATRIX_MAX_M, n_s > MXE_FULLMATRIX_MAX_NS, or more than 160 KB of LDS (a block
+ * of 16 right-hand sides of order d <= 1024 fills 141 KB).  MXE_ERR_NODEVICE: no device. */
+#define MXE_FULLMATRIX_POSTVAR_SCRATCH_BYTES  (1ull << 30)
+int  mxe_fullmatrix_posterior_var(int device, int n_job, int m, int is_complex, int n_omega, int n_s, int n_f,
+                                  const double* V, const double* c, const double* D, const double* alpha,
+                                  const double* u, const double* F, int want_diag,
+                                  double* out_value, double* out_var, double* out_prior,
+                                  double* out_diag_var, double* out_diag_prior, double* out_h, float* out_ms);
+
 #ifdef __cplusplus
 }
 #endif

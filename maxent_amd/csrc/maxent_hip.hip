@@ -3741,3 +3741,75 @@ try {
                                 ghat, cperp, u0, maxiter, tol_h, out_u, out_H, out_chi2, out_S, out_Q, out_niter, out_conv, out_ms);
 }
 MXE_CATCH_ALL
+
+// ---- posterior variances of the whole-matrix continuation (mxe_fullmatrix_postvar.hip.h) ----
+#include "mxe_fullmatrix_postvar.hip.h"
+
+extern "C" int mxe_fullmatrix_posterior_var(int device, int n_job, int m, int is_complex, int n_omega, int n_s, int n_f,
+                                            const double* V, const double* c, const double* D, const double* alpha,
+                                            const double* u, const double* F, int want_diag,
+                                            double* out_value, double* out_var, double* out_prior,
+                                            double* out_diag_var, double* out_diag_prior, double* out_h, float* out_ms)
+try {
+    if (n_job < 1 || m < 1 || (is_complex != 0 && is_complex != 1) || n_omega < 1 || n_s < 1 || n_f < 0 ||
+        (want_diag != 0 && want_diag != 1) || (n_f == 0 && !want_diag) || !V || !c || !D || !alpha || !u ||
+        (n_f > 0 && (!F || !out_value || !out_var || !out_prior)) || (want_diag && (!out_diag_var || !out_diag_prior || !out_h)))
+        return MXE_ERR_ARG;
+    if (m > mxe::FM_MAX_M || n_s > mxe::FM_MAX_NS) return MXE_ERR_LIMIT;
+    const bool cplx = is_complex != 0;
+    const size_t nj = n_job, nw = n_omega, ns = n_s, nf = n_f, P = mxe::fm_P(m, cplx), d = P * ns, npw = P * nw;
+    if (nw * ns > 0x7fffffffull || nj * npw > 0x7fffffffull || nj * d > 0x7fffffffull || nf * npw > 0x7fffffffull ||
+        nj * nf > 0x7fffffffull || P * (P + 1) / 2 * nw > 0x7fffffffull || 16 * npw > 0x7fffffffull)
+        return MXE_ERR_ARG;
+    // (u is not looked at: a job whose u is not finite gets NaN from the kernel, its neighbours are not touched)
+    if (!all_finite(V, nw * ns) || !all_finite(c, ns) || !all_finite(D, nw) || !all_finite(alpha, nj) || (nf && !all_finite(F, nf * npw)))
+        return MXE_ERR_ARG;
+    for (size_t i = 0; i < nw; ++i) if (!(D[i] > 0.0)) return MXE_ERR_ARG;
+    for (size_t k = 0; k < ns; ++k) if (!(c[k] > 0.0)) return MXE_ERR_ARG;
+    for (size_t a = 0; a < nj; ++a) if (!(alpha[a] > 0.0)) return MXE_ERR_ARG;
+    const size_t lds = mxe::fmpv_lds_doubles((int)d) * sizeof(double);
+    if (lds > 160 * 1024) return MXE_ERR_LIMIT;
+    // the scratch: one slice per workgroup, as many workgroups as fit below MXE_FULLMATRIX_POSTVAR_SCRATCH_BYTES (one at least)
+    const size_t scr = mxe::fmpv_scratch_doubles(m, cplx, n_omega, n_s);
+    size_t n_slices = (size_t)MXE_FULLMATRIX_POSTVAR_SCRATCH_BYTES / (scr * sizeof(double));
+    if (n_slices < 1) n_slices = 1;
+    if (n_slices > nj) n_slices = nj;
+    Stage sg;
+    if (int rc = sg.open(device); rc != MXE_OK) return rc;
+    mxe::FullMatrixPostVarParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.n_job = n_job; p.n_omega = n_omega; p.n_s = n_s; p.n_f = n_f; p.want_diag = want_diag;
+    Block in;
+    const size_t oV = in.add(nw * ns), oc = in.add(ns), oD = in.add(nw), oa = in.add(nj), ou = in.add(nj * d), oF = in.add(nf * npw);
+    double* din;
+    STGCHK(sg, sg.alloc(&din, in.total));
+    STGCHK(sg, sg.upload(din + oV, V, nw * ns)); STGCHK(sg, sg.upload(din + oc, c, ns));
+    STGCHK(sg, sg.upload(din + oD, D, nw)); STGCHK(sg, sg.upload(din + oa, alpha, nj));
+    STGCHK(sg, sg.upload(din + ou, u, nj * d)); STGCHK(sg, sg.upload(din + oF, F, nf * npw));
+    p.V = din + oV; p.c = din + oc; p.D = din + oD; p.alpha = din + oa; p.u = din + ou; p.F = nf ? din + oF : nullptr;
+    STGCHK(sg, sg.alloc(&p.scratch, n_slices * scr));
+    const size_t nd = want_diag ? nj * npw : 0;
+    Block out;
+    const size_t ox = out.add(nj * nf), ov = out.add(nj * nf), op = out.add(nj * nf), odv = out.add(nd), odp = out.add(nd),
+                 oh = out.add(nd);
+    double* dout;
+    STGCHK(sg, sg.alloc(&dout, out.total));
+    p.out_value = dout + ox; p.out_var = dout + ov; p.out_prior = dout + op;
+    p.out_diag = dout + odv; p.out_dprior = dout + odp; p.out_h = dout + oh;
+    typedef void (*kernel_t)(const mxe::FullMatrixPostVarParams);
+    static const kernel_t kernels[2][4] = {
+        {mxe::fullmatrix_postvar_kernel<1, false>, mxe::fullmatrix_postvar_kernel<2, false>,
+         mxe::fullmatrix_postvar_kernel<3, false>, mxe::fullmatrix_postvar_kernel<4, false>},
+        {mxe::fullmatrix_postvar_kernel<1, true>, mxe::fullmatrix_postvar_kernel<2, true>,
+         mxe::fullmatrix_postvar_kernel<3, true>, mxe::fullmatrix_postvar_kernel<4, true>}};
+    STGCHK(sg, sg.time_begin(out_ms != nullptr));
+    STGCHK(sg, launch_lds(kernels[cplx ? 1 : 0][m - 1], dim3((unsigned)n_slices), dim3(mxe::FM_T), lds, sg.stream, p));
+    STGCHK(sg, sg.time_end());
+    STGCHK(sg, sg.fetch(out_value, p.out_value, nj * nf)); STGCHK(sg, sg.fetch(out_var, p.out_var, nj * nf));
+    STGCHK(sg, sg.fetch(out_prior, p.out_prior, nj * nf));
+    STGCHK(sg, sg.fetch(out_diag_var, p.out_diag, nd)); STGCHK(sg, sg.fetch(out_diag_prior, p.out_dprior, nd));
+    STGCHK(sg, sg.fetch(out_h, p.out_h, nd));
+    STGCHK(sg, sg.finish(out_ms));
+    return MXE_OK;
+}
+MXE_CATCH_ALL

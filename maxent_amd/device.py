@@ -194,6 +194,8 @@ SYMBOLS = [
                                            [_ip, _ip, ctypes.POINTER(ctypes.c_float)]),
     ('mxe_fullmatrix_solve_metric', ctypes.c_int, [ctypes.c_int] * 7 + [_dp] * 8 + [ctypes.c_int, ctypes.c_double] +
                                                   [_dp] * 5 + [_ip, _ip, ctypes.POINTER(ctypes.c_float)]),
+    ('mxe_fullmatrix_posterior_var', ctypes.c_int, [ctypes.c_int] * 7 + [_dp] * 6 + [ctypes.c_int] + [_dp] * 6 +
+                                                   [ctypes.POINTER(ctypes.c_float)]),
 ]
 
 
@@ -1045,6 +1047,67 @@ def fullmatrix_solve_metric(V, R, A, D, alpha, ghat, cperp, m, use_complex, u0=N
     Hm = H[:, :, 0] + 1.0j * H[:, :, 1] if use_complex else H[:, :, 0]          # (n_prob, n_alpha, m, m, n_omega)
     return dict(u=u, H=np.ascontiguousarray(np.moveaxis(Hm, 1, 3)), chi2=chi2, S=S, Q=Q, n_iter=n_iter,
                 converged=conv != 0)
+
+
+def fullmatrix_posterior_var(V, c, D, alpha, u, m, use_complex, F=None, want_diag=False, device=0, timing=None):
+    """``mxe_fullmatrix_posterior_var``: posterior variances of the whole-matrix continuation.  ``V`` (n_omega, n_s),
+    ``c`` (n_s,), ``D`` (n_omega,) as for :func:`fullmatrix_solve`; a job is one pair of ``alpha`` (n_job,) and ``u``
+    (n_job, P, n_s); ``F`` (n_f, P, n_omega): the coordinates Tr(E_p F_i) of Hermitian weights on H, shared by the jobs.
+    Returns a dict: ``value``, ``var``, ``prior`` (n_job, n_f) and, with ``want_diag``, ``diag_var``, ``diag_prior``, ``h``
+    (n_job, P, n_omega), the variance of every coordinate h_p,i, the variance the entropy alone leaves, and h itself.  A job
+    whose ``u`` or H is not finite or whose curvature is not positive definite is NaN throughout; ``u`` is therefore the one
+    input that may hold a NaN.  ``timing``: a dict that receives the device time ``ms`` of the kernel.  The refusals are
+    those of :func:`fullmatrix_solve`: arguments the library would refuse raise ValueError before it is called."""
+    V, c, D, alpha, u = _c(V), _c(c), _c(D), _c(alpha), _c(u)
+    m, use_complex, want_diag = int(m), bool(use_complex), bool(want_diag)
+    if m < 1 or m > FULLMATRIX_MAX_M:
+        raise ValueError('fullmatrix_posterior_var: matrices of %d x %d; 1 to %d are supported' % (m, m, FULLMATRIX_MAX_M))
+    if V.ndim != 2 or V.shape[0] < 1 or V.shape[1] < 1:
+        raise ValueError('fullmatrix_posterior_var: V must be (n_omega, n_s); got %s' % (V.shape,))
+    n_omega, n_s = V.shape
+    if n_s > FULLMATRIX_MAX_NS:
+        raise ValueError('fullmatrix_posterior_var: %d singular values; at most %d are supported: cut the singular space with '
+                         'reduce_singular_space' % (n_s, FULLMATRIX_MAX_NS))
+    P = fullmatrix_P(m, use_complex)
+    if c.shape != (n_s,) or D.shape != (n_omega,) or alpha.ndim != 1 or alpha.size < 1:
+        raise ValueError('fullmatrix_posterior_var: c must be (n_s,), D (n_omega,), alpha one-dimensional and not empty')
+    n_job = alpha.size
+    if u.shape != (n_job, P, n_s):
+        raise ValueError('fullmatrix_posterior_var: u must be (n_job, %d, %d) for %d alphas; got %s' % (P, n_s, n_job, u.shape))
+    if F is not None:
+        F = _c(F)
+        if F.ndim != 3 or F.shape[1:] != (P, n_omega):
+            raise ValueError('fullmatrix_posterior_var: F must be (n_f, %d, %d); got %s' % (P, n_omega, F.shape))
+        if F.shape[0] == 0:
+            F = None
+    n_f = 0 if F is None else F.shape[0]
+    if n_f == 0 and not want_diag:
+        raise ValueError('fullmatrix_posterior_var: nothing to compute: give F or want_diag')
+    for name, a in (('V', V), ('c', c), ('D', D), ('alpha', alpha), ('F', F)):
+        if a is not None and not np.all(np.isfinite(a)):
+            raise ValueError('fullmatrix_posterior_var: %s is not finite' % name)
+    if not (np.all(c > 0) and np.all(D > 0) and np.all(alpha > 0)):
+        raise ValueError('fullmatrix_posterior_var: c, D and alpha must be positive')
+    if max(n_job * P * n_omega, n_job * P * n_s, n_omega * n_s, n_f * P * n_omega, n_job * n_f, 16 * P * n_omega,
+           P * (P + 1) // 2 * n_omega) > 2 ** 31 - 1:
+        raise ValueError('fullmatrix_posterior_var: the arrays of this call hold more than 2^31 - 1 numbers')
+    lib = load_library()
+    if device_count() < 1:
+        raise MaxEntDeviceError('no HIP device visible; mxe_fullmatrix_posterior_var has no CPU fallback')
+    value, var, prior = (np.empty((n_job, n_f)) for _ in range(3))
+    dv, dp, h = (np.empty((n_job, P, n_omega)) if want_diag else None for _ in range(3))
+    ms = ctypes.c_float(0)
+    rc = lib.mxe_fullmatrix_posterior_var(int(device), n_job, m, 1 if use_complex else 0, n_omega, n_s, n_f, _p(V), _p(c), _p(D),
+                                          _p(alpha), _p(u), _p(F), 1 if want_diag else 0, _p(value), _p(var), _p(prior),
+                                          _p(dv), _p(dp), _p(h), ctypes.byref(ms))
+    if rc != 0:
+        raise MaxEntDeviceError('mxe_fullmatrix_posterior_var failed: ' + lib.mxe_strerror(rc).decode())
+    if timing is not None:
+        timing['ms'] = float(ms.value)
+    out = dict(value=value, var=var, prior=prior)
+    if want_diag:
+        out.update(diag_var=dv, diag_prior=dp, h=h)
+    return out
 
 
 class DeviceContext(object):

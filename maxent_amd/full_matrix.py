@@ -17,6 +17,11 @@ diagonal S / sigma); the default model D(omega) times the unit matrix; M <= 4 an
 bosonic data, ``set_cov``, bins, preblur, a matrix-valued default model, the probability-based analyzers (Bryan, Classic)
 and ``probability=``.
 
+Error bars: ``FullMatrixMaxEnt.posterior_errors`` / :func:`full_matrix_posterior_errors` (``mxe_fullmatrix_posterior_var``,
+DESIGN 4za), the Gaussian posterior around the minimiser for spectral weights in windows, linear functionals and every
+A_ab(omega_i); for a job with one error for all matrix elements.  The other result-taking methods of the scalar worker
+(samples, diagnostics, response, resampling, bootstrap, model scans, bin checks) are refused, not forwarded.
+
 alpha is scaled by n_tau, the number of data of ONE matrix element (``scale_alpha='Ndata'``): block-diagonal data then
 decouple into exactly the ``DiagonalMaxEnt`` problems at the same mesh alpha.
 """
@@ -231,6 +236,182 @@ def full_matrix_continue(G_batch, U, S, V, D, alpha, err=None, use_complex=False
     return out
 
 
+# ---- posterior error bars ------------------------------------------------------------------------------------
+
+def functional_coordinates(functionals, M, use_complex, n_omega):
+    """The coordinates f_p,i = Tr(E_p F_i) (n_f, P, n_omega) of the weights ``functionals``, (n_f, M, M, n_omega) or
+    (M, M, n_omega), Hermitian at every omega; x = sum_i Tr(F_i H_i) = sum_p,i f_p,i h_p,i.  ValueError for anything else;
+    complex weights need ``use_complex``."""
+    F = np.asarray(functionals)
+    if F.dtype.kind not in 'biufc':
+        raise ValueError('functionals: numbers are needed, got %s' % F.dtype)
+    if F.ndim == 3:
+        F = F[None]
+    if F.ndim != 4 or F.shape[1:] != (M, M, n_omega):
+        raise ValueError('functionals: shape (n_f, %d, %d, %d) or (%d, %d, %d) is needed, got %s'
+                         % (M, M, n_omega, M, M, n_omega, np.shape(functionals)))
+    if not np.all(np.isfinite(F)):
+        raise ValueError('functionals hold values that are not finite')
+    if np.iscomplexobj(F) and not use_complex and np.any(F.imag != 0.0):
+        raise ValueError('functionals are complex; construct FullMatrixMaxEnt(use_complex=True)')
+    F = np.array(F, dtype=complex)
+    asym = np.abs(F - np.conj(np.swapaxes(F, 1, 2)))
+    if np.any(asym > 8.0 * np.finfo(float).eps * max(1.0, float(np.max(np.abs(F))) if F.size else 1.0)):
+        n, a, b, i = (int(x) for x in np.argwhere(asym == asym.max())[0])
+        raise ValueError('functionals: weight %d is not Hermitian at point %d: |F[%d, %d] - conj(F[%d, %d])| = %.3g'
+                         % (n, i, a, b, b, a, asym[n, a, b, i]))
+    return np.ascontiguousarray(np.einsum('pba,nabi->npi', hermitian_basis(M, use_complex), F).real)
+
+
+def window_coordinates(omega, windows, M, use_complex):
+    """The functionals of the windows ``[(lo, hi), ...]`` as coordinates (n_win (P + 1), P, n_omega): per window the P
+    coordinate functionals sum_{i in window} h_p,i, p in the order of :func:`hermitian_basis`, then the trace
+    sum_{i in window} Tr H_i"""
+    from .posterior import window_rows
+    rows = window_rows(omega, windows)                           # (n_win, n_omega)
+    P = _dev.fullmatrix_P(M, use_complex)
+    f = np.zeros((len(rows), P + 1, P, rows.shape[1]))
+    for p in range(P):
+        f[:, p, p, :] = rows
+    for a in range(M):
+        f[:, P, a, :] = rows
+    return f.reshape(len(rows) * (P + 1), P, rows.shape[1])
+
+
+def elements_of_coordinates(x, M, use_complex):
+    """(re, im), each (..., M, M): the matrix sum_p x_p E_p of coordinates ``x`` (..., P): re[a, a] = x_a and, for the pair
+    p of a < b, re[a, b] = re[b, a] = x_p / sqrt 2, im[a, b] = -im[b, a] = x_p' / sqrt 2 (p' the antisymmetric partner;
+    zero without ``use_complex``)"""
+    x = np.asarray(x, dtype=float)
+    re, im = np.zeros(x.shape[:-1] + (M, M)), np.zeros(x.shape[:-1] + (M, M))
+    pairs = [(a, b) for a in range(M) for b in range(a + 1, M)]
+    for a in range(M):
+        re[..., a, a] = x[..., a]
+    for k, (a, b) in enumerate(pairs):
+        re[..., a, b] = re[..., b, a] = x[..., M + k] / np.sqrt(2.0)
+        if use_complex:
+            im[..., a, b] = x[..., M + len(pairs) + k] / np.sqrt(2.0)
+            im[..., b, a] = -im[..., a, b]
+    return re, im
+
+
+def element_errors_of_coordinates(var, M, use_complex):
+    """(err_re, err_im), each (..., M, M): the standard deviations of the real and of the imaginary part of the matrix
+    elements from the variances ``var`` (..., P) of its coordinates: sqrt(var_a) on the diagonal, sqrt(var_p / 2) for both
+    elements of a pair; err_im is symmetric, zero on the diagonal and zero without ``use_complex``"""
+    re, im = elements_of_coordinates(np.sqrt(np.asarray(var, dtype=float)), M, use_complex)
+    return re, np.abs(im)
+
+
+def full_matrix_posterior_errors(u, U, S, V, D, alpha, err, use_complex=False, functionals=None, windows=None, omega=None,
+                                 pointwise=False, device=0):
+    """Posterior error bars of whole-matrix continuations with one error for all matrix elements, in the Gaussian
+    approximation around the minimisers ``u`` (n_prob, n_alpha', P, n_s) of :func:`full_matrix_continue` at the scaled
+    ``alpha`` (n_alpha',), on the device (``mxe_fullmatrix_posterior_var``, one workgroup per (problem, alpha)).
+    ``U, S, V, D, err`` as there (with one error per data point u is rotated into the whitened basis exactly as there).
+
+    ``functionals``: (n_f, M, M, n_omega) or (M, M, n_omega), Hermitian weights F on A delta_omega, x = sum_i Tr(F_i H_i);
+    ``windows=[(lo, hi), ...]`` on the mesh ``omega``: the spectral weight of every matrix element and of the trace inside;
+    ``pointwise``: the error of every A_ab(omega_i) (``omega``: a mesh with ``delta``, or the points) -- large and strongly
+    correlated between neighbours: only integrated quantities have meaningful errors.
+
+    Returns a dict, every array with (n_prob, n_alpha') in front: ``functional_value``, ``functional_err``,
+    ``functional_prior_err`` (n_f); ``window_weight``, ``window_err``, ``window_prior_err`` (n_win, M, M), the integral of
+    Re A_ab and its standard deviation, with ``use_complex`` also ``window_weight_imag``, ``window_err_imag``;
+    ``window_trace``, ``window_trace_err``, ``window_trace_prior_err`` (n_win); ``A``, ``A_err``, ``A_prior_err`` (M, M,
+    n_omega), ``A_err`` the standard deviation of Re A_ab(omega_i), with ``use_complex`` also ``A_err_imag`` (zero on the
+    diagonal); ``alpha``; ``info`` (``kernel_ms``; ``nan_jobs``: the (problem, alpha) pairs whose u or H is not finite or
+    whose curvature is not positive definite: they are NaN).  The prior errors are what the entropy alone would leave."""
+    u = np.asarray(u, dtype=float)
+    U, S, V, D = (np.asarray(x, dtype=float) for x in (U, S, V, D))
+    alpha = np.atleast_1d(np.asarray(alpha, dtype=float))
+    if u.ndim != 4 or alpha.ndim != 1 or u.shape[1] != len(alpha):
+        raise ValueError('full_matrix_posterior_errors: u must be (n_prob, n_alpha, P, n_s) with one alpha per row; got %s and '
+                         '%d alphas' % (u.shape, alpha.size))
+    n_prob, n_alpha, P, n_s = u.shape
+    Ms = [m for m in range(1, MAX_M + 1) if _dev.fullmatrix_P(m, use_complex) == P]
+    if not Ms:
+        raise ValueError('full_matrix_posterior_errors: %d components are no %s matrix of at most %d x %d'
+                         % (P, 'complex Hermitian' if use_complex else 'real symmetric', MAX_M, MAX_M))
+    M = Ms[0]
+    if U.ndim != 2 or S.shape != (U.shape[1],) or V.ndim != 2 or V.shape[1] != U.shape[1] or n_s != U.shape[1]:
+        raise ValueError('full_matrix_posterior_errors: U must be (n_data, n_s), S (n_s,), V (n_omega, n_s), u (..., n_s); got '
+                         '%s, %s, %s, %s' % (U.shape, S.shape, V.shape, u.shape))
+    if n_s > MAX_NS:
+        raise ValueError('full_matrix_posterior_errors: %d singular values; at most %d are supported: cut the singular space '
+                         'with reduce_singular_space' % (n_s, MAX_NS))
+    n_omega = V.shape[0]
+    if D.shape != (n_omega,):
+        raise NotImplementedError('full_matrix_posterior_errors: the default model must be one D(omega) of shape (%d,); a '
+                                  'matrix-valued model is not supported; got %s' % (n_omega, D.shape))
+    err = np.asarray(err, dtype=float)
+    if err.ndim > 1 or (err.ndim == 1 and err.shape != (U.shape[0],)):
+        raise ValueError('full_matrix_posterior_errors: one error for all data or one per data point, shared by all matrix '
+                         'elements; got shape %s' % (err.shape,))
+    if not (np.all(np.isfinite(err)) and np.all(err > 0)):
+        raise ValueError('full_matrix_posterior_errors: the error must be positive and finite')
+    n_win = 0 if windows is None else len(windows)
+    if (n_win or pointwise) and omega is None:
+        raise ValueError('full_matrix_posterior_errors: windows and pointwise need the mesh omega')
+    rows = []
+    if n_win:
+        if len(np.asarray(omega, dtype=float)) != n_omega:
+            raise ValueError('full_matrix_posterior_errors: omega has %d points, V %d' % (len(np.asarray(omega)), n_omega))
+        rows.append(window_coordinates(omega, windows, M, use_complex))
+    n_fun = 0
+    if functionals is not None:
+        rows.append(functional_coordinates(functionals, M, use_complex, n_omega))
+        n_fun = len(rows[-1])
+    if not rows and not pointwise:
+        raise ValueError('nothing to compute: give windows=, functionals= or pointwise=True')
+    F = np.concatenate(rows) if rows else None
+    _, c, Vw, Q = whiten(U, S, V, err)
+    uw = u if Q is None else np.dot(u, Q)                       # u' = Q^T u
+    t = {}
+    out = _dev.fullmatrix_posterior_var(Vw, c, D, np.tile(alpha, n_prob), uw.reshape(n_prob * n_alpha, P, n_s), M, use_complex,
+                                        F=F, want_diag=pointwise, device=device, timing=t)
+    lead = (n_prob, n_alpha)
+    res = dict(alpha=np.array(alpha))
+    nan = np.zeros(lead, dtype=bool)
+    if F is not None:
+        val, var, pri = (out[k].reshape(lead + (-1,)) for k in ('value', 'var', 'prior'))
+        nan |= np.any(np.isnan(var), axis=-1)
+        if n_win:
+            nw1 = P + 1
+            wv, wvar, wpri = (x[..., :n_win * nw1].reshape(lead + (n_win, nw1)) for x in (val, var, pri))
+            res['window_weight'], wim = elements_of_coordinates(wv[..., :P], M, use_complex)
+            res['window_err'], eim = element_errors_of_coordinates(wvar[..., :P], M, use_complex)
+            res['window_prior_err'] = element_errors_of_coordinates(wpri[..., :P], M, use_complex)[0]
+            if use_complex:
+                res['window_weight_imag'], res['window_err_imag'] = wim, eim
+            res['window_trace'] = wv[..., P]
+            res['window_trace_err'], res['window_trace_prior_err'] = np.sqrt(wvar[..., P]), np.sqrt(wpri[..., P])
+        if n_fun:
+            o = n_win * (P + 1)
+            res['functional_value'] = val[..., o:]
+            res['functional_err'], res['functional_prior_err'] = np.sqrt(var[..., o:]), np.sqrt(pri[..., o:])
+    if pointwise:
+        delta = np.asarray(omega.delta, dtype=float) if hasattr(omega, 'delta') else None
+        if delta is None:
+            from .analyzers import get_delta
+            delta = get_delta(np.asarray(omega, dtype=float))
+        if delta.shape != (n_omega,):
+            raise ValueError('full_matrix_posterior_errors: omega has %d points, V %d' % (len(delta), n_omega))
+        h, dv, dp = (np.moveaxis(out[k].reshape(lead + (P, n_omega)), -2, -1) for k in ('h', 'diag_var', 'diag_prior'))
+        nan |= np.any(np.isnan(dv), axis=(-2, -1))
+        to_A = lambda x: np.moveaxis(x, -3, -1) / delta                       # (..., n_omega, M, M) -> (..., M, M, n_omega)
+        re, im = elements_of_coordinates(h, M, use_complex)
+        res['A'] = to_A(re + 1.0j * im) if use_complex else to_A(re)
+        ere, eim = element_errors_of_coordinates(dv, M, use_complex)
+        res['A_err'] = to_A(ere)
+        res['A_prior_err'] = to_A(element_errors_of_coordinates(dp, M, use_complex)[0])
+        if use_complex:
+            res['A_err_imag'] = to_A(eim)
+    res['info'] = dict(kernel_ms=t.get('ms', 0.0), kernel='mxe_fullmatrix_posterior_var',
+                       nan_jobs=[(int(a), int(b)) for a, b in np.argwhere(nan)])
+    return res
+
+
 class FullMatrixResult(MaxEntResult):
     """the :class:`MaxEntResult` of a whole-matrix job: ``A`` and ``H`` are (M, M, n_alpha, n_omega), ``chi2``, ``S``, ``Q``
     (n_alpha,) belong to the matrix, ``v`` holds u (n_alpha, P, n_s); an analyzer picks one alpha for the whole matrix and
@@ -246,7 +427,12 @@ class FullMatrixResult(MaxEntResult):
 _REFUSED = dict(set_G_iw_data='Matsubara data', set_G_iw='Matsubara data', set_chi_tau_data='bosonic data',
                 set_chi_iw_data='bosonic data', set_cov='a covariance matrix', set_cov_file='a covariance matrix',
                 set_G_tau_bins='Monte Carlo bins', set_G_iw_bins='Monte Carlo bins', set_G_l_bins='Monte Carlo bins',
-                set_G_tau='TRIQS Green functions (use set_G_tau_data)', set_G_tau_file='a file of one element (use set_G_tau_data)')
+                set_G_tau='TRIQS Green functions (use set_G_tau_data)', set_G_tau_file='a file of one element (use set_G_tau_data)',
+                # what the scalar worker computes from a result has no whole-matrix meaning yet (posterior_errors has)
+                posterior_samples='posterior sampling of the whole matrix', fit_diagnostics='the hat matrix of the whole matrix',
+                resolution='the linear response of the whole matrix', default_model_response='the linear response of the whole matrix',
+                resample_errors='resampling of Monte Carlo bins', parametric_bootstrap='the parametric bootstrap',
+                default_model_scan='a default-model scan (it needs the evidence)', check_bins='Monte Carlo bins')
 
 
 class FullMatrixMaxEnt(object):
@@ -404,6 +590,43 @@ class FullMatrixMaxEnt(object):
                                                       kernel='mxe_fullmatrix_solve' if job['element_err'] is None
                                                       else 'mxe_fullmatrix_solve_metric'))
         return res
+
+    def posterior_errors(self, result=None, alpha=None, windows=None, functionals=None, pointwise=False):
+        """Posterior error bars of the whole-matrix result (default: ``run()``) in the Gaussian approximation around the
+        minimiser, on the device (:func:`full_matrix_posterior_errors`, which describes the keys).  ``alpha``:
+        None -- the alpha of the default analyzer --, an analyzer name, an index into the alpha mesh, a sequence of indices or
+        ``'all'`` (the last two keep an alpha axis in front); ``'bryan'`` is a ValueError: the whole-matrix problem has no
+        probability.  ``windows=[(lo, hi), ...]``: the spectral weight of every matrix element, and of the trace, inside, with
+        its error; ``functionals``: (n_f, M, M, n_omega) or (M, M, n_omega) Hermitian weights on A delta_omega;
+        ``pointwise``: the error of every A_ab(omega_i).  The dict also holds ``alpha`` and ``alpha_index``, what was taken, and
+        ``info``: ``kernel_ms``, the device time of the kernel, ``kernel``, and ``nan_rows``, the indices into the alpha mesh
+        whose u or H is not finite or whose curvature is not positive definite (they are NaN; the name is that of
+        ``TauMaxEnt.posterior_errors``, the plain function reports (problem, alpha) pairs as ``nan_jobs``).  A job with ``set_element_errors`` is refused with NotImplementedError."""
+        from .posterior import choose_alpha
+        if isinstance(alpha, str) and alpha == 'bryan':
+            raise ValueError("FullMatrixMaxEnt.posterior_errors: alpha='bryan' needs the probability of alpha, which the "
+                             'whole-matrix problem does not have')
+        if self.element_err is not None:
+            raise NotImplementedError('FullMatrixMaxEnt.posterior_errors: a job with set_element_errors (one error bar per '
+                                      'matrix element) is not supported yet; use set_error')
+        res = self.run() if result is None else result
+        job = self._job()
+        al = np.asarray(res.alpha, dtype=float)
+        if al.shape != job['alpha'].shape or not np.allclose(al, job['alpha'], rtol=1e-12, atol=0.0):
+            raise ValueError('FullMatrixMaxEnt.posterior_errors: the result was not made with the alpha mesh of this object')
+        idx, how = choose_alpha(alpha, len(al), res.analyzer_results, res.default_analyzer_name)
+        u = np.asarray(res.v, dtype=float)[idx]
+        out = full_matrix_posterior_errors(u[None], job['U'], job['S'], job['V'], job['D'], al[idx], job['err'],
+                                           use_complex=self.use_complex, functionals=functionals, windows=windows,
+                                           omega=self.maxent.omega, pointwise=pointwise,
+                                           device=self.maxent.maxent_loop.device_id)
+        info = out.pop('info')
+        out = dict((k, v[0] if k != 'alpha' else v) for k, v in out.items())
+        out['alpha_index'] = np.array(idx)
+        if how == 'one':
+            out = dict((k, v[0]) for k, v in out.items())
+        out['info'] = dict(kernel_ms=info['kernel_ms'], kernel=info['kernel'], nan_rows=[idx[b] for _, b in info['nan_jobs']])
+        return out
 
     def positivity(self, result=None, alpha=None, floor=0.0, keep_vectors=False):
         """:func:`maxent_amd.positivity.matrix_positivity` of the result (default: ``run()``): ``alpha`` None -- ``A_out`` of
