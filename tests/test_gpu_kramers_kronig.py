@@ -4,6 +4,10 @@ self-energy workflow of SigmaContinuator.set_Gaux_w_from_Aaux_w.
 The reference's transform needs TRIQS, so no fixture of it exists; the formula of maxent_util.py:91-130 is restated
 here in numpy (``kk_np``) and pinned by the reference's own closed-form case (test/python/G_w_from_A_w.py).
 Gate: max |G_dev - G_np| <= 1e-12 * max_o sum_j |A_j c_oj|, relative to the sum of absolute terms.
+
+The sizes on both sides of every tile of kk_partial and of every decision of mxe_kramers_kronig are held to a
+np.longdouble restatement instead, within (KK_SLICE + n_slice + 8) 2^-52 of the same scale: the fixed summation order
+csrc/mxe_kk.hip.h documents, turned into a bound.
 """
 import numpy as np
 import pytest
@@ -71,6 +75,78 @@ def test_device_matches_the_restatement(kind, n_w):
                 check(Gc, Ac, w, w_out, bf)
     if n_w == 1:
         assert np.all(G == 0)
+
+
+# ---- the tile edges of kk_partial and the decisions of mxe_kramers_kronig ---------------------------------------------
+EPS = 2.0 ** -52
+KK_T, KK_SLICE, KK_CHUNK = 256, 256, 64          # csrc/mxe_kk.hip.h: output points of a tile, j values of a slice, of a chunk
+# mxe_kramers_kronig: TS = 2 spectra per workgroup up to n_spec = 2, 8 up to 8, 16 beyond (17: a second tile of one
+# spectrum); one workgroup per j slice ("split") where n_slice > 1 and the unsplit grid ceil(n_spec / TS) *
+# ceil(n_out / KK_T) has fewer than KK_SPLIT_BELOW workgroups, else every workgroup adds the slices itself ("combine")
+KK_TS_EDGES = (2, 8, 16)
+KK_SPLIT_BELOW = 1024
+KK_POOL = 17                                     # distinct spectra of a large batch (coprime to every TS)
+
+
+def kk_edge_spectra(n_w, n_out):
+    """seeded grids, weights and a pool of signed spectra for one (n_w, n_out), with the longdouble restatement
+    G = sum_j A_j weight_j / (w_out - w_j + i eta_j) of the pool and its scale max_o sum_j |A_j c_oj|"""
+    Lf = np.longdouble
+    rng = np.random.RandomState(1000 * n_w + n_out)
+    w = np.asarray(mx.HyperbolicOmegaMesh(-5.0, 5.0, n_w))
+    weight, eta = 0.01 + 0.05 * rng.rand(n_w), 0.02 + 0.2 * rng.rand(n_w)
+    w_out = np.linspace(-6.1, 5.3, n_out)
+    pool = rng.rand(KK_POOL, n_w) - 0.3
+    x = w_out.astype(Lf)[:, None] - w.astype(Lf)[None, :]
+    den = x * x + (eta.astype(Lf) ** 2)[None, :]
+    c_re = weight.astype(Lf)[None, :] * x / den
+    c_im = -(weight.astype(Lf) * eta.astype(Lf))[None, :] / den
+    G_re, G_im = pool.astype(Lf) @ c_re.T, pool.astype(Lf) @ c_im.T
+    scale = (np.abs(pool) @ np.asarray(np.sqrt(c_re ** 2 + c_im ** 2), dtype=float).T).max(axis=-1)
+    return w, weight, eta, w_out, pool, G_re, G_im, scale
+
+
+def kk_edge_check(n_w, n_out, n_spec, case):
+    """``n_spec`` spectra (row r is pool row r mod KK_POOL: the bits of a spectrum do not depend on its place) through
+    device.kramers_kronig; every value within (KK_SLICE + n_slice + 8) EPS scale of the restatement: at most KK_SLICE
+    fma in a row, n_slice partial sums added in order (the header's fixed summation order), 8 for c_oj itself"""
+    w, weight, eta, w_out, pool, G_re, G_im, scale = case
+    idx = np.arange(n_spec) % KK_POOL
+    G = device.kramers_kronig(w, weight, eta, w_out, pool[idx])
+    assert G.shape == (n_spec, n_out) and np.all(np.isfinite(G))
+    n_slice = -(-n_w // KK_SLICE)
+    gate = (KK_SLICE + n_slice + 8) * EPS * scale[idx]
+    err = np.asarray(np.sqrt((G.real - G_re[idx]) ** 2 + (G.imag - G_im[idx]) ** 2), dtype=float).max(axis=-1)
+    assert np.all(err <= gate), (n_w, n_out, n_spec, (err / gate).max())
+    return float((err / gate).max())
+
+
+@pytest.mark.parametrize('n_w', [KK_CHUNK - 1, KK_CHUNK, KK_CHUNK + 1, KK_SLICE - 1, KK_SLICE, KK_SLICE + 1,
+                                 2 * KK_SLICE + 1])
+def test_tile_edges_against_the_longdouble_restatement(n_w):
+    """n_w on both sides of a chunk, of a slice (one slice / two: the split decision) and two slices plus one value;
+    n_out on both sides of an output tile; n_spec on both sides of every tile size"""
+    worst = 0.0
+    for n_out in (KK_T - 1, KK_T, KK_T + 1):
+        case = kk_edge_spectra(n_w, n_out)
+        for n_spec in sorted({1} | {e + d for e in KK_TS_EDGES for d in (0, 1)}):
+            worst = max(worst, kk_edge_check(n_w, n_out, n_spec, case))
+    print('kramers_kronig tile edges n_w=%d: worst ratio to the bound %.3f' % (n_w, worst))
+
+
+@pytest.mark.parametrize('n_out', [KK_T, KK_T + 1])
+def test_split_and_combine_against_the_longdouble_restatement(n_out):
+    """the largest batch that is still split over the j slices and the smallest that is not, with one output tile and
+    with two, at the smallest n_w that has two slices.  (The other clause of that decision, a gigabyte of partial sums,
+    is out of a quick test's reach.)"""
+    n_w = KK_SLICE + 1
+    tiles_out = -(-n_out // KK_T)
+    n_last_split = ((KK_SPLIT_BELOW - 1) // tiles_out) * KK_TS_EDGES[-1]      # 16368 with one output tile, 8176 with two
+    case = kk_edge_spectra(n_w, n_out)
+    for n_spec in (n_last_split, n_last_split + 1):
+        worst = kk_edge_check(n_w, n_out, n_spec, case)
+        print('kramers_kronig n_w=%d n_out=%d n_spec=%d (%s): worst ratio to the bound %.3f'
+              % (n_w, n_out, n_spec, 'split' if n_spec == n_last_split else 'combine', worst))
 
 
 def test_leading_shapes_and_the_device_binding():
