@@ -1011,6 +1011,29 @@ int  mxe_fullmatrix_posterior_var(int device, int n_job, int m, int is_complex, 
                                   double* out_value, double* out_var, double* out_prior,
                                   double* out_diag_var, double* out_diag_prior, double* out_h, float* out_ms);
 
+/* The evidence of alpha of the whole-matrix continuation with one error for all matrix elements, around the u of
+ * mxe_fullmatrix_solve (the same V', c, D, scaled alpha and basis E_p as mxe_fullmatrix_posterior_var).  With
+ * B = alpha I + c W c = L_B L_B^T of order d = P n_s, l_jj the diagonal of L_B:
+ *   out_logdet  n_job: log det(I_d + c W c / alpha) = sum_j log(l_jj^2 / alpha), summed pivot by pivot (no term is negative
+ *               but for the rounding of a pivot; nothing cancels at large alpha);
+ *               log p(alpha | G) = -1/2 logdet - Q - log alpha, as from mxe_logdet for a scalar problem
+ *   want_ngood  1: also out_ngood
+ *   out_ngood   n_job (want_ngood; may be NULL otherwise): the number of good data N_g = tr(c W c B^-1)
+ *               = d - alpha |L_B^-1|_F^2, the identity through the forward substitution of the variance kernel (a negative
+ *               difference is returned as 0, a NaN stays one)
+ *   out_ms      device time of the kernel (may be NULL)
+ * One workgroup per job, a job being one (u, alpha) pair.  A job whose u or H is not finite, or whose B is not positive
+ * definite in binary64, gets NaN in its outputs; the other jobs are not touched.  No atomics, fixed summation order: the bits
+ * of a job do not depend on the batch or on the number of scratch slices, those of out_logdet not on want_ngood.  The
+ * scratch is cut as for mxe_fullmatrix_posterior_var, below the same MXE_FULLMATRIX_POSTVAR_SCRATCH_BYTES (the environment
+ * variable MXE_FULLMATRIX_LOGDET_SLICES = n caps the number of slices further; a test aid).
+ * MXE_ERR_ARG (nothing is launched): a size < 1, want_ngood neither 0 nor 1, a NULL among the arrays that are needed, a NaN or
+ * an Inf in V, c, D or alpha, a c, D or alpha that is not positive, sizes whose products exceed 2^31 - 1.  MXE_ERR_LIMIT:
+ * m > MXE_FULLMATRIX_MAX_M, n_s > MXE_FULLMATRIX_MAX_NS, or more than 160 KB of LDS.  MXE_ERR_NODEVICE: no device. */
+int  mxe_fullmatrix_logdet(int device, int n_job, int m, int is_complex, int n_omega, int n_s,
+                           const double* V, const double* c, const double* D, const double* alpha, const double* u,
+                           int want_ngood, double* out_logdet, double* out_ngood, float* out_ms);
+
 #ifdef __cplusplus
 }
 #endif

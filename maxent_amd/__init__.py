@@ -46,6 +46,7 @@ from .bin_checks import check_bins, rebin_bins, shrink_bins      # noqa: F401
 from .positivity import matrix_positivity           # noqa: F401
 from .full_matrix import FullMatrixMaxEnt, FullMatrixResult, full_matrix_continue   # noqa: F401
 from .full_matrix import full_matrix_posterior_errors   # noqa: F401
+from .full_matrix import full_matrix_log_probability    # noqa: F401
 from . import _layout as _layout        # the reference's sub-module paths (analyzers.linefit_analyzer, ...)
 _layout.register(__name__)
 

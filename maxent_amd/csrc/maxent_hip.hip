@@ -3813,3 +3813,68 @@ try {
     return MXE_OK;
 }
 MXE_CATCH_ALL
+
+// ---- the evidence of alpha of the whole-matrix continuation (mxe_fullmatrix_logdet.hip.h) ----
+#include "mxe_fullmatrix_logdet.hip.h"
+
+extern "C" int mxe_fullmatrix_logdet(int device, int n_job, int m, int is_complex, int n_omega, int n_s,
+                                     const double* V, const double* c, const double* D, const double* alpha, const double* u,
+                                     int want_ngood, double* out_logdet, double* out_ngood, float* out_ms)
+try {
+    if (n_job < 1 || m < 1 || (is_complex != 0 && is_complex != 1) || n_omega < 1 || n_s < 1 ||
+        (want_ngood != 0 && want_ngood != 1) || !V || !c || !D || !alpha || !u || !out_logdet || (want_ngood && !out_ngood))
+        return MXE_ERR_ARG;
+    if (m > mxe::FM_MAX_M || n_s > mxe::FM_MAX_NS) return MXE_ERR_LIMIT;
+    const bool cplx = is_complex != 0;
+    const size_t nj = n_job, nw = n_omega, ns = n_s, P = mxe::fm_P(m, cplx), d = P * ns;
+    // (what the kernel indexes with an int: V, u, and L, the largest of a job's arrays of n_omega)
+    if (nw * ns > 0x7fffffffull || nj * d > 0x7fffffffull || P * (P + 1) / 2 * nw > 0x7fffffffull) return MXE_ERR_ARG;
+    // (u is not looked at: a job whose u is not finite gets NaN from the kernel, its neighbours are not touched)
+    if (!all_finite(V, nw * ns) || !all_finite(c, ns) || !all_finite(D, nw) || !all_finite(alpha, nj)) return MXE_ERR_ARG;
+    for (size_t i = 0; i < nw; ++i) if (!(D[i] > 0.0)) return MXE_ERR_ARG;
+    for (size_t k = 0; k < ns; ++k) if (!(c[k] > 0.0)) return MXE_ERR_ARG;
+    for (size_t a = 0; a < nj; ++a) if (!(alpha[a] > 0.0)) return MXE_ERR_ARG;
+    const size_t lds = mxe::fmpv_lds_doubles((int)d) * sizeof(double);
+    if (lds > 160 * 1024) return MXE_ERR_LIMIT;
+    // the scratch: one slice per workgroup, as for mxe_fullmatrix_posterior_var
+    const size_t scr = mxe::fmld_scratch_doubles(m, cplx, n_omega, n_s);
+    size_t n_slices = (size_t)MXE_FULLMATRIX_POSTVAR_SCRATCH_BYTES / (scr * sizeof(double));
+    if (const char* e = getenv("MXE_FULLMATRIX_LOGDET_SLICES"))       // (tests: fewer slices than jobs)
+        if (const long cap = atol(e); cap >= 1 && (size_t)cap < n_slices) n_slices = (size_t)cap;
+    if (n_slices < 1) n_slices = 1;
+    if (n_slices > nj) n_slices = nj;
+    Stage sg;
+    if (int rc = sg.open(device); rc != MXE_OK) return rc;
+    mxe::FullMatrixLogdetParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.n_job = n_job; p.n_omega = n_omega; p.n_s = n_s; p.want_ngood = want_ngood;
+    Block in;
+    const size_t oV = in.add(nw * ns), oc = in.add(ns), oD = in.add(nw), oa = in.add(nj), ou = in.add(nj * d);
+    double* din;
+    STGCHK(sg, sg.alloc(&din, in.total));
+    STGCHK(sg, sg.upload(din + oV, V, nw * ns)); STGCHK(sg, sg.upload(din + oc, c, ns));
+    STGCHK(sg, sg.upload(din + oD, D, nw)); STGCHK(sg, sg.upload(din + oa, alpha, nj));
+    STGCHK(sg, sg.upload(din + ou, u, nj * d));
+    p.V = din + oV; p.c = din + oc; p.D = din + oD; p.alpha = din + oa; p.u = din + ou;
+    STGCHK(sg, sg.alloc(&p.scratch, n_slices * scr));
+    const size_t ng = want_ngood ? nj : 0;
+    Block out;
+    const size_t ol = out.add(nj), on = out.add(ng);
+    double* dout;
+    STGCHK(sg, sg.alloc(&dout, out.total));
+    p.out_logdet = dout + ol; p.out_ngood = dout + on;
+    typedef void (*kernel_t)(const mxe::FullMatrixLogdetParams);
+    static const kernel_t kernels[2][4] = {
+        {mxe::fullmatrix_logdet_kernel<1, false>, mxe::fullmatrix_logdet_kernel<2, false>,
+         mxe::fullmatrix_logdet_kernel<3, false>, mxe::fullmatrix_logdet_kernel<4, false>},
+        {mxe::fullmatrix_logdet_kernel<1, true>, mxe::fullmatrix_logdet_kernel<2, true>,
+         mxe::fullmatrix_logdet_kernel<3, true>, mxe::fullmatrix_logdet_kernel<4, true>}};
+    STGCHK(sg, sg.time_begin(out_ms != nullptr));
+    STGCHK(sg, launch_lds(kernels[cplx ? 1 : 0][m - 1], dim3((unsigned)n_slices), dim3(mxe::FM_T), lds, sg.stream, p));
+    STGCHK(sg, sg.time_end());
+    STGCHK(sg, sg.fetch(out_logdet, p.out_logdet, nj));
+    STGCHK(sg, sg.fetch(out_ngood, p.out_ngood, ng));
+    STGCHK(sg, sg.finish(out_ms));
+    return MXE_OK;
+}
+MXE_CATCH_ALL

@@ -14,7 +14,8 @@
 // Both are differences of two sums of non-negative terms, formed as written; B^-1 is never formed.  A difference that rounding
 // makes negative is returned as 0 by a comparison: a NaN stays a NaN.  For M = 1 this is postvar_kernel with w = H.
 //
-// One workgroup of 256 threads per job; the jobs are independent.  The parts:
+// One workgroup of 256 threads per job; the jobs are independent.  The parts (1 to 3 are fmpv_factor, which
+// fullmatrix_logdet_kernel of mxe_fullmatrix_logdet.hip.h calls too):
 //   1. the evaluation at u of fullmatrix_kernel (a copy of its code: the solver's instantiations are not touched): Gamma
 //      coordinates, the Jacobi in registers, W_i, D phi, the H coordinates;
 //   2. L, then the P (P + 1) / 2 Gram products on v_mfma_f64_16x16x4_f64 as in the solver; the epilogue writes
@@ -79,16 +80,17 @@ __device__ inline int fmpv_pair(int a, int b, int P)
 }
 
 // L_B Z = Y for the 16 columns of Y [d][FM_LDP] in the LDS (overwritten by Z), L_B the lower triangle of Bm [d][d]; returns
-// |z_j|^2 to the threads j < 16.  Called by all threads.
-__device__ inline double fmpv_forward(const double* Bm, int d, double* Ysh, double* part, int tid)
+// |z_j|^2 to the threads j < 16.  Called by all threads.  r_begin, a multiple of 16: the rows of Y above it are zero (and are
+// not read); the substitution and the sums start there.
+__device__ inline double fmpv_forward(const double* Bm, int d, double* Ysh, double* part, int tid, int r_begin = 0)
 {
     const int rr = tid >> 4, j = tid & 15;
-    for (int r0 = 0; r0 < d; r0 += 16) {
+    for (int r0 = r_begin; r0 < d; r0 += 16) {
         const int row = r0 + rr, r1 = min(d, r0 + 16);
-        if (row < d && r0 > 0) {
+        if (row < d && r0 > r_begin) {
             const double* Lr = Bm + (size_t)row * d;
             double s = 0.0;
-            for (int k = 0; k < r0; ++k) s = fma(Lr[k], Ysh[k * FM_LDP + j], s);
+            for (int k = r_begin; k < r0; ++k) s = fma(Lr[k], Ysh[k * FM_LDP + j], s);
             Ysh[row * FM_LDP + j] -= s;
         }
         __syncthreads();
@@ -103,7 +105,7 @@ __device__ inline double fmpv_forward(const double* Bm, int d, double* Ysh, doub
         __syncthreads();
     }
     double s = 0.0;
-    for (int r = rr; r < d; r += 16) { const double z = Ysh[r * FM_LDP + j]; s = fma(z, z, s); }
+    for (int r = r_begin + rr; r < d; r += 16) { const double z = Ysh[r * FM_LDP + j]; s = fma(z, z, s); }
     part[rr * 16 + j] = s;
     __syncthreads();
     double q = 0.0;
@@ -113,12 +115,221 @@ __device__ inline double fmpv_forward(const double* Bm, int d, double* Ysh, doub
     return q;
 }
 
+// Parts 1 to 3 of a job, shared by fullmatrix_postvar_kernel and fullmatrix_logdet_kernel (mxe_fullmatrix_logdet.hip.h): the
+// evaluation at u, L, B = alpha I + c W c and its Cholesky factor, which is left in the lower triangle of Bm [d][d].  The
+// arrays are the caller's slice of the scratch: gam, hc [P][nw] (Gamma and H coordinates), Wv [nw][WPL][M][M], phiD
+// [nw][M][M], Lp [NPAIR][nw]; Ysh [d][FM_LDP] is the panel in the LDS; flag: [0] the job is bad, [1] B is positive definite
+// so far.  Called by all threads; returns (the same in every thread) whether u and H are finite and every pivot is positive
+// and finite.  What is left in hc, Lp and Bm is valid only then.
+template <int M, bool C>
+__device__ __forceinline__ bool fmpv_factor(const double* V, const double* cc, const double* Dm, const double* u,
+                                            const double alpha, const int nw, const int ns, double* gam, double* hc, double* Wv,
+                                            double* phiD, double* Lp, double* Bm, double* Ysh, int* flag)
+{
+    constexpr int P = C ? M * M : M * (M + 1) / 2, NPAIR = P * (P + 1) / 2, MM = M * M, WPL = C ? 2 : 1;
+    constexpr double R2 = 1.41421356237309504880;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int d = P * ns, npw = P * nw;
+    const int kq = lane >> 4, cn = lane & 15;
+    const int ntile = (ns + 15) >> 4, n_groups = (nw + 3) >> 2;
+    // ================= 1. evaluation at u (fullmatrix_kernel, part 1) =================
+    if (tid == 0) { flag[0] = 0; flag[1] = 1; }
+    bool bad = false;
+    for (int k = tid; k < d; k += FM_T) bad |= !isfinite(u[k]);
+    for (int idx = tid; idx < npw; idx += FM_T) {
+        const int pp = idx / nw, i = idx - pp * nw;
+        const double* vr = V + (size_t)i * ns;
+        const double* xr = u + pp * ns;
+        double s = 0.0;
+        for (int k = 0; k < ns; ++k) s = fma(vr[k], xr[k], s);
+        gam[idx] = s;
+    }
+    __syncthreads();
+    for (int i = tid; i < nw; i += FM_T) {
+        double ar[M][M], ai[M][M], wr[M][M], wi[M][M];
+        {
+            int pp = M;
+#pragma unroll
+            for (int a = 0; a < M; ++a) { ar[a][a] = gam[a * nw + i]; ai[a][a] = 0.0; }
+#pragma unroll
+            for (int a = 0; a < M; ++a)
+#pragma unroll
+                for (int b = a + 1; b < M; ++b) {
+                    const double re = gam[pp * nw + i] / R2;
+                    const double im = C ? gam[(pp + M * (M - 1) / 2) * nw + i] / R2 : 0.0;
+                    ar[a][b] = re; ar[b][a] = re; ai[a][b] = im; ai[b][a] = -im;
+                    ++pp;
+                }
+        }
+        fm_jacobi<M, C>(ar, ai, wr, wi);
+        const double Di = Dm[i];
+        double gk[M], eh[M];
+#pragma unroll
+        for (int k = 0; k < M; ++k) {
+            gk[k] = ar[k][k];
+            eh[k] = exp(0.5 * gk[k]);
+        }
+        // H = D B B^H, B_ak = W_ak e^(gamma_k / 2): the upper triangle
+        {
+            int pp = M;
+#pragma unroll
+            for (int a = 0; a < M; ++a)
+#pragma unroll
+                for (int b = a; b < M; ++b) {
+                    double sr = 0.0, si = 0.0;
+#pragma unroll
+                    for (int k = 0; k < M; ++k) {
+                        const double xr_ = wr[a][k] * eh[k], yr_ = wr[b][k] * eh[k];
+                        if (C) {
+                            const double xi_ = wi[a][k] * eh[k], yi_ = wi[b][k] * eh[k];
+                            sr += xr_ * yr_ + xi_ * yi_;
+                            si += xi_ * yr_ - xr_ * yi_;
+                        } else {
+                            sr += xr_ * yr_;
+                        }
+                    }
+                    sr *= Di; si *= Di;
+                    bad |= !isfinite(sr) || !isfinite(si);
+                    if (a == b) {
+                        hc[a * nw + i] = sr;
+                    } else {
+                        hc[pp * nw + i] = R2 * sr;
+                        if (C) hc[(pp + M * (M - 1) / 2) * nw + i] = R2 * si;
+                        ++pp;
+                    }
+                }
+        }
+        double* wo = Wv + (size_t)i * WPL * MM;
+        double* po = phiD + (size_t)i * MM;
+#pragma unroll
+        for (int a = 0; a < M; ++a)
+#pragma unroll
+            for (int k = 0; k < M; ++k) {
+                wo[a * M + k] = wr[a][k];
+                if (C) wo[MM + a * M + k] = wi[a][k];
+                const double ph = Di * fm_phi(gk[a], gk[k]);
+                bad |= !isfinite(ph);
+                po[a * M + k] = ph;
+            }
+    }
+    if (bad) flag[0] = 1;
+    __syncthreads();
+    bool job_ok = flag[0] == 0;                  // (the same in every thread)
+
+    if (job_ok) {
+        // ================= 2. L and B = alpha I + c W c (fullmatrix_kernel, part 2) =================
+        for (int idx = tid; idx < NPAIR * nw; idx += FM_T) {
+            const int pair = idx / nw, i = idx - pair * nw;
+            int pp = 0, rem = pair;
+            while (rem >= P - pp) { rem -= P - pp; ++pp; }
+            const int qq = pp + rem;
+            int k1, a1, b1, k2, a2, b2;
+            fm_basis(pp, M, k1, a1, b1);
+            fm_basis(qq, M, k2, a2, b2);
+            const double* Wr = Wv + (size_t)i * WPL * MM;
+            const double* Wi = Wr + (C ? MM : 0);
+            const double* ph = phiD + (size_t)i * MM;
+            double s = 0.0;
+            for (int k = 0; k < M; ++k)
+                for (int l = 0; l < M; ++l) {
+                    double xr, xi, yr, yi;
+                    fm_xkl<M, C>(k1, a1, b1, Wr, Wi, k, l, xr, xi);
+                    fm_xkl<M, C>(k2, a2, b2, Wr, Wi, k, l, yr, yi);
+                    s = fma(ph[k * M + l], xr * yr + xi * yi, s);
+                }
+            Lp[idx] = s;
+        }
+        __syncthreads();
+        const int ntp = ntile * (ntile + 1) / 2;
+        for (int item = wave; item < NPAIR * ntp; item += 4) {
+            const int pair = item / ntp;
+            int ti = 0, rem = item - pair * ntp;
+            while (rem >= ntile - ti) { rem -= ntile - ti; ++ti; }
+            const int tj = ti + rem;
+            int pp = 0;
+            rem = pair;
+            while (rem >= P - pp) { rem -= P - pp; ++pp; }
+            const int qq = pp + rem;
+            const double* Lr = Lp + (size_t)pair * nw;
+            const int sa = 16 * ti + cn, sb = 16 * tj + cn;
+            d4 acc = d4{0.0, 0.0, 0.0, 0.0};
+            for (int g = 0; g < n_groups; ++g) {
+                const int i = 4 * g + kq;
+                const bool iv = i < nw;
+                const double a = (iv && sa < ns) ? V[(size_t)i * ns + sa] * Lr[i] : 0.0;
+                const double b = (iv && sb < ns) ? V[(size_t)i * ns + sb] : 0.0;
+                acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc, 0, 0, 0);
+            }
+            // as in the solver every entry of B has one writer or equal writers; B is symmetric to the bit
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int s = 16 * ti + kq + 4 * r, t = sb;
+                if (s >= ns || t >= ns || (ti == tj && s > t)) continue;
+                double w = cc[s] * cc[t] * acc[r];
+                if (pp == qq && s == t) w += alpha;
+                const size_t ps = (size_t)pp * ns + s, pt = (size_t)pp * ns + t, qs = (size_t)qq * ns + s, qt = (size_t)qq * ns + t;
+                Bm[ps * d + qt] = w;
+                Bm[pt * d + qs] = w;
+                if (pp != qq) {
+                    Bm[qs * d + pt] = w;
+                    Bm[qt * d + ps] = w;
+                }
+            }
+        }
+        __syncthreads();
+
+        // ================= 3. B = L_B L_B^T =================
+        for (int k0 = 0; k0 < d && job_ok; k0 += FM_NB) {
+            const int nb = min(FM_NB, d - k0), mrows = d - k0;
+            for (int idx = tid; idx < mrows * nb; idx += FM_T) {
+                const int r = idx / nb, c = idx - r * nb;
+                Ysh[r * FM_LDP + c] = Bm[(size_t)(k0 + r) * d + k0 + c];
+            }
+            __syncthreads();
+            for (int j = 0; j < nb; ++j) {
+                const double pv = Ysh[j * FM_LDP + j];
+                if (tid == 0 && !(pv > 0.0 && pv <= 1.79769313486231570815e308)) flag[1] = 0;
+                const double dj = sqrt(pv);
+                __syncthreads();                              // (everybody has read the pivot)
+                for (int r = j + 1 + tid; r < mrows; r += FM_T) Ysh[r * FM_LDP + j] /= dj;
+                if (tid == 0) Ysh[j * FM_LDP + j] = dj;
+                __syncthreads();
+                const int nc = nb - j - 1;
+                for (int idx = tid; idx < (mrows - j - 1) * nc; idx += FM_T) {
+                    const int r = j + 1 + idx / nc, c = j + 1 + idx % nc;
+                    if (c <= r) Ysh[r * FM_LDP + c] = fma(-Ysh[r * FM_LDP + j], Ysh[c * FM_LDP + j], Ysh[r * FM_LDP + c]);
+                }
+                __syncthreads();
+            }
+            job_ok = flag[1] != 0;
+            if (!job_ok) break;
+            for (int idx = tid; idx < mrows * nb; idx += FM_T) {
+                const int r = idx / nb, c = idx - r * nb;
+                if (c <= r) Bm[(size_t)(k0 + r) * d + k0 + c] = Ysh[r * FM_LDP + c];
+            }
+            // A22 <- A22 - L21 L21^T, the lower triangle, in tiles of 16 x 16: a thread per entry, the sum in index order
+            const int n2 = mrows - nb, nt2 = (n2 + 15) >> 4;
+            for (int ti = 0; ti < nt2; ++ti)
+                for (int tj = 0; tj <= ti; ++tj) {
+                    const int r = nb + 16 * ti + (tid >> 4), c = nb + 16 * tj + (tid & 15);
+                    if (r < mrows && c <= r) {
+                        double s = Bm[(size_t)(k0 + r) * d + k0 + c];
+#pragma unroll
+                        for (int l = 0; l < FM_NB; ++l) s = fma(-Ysh[r * FM_LDP + l], Ysh[c * FM_LDP + l], s);
+                        Bm[(size_t)(k0 + r) * d + k0 + c] = s;
+                    }
+                }
+            __syncthreads();
+        }
+    }
+    return job_ok;
+}
+
 template <int M, bool C>
 __global__ __launch_bounds__(FM_T)
 void fullmatrix_postvar_kernel(const FullMatrixPostVarParams p)
 {
     constexpr int P = C ? M * M : M * (M + 1) / 2, NPAIR = P * (P + 1) / 2, MM = M * M, WPL = C ? 2 : 1;
-    constexpr double R2 = 1.41421356237309504880;
     extern __shared__ double fmpv_smem[];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int nw = p.n_omega, ns = p.n_s, d = P * ns, n_f = p.n_f, npw = P * nw;
@@ -155,196 +366,8 @@ void fullmatrix_postvar_kernel(const FullMatrixPostVarParams p)
         double* o_dp = p.want_diag ? p.out_dprior + (size_t)job * npw : nullptr;
         double* o_h = p.want_diag ? p.out_h + (size_t)job * npw : nullptr;
 
-        // ================= 1. evaluation at u (fullmatrix_kernel, part 1) =================
-        if (tid == 0) { flag[0] = 0; flag[1] = 1; }
-        bool bad = false;
-        for (int k = tid; k < d; k += FM_T) bad |= !isfinite(u[k]);
-        for (int idx = tid; idx < npw; idx += FM_T) {
-            const int pp = idx / nw, i = idx - pp * nw;
-            const double* vr = V + (size_t)i * ns;
-            const double* xr = u + pp * ns;
-            double s = 0.0;
-            for (int k = 0; k < ns; ++k) s = fma(vr[k], xr[k], s);
-            gam[idx] = s;
-        }
-        __syncthreads();
-        for (int i = tid; i < nw; i += FM_T) {
-            double ar[M][M], ai[M][M], wr[M][M], wi[M][M];
-            {
-                int pp = M;
-#pragma unroll
-                for (int a = 0; a < M; ++a) { ar[a][a] = gam[a * nw + i]; ai[a][a] = 0.0; }
-#pragma unroll
-                for (int a = 0; a < M; ++a)
-#pragma unroll
-                    for (int b = a + 1; b < M; ++b) {
-                        const double re = gam[pp * nw + i] / R2;
-                        const double im = C ? gam[(pp + M * (M - 1) / 2) * nw + i] / R2 : 0.0;
-                        ar[a][b] = re; ar[b][a] = re; ai[a][b] = im; ai[b][a] = -im;
-                        ++pp;
-                    }
-            }
-            fm_jacobi<M, C>(ar, ai, wr, wi);
-            const double Di = p.D[i];
-            double gk[M], eh[M];
-#pragma unroll
-            for (int k = 0; k < M; ++k) {
-                gk[k] = ar[k][k];
-                eh[k] = exp(0.5 * gk[k]);
-            }
-            // H = D B B^H, B_ak = W_ak e^(gamma_k / 2): the upper triangle
-            {
-                int pp = M;
-#pragma unroll
-                for (int a = 0; a < M; ++a)
-#pragma unroll
-                    for (int b = a; b < M; ++b) {
-                        double sr = 0.0, si = 0.0;
-#pragma unroll
-                        for (int k = 0; k < M; ++k) {
-                            const double xr_ = wr[a][k] * eh[k], yr_ = wr[b][k] * eh[k];
-                            if (C) {
-                                const double xi_ = wi[a][k] * eh[k], yi_ = wi[b][k] * eh[k];
-                                sr += xr_ * yr_ + xi_ * yi_;
-                                si += xi_ * yr_ - xr_ * yi_;
-                            } else {
-                                sr += xr_ * yr_;
-                            }
-                        }
-                        sr *= Di; si *= Di;
-                        bad |= !isfinite(sr) || !isfinite(si);
-                        if (a == b) {
-                            hc[a * nw + i] = sr;
-                        } else {
-                            hc[pp * nw + i] = R2 * sr;
-                            if (C) hc[(pp + M * (M - 1) / 2) * nw + i] = R2 * si;
-                            ++pp;
-                        }
-                    }
-            }
-            double* wo = Wv + (size_t)i * WPL * MM;
-            double* po = phiD + (size_t)i * MM;
-#pragma unroll
-            for (int a = 0; a < M; ++a)
-#pragma unroll
-                for (int k = 0; k < M; ++k) {
-                    wo[a * M + k] = wr[a][k];
-                    if (C) wo[MM + a * M + k] = wi[a][k];
-                    const double ph = Di * fm_phi(gk[a], gk[k]);
-                    bad |= !isfinite(ph);
-                    po[a * M + k] = ph;
-                }
-        }
-        if (bad) flag[0] = 1;
-        __syncthreads();
-        bool job_ok = flag[0] == 0;                  // (the same in every thread)
-
-        if (job_ok) {
-            // ================= 2. L and B = alpha I + c W c (fullmatrix_kernel, part 2) =================
-            for (int idx = tid; idx < NPAIR * nw; idx += FM_T) {
-                const int pair = idx / nw, i = idx - pair * nw;
-                int pp = 0, rem = pair;
-                while (rem >= P - pp) { rem -= P - pp; ++pp; }
-                const int qq = pp + rem;
-                int k1, a1, b1, k2, a2, b2;
-                fm_basis(pp, M, k1, a1, b1);
-                fm_basis(qq, M, k2, a2, b2);
-                const double* Wr = Wv + (size_t)i * WPL * MM;
-                const double* Wi = Wr + (C ? MM : 0);
-                const double* ph = phiD + (size_t)i * MM;
-                double s = 0.0;
-                for (int k = 0; k < M; ++k)
-                    for (int l = 0; l < M; ++l) {
-                        double xr, xi, yr, yi;
-                        fm_xkl<M, C>(k1, a1, b1, Wr, Wi, k, l, xr, xi);
-                        fm_xkl<M, C>(k2, a2, b2, Wr, Wi, k, l, yr, yi);
-                        s = fma(ph[k * M + l], xr * yr + xi * yi, s);
-                    }
-                Lp[idx] = s;
-            }
-            __syncthreads();
-            const int ntp = ntile * (ntile + 1) / 2;
-            for (int item = wave; item < NPAIR * ntp; item += 4) {
-                const int pair = item / ntp;
-                int ti = 0, rem = item - pair * ntp;
-                while (rem >= ntile - ti) { rem -= ntile - ti; ++ti; }
-                const int tj = ti + rem;
-                int pp = 0;
-                rem = pair;
-                while (rem >= P - pp) { rem -= P - pp; ++pp; }
-                const int qq = pp + rem;
-                const double* Lr = Lp + (size_t)pair * nw;
-                const int sa = 16 * ti + cn, sb = 16 * tj + cn;
-                d4 acc = d4{0.0, 0.0, 0.0, 0.0};
-                for (int g = 0; g < n_groups; ++g) {
-                    const int i = 4 * g + kq;
-                    const bool iv = i < nw;
-                    const double a = (iv && sa < ns) ? V[(size_t)i * ns + sa] * Lr[i] : 0.0;
-                    const double b = (iv && sb < ns) ? V[(size_t)i * ns + sb] : 0.0;
-                    acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc, 0, 0, 0);
-                }
-                // as in the solver every entry of B has one writer or equal writers; B is symmetric to the bit
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int s = 16 * ti + kq + 4 * r, t = sb;
-                    if (s >= ns || t >= ns || (ti == tj && s > t)) continue;
-                    double w = cc[s] * cc[t] * acc[r];
-                    if (pp == qq && s == t) w += alpha;
-                    const size_t ps = (size_t)pp * ns + s, pt = (size_t)pp * ns + t, qs = (size_t)qq * ns + s, qt = (size_t)qq * ns + t;
-                    Bm[ps * d + qt] = w;
-                    Bm[pt * d + qs] = w;
-                    if (pp != qq) {
-                        Bm[qs * d + pt] = w;
-                        Bm[qt * d + ps] = w;
-                    }
-                }
-            }
-            __syncthreads();
-
-            // ================= 3. B = L_B L_B^T =================
-            for (int k0 = 0; k0 < d && job_ok; k0 += FM_NB) {
-                const int nb = min(FM_NB, d - k0), mrows = d - k0;
-                for (int idx = tid; idx < mrows * nb; idx += FM_T) {
-                    const int r = idx / nb, c = idx - r * nb;
-                    Ysh[r * FM_LDP + c] = Bm[(size_t)(k0 + r) * d + k0 + c];
-                }
-                __syncthreads();
-                for (int j = 0; j < nb; ++j) {
-                    const double pv = Ysh[j * FM_LDP + j];
-                    if (tid == 0 && !(pv > 0.0 && pv <= 1.79769313486231570815e308)) flag[1] = 0;
-                    const double dj = sqrt(pv);
-                    __syncthreads();                              // (everybody has read the pivot)
-                    for (int r = j + 1 + tid; r < mrows; r += FM_T) Ysh[r * FM_LDP + j] /= dj;
-                    if (tid == 0) Ysh[j * FM_LDP + j] = dj;
-                    __syncthreads();
-                    const int nc = nb - j - 1;
-                    for (int idx = tid; idx < (mrows - j - 1) * nc; idx += FM_T) {
-                        const int r = j + 1 + idx / nc, c = j + 1 + idx % nc;
-                        if (c <= r) Ysh[r * FM_LDP + c] = fma(-Ysh[r * FM_LDP + j], Ysh[c * FM_LDP + j], Ysh[r * FM_LDP + c]);
-                    }
-                    __syncthreads();
-                }
-                job_ok = flag[1] != 0;
-                if (!job_ok) break;
-                for (int idx = tid; idx < mrows * nb; idx += FM_T) {
-                    const int r = idx / nb, c = idx - r * nb;
-                    if (c <= r) Bm[(size_t)(k0 + r) * d + k0 + c] = Ysh[r * FM_LDP + c];
-                }
-                // A22 <- A22 - L21 L21^T, the lower triangle, in tiles of 16 x 16: a thread per entry, the sum in index order
-                const int n2 = mrows - nb, nt2 = (n2 + 15) >> 4;
-                for (int ti = 0; ti < nt2; ++ti)
-                    for (int tj = 0; tj <= ti; ++tj) {
-                        const int r = nb + 16 * ti + (tid >> 4), c = nb + 16 * tj + (tid & 15);
-                        if (r < mrows && c <= r) {
-                            double s = Bm[(size_t)(k0 + r) * d + k0 + c];
-#pragma unroll
-                            for (int l = 0; l < FM_NB; ++l) s = fma(-Ysh[r * FM_LDP + l], Ysh[c * FM_LDP + l], s);
-                            Bm[(size_t)(k0 + r) * d + k0 + c] = s;
-                        }
-                    }
-                __syncthreads();
-            }
-        }
+        // ================= 1 to 3. evaluation at u, L, B = alpha I + c W c = L_B L_B^T =================
+        const bool job_ok = fmpv_factor<M, C>(V, cc, p.D, u, alpha, nw, ns, gam, hc, Wv, phiD, Lp, Bm, Ysh, flag);
 
         if (!job_ok) {
             for (int j = tid; j < n_f; j += FM_T) { o_val[j] = nan; o_var[j] = nan; o_pri[j] = nan; }

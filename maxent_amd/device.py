@@ -196,6 +196,8 @@ SYMBOLS = [
                                                   [_dp] * 5 + [_ip, _ip, ctypes.POINTER(ctypes.c_float)]),
     ('mxe_fullmatrix_posterior_var', ctypes.c_int, [ctypes.c_int] * 7 + [_dp] * 6 + [ctypes.c_int] + [_dp] * 6 +
                                                    [ctypes.POINTER(ctypes.c_float)]),
+    ('mxe_fullmatrix_logdet', ctypes.c_int, [ctypes.c_int] * 6 + [_dp] * 5 + [ctypes.c_int, _dp, _dp,
+                                                                                ctypes.POINTER(ctypes.c_float)]),
 ]
 
 
@@ -1107,6 +1109,54 @@ def fullmatrix_posterior_var(V, c, D, alpha, u, m, use_complex, F=None, want_dia
     out = dict(value=value, var=var, prior=prior)
     if want_diag:
         out.update(diag_var=dv, diag_prior=dp, h=h)
+    return out
+
+
+def fullmatrix_logdet(V, c, D, alpha, u, m, use_complex, want_ngood=True, device=0, timing=None):
+    """``mxe_fullmatrix_logdet``: the evidence of alpha of the whole-matrix continuation.  ``V``, ``c``, ``D``, ``alpha``
+    (n_job,) and ``u`` (n_job, P, n_s) as for :func:`fullmatrix_posterior_var`.  Returns a dict: ``logdet`` (n_job,),
+    log det(I + c W c / alpha) of order d = P n_s, and, with ``want_ngood``, ``n_good`` (n_job,), the number of good data
+    tr(c W c (alpha I + c W c)^-1).  A job whose ``u`` or H is not finite or whose curvature is not positive definite is
+    NaN; ``u`` is therefore the one input that may hold a NaN.  ``timing``: a dict that receives the device time ``ms`` of
+    the kernel.  Arguments the library would refuse raise ValueError before it is called."""
+    V, c, D, alpha, u = _c(V), _c(c), _c(D), _c(alpha), _c(u)
+    m, use_complex, want_ngood = int(m), bool(use_complex), bool(want_ngood)
+    if m < 1 or m > FULLMATRIX_MAX_M:
+        raise ValueError('fullmatrix_logdet: matrices of %d x %d; 1 to %d are supported' % (m, m, FULLMATRIX_MAX_M))
+    if V.ndim != 2 or V.shape[0] < 1 or V.shape[1] < 1:
+        raise ValueError('fullmatrix_logdet: V must be (n_omega, n_s); got %s' % (V.shape,))
+    n_omega, n_s = V.shape
+    if n_s > FULLMATRIX_MAX_NS:
+        raise ValueError('fullmatrix_logdet: %d singular values; at most %d are supported: cut the singular space with '
+                         'reduce_singular_space' % (n_s, FULLMATRIX_MAX_NS))
+    P = fullmatrix_P(m, use_complex)
+    if c.shape != (n_s,) or D.shape != (n_omega,) or alpha.ndim != 1 or alpha.size < 1:
+        raise ValueError('fullmatrix_logdet: c must be (n_s,), D (n_omega,), alpha one-dimensional and not empty')
+    n_job = alpha.size
+    if u.shape != (n_job, P, n_s):
+        raise ValueError('fullmatrix_logdet: u must be (n_job, %d, %d) for %d alphas; got %s' % (P, n_s, n_job, u.shape))
+    for name, a in (('V', V), ('c', c), ('D', D), ('alpha', alpha)):
+        if not np.all(np.isfinite(a)):
+            raise ValueError('fullmatrix_logdet: %s is not finite' % name)
+    if not (np.all(c > 0) and np.all(D > 0) and np.all(alpha > 0)):
+        raise ValueError('fullmatrix_logdet: c, D and alpha must be positive')
+    if max(n_job * P * n_s, n_omega * n_s, P * (P + 1) // 2 * n_omega) > 2 ** 31 - 1:
+        raise ValueError('fullmatrix_logdet: the arrays of this call hold more than 2^31 - 1 numbers')
+    lib = load_library()
+    if device_count() < 1:
+        raise MaxEntDeviceError('no HIP device visible; mxe_fullmatrix_logdet has no CPU fallback')
+    logdet = np.empty(n_job)
+    n_good = np.empty(n_job) if want_ngood else None
+    ms = ctypes.c_float(0)
+    rc = lib.mxe_fullmatrix_logdet(int(device), n_job, m, 1 if use_complex else 0, n_omega, n_s, _p(V), _p(c), _p(D), _p(alpha),
+                                   _p(u), 1 if want_ngood else 0, _p(logdet), _p(n_good), ctypes.byref(ms))
+    if rc != 0:
+        raise MaxEntDeviceError('mxe_fullmatrix_logdet failed: ' + lib.mxe_strerror(rc).decode())
+    if timing is not None:
+        timing['ms'] = float(ms.value)
+    out = dict(logdet=logdet)
+    if want_ngood:
+        out['n_good'] = n_good
     return out
 
 

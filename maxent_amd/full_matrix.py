@@ -19,7 +19,9 @@ and ``probability=``.
 
 Error bars: ``FullMatrixMaxEnt.posterior_errors`` / :func:`full_matrix_posterior_errors` (``mxe_fullmatrix_posterior_var``,
 DESIGN 4za), the Gaussian posterior around the minimiser for spectral weights in windows, linear functionals and every
-A_ab(omega_i); for a job with one error for all matrix elements.  The other result-taking methods of the scalar worker
+A_ab(omega_i); for a job with one error for all matrix elements.  The probability of alpha: ``FullMatrixMaxEnt.evidence`` /
+:func:`full_matrix_log_probability` (``mxe_fullmatrix_logdet``), after ``run()``: the classic and Bryan choices
+of alpha, the number of good data and the evidence, for the same jobs.  The other result-taking methods of the scalar worker
 (samples, diagnostics, response, resampling, bootstrap, model scans, bin checks) are refused, not forwarded.
 
 alpha is scaled by n_tau, the number of data of ONE matrix element (``scale_alpha='Ndata'``): block-diagonal data then
@@ -303,6 +305,39 @@ def element_errors_of_coordinates(var, M, use_complex):
     return re, np.abs(im)
 
 
+def _check_minimisers(what, u, U, S, V, D, alpha, err, use_complex):
+    """the shape checks of what works on the minimisers u (n_prob, n_alpha, P, n_s) of :func:`full_matrix_continue`;
+    returns the arrays as float, alpha one-dimensional, and M"""
+    u = np.asarray(u, dtype=float)
+    U, S, V, D = (np.asarray(x, dtype=float) for x in (U, S, V, D))
+    alpha = np.atleast_1d(np.asarray(alpha, dtype=float))
+    if u.ndim != 4 or alpha.ndim != 1 or u.shape[1] != len(alpha):
+        raise ValueError('%s: u must be (n_prob, n_alpha, P, n_s) with one alpha per row; got %s and '
+                         '%d alphas' % (what, u.shape, alpha.size))
+    n_prob, n_alpha, P, n_s = u.shape
+    Ms = [m for m in range(1, MAX_M + 1) if _dev.fullmatrix_P(m, use_complex) == P]
+    if not Ms:
+        raise ValueError('%s: %d components are no %s matrix of at most %d x %d'
+                         % (what, P, 'complex Hermitian' if use_complex else 'real symmetric', MAX_M, MAX_M))
+    if U.ndim != 2 or S.shape != (U.shape[1],) or V.ndim != 2 or V.shape[1] != U.shape[1] or n_s != U.shape[1]:
+        raise ValueError('%s: U must be (n_data, n_s), S (n_s,), V (n_omega, n_s), u (..., n_s); got '
+                         '%s, %s, %s, %s' % (what, U.shape, S.shape, V.shape, u.shape))
+    if n_s > MAX_NS:
+        raise ValueError('%s: %d singular values; at most %d are supported: cut the singular space '
+                         'with reduce_singular_space' % (what, n_s, MAX_NS))
+    n_omega = V.shape[0]
+    if D.shape != (n_omega,):
+        raise NotImplementedError('%s: the default model must be one D(omega) of shape (%d,); a '
+                                  'matrix-valued model is not supported; got %s' % (what, n_omega, D.shape))
+    err = np.asarray(err, dtype=float)
+    if err.ndim > 1 or (err.ndim == 1 and err.shape != (U.shape[0],)):
+        raise ValueError('%s: one error for all data or one per data point, shared by all matrix '
+                         'elements; got shape %s' % (what, err.shape,))
+    if not (np.all(np.isfinite(err)) and np.all(err > 0)):
+        raise ValueError('%s: the error must be positive and finite' % what)
+    return u, U, S, V, D, alpha, err, Ms[0]
+
+
 def full_matrix_posterior_errors(u, U, S, V, D, alpha, err, use_complex=False, functionals=None, windows=None, omega=None,
                                  pointwise=False, device=0):
     """Posterior error bars of whole-matrix continuations with one error for all matrix elements, in the Gaussian
@@ -322,34 +357,9 @@ def full_matrix_posterior_errors(u, U, S, V, D, alpha, err, use_complex=False, f
     n_omega), ``A_err`` the standard deviation of Re A_ab(omega_i), with ``use_complex`` also ``A_err_imag`` (zero on the
     diagonal); ``alpha``; ``info`` (``kernel_ms``; ``nan_jobs``: the (problem, alpha) pairs whose u or H is not finite or
     whose curvature is not positive definite: they are NaN).  The prior errors are what the entropy alone would leave."""
-    u = np.asarray(u, dtype=float)
-    U, S, V, D = (np.asarray(x, dtype=float) for x in (U, S, V, D))
-    alpha = np.atleast_1d(np.asarray(alpha, dtype=float))
-    if u.ndim != 4 or alpha.ndim != 1 or u.shape[1] != len(alpha):
-        raise ValueError('full_matrix_posterior_errors: u must be (n_prob, n_alpha, P, n_s) with one alpha per row; got %s and '
-                         '%d alphas' % (u.shape, alpha.size))
+    u, U, S, V, D, alpha, err, M = _check_minimisers('full_matrix_posterior_errors', u, U, S, V, D, alpha, err, use_complex)
     n_prob, n_alpha, P, n_s = u.shape
-    Ms = [m for m in range(1, MAX_M + 1) if _dev.fullmatrix_P(m, use_complex) == P]
-    if not Ms:
-        raise ValueError('full_matrix_posterior_errors: %d components are no %s matrix of at most %d x %d'
-                         % (P, 'complex Hermitian' if use_complex else 'real symmetric', MAX_M, MAX_M))
-    M = Ms[0]
-    if U.ndim != 2 or S.shape != (U.shape[1],) or V.ndim != 2 or V.shape[1] != U.shape[1] or n_s != U.shape[1]:
-        raise ValueError('full_matrix_posterior_errors: U must be (n_data, n_s), S (n_s,), V (n_omega, n_s), u (..., n_s); got '
-                         '%s, %s, %s, %s' % (U.shape, S.shape, V.shape, u.shape))
-    if n_s > MAX_NS:
-        raise ValueError('full_matrix_posterior_errors: %d singular values; at most %d are supported: cut the singular space '
-                         'with reduce_singular_space' % (n_s, MAX_NS))
     n_omega = V.shape[0]
-    if D.shape != (n_omega,):
-        raise NotImplementedError('full_matrix_posterior_errors: the default model must be one D(omega) of shape (%d,); a '
-                                  'matrix-valued model is not supported; got %s' % (n_omega, D.shape))
-    err = np.asarray(err, dtype=float)
-    if err.ndim > 1 or (err.ndim == 1 and err.shape != (U.shape[0],)):
-        raise ValueError('full_matrix_posterior_errors: one error for all data or one per data point, shared by all matrix '
-                         'elements; got shape %s' % (err.shape,))
-    if not (np.all(np.isfinite(err)) and np.all(err > 0)):
-        raise ValueError('full_matrix_posterior_errors: the error must be positive and finite')
     n_win = 0 if windows is None else len(windows)
     if (n_win or pointwise) and omega is None:
         raise ValueError('full_matrix_posterior_errors: windows and pointwise need the mesh omega')
@@ -412,6 +422,71 @@ def full_matrix_posterior_errors(u, U, S, V, D, alpha, err, use_complex=False, f
     return res
 
 
+# ---- the evidence of alpha -----------------------------------------------------------------------------------
+
+def full_matrix_log_probability(u, U, S, V, D, alpha, err, Q, use_complex=False, probability=None, device=0, S_entropy=None):
+    """log p(alpha | G) of whole-matrix continuations with one error for all matrix elements, in the Gaussian approximation
+    around the minimisers ``u`` (n_prob, n_alpha, P, n_s) of :func:`full_matrix_continue` at the scaled ``alpha`` (n_alpha,),
+    on the device (``mxe_fullmatrix_logdet``, one workgroup per (problem, alpha)).  ``U, S, V, D, err`` as there
+    (with one error per data point u is rotated into the whitened basis exactly as there); ``Q`` (n_prob, n_alpha), the cost
+    at the minimisers as :func:`full_matrix_continue` returns it.  ``probability``: a :class:`NormalLogProbability` (its
+    ``log_norm_S`` and ``log_prior_alpha`` are honoured, ``log_norm_S`` with P n_omega unknowns); ``S_entropy``
+    (n_prob, n_alpha), optional: the entropy at the minimisers, for ``classic_ratio``.
+
+    Returns a dict: ``logdet`` (n_prob, n_alpha), log det(I + c W c / alpha) of order P n_s; ``n_good``, the number of good
+    data tr(c W c (alpha I + c W c)^-1); ``log_probability`` = -logdet / 2 - Q - log alpha; ``alpha_index_classic``
+    (n_prob,), its maximum (-1 where no alpha is finite); ``weights`` (n_prob, n_alpha), exp(log p - max) normalised to sum
+    one over the finite entries (0 for the others): the default rule of ``BryanAnalyzer``; ``classic_ratio`` =
+    -2 alpha S / N_g, one at the classic alpha (with ``S_entropy``); ``log_evidence`` (n_prob,) = log sum_k p_k |delta alpha_k|
+    over the finite entries with the measure of ``model_scan.log_measure``; ``alpha_at_edge`` (n_prob,): the maximum sits on
+    the first or the last alpha, so the mesh may not hold it; ``alpha``; ``info``: ``kernel``, ``kernel_ms``, ``nan_jobs``, the
+    (problem, alpha) pairs whose u or H is not finite or whose curvature is not positive definite (they are NaN).
+
+    ``log_probability`` lacks the constants that do not depend on alpha, and the evidence those that depend on the data, the
+    error and the meshes: two values of ``log_evidence`` are comparable only between calls on the same data, error, omega
+    mesh and alpha mesh -- between default models, say."""
+    from .model_scan import log_measure
+    from .probabilities import NormalLogProbability
+    what = 'full_matrix_log_probability'
+    u, U, S, V, D, alpha, err, M = _check_minimisers(what, u, U, S, V, D, alpha, err, use_complex)
+    n_prob, n_alpha, P, n_s = u.shape
+    Q = np.asarray(Q, dtype=float)
+    if Q.shape != (n_prob, n_alpha):
+        raise ValueError('%s: Q must be (n_prob, n_alpha) = (%d, %d); got %s' % (what, n_prob, n_alpha, Q.shape))
+    if S_entropy is not None:
+        S_entropy = np.asarray(S_entropy, dtype=float)
+        if S_entropy.shape != (n_prob, n_alpha):
+            raise ValueError('%s: S_entropy must be (n_prob, n_alpha) = (%d, %d); got %s' % (what, n_prob, n_alpha, S_entropy.shape))
+    if not (np.all(np.isfinite(alpha)) and np.all(alpha > 0)):
+        raise ValueError('%s: alpha must be positive and finite' % what)
+    measure = log_measure(alpha)
+    _, c, Vw, Qr = whiten(U, S, V, err)
+    uw = u if Qr is None else np.dot(u, Qr)                     # u' = Q^T u
+    t = {}
+    out = _dev.fullmatrix_logdet(Vw, c, D, np.tile(alpha, n_prob), uw.reshape(n_prob * n_alpha, P, n_s), M, use_complex,
+                                 want_ngood=True, device=device, timing=t)
+    logdet, n_good = out['logdet'].reshape(n_prob, n_alpha), out['n_good'].reshape(n_prob, n_alpha)
+    prob = NormalLogProbability() if probability is None else probability
+    logp = np.stack([np.asarray(prob.from_logdet(logdet[n], alpha, Q[n], P * V.shape[0]), dtype=float) for n in range(n_prob)])
+    good = np.isfinite(logp)
+    some = np.any(good, axis=1)
+    masked = np.where(good, logp, -np.inf)
+    top = np.where(some, np.max(masked, axis=1), 0.0)
+    idx = np.where(some, np.argmax(masked, axis=1), -1)
+    w = np.where(good, np.exp(masked - top[:, None]), 0.0)
+    with np.errstate(invalid='ignore', divide='ignore'):
+        weights = np.where(some[:, None], w / np.sum(w, axis=1, keepdims=True), np.nan)
+        log_ev = np.where(some, top + np.log(np.sum(np.where(good, np.exp(masked - top[:, None] + measure), 0.0), axis=1)), np.nan)
+    res = dict(alpha=np.array(alpha), logdet=logdet, n_good=n_good, log_probability=logp, alpha_index_classic=idx,
+               weights=weights, log_evidence=log_ev, alpha_at_edge=some & ((idx == 0) | (idx == n_alpha - 1)))
+    if S_entropy is not None:
+        with np.errstate(invalid='ignore', divide='ignore'):
+            res['classic_ratio'] = -2.0 * alpha * S_entropy / n_good
+    res['info'] = dict(kernel_ms=t.get('ms', 0.0), kernel='mxe_fullmatrix_logdet',
+                       nan_jobs=[(int(a), int(b)) for a, b in np.argwhere(np.isnan(logdet))])
+    return res
+
+
 class FullMatrixResult(MaxEntResult):
     """the :class:`MaxEntResult` of a whole-matrix job: ``A`` and ``H`` are (M, M, n_alpha, n_omega), ``chi2``, ``S``, ``Q``
     (n_alpha,) belong to the matrix, ``v`` holds u (n_alpha, P, n_s); an analyzer picks one alpha for the whole matrix and
@@ -422,6 +497,15 @@ class FullMatrixResult(MaxEntResult):
         if name in ('A', 'H'):
             return arr[:, :, int(idx)]
         return arr[idx]
+
+    def attach_probability(self, log_probability, analyzer_results):
+        """write ``log_probability`` (n_alpha,) into ``probability`` and add ``analyzer_results`` (:class:`AnalyzerResult`
+        objects with a ``name``) beside those of ``run()``; the default analyzer stays what it was"""
+        self._records[None]['probability'] = np.array(log_probability, dtype=float)
+        for ar in analyzer_results:
+            ar.maxent_result = self
+            self._analysis.setdefault(None, {})[ar['name']] = ar
+        self._cache = dict()
 
 
 _REFUSED = dict(set_G_iw_data='Matsubara data', set_G_iw='Matsubara data', set_chi_tau_data='bosonic data',
@@ -626,6 +710,55 @@ class FullMatrixMaxEnt(object):
         if how == 'one':
             out = dict((k, v[0]) for k, v in out.items())
         out['info'] = dict(kernel_ms=info['kernel_ms'], kernel=info['kernel'], nan_rows=[idx[b] for _, b in info['nan_jobs']])
+        return out
+
+    def evidence(self, result=None, attach=True):
+        """log p(alpha | G) of the whole-matrix result (default: ``run()``) in the Gaussian approximation around the
+        minimisers, on the device (:func:`full_matrix_log_probability`, which describes the keys): ``logdet``,
+        ``n_good``, ``log_probability``, ``weights``, ``classic_ratio`` (n_alpha,), ``alpha_index_classic``, ``log_evidence``,
+        ``alpha_at_edge``, ``alpha``; ``A_classic`` (M, M, n_omega), A at the maximum of the probability, and ``A_bryan`` =
+        sum_k weights_k A[:, :, k, :]: a convex mixture of positive semi-definite matrices; ``info``: ``kernel``,
+        ``kernel_ms`` and ``nan_rows``, the indices into the alpha mesh that are NaN.  ``run()`` itself still computes no
+        probability and still refuses ``BryanAnalyzer``, ``ClassicAnalyzer`` and ``probability=``: this is the way to them.
+
+        ``attach``: write ``log_probability`` into ``result.probability`` and add the entries ``'ClassicAnalyzer'`` (``name``,
+        ``alpha_index``, ``A_out``, ``info``) and ``'BryanAnalyzer'`` (``name``, ``A_out``, ``info``) to
+        ``result.analyzer_results``, so that ``result.get_A_out('ClassicAnalyzer')``, ``posterior_errors(result,
+        alpha='ClassicAnalyzer')`` and ``positivity(result, alpha='BryanAnalyzer')`` work; the default analyzer stays what it
+        was.  A job with ``set_element_errors`` is refused with NotImplementedError; a result of another alpha mesh is a
+        ValueError, and so is a result whose probability is NaN at every alpha (there is no classic alpha and no weight to
+        mix with: nothing is attached)."""
+        from .analyzers import AnalyzerResult
+        if self.element_err is not None:
+            raise NotImplementedError('FullMatrixMaxEnt.evidence: a job with set_element_errors (one error bar per matrix '
+                                      'element) is not supported yet; use set_error')
+        res = self.run() if result is None else result
+        job = self._job()
+        al = np.asarray(res.alpha, dtype=float)
+        if al.shape != job['alpha'].shape or not np.allclose(al, job['alpha'], rtol=1e-12, atol=0.0):
+            raise ValueError('FullMatrixMaxEnt.evidence: the result was not made with the alpha mesh of this object')
+        out = full_matrix_log_probability(np.asarray(res.v, dtype=float)[None], job['U'], job['S'], job['V'], job['D'], al,
+                                          job['err'], np.asarray(res.Q, dtype=float)[None], use_complex=self.use_complex,
+                                          device=self.maxent.maxent_loop.device_id,
+                                          S_entropy=np.asarray(res.S, dtype=float)[None])
+        info = out.pop('info')
+        out = dict((k, v[0] if k != 'alpha' else v) for k, v in out.items())
+        A = np.asarray(res.A)
+        idx = int(out['alpha_index_classic'])
+        if idx < 0:
+            raise ValueError('FullMatrixMaxEnt.evidence: the probability is NaN at every alpha (u or H is not finite, or the '
+                             'curvature is not positive definite)')
+        out['A_classic'] = np.array(A[:, :, idx])
+        sel = np.isfinite(out['log_probability'])                  # (a NaN row has the weight 0 and is not read)
+        out['A_bryan'] = np.einsum('k,abki->abi', out['weights'][sel], A[:, :, sel])
+        out['info'] = dict(kernel_ms=info['kernel_ms'], kernel=info['kernel'], nan_rows=[b for _, b in info['nan_jobs']])
+        if attach:
+            classic, bryan = AnalyzerResult(), AnalyzerResult()
+            classic.update(name='ClassicAnalyzer', alpha_index=idx, A_out=out['A_classic'],
+                           info='Ideal alpha (classic): {} (= index {} zero-based)'.format(al[idx], idx))
+            bryan.update(name='BryanAnalyzer', A_out=out['A_bryan'],
+                         info='Bryan analyzer: average of A weighted by probability calculated.')
+            res.attach_probability(out['log_probability'], (classic, bryan))
         return out
 
     def positivity(self, result=None, alpha=None, floor=0.0, keep_vectors=False):
