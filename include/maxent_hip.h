@@ -59,6 +59,8 @@
  *   (nothing: users loop run() over mock data by hand)     | mxe_mock_data (mock data drawn from continued spectra
  *                                                          |   with the noise of the job), mxe_resample_quantiles
  *                                                          |   (percentile bands of the H rows of resamples or mocks)
+ *   (nothing: no rule for alpha looks at held-out data)    | mxe_cv_score (out-of-sample chi2 of the training scans
+ *                                                          |   of a k-fold split of the bins, for every alpha)
  *   (nothing: users rebin by hand until the errors settle) | mxe_bins_check (blocking ladder, skewness and
  *                                                          |   kurtosis of the block means of the bins)
  *   (nothing: few bins give a biased covariance)           | mxe_bins_eig_shrunk (shrinkage intensity from the
@@ -817,6 +819,37 @@ int  mxe_resample_quantiles(mxe_ctx* ctx, int n_groups, const int32_t* group_off
 int  mxe_mock_data(int device, int n_sets, int n_mock, int n_data, int n_omega,
                    const double* K, const double* H0, const double* err, const double* T, const int32_t* rank,
                    uint64_t seed, const uint64_t* stream, double* out_model, double* out_G, float* out_ms);
+
+/* ---- k-fold cross-validation of alpha over the bins (no counterpart in the reference) ---- */
+/* The out-of-sample chi2 of hidden images against held-out data, all groups in one launch (one workgroup per tile of 16
+ * rows of a group), then one small launch that counts the finite rows.  The groups, H and problem_index are those of
+ * mxe_resample_reduce (also the rows of the last launch with H == NULL, read where they lie, and MXE_ERR_STATE).  A group is
+ * one (matrix element, fold); its rows are the alphas of that fold's training scan.
+ *   n_data, n_omega   the sizes of K; with H == NULL n_omega must be that of ctx
+ *   K           n_data x n_omega: the job's kernel as mxe_mock_data takes it (not rotated by a covariance; stacked or
+ *               pre-blurred as the job has it), shared by the groups
+ *   T, rank     both NULL (the identity, n_data), or n_groups x n_data x n_data and n_groups: out_T and out_rank of
+ *               mxe_bins_eig; rows k >= rank do not count
+ *   Gval        n_groups x n_data: the validation data in the rotated basis (a row of out_G of mxe_bins_resample)
+ *   w           n_groups x n_data: weights >= 0, finite (the inverse variance of the validation data)
+ *   out_z       rows x n_data: out_z[r][k] = sqrt(w[g][k]) (sum_j T[g][k][j] (sum_i K[j][i] H[r][i]) - Gval[g][k]) for
+ *               k < rank[g], 0 behind it.  May be NULL.
+ *   out_score   rows: sum_k out_z[r][k]^2
+ *   out_used    n_groups: the rows of the group that are finite (may be NULL).  A failed alpha leaves H = NaN; such a row
+ *               has NaN in out_score and in all of its out_z and does not touch its neighbours.
+ *   out_ms      device time of the two kernels (may be NULL)
+ * K H runs as v_mfma_f64_16x16x4_f64 tiles (16 data rows x 16 H rows, one wavefront per tile, the omega sum in index order
+ * inside one chain, zeros beyond the edges), T (K H) as the same tiles over the n_data sum in index order; the sum of
+ * squares is taken by lane l over k = l, l + 64, ... and a butterfly over the 64 lanes, an order that depends on n_data
+ * alone.  No atomics: a row's bits do not depend on the other rows of its group, on the other groups or on H being on the
+ * host or on the device, and repeat.  MXE_ERR_ARG (nothing is launched, nothing is written): a size below 1, offsets that
+ * decrease or do not start at 0, a problem_index outside the last launch, exactly one of T and rank NULL, a rank outside
+ * 0 .. n_data, a w that is negative or not finite, a NaN or an Inf in K, T or Gval, sizes whose products exceed 2^31 - 1,
+ * with H == NULL an n_omega that is not the launch's. */
+int  mxe_cv_score(mxe_ctx* ctx, int n_groups, const int32_t* group_offset, const double* H,
+                  const int32_t* problem_index, int n_data, int n_omega, const double* K,
+                  const double* T, const int32_t* rank, const double* Gval, const double* w,
+                  double* out_score, double* out_z, int32_t* out_used, float* out_ms);
 
 /* ---- default-model scans: evidence and model averages (no counterpart in the reference) ---- */
 /* The same data continued under a family of default models: the alpha-integrated evidence of every scan, the row it stands

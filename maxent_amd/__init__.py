@@ -43,6 +43,7 @@ from .maxent_util import (ArrayGf, get_G_w_from_A_w, get_G_tau_from_A_w,   # noq
 from .sigma_continuator import (SigmaContinuator, InversionSigmaContinuator,   # noqa: F401
                                 DirectSigmaContinuator)
 from .bin_checks import check_bins, rebin_bins, shrink_bins      # noqa: F401
+from .cross_validation import cross_validation_score, fold_counts   # noqa: F401
 from .positivity import matrix_positivity           # noqa: F401
 from .full_matrix import FullMatrixMaxEnt, FullMatrixResult, full_matrix_continue   # noqa: F401
 from .full_matrix import full_matrix_posterior_errors   # noqa: F401

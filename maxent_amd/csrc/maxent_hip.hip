@@ -3436,6 +3436,87 @@ try {
 }
 MXE_CATCH_ALL
 
+// ---- cross-validation over the bins: the out-of-sample chi2 of the H rows of training scans (mxe_cv.hip.h) ----
+#include "mxe_cv.hip.h"
+
+extern "C" int mxe_cv_score(mxe_ctx* ctx, int n_groups, const int32_t* group_offset, const double* H,
+                            const int32_t* problem_index, int n_data, int n_omega, const double* K,
+                            const double* T, const int32_t* rank, const double* Gval, const double* w,
+                            double* out_score, double* out_z, int32_t* out_used, float* out_ms)
+try {
+    if (!ctx || n_groups < 1 || n_data < 1 || n_omega < 1 || !group_offset || !K || !Gval || !w || !out_score) return MXE_ERR_ARG;
+    if ((T == nullptr) != (rank == nullptr)) return MXE_ERR_ARG;
+    if (!group_offsets_ok(group_offset, n_groups)) return MXE_ERR_ARG;
+    if (!H && !ctx->launched) return MXE_ERR_STATE;
+    if (!H && n_omega != ctx->n_omega) return MXE_ERR_ARG;
+    const size_t rows = (size_t)group_offset[n_groups], nw = n_omega, n = n_data, ng = n_groups;
+    if (rows * nw > 0x7fffffffull || rows * n > 0x7fffffffull || n * nw > 0x7fffffffull || ng * n > 0x7fffffffull ||
+        (T && ng * n * n > 0x7fffffffull)) return MXE_ERR_ARG;
+    if (T) for (size_t g = 0; g < ng; ++g) if (rank[g] < 0 || rank[g] > n_data) return MXE_ERR_ARG;
+    if (!all_finite(K, n * nw) || !all_finite(Gval, ng * n) || !all_finite(w, ng * n) || (T && !all_finite(T, ng * n * n)))
+        return MXE_ERR_ARG;
+    for (size_t i = 0; i < ng * n; ++i) if (!(w[i] >= 0.0)) return MXE_ERR_ARG;
+    size_t nt = 0;                                            // tiles of 16 rows, none across two groups
+    for (size_t g = 0; g < ng; ++g) nt += ((size_t)(group_offset[g + 1] - group_offset[g]) + 15) / 16;
+    Block bi;                                                 // rr_i
+    const size_t iO = bi.add(ng + 1);                         // offsets [ng + 1]
+    const size_t iRk = bi.add(ng);                            // rank [ng]
+    const size_t iTg = bi.add(nt);                            // group of a tile [nt]
+    const size_t iT0 = bi.add(nt);                            // first row of a tile [nt]
+    const size_t iK = bi.add(rows);                           // flags [rows]
+    const size_t iU = bi.add(ng);                             // used [ng]
+    const size_t iR = bi.add(H ? 0 : rows);                   // rows of the launch [rows] (H == NULL)
+    std::vector<int> hi(group_offset, group_offset + ng + 1);
+    hi.resize(bi.total, 0);
+    if (!H && !launch_rows(problem_index, rows, (size_t)ctx->n_chain * ctx->n_alpha, hi.data() + iR)) return MXE_ERR_ARG;
+    for (size_t g = 0, t = 0; g < ng; ++g) {
+        hi[iRk + g] = rank ? rank[g] : n_data;
+        for (int r = group_offset[g]; r < group_offset[g + 1]; r += 16, ++t) { hi[iTg + t] = (int)g; hi[iT0 + t] = r; }
+    }
+    Stage sg;
+    if (int rc = sg.open(ctx); rc != MXE_OK) return rc;
+    Block b;                                                  // rr_d
+    const size_t oK = b.add(n * nw);                          // K [n][nw]
+    const size_t oH = b.add(H ? rows * nw : 0);               // H [rows][nw], when handed in
+    const size_t oT = b.add(T ? ng * n * n : 0);              // T [ng][n][n]
+    const size_t oG = b.add(ng * n);                          // Gval [ng][n]
+    const size_t oW = b.add(ng * n);                          // w [ng][n]
+    const size_t oM = b.add(T ? rows * n : 0);                // K H before the rotation [rows][n]
+    const size_t oZ = b.add(rows * n);                        // z [rows][n]
+    const size_t oS = b.add(rows);                            // score [rows]
+    STGCHK(sg, ctx->rr_d.ensure(b.total));
+    STGCHK(sg, ctx->rr_i.ensure(bi.total));
+    double* d = ctx->rr_d.p;
+    int* di = ctx->rr_i.p;
+    STGCHK(sg, sg.upload(d + oK, K, n * nw)); STGCHK(sg, sg.upload(d + oH, H, rows * nw));
+    STGCHK(sg, sg.upload(d + oT, T, ng * n * n)); STGCHK(sg, sg.upload(d + oG, Gval, ng * n));
+    STGCHK(sg, sg.upload(d + oW, w, ng * n)); STGCHK(sg, sg.upload(di, hi.data(), bi.total));
+    mxe::CvParams cp;
+    cp.n = n_data; cp.nw = n_omega; cp.n_groups = n_groups;
+    cp.K = d + oK; cp.H = H ? d + oH : ctx->dout_H.p; cp.row = H ? nullptr : di + iR;
+    cp.off = di + iO; cp.tile_g = di + iTg; cp.tile_r0 = di + iT0;
+    cp.T = T ? d + oT : nullptr; cp.rank = di + iRk; cp.Gval = d + oG; cp.w = d + oW;
+    cp.kh = d + oM; cp.z = d + oZ; cp.score = d + oS; cp.ok = di + iK; cp.used = di + iU;
+    STGCHK(sg, sg.time_begin(out_ms != nullptr));
+    if (nt) {
+        hipLaunchKernelGGL(mxe::cv_score_kernel, dim3((unsigned)nt), dim3(mxe::CV_T), 0, ctx->stream, cp);
+        STGCHK(sg, hipGetLastError());
+    }
+    hipLaunchKernelGGL(mxe::cv_used_kernel, dim3((unsigned)((ng + 255) / 256)), dim3(256), 0, ctx->stream, cp);
+    STGCHK(sg, hipGetLastError());
+    STGCHK(sg, sg.time_end());
+    std::vector<double> hs(rows), hz(out_z ? rows * n : 0);   // (nothing is written to the caller's arrays before the stream is through)
+    std::vector<int> hused(out_used ? ng : 0);
+    STGCHK(sg, sg.fetch(hs.data(), d + oS, hs.size())); STGCHK(sg, sg.fetch(hz.data(), d + oZ, hz.size()));
+    STGCHK(sg, sg.fetch(hused.data(), di + iU, hused.size()));
+    STGCHK(sg, sg.finish(out_ms));
+    std::copy(hs.begin(), hs.end(), out_score);
+    std::copy(hz.begin(), hz.end(), out_z);
+    std::copy(hused.begin(), hused.end(), out_used);
+    return MXE_OK;
+}
+MXE_CATCH_ALL
+
 // ---- default-model scans: the evidence of every scan, the model averages of every group of scans (mxe_evidence.hip.h) ----
 #include "mxe_evidence.hip.h"
 

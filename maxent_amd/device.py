@@ -183,6 +183,8 @@ SYMBOLS = [
                                               ctypes.POINTER(ctypes.c_float)]),
     ('mxe_mock_data', ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, _dp, _ip,
                                      ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), _dp, _dp, ctypes.POINTER(ctypes.c_float)]),
+    ('mxe_cv_score', ctypes.c_int, [_vp, ctypes.c_int, _ip, _dp, _ip, ctypes.c_int, ctypes.c_int, _dp, _dp, _ip, _dp, _dp,
+                                    _dp, _dp, _ip, ctypes.POINTER(ctypes.c_float)]),
     ('mxe_evidence_reduce', ctypes.c_int, [_vp, ctypes.c_int, _ip, ctypes.c_int, _dp, _ip, _dp, _dp, _dp, _dp, ctypes.c_int, _ip,
                                            ctypes.c_int, _dp, _dp, _ip, _ip, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _ip,
                                            ctypes.POINTER(ctypes.c_float)]),
@@ -1693,6 +1695,73 @@ class DeviceContext(object):
         if timing is not None:
             timing['ms'] = float(ms.value)
         return dict(q=out, used=used)
+
+    def cv_score(self, group_offset, K, Gval, w, T=None, rank=None, H=None, problem_index=None, want_z=True, timing=None):
+        """``mxe_cv_score``: the out-of-sample chi2 of groups of hidden images against held-out data.  The groups, ``H``
+        and ``problem_index`` are those of :meth:`resample_reduce`; a group is one (element, fold), its rows the alphas of
+        the fold's training scan.  ``K``: (n_data, n_omega), the job's kernel as :func:`mock_data` takes it; ``Gval``,
+        ``w``: (n_groups, n_data) validation data in the rotated basis and weights >= 0; ``T``, ``rank``: both None or
+        (n_groups, n_data, n_data) and (n_groups,) as :func:`bins_eig` returns them (rows behind the rank zero).  Returns a
+        dict: ``score`` (rows,), ``z`` (rows, n_data; with ``want_z``) -- ``z[r, k] = sqrt(w[g, k]) ((T_g K H_r)[k] -
+        Gval[g, k])`` for k < rank, 0 behind it, ``score = sum_k z^2``; NaN for a row whose H is not finite -- and ``used``
+        (n_groups: finite rows).  ``timing``: a dict that receives the device time ``ms`` of the kernels."""
+        off = _c(np.atleast_1d(group_offset), np.int32)
+        ng = len(off) - 1
+        if ng < 1 or off[0] != 0 or np.any(np.diff(off) < 0):
+            raise ValueError('cv_score: group_offset must start at 0, not decrease and name at least one group')
+        rows = int(off[-1])
+        Km = _c(np.atleast_2d(K))
+        n_data, n_omega = Km.shape
+        if n_data < 1 or n_omega < 1:
+            raise ValueError('cv_score: K must be (n_data, n_omega), got %r' % (Km.shape,))
+        Gv, wm = _c(Gval).reshape(-1, n_data), _c(w).reshape(-1, n_data)
+        if Gv.shape != (ng, n_data) or wm.shape != (ng, n_data):
+            raise ValueError('cv_score: Gval and w must be (n_groups, n_data) = %r' % ((ng, n_data),))
+        if not (np.all(np.isfinite(Km)) and np.all(np.isfinite(Gv))):
+            raise ValueError('cv_score: K or Gval holds values that are not finite')
+        if not (np.all(np.isfinite(wm)) and np.all(wm >= 0.0)):
+            raise ValueError('cv_score: every weight must be finite and >= 0')
+        if (T is None) != (rank is None):
+            raise ValueError('cv_score: T and rank go together')
+        Tm = rk = None
+        if T is not None:
+            Tm = _c(T).reshape(-1, n_data, n_data)
+            rk = _c(np.broadcast_to(np.asarray(rank, dtype=np.int32), (ng,)), np.int32)
+            if Tm.shape[0] != ng or not np.all(np.isfinite(Tm)):
+                raise ValueError('cv_score: T must be (n_groups, n_data, n_data) and finite')
+            if rk.min() < 0 or rk.max() > n_data:
+                raise ValueError('cv_score: every rank must lie in 0 .. n_data')
+        pi = None
+        if H is not None:
+            H = _c(H).reshape(rows, n_omega)
+        else:
+            if n_omega != self.n_omega:
+                raise ValueError('cv_score: K has %d columns, the omega mesh of the launch %d points' % (n_omega, self.n_omega))
+            pi = _c(np.arange(rows) if problem_index is None else np.atleast_1d(problem_index), np.int32)
+            n_last = self._n_chain * self._n_alpha           # (0: nothing was staged -- the library answers MXE_ERR_STATE)
+            if len(pi) != rows or (rows and n_last and (pi.min() < 0 or pi.max() >= n_last)):
+                raise ValueError('cv_score: problem_index must name %d problems of the last launch (%d x %d)'
+                                 % (rows, self._n_chain, self._n_alpha))
+        score = np.empty(rows)
+        z = np.empty((rows, n_data)) if want_z else None
+        used = np.zeros(ng, dtype=np.int32)
+        ms = ctypes.c_float(0)
+        rc = self._lib.mxe_cv_score(self._h, ng, _p(off), _p(H), _p(pi), n_data, n_omega, _p(Km), _p(Tm), _p(rk), _p(Gv), _p(wm),
+                                    _p(score), _p(z), _p(used), ctypes.byref(ms))
+        if rc == _MXE_ERR_ARG:
+            raise ValueError('mxe_cv_score refused its arguments (%d rows in %d groups, %d data values, %d omega points, H %s): it '
+                             'takes sizes of at least 1 whose products stay within 2^31 - 1, offsets that start at 0 and do not '
+                             'decrease, problem_index inside the last launch and its n_omega, T and rank together, ranks in '
+                             '0 .. n_data, finite K, T, Gval and finite w >= 0'
+                             % (rows, ng, n_data, n_omega, 'handed in' if H is not None else 'of the last launch (%d x %d problems)'
+                                % (self._n_chain, self._n_alpha)))
+        self._check(rc, 'mxe_cv_score')
+        if timing is not None:
+            timing['ms'] = float(ms.value)
+        out = dict(score=score, used=used)
+        if want_z:
+            out['z'] = z
+        return out
 
     def evidence_reduce(self, group_offset, logp, log_quad, log_mix=None, H=None, chain_index=None, log_prior=None,
                         row_mode=0, pick=None, F=None,

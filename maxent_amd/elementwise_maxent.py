@@ -926,6 +926,20 @@ class ElementwiseMaxEnt(object):
                                                      functionals=functionals, pointwise=pointwise,
                                                      keep_samples=keep_samples, keep_data=keep_data, timing=timing)
 
+    def cross_validate(self, bins, n_folds=5, rule='min', result=None, keep_rows=False, timing=None):
+        """:meth:`TauMaxEnt.cross_validate` for every matrix element: ``bins`` are those the last ``set_G_tau_bins`` /
+        ``set_G_iw_bins`` call received; all elements see the same folds (bins are joint measurements).  The rotated data
+        of the folds of all sets come from one ``mxe_bins_resample`` call on the first device, every phase is one launch
+        per device for the 1 + K scans of all elements and one ``mxe_cv_score`` call per device behind it.  Returns a dict
+        of arrays laid out like :meth:`resample_errors`' (matrix indices, then the complex index with ``use_complex``;
+        elements that were not computed hold NaN, -1 for indices; those that follow from hermiticity are filled from
+        their partners, ``A_cv`` and ``A_one_se`` of an imaginary part with the other sign); ``z`` is padded with NaN to
+        the largest rank; ``left_out`` is a dict keyed by element.  With ``result``, every computed element gets its
+        ``'CrossValidationAnalyzer'`` entry."""
+        from . import cross_validation
+        return cross_validation.elementwise_cross_validate(self, bins, n_folds=n_folds, rule=rule, result=result,
+                                                           keep_rows=keep_rows, timing=timing)
+
     def default_model_scan(self, models, prior=None, alpha='bryan', windows=None, functionals=None, pointwise=True,
                            keep_models=True, timing=None):
         """:meth:`TauMaxEnt.default_model_scan` for every matrix element: the same ``models`` go to every computed element
@@ -1453,6 +1467,12 @@ class PoormanMaxEnt(ElementwiseMaxEnt):
         raise NotImplementedError('PoormanMaxEnt.parametric_bootstrap: the default model of an off-diagonal element is built '
                                   'from the diagonal results, so every mock would need the diagonal results of that mock '
                                   'first -- two dependent launches per mock, which this driver does not do; use '
+                                  'ElementwiseMaxEnt or DiagonalMaxEnt')
+
+    def cross_validate(self, *args, **kwargs):
+        raise NotImplementedError('PoormanMaxEnt.cross_validate: the default model of an off-diagonal element is built from '
+                                  'the diagonal results, so every fold would need the diagonal results of that fold first '
+                                  '-- two dependent launches per fold, which this driver does not do; use '
                                   'ElementwiseMaxEnt or DiagonalMaxEnt')
 
     def default_model_scan(self, *args, **kwargs):

@@ -379,16 +379,17 @@ def _element_output(got, le, picks, spec, delta, B, method, n_win, n_fun, pointw
 
 # ---- TauMaxEnt ---------------------------------------------------------------------------------------------------------
 
-def _stacked_single(tm, bins):
-    """``bins`` as the real (n_bins, n_data) sets ``set_G_tau_bins`` / ``set_G_iw_bins`` send down"""
+def _stacked_single(tm, bins, who='resample_errors'):
+    """``bins`` as the real (n_bins, n_data) sets ``set_G_tau_bins`` / ``set_G_iw_bins`` send down; ``who``: the caller an
+    error message names"""
     b = np.asarray(bins)
     if b.ndim != 2:
-        raise ValueError('resample_errors: bins must be (n_bins, n_points); their shape is {}'.format(b.shape))
+        raise ValueError('{}: bins must be (n_bins, n_points); their shape is {}'.format(who, b.shape))
     if getattr(tm._inner_kernel(), 'kind', None) == 'iomega':           # (set_G_iw_bins: the only complex bins there are)
         from .kernels import stack_complex
         return np.ascontiguousarray(stack_complex(b), dtype=float)
     if np.iscomplexobj(b):
-        raise ValueError('resample_errors: G(tau) bins must be real')
+        raise ValueError('{}: G(tau) bins must be real'.format(who))
     return np.ascontiguousarray(b, dtype=float)
 
 
@@ -431,13 +432,14 @@ def tau_resample_errors(tm, bins, method='jackknife', block=1, n_resamples=None,
 
 # ---- ElementwiseMaxEnt / DiagonalMaxEnt --------------------------------------------------------------------------------
 
-def _sets_of(ew, bins):
-    """the real sets of element (i, j) as ``ElementwiseMaxEnt.set_G_tau_bins`` / ``set_G_iw_bins`` form them"""
+def _sets_of(ew, bins, who='resample_errors'):
+    """the real sets of element (i, j) as ``ElementwiseMaxEnt.set_G_tau_bins`` / ``set_G_iw_bins`` form them; ``who``: the
+    caller an error message names"""
     n_iw = ew.__dict__.get('_n_iw')
     if n_iw is None:
         cplx = np.iscomplexobj(bins)
         if cplx and not ew.use_complex:
-            raise ValueError('resample_errors: complex G(tau) bins need use_complex=True')
+            raise ValueError('{}: complex G(tau) bins need use_complex=True'.format(who))
 
         def sets_of(i, j):
             b = bins[:, i, j, :]

@@ -593,6 +593,41 @@ class TauMaxEnt(object):
                                              pointwise=pointwise, keep_samples=keep_samples, keep_data=keep_data,
                                              timing=timing)
 
+    def cross_validate(self, bins, n_folds=5, rule='min', result=None, keep_rows=False, timing=None):
+        """k-fold cross-validation of alpha over the Monte Carlo ``bins`` the last ``set_G_tau_bins`` / ``set_G_iw_bins`` /
+        ``set_G_l_bins`` call of this object received: does the spectrum continued from one part of the bins predict the
+        other part?  The bins are cut into ``n_folds`` contiguous folds (the bin index is Monte Carlo time); the mean of the
+        bins outside fold f is continued over the whole alpha mesh -- the full sample and the folds are one launch, with
+        the covariance of the full sample as ``set_G_*_bins`` staged it --, and every H row of that scan is scored on the
+        device against the mean of fold f (``mxe_cv_score``, :mod:`maxent_amd.cross_validation`):
+        ``chi2_val = sum_k w_k ((T K H)_k - (T mean_f)_k)^2`` with ``w_k = N_f / (N sigma_k^2)``, sigma_k the error of the
+        full-sample mean along eigen-direction k.  The object is not changed.  Not in the reference.
+
+        The training solve at mesh alpha uses the full-sample sigma; a training mean of N - N_f bins is noisier by
+        N / (N - N_f), so the solve equals one with the training mean's own error at alpha (N - N_f) / N
+        (``info['alpha_train_factor']``).  The pick is applied to the full sample at the same mesh index (the plug-in
+        rule); sigma is estimated from all bins, the validation fold included; with few bins per fold the score is noisy,
+        ``score_err`` says how noisy.
+
+        Returns a dict: ``alpha`` (the mesh); ``fold_scores`` (K, n_alpha) = chi2_val / rank; ``score`` (their mean over
+        the folds) and ``score_err`` (their standard deviation / sqrt(K)); ``train_chi2`` (K, n_alpha); ``alpha_index_cv``
+        (the argmin of ``score`` over the alphas at which every fold is finite, -1 if there is none; of equal scores the
+        larger alpha); ``alpha_index_one_se`` (the largest alpha whose score is <= the minimum + ``score_err`` at the
+        minimum); ``alpha_at_edge`` (the minimum sits on an end of the mesh: widen it); ``A_cv``, ``A_one_se`` (the rows of
+        the full-sample scan at those indices; with a ``PreblurKernel`` A = B H); ``z`` (K, rank), the out-of-sample
+        whitened residuals at ``alpha_index_cv``, and ``calibration``, the mean of z^2 (about 1 when the error bars are
+        right); ``left_out`` (the (fold, alpha) pairs that were not finite); ``folds`` (the bin ranges); ``info``
+        (``kernel_ms``, ``score_ms``, ``launches``, ``devices``, ``alpha_train_factor``).  ``keep_rows``: also ``rows_H``
+        (K, n_alpha, n_omega), the H rows that were scored.
+
+        ``result``: a result of ``run()`` on the same alpha mesh (another mesh raises ``ValueError``) gets the entry
+        ``analyzer_results['CrossValidationAnalyzer']`` whose ``alpha_index`` and ``A_out`` follow ``rule`` (``'min'`` or
+        ``'one_se'``): ``result.get_A_out('CrossValidationAnalyzer')`` and ``posterior_errors(result,
+        alpha='CrossValidationAnalyzer')`` then work; the default analyzer stays what it was."""
+        from . import cross_validation
+        return cross_validation.tau_cross_validate(self, bins, n_folds=n_folds, rule=rule, result=result, keep_rows=keep_rows,
+                                                   timing=timing)
+
     def default_model_scan(self, models, prior=None, alpha='bryan', windows=None, functionals=None, pointwise=True,
                            keep_models=True, timing=None):
         """Continue the data of this object under a family of default models in one launch and let the data say which
